@@ -2,6 +2,7 @@
 """bench.py -- nonzeros/sec per full A+B sweep of the factor-update hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--method pg|cg|tncg] [--maxupd M] [--fp64] [--no-cpu] [--no-extra]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,11 +11,14 @@ included) on synthetic data that is already resident in HBM when the timed regio
 
 Workload (every N): the matrix BASELINE.json quotes the metric on -- uniform 1 000 000 x 100 000, 1e8 triplets
 (seed 1; ~9.995e7 nonzeros after duplicate summing), k = 50 (configs C3 / C4).  The headline line is method = pg,
-fp32, the reference's Python defaults (l2 1e9, step 1e-7, maxupd 10); at N = 1 `extra` carries the other points of
-the metric on the SAME matrix, each with its own roofline block: pg with maxupd = 1 (the bandwidth point, R's
-default), pg with hyper-parameters that keep the factors finite (same work per sweep), cg and tncg fp32 (the solvers config
+fp32, maxupd 10, with hyper-parameters that keep the factors alive (PG_LIVE: l2 1e3, step 1e-9) -- the reference's Python
+defaults (l2 1e9, step 1e-7) zero this matrix's factors within the first sweeps, so a run on them computes nothing; at N = 1
+`extra` carries the other points of the metric on the SAME matrix, each with its own roofline block: pg with maxupd = 1 (the
+bandwidth point, R's default), pg with the reference's defaults (same work per sweep), cg and tncg fp32 (the solvers config
 C4's matrix is not quoted on, for completeness), cg fp64 (config C3) -- and `tncg_f64_c5`: config C5's own matrix (Last.FM-shaped
-358 858 x 160 112, power-law item degrees, k = 100, tncg fp64, l2 1e3, maxupd 1500), steady-state sweeps.  Every block carries the
+358 858 x 160 112, power-law item degrees, k = 100, tncg fp64, l2 1e3, maxupd 1500), steady-state sweeps.  `--steps K` is the
+number of timed sweeps of the headline and `ms_per_step` the wall time of one of them; `--dump-outputs DIR` writes the factors
+the headline's last timed sweep left (see dump_outputs): the inputs are seeded, so two builds can be compared output for output.  Every block carries the
 HBM roofline of SURVEY.md 8(d) AND a vector-ALU roofline (`roofline.valu`: the flops the reference's arithmetic needs for the
 decisions the solvers took, against the fp32 / fp64 vector peak) -- the multi-pass solvers are not HBM-bound.
 N > 1 is STRONG scaling of that one matrix: A rows and B rows are cut into per-rank ranges with balanced nonzero
@@ -25,7 +29,7 @@ Rank 0 prints ONE JSON line (see the driver contract); `roofline` prices the row
 peak with SURVEY.md 8(d)'s algorithmic bytes, `cpu_baseline` is the compiled reference (oracle/_ref, kind
 "reference") timed on this box's host cores on the same matrix (steady state: the difference of a 2-iteration
 and a 1-iteration run).  `roofline.by_config` / `cpu_baseline.by_config` put the three lines of the metric side by side:
-PG with the reference's defaults (the headline), PG with hyper-parameters that keep the factors alive, CG fp64.
+PG with hyper-parameters that keep the factors alive (the headline), PG with the reference's defaults, CG fp64.
 """
 import argparse
 import json
@@ -67,6 +71,15 @@ WORKLOADS = {
 }
 K = 50
 C5_K, C5_MAXUPD, C5_L2 = 100, 1500, 1e3   # BASELINE config 5: tncg fp64, k = 100, maxupd = 15 k, l2 = the tncg default
+# PG with the reference's Python defaults (l2 1e9, step 1e-7) scales this matrix's factors by ~1/201 per update: fp32 flushes them to
+# exact zeros within the first sweeps, and such a run computes nothing that two builds could be compared on.  The timed
+# PG headline runs with hyper-parameters that keep the factors alive (the same work per sweep); the defaults are one of the extra lines.
+PG_LIVE = dict(l2=1e3, step0=1e-9)
+
+
+def traffic_key(workload, method, maxupd, prec, kw):
+    """the run's entry in profiles/hbm_traffic.json (the PG entries without `_finite` were counted on the reference's defaults)"""
+    return f"{workload}_{method}_maxupd{maxupd}_{prec}" + ("_finite" if kw == PG_LIVE else "")
 
 
 def algorithmic_bytes_half(nnz, dimM, k, s):
@@ -119,10 +132,11 @@ class Job:
         self.A0, self.B0 = harness.initialize_matrices(self.dimA, self.dimB, k, use_float, 1)
         self.nnz_local = (self.be.sess.nnz(0), self.be.sess.nnz(1))
 
-    def run(self, method, maxupd, steps, warmup, l2=None, step0=1e-7, profile_steps=None):
+    def run(self, method, maxupd, steps, warmup, l2=None, step0=1e-7, profile_steps=None, keep_factors=False):
         """warmup + `steps` timed sweeps with profiling OFF (the product configuration), then a separate profiled pass
         (HIP events around the row-kernel launches of each half, per-row pass counters) of `profile_steps` sweeps from
-        the same starting point for the kernel time and the pass-weighted traffic."""
+        the same starting point for the kernel time and the pass-weighted traffic.  keep_factors: the result also carries
+        `factors`, the host (A, B) the last timed sweep left."""
         l2d, mu, _ = harness.auto_defaults(method, self.k)
         l2 = l2d if l2 is None else l2
         maxupd = mu if maxupd is None else maxupd
@@ -142,6 +156,7 @@ class Job:
         finite = bool(np.isfinite(A).all() and np.isfinite(B).all())
         # "finite" only says no NaN / inf; a factor the solver has driven to all zeros is finite too -- report how much is alive
         alive = {"A_nonzero_frac": float(np.count_nonzero(A)) / A.size, "B_nonzero_frac": float(np.count_nonzero(B)) / B.size}
+        factors = (A, B) if keep_factors else None
         del A, B
         psteps = profile_steps or min(steps, 5)
         alt = fresh()
@@ -162,7 +177,7 @@ class Job:
         lprof = [sess.launch_profile(w) for w in (0, 1)]
         sess.profile(False)
         return dict(method=method, maxupd=maxupd, l2=l2, step0=step0, steps=steps, seconds=dt, finite=finite, alive=alive, psteps=psteps,
-                    kernel_ms=k_ms, ev_stats=ev_stats, dec_stats=dec_stats, plan=plan, lprof=lprof, exchange=exchange)
+                    kernel_ms=k_ms, ev_stats=ev_stats, dec_stats=dec_stats, plan=plan, lprof=lprof, exchange=exchange, factors=factors)
 
     def close(self):
         self.be.close()
@@ -473,6 +488,34 @@ def compact_line(full):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6 - 4096   # --dump-outputs: at most 64 MB in all (array data; the rest covers the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_outputs(outdir, factors, budget=DUMP_BYTES):
+    """--dump-outputs: the factors the headline's last timed sweep left on the device, as run_poismf hands them to its caller,
+    written as <outdir>/<name>.npy in the run's precision (float32, or float64 with --fp64).  A factor that fits its share of
+    `budget` (the smaller factor first, then what is left) is written whole as A.npy / B.npy; a larger one as A_sample.npy /
+    B_sample.npy: the rows np.sort(np.random.default_rng(DUMP_SEED).choice(rows, n, replace=False)), the same rows on every
+    run of the same shape.  Returns {file name: (shape, whole)}."""
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    left = budget
+    items = sorted(factors.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, M) in enumerate(items):
+        share = left // (len(items) - i)
+        if M.nbytes <= share:
+            out, fname = M, f"{name}.npy"
+        else:
+            n = share // (M.shape[1] * M.itemsize)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(M.shape[0], n, replace=False))
+            out, fname = M[rows], f"{name}_sample.npy"
+        np.save(os.path.join(outdir, fname), np.ascontiguousarray(out))
+        left -= out.nbytes
+        written[fname] = (out.shape, out is M)
+    return written
+
+
 def write_full(full):
     """the whole object (launch lists, notes, per-block rooflines, CPU legs) next to bench.py and, on a gpurun box, under gpurun_out/"""
     for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
@@ -546,6 +589,9 @@ def main():
     ap.add_argument("--segments", type=int, default=None, help="segments of the A half (multi-GPU exchange / compute overlap)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the factors the headline's last timed sweep left as DIR/<name>.npy (at most 64 MB: a seeded row sample "
+                         "of a factor that does not fit)")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -594,9 +640,16 @@ def main():
     gen_s = time.perf_counter() - t0
     segA = a.segments if a.segments is not None else (4 if world > 1 else 1)
     job = Job(trip, rangesA, rangesB, rank, device, use_float, segA)
-    res = job.run(a.method, a.maxupd, a.steps, a.warmup)
+    hkw = PG_LIVE if a.method == "pg" else {}
+    res = job.run(a.method, a.maxupd, a.steps, a.warmup, keep_factors=bool(a.dump_outputs) and rank == 0, **hkw)
     prec = "f32" if use_float else "f64"
-    headline_roofline = roofline_block(job, res, f"{a.workload}_{a.method}_maxupd{res['maxupd']}_{prec}")
+    if res["factors"] is not None:
+        A, B = res.pop("factors")
+        for fname, (shape, whole) in dump_outputs(a.dump_outputs, {"A": A, "B": B}).items():
+            print(f"bench: dumped {os.path.join(a.dump_outputs, fname)} {shape} {'' if whole else 'seeded row sample '}({prec})",
+                  file=sys.stderr)
+        del A, B
+    headline_roofline = roofline_block(job, res, traffic_key(a.workload, a.method, res["maxupd"], prec, hkw))
     headline_setup_s = job.setup_s
 
     # whole-job totals
@@ -614,12 +667,13 @@ def main():
         # (name, method, fp32?, maxupd, timed sweeps, warm-up sweeps, overrides): TNCG's first sweeps from the random start cost a
         # multiple of the later ones -- two warm-up sweeps, so that the timed ones are steady state
         for name, method, uf, mu, st, wu, kw in (("pg_maxupd1_f32", "pg", True, 1, 10, 1, {}),
-                                                 ("pg_maxupd10_f32_finite", "pg", True, 10, 5, 1, dict(l2=1e3, step0=1e-9)),
+                                                 ("pg_maxupd10_f32_defaults", "pg", True, 10, 5, 1, {}),
+                                                 ("pg_maxupd10_f32_finite", "pg", True, 10, 5, 1, PG_LIVE),
                                                  ("cg_f32", "cg", True, None, 3, 1, {}),
                                                  ("tncg_f32", "tncg", True, None, 3, 2, {}),
                                                  ("cg_f64", "cg", False, None, 3, 1, {})):
-            if (name.startswith("pg") and a.method == "pg" and use_float and mu == res["maxupd"] and not kw):
-                continue
+            if (method, uf, mu, kw) == (a.method, use_float, res["maxupd"], hkw):
+                continue   # (the headline itself)
             j2 = job
             if uf != job.use_float:
                 job.close()
@@ -628,7 +682,7 @@ def main():
             extra[name] = {"value": j2.nnz_local[1] * st / r["seconds"], "unit": "nnz/s", "ms_per_step": r["seconds"] / st * 1e3,
                            "dtype": "f32" if uf else "f64", "method": method, "maxupd": r["maxupd"], "l2": r["l2"], "step": r["step0"],
                            "steps": st, "warmup": wu, "finite": r["finite"], "alive": r["alive"],
-                           "roofline": roofline_block(j2, r, f"{a.workload}_{method}_maxupd{r['maxupd']}_{'f32' if uf else 'f64'}")}
+                           "roofline": roofline_block(j2, r, traffic_key(a.workload, method, r["maxupd"], "f32" if uf else "f64", kw))}
         if a.workload == "C4" and not os.environ.get("POISMF_BENCH_SCALE"):
             # BASELINE config C5 on ITS matrix ("and TNCG for C5"): Last.FM-shaped, power-law item degrees up to 1.4e5,
             # k = 100, tncg fp64, l2 1e3, maxupd 1500 = 15 k, rows start from the previous sweep's (reuse_prev); steady-state sweeps
@@ -656,7 +710,7 @@ def main():
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32" if use_float else "f64", "data": "synthetic",
             "config": {"workload": f"uniform {dimA}x{dimB}, {nnz_total} nnz ({ntrip} triplets, seed 1, duplicates summed), "
-                                   f"k={K}, method={a.method}, maxupd={res['maxupd']}, l2={res['l2']:g}, step=1e-7",
+                                   f"k={K}, method={a.method}, maxupd={res['maxupd']}, l2={res['l2']:g}, step={res['step0']:g}",
                        "baseline_config": {"C4": "C4 (= C3's matrix): the 1M x 100K, 100M-nnz matrix of the metric", "C2": "C2"}[a.workload]
                                           if not os.environ.get("POISMF_BENCH_SCALE") else f"{a.workload} shrunk (testing)",
                        "sharding": "none" if single else f"one fixed matrix: A rows {rangesA} and B rows {rangesB} over {world} ranks "
@@ -671,15 +725,16 @@ def main():
             "results_finite": res["finite"],
             "results_alive": dict(res["alive"], note="results_finite = no NaN / inf anywhere; it does NOT mean the factors are alive: with the "
                                   "reference's Python defaults for pg (l2 1e9, step 1e-7) the reference's own arithmetic drives this matrix's "
-                                  "factors to exact zeros within the first sweeps (DESIGN.md 6.2) -- A/B_nonzero_frac say how much is left; the "
-                                  "by_config.pg_finite line times the same kernels on factors that stay positive"),
+                                  "factors to exact zeros within the first sweeps (DESIGN.md 6.2) -- A/B_nonzero_frac say how much is left.  The "
+                                  "pg headline therefore runs with l2 1e3, step 1e-9 (same work per sweep, factors stay positive); "
+                                  "by_config.pg_maxupd10_f32_defaults times the same kernels on the defaults"),
         }
         if extra:
             out["extra"] = extra
-        # the lines of the metric side by side in the parsed line: PG with the reference's defaults (the headline), PG with
-        # hyper-parameters that keep the factors alive (same work per sweep), CG / TNCG fp32, CG fp64 (config C3), TNCG fp64 on
+        # the lines of the metric side by side in the parsed line: PG with hyper-parameters that keep the factors alive (the
+        # headline), PG with the reference's defaults (same work per sweep), CG / TNCG fp32, CG fp64 (config C3), TNCG fp64 on
         # config C5's matrix -- each with its two roofline fractions
-        head_name = f"{a.method}_maxupd{res['maxupd']}_{prec}_defaults"
+        head_name = f"{a.method}_maxupd{res['maxupd']}_{prec}_{'finite' if hkw else 'defaults'}"
         byc = {head_name: {"value": out["value"], "ms_per_step": out["ms_per_step"], "frac": headline_roofline["frac"],
                            "frac_valu": headline_roofline["valu"]["frac"],
                            "frac_row_kernels": headline_roofline["frac_row_kernels"], "dominant_kernel": headline_roofline["dominant_kernel"]}}
@@ -691,7 +746,7 @@ def main():
         final_line = out
     if single and not a.no_cpu and rank == 0:
         job.close()
-        cb = cpu_baseline(trip, a.method, use_float, a.maxupd)
+        cb = cpu_baseline(trip, a.method, use_float, a.maxupd, **hkw)
         final_line["cpu_baseline"] = cb
         csr, csc, _ = _cpu_inputs(trip, use_float)
         final_line.setdefault("extra", {})["run_poismf_abi"] = abi_timing(csr, csc, dimA, dimB, a.method, use_float, a.maxupd)
@@ -700,7 +755,8 @@ def main():
         if not a.no_extra:
             # the other lines of the metric get their CPU number too (fp32 inputs are still cached for the first); cg / tncg fp32 on
             # the C4 matrix are not lines of the metric and have none (a TNCG fp32 sweep of 1e8 nonzeros is minutes of CPU time)
-            for name, tr, method, uf, mu, kw in (("pg_maxupd10_f32_finite", trip, "pg", True, None, dict(l2=1e3, step0=1e-9)),
+            for name, tr, method, uf, mu, kw in (("pg_maxupd10_f32_defaults", trip, "pg", True, None, {}),
+                                                 ("pg_maxupd10_f32_finite", trip, "pg", True, None, PG_LIVE),
                                                  ("cg_f64", trip, "cg", False, None, {}),
                                                  ("tncg_f64_c5", c5, "tncg", False, C5_MAXUPD,
                                                   dict(l2=C5_L2, k=C5_K, what="config C5's whole matrix"))):

@@ -5,6 +5,8 @@ TEST INFRASTRUCTURE ONLY: importable from tests/, scripts/make_golden.py, __graf
 and bench.py's cpu_baseline leg -- never from the poismf_amd package.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -16,10 +18,12 @@ METHOD = {"tncg": 1, "cg": 2, "pg": 3}  # ref: src/poismf.h:225
 
 
 def build(ref=False):
-    """Compile the oracle (and optionally the reference, only possible where /root/reference exists)."""
+    """Compile the oracle (and optionally the reference, only possible where /root/reference exists).  ref=True also
+    builds the BLAS-routed flavour of the oracle (oracle/_ref/liboracle_blas_*.so: this repo's source and SciPy's
+    OpenBLAS), with or without the reference."""
     subprocess.check_call(["make", "-s", "-C", HERE, "oracle"])
-    if ref and os.path.isdir("/root/reference/src"):
-        subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+    if ref:
+        subprocess.check_call(["make", "-s", "-C", HERE, "ref" if os.path.isdir("/root/reference/src") else "blas"])
 
 
 def _dt(is_float):
@@ -49,7 +53,7 @@ class Oracle(_Lib):
 
     def __init__(self, is_float=False, blas_flavour=False, fma_axpy=False):
         """blas_flavour=True loads oracle/_ref/liboracle_blas_*.so: the same restatement with its k-length
-        sums routed through the reference's own BLAS (only exists next to the compiled reference).
+        sums routed through the reference's own BLAS (SciPy's OpenBLAS; `make -C oracle blas`).
         fma_axpy=True loads liboracle_fma_*.so: y += a x rounded once per element, as a BLAS with fused
         multiply-add (and the GPU) computes it -- see vaxpy in poismf_oracle.c for why that matters in fp32 CG."""
         if blas_flavour:
@@ -383,3 +387,121 @@ class Reference(_Lib):
         rc = self.lib.topN(_p(a_vec), _p(B), B.shape[1], _p(inc) if len(inc) else None, len(inc), _p(exc) if len(exc) else None,
                            len(exc), _p(ix), _p(sc), n_top, B.shape[0], 1)
         return rc, ix, sc
+
+
+# ---- the reference's answers, recorded -----------------------------------------------------
+# tests/test_oracle_vs_ref.py holds the oracle to the compiled reference.  Where the reference cannot be compiled (it is not
+# part of this repo), the same calls are answered from a recording of the compiled reference's outputs (tests/golden/):
+# every call is keyed by a digest of its method name and arguments (array bytes, dtypes, shapes, scalar values), and replays
+# the return value and the arrays the reference wrote in place.  The inputs are all seeded, so the keys are the same anywhere.
+
+def _call_key(name, args, kwargs):
+    h = hashlib.sha256(name.encode())
+
+    def put(x):
+        if isinstance(x, np.ndarray):
+            h.update(f"a{x.dtype.str}{x.shape}".encode() + np.ascontiguousarray(x).tobytes())
+        elif isinstance(x, (tuple, list)):
+            h.update(b"(")
+            for y in x:
+                put(y)
+            h.update(b")")
+        elif isinstance(x, np.generic):
+            h.update(f"s{x.dtype.str}{x.item()!r}".encode())
+        else:
+            h.update(f"p{type(x).__name__}{x!r}".encode())
+    put(list(args))
+    put(sorted(kwargs.items()))
+    return h.hexdigest()[:32]
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def _scalar_kind(v):
+    return "b" if isinstance(v, (bool, np.bool_)) else "i" if isinstance(v, (int, np.integer)) else "f"
+
+
+class RecordingReference:
+    """Wraps a Reference; every call is passed on and its answer kept in `calls` (key -> (meta, arrays)) for save_recording()."""
+
+    def __init__(self, ref, calls):
+        self.ref, self.calls = ref, calls
+        self.is_float = ref.is_float
+
+    def __getattr__(self, name):
+        fn = getattr(self.ref, name)
+
+        def call(*args, **kwargs):
+            key = _call_key(name, args, kwargs)
+            before = [a.copy() if isinstance(a, np.ndarray) else None for a in args]
+            ret = fn(*args, **kwargs)
+            items = ret if isinstance(ret, tuple) else (ret,)
+            meta = {"tuple": isinstance(ret, tuple), "ret": [], "mut": []}
+            arrays = {}
+            for i, v in enumerate(items):
+                if v is None:
+                    meta["ret"].append("n")
+                    continue
+                meta["ret"].append("a" if isinstance(v, np.ndarray) else _scalar_kind(v))
+                arrays[f"r{i}"] = np.array(v)   # (a copy: callers scale returned arrays in place)
+            for j, (a, b) in enumerate(zip(args, before)):
+                if b is not None and not _same_bits(a, b):
+                    meta["mut"].append(j)
+                    arrays[f"m{j}"] = a.copy()
+            self.calls.setdefault(key, (meta, arrays))   # (a repeated call keeps its first answer)
+            return ret
+        return call
+
+
+def save_recording(path, calls, blas_core):
+    out = {"__meta__": np.array(json.dumps({"blas_core": blas_core, "calls": {k: m for k, (m, _) in calls.items()}}))}
+    for key, (_, arrays) in calls.items():
+        for n, v in arrays.items():
+            out[f"{key}.{n}"] = v
+    np.savez_compressed(path, **out)
+
+
+class RecordedReference:
+    """The compiled reference's answers to the calls tests/test_oracle_vs_ref.py makes, replayed from a recording."""
+
+    def __init__(self, is_float, path):
+        self.is_float = is_float
+        self.path = path
+        self.z = np.load(path, allow_pickle=False)
+        meta = json.loads(str(self.z["__meta__"]))
+        self.blas_core, self.meta = meta["blas_core"], meta["calls"]
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+
+        def call(*args, **kwargs):
+            key = _call_key(name, args, kwargs)
+            if key not in self.meta:
+                raise KeyError(f"{name}: no recorded reference answer for these arguments in {os.path.basename(self.path)} "
+                               "(inputs changed since it was recorded: re-record with scripts/make_golden.py where the reference exists)")
+            meta = self.meta[key]
+            for j in meta["mut"]:
+                np.copyto(args[j], self.z[f"{key}.m{j}"])
+            items = []
+            for i, kind in enumerate(meta["ret"]):
+                v = None if kind == "n" else self.z[f"{key}.r{i}"]
+                items.append(v if kind in ("n", "a") else {"b": bool, "i": int, "f": float}[kind](v))
+            return tuple(items) if meta["tuple"] else items[0]
+        return call
+
+
+def openblas_core(lib):
+    """The OpenBLAS kernel set the library's BLAS runs (SciPy's OpenBLAS picks one per CPU at load time; the BLAS-routed
+    flavour agrees with a recording bit for bit only where the same kernels run).  None where the BLAS does not say."""
+    for sym in ("scipy_openblas_get_corename", "openblas_get_corename"):
+        try:
+            fn = getattr(lib.lib, sym)
+        except AttributeError:
+            continue
+        fn.restype = C.c_char_p
+        fn.argtypes = []
+        return fn().decode()
+    return None

@@ -5,9 +5,11 @@
 Only runs where /root/reference exists (the development container).  The fixtures are data: inputs and
 the reference's outputs.  Levels follow SURVEY.md section 8c (G1 primitives ... G5 edge cases).
 
-    python scripts/make_golden.py
+    python scripts/make_golden.py               # everything
+    python scripts/make_golden.py --calls-only  # only tests/golden/ref_calls_*.npz
 """
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -127,15 +129,26 @@ def factors_fixture(ref, is_float):
     return d
 
 
+def record_reference_calls():
+    """tests/golden/ref_calls_{f32,f64}.npz: the compiled reference's answers to every call tests/test_oracle_vs_ref.py makes
+    (that module records them itself under POISMF_RECORD_REFERENCE=1, and replays them where the reference is absent)."""
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join("tests", "test_oracle_vs_ref.py")],
+                          cwd=ROOT, env=dict(os.environ, POISMF_RECORD_REFERENCE="1"))
+
+
 def main():
     bindings.build(ref=True)
     os.makedirs(OUT, exist_ok=True)
+    if "--calls-only" in sys.argv[1:]:
+        record_reference_calls()
+        return
     for is_float in (False, True):
         ref = bindings.Reference(is_float)
         tag = "f32" if is_float else "f64"
         np.savez_compressed(os.path.join(OUT, f"rows_{tag}.npz"), **rows_fixture(ref, is_float))
         np.savez_compressed(os.path.join(OUT, f"full_{tag}.npz"), **full_fixture(ref, is_float))
         np.savez_compressed(os.path.join(OUT, f"factors_{tag}.npz"), **factors_fixture(ref, is_float))
+    record_reference_calls()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

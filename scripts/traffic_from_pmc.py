@@ -15,7 +15,8 @@ round_tag = sys.argv[2] if len(sys.argv) > 2 else "?"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poismf_amd import build  # noqa: E402  (the hash of the kernel sources + flags these counters were recorded from)
 # name -> (key in profiles/hbm_traffic.json, sweeps per profiled run = 2 x (warmup + steps) of scripts/profile_round.sh)
-RUNS = {"pg10": ("C4_pg_maxupd10_f32", 12), "pg1": ("C4_pg_maxupd1_f32", 12), "cg64": ("C4_cg_maxupd5_f64", 6),
+# (pg10 / pg1 are bench.py's pg headline: hyper-parameters that keep the factors alive, bench.PG_LIVE -> the `_finite` keys)
+RUNS = {"pg10": ("C4_pg_maxupd10_f32_finite", 12), "pg1": ("C4_pg_maxupd1_f32_finite", 12), "cg64": ("C4_cg_maxupd5_f64", 6),
         "cg32": ("C4_cg_maxupd5_f32", 6), "tncg32": ("C4_tncg_maxupd750_f32", 6),
         # config C5 through scripts/run_config.py (--warmup 2 --sweeps 3): five sweeps, the first two from the random start
         "c5": ("C5_tncg_maxupd1500_f64", 5)}

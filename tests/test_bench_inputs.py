@@ -105,3 +105,22 @@ def test_valu_roofline_counts_the_references_flops():
     assert v["flops_per_sweep"] == 1000 * 201 + (1000 + 1800) * 125 and v["peak"] == 78.6
     v = b.valu_block(J, dict(method="tncg", psteps=1, ev_stats=None, dec_stats=d), sweep_ms=2.0)
     assert v["flops_per_sweep"] == 1800 * 226
+
+
+def test_pg_headline_hyper_parameters_keep_the_factors_alive():
+    """bench.py's pg headline runs with PG_LIVE (the reference's defaults, l2 1e9 / step 1e-7, flush the headline matrix's fp32 factors to
+    exact zeros within the first sweeps: measured on the GPU and in the reference, results_alive 0.0).  On rows and columns of the headline's
+    lengths (100 / 1000 nonzeros, k = 50, fp32) the oracle's PG(10) with PG_LIVE leaves factors that are finite, positive and moved by far
+    more than rounding -- outputs two builds can be compared on."""
+    import scipy.sparse as sp
+    from oracle import bindings
+    from poismf_amd import harness
+    b = _bench()
+    t = synth.uniform_triplets(10000, 1000, 1000000, seed=1)
+    csr, csc = harness.process_data(sp.coo_matrix((t.data, (t.row, t.col)), shape=t.shape), True)
+    A0, B0 = harness.initialize_matrices(10000, 1000, b.K, True, 1)
+    A, B = A0.copy(), B0.copy()
+    bindings.Oracle(True).run_poismf(A, csr[0], csr[2], csr[1], B, csc[0], csc[2], csc[1], b.PG_LIVE["l2"], 0.0, 1.0, b.PG_LIVE["step0"],
+                                     "pg", True, 3, 10, False, True, True, 4)
+    for M, M0 in ((A, A0), (B, B0)):   # (moved 1e-5 .. 6e-5 here; 64 ulps of 0.31 = 1.9e-6)
+        assert np.isfinite(M).all() and (M > 0).all() and np.abs(M - M0).max() > 64 * np.spacing(np.float32(0.31))

@@ -97,3 +97,29 @@ def test_bench_gpus_n_starts_its_own_ranks_and_returns_their_exit_code():
         return   # (on a GPU box the real run is tests/test_gpu_dist2.py's)
     assert res.returncode != 0
     assert "needs an MI355X" in out and "launch with torch.distributed.run" not in out
+
+
+def test_dump_outputs_writes_the_factors_within_64_mb_and_samples_the_same_rows(tmp_path):
+    """--dump-outputs: a factor that fits its share is written whole; a larger one as a seeded row sample, the same rows on every run;
+    the precision is kept; on the headline's own shapes (1M x 50 and 100K x 50, fp32 and fp64) the files stay within 64 MB."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(3)
+    A, B = rng.random((5000, 50)).astype(np.float32), rng.random((500, 50)).astype(np.float32)
+    budget = 400_000
+    runs = [tmp_path / "one", tmp_path / "two"]
+    for d in runs:
+        assert set(b.dump_outputs(str(d), {"A": A, "B": B}, budget)) == {"B.npy", "A_sample.npy"}
+    Bd, As = np.load(runs[0] / "B.npy"), np.load(runs[0] / "A_sample.npy")
+    assert Bd.dtype == np.float32 and As.dtype == np.float32 and np.array_equal(Bd, B)
+    assert As.nbytes + Bd.nbytes <= budget and len(As) > 0
+    assert np.array_equal(As, A[np.sort(np.random.default_rng(b.DUMP_SEED).choice(len(A), len(As), replace=False))])
+    for name in ("B.npy", "A_sample.npy"):
+        assert (runs[0] / name).read_bytes() == (runs[1] / name).read_bytes()
+    w = b.dump_outputs(str(tmp_path / "whole"), {"A": A.astype(np.float64), "B": B.astype(np.float64)})
+    assert set(w) == {"A.npy", "B.npy"} and np.load(tmp_path / "whole" / "A.npy").dtype == np.float64
+    for dt in (np.float32, np.float64):
+        d = tmp_path / f"c4_{np.dtype(dt).name}"
+        b.dump_outputs(str(d), {"A": np.broadcast_to(dt(0.5), (10 ** 6, 50)), "B": np.broadcast_to(dt(0.25), (10 ** 5, 50))})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
+        assert all(np.load(f).dtype == dt for f in d.iterdir())

@@ -1,11 +1,15 @@
 """Pins the oracle: the C restatement (oracle/poismf_oracle.c) against the REAL reference compiled in
-place from /root/reference/src (oracle/_ref, built by `make -C oracle ref`).
+place from /root/reference/src (oracle/_ref, built by `make -C oracle ref`) -- or, where the reference is
+not there to compile, against its recorded answers to these very calls (tests/golden/ref_calls_*.npz,
+oracle/bindings.py RecordedReference; recorded by scripts/make_golden.py).
 
 Levels follow SURVEY.md section 8c: G1 primitives, G2 single-row solvers, G3 half-sweeps, G4 full
 run_poismf, G5 edge cases.  Tolerances come from the reference's own self-variance across BLAS
 builds (SURVEY.md section 7 / BASELINE.md section 2): the restatement uses plain left-to-right
 k-length sums whereas the compiled reference calls SciPy's OpenBLAS (SIMD summation order + FMA).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -13,8 +17,15 @@ from oracle import bindings
 from poismf_amd import harness
 from tests import helpers as H
 
-pytestmark = pytest.mark.skipif(not (bindings.ref_available(False) and bindings.ref_available(True)),
-                                reason="compiled reference (oracle/_ref) not present")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# POISMF_RECORD_REFERENCE=1 (scripts/make_golden.py, where the compiled reference exists): the reference's answers to the
+# calls below are written to tests/golden/ref_calls_{f32,f64}.npz when the module ends
+RECORD = os.environ.get("POISMF_RECORD_REFERENCE") == "1"
+_RECORDED_CALLS = {}
+
+
+def _recording(is_float):
+    return os.path.join(GOLD, f"ref_calls_{'f32' if is_float else 'f64'}.npz")
 
 
 # Two flavours of the SAME restatement source are pinned:
@@ -29,9 +40,24 @@ _EXACT = {"on": False}
 @pytest.fixture(scope="module", params=[(False, False), (True, False), (False, True), (True, True)],
                 ids=["f64-plain", "f32-plain", "f64-blas", "f32-blas"])
 def libs(request):
+    """(oracle flavour, reference, is_float).  The reference is the compiled one where it exists, else its recorded answers.
+    Those were recorded with one CPU's OpenBLAS kernels: the bit-exact flavour is held to them where the same kernels run."""
     is_float, blas = request.param
     _EXACT["on"] = blas
-    return bindings.Oracle(is_float, blas_flavour=blas), bindings.Reference(is_float), is_float
+    orc = bindings.Oracle(is_float, blas_flavour=blas)
+    if bindings.ref_available(is_float):
+        ref = bindings.Reference(is_float)
+        if RECORD:
+            calls = _RECORDED_CALLS.setdefault(is_float, {})
+            ref = bindings.RecordingReference(ref, calls)
+            request.addfinalizer(lambda: bindings.save_recording(_recording(is_float), calls, bindings.openblas_core(ref.ref)))
+        return orc, ref, is_float
+    assert not RECORD, "POISMF_RECORD_REFERENCE=1 needs the compiled reference (oracle/_ref)"
+    ref = bindings.RecordedReference(is_float, _recording(is_float))
+    if blas and bindings.openblas_core(orc) != ref.blas_core:
+        pytest.skip(f"bit-exact flavour vs the recorded reference: recorded with OpenBLAS kernels {ref.blas_core}, "
+                    f"this CPU runs {bindings.openblas_core(orc)}")
+    return orc, ref, is_float
 
 
 def tol(is_float, t64, t32):
