@@ -399,16 +399,19 @@ constexpr int reg_waves(int tile_regs, int method)
     return 1;
 }
 // Register-tile engine (reg_eval.hpp) for rows of at most (64 / G) S nonzeros: no LDS at all, waves per CU set by VGPRs.
+// PG on floats keeps the tile step-interleaved (reg_eval.hpp, PAIR_); CG and TNCG keep the slot layout.
+template <class T, int METHOD, int G, int NS> constexpr bool reg_pairs() { return METHOD == K_PG && sizeof(T) == 4 && G == 16 && NS == 1; }
 template <class T, int METHOD, int S, int G, int NS>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(4 * S * NS, METHOD)))) void half_sweep_reg_kernel(const HalfArgs<T> a)
 {
-    RegEval<T, S, G, NS> ev;
-    constexpr int SMEM = RegEval<T, S, G, NS>::SMEM_BYTES;   // (only CG on doubles parks k-vectors here)
+    using EV = RegEval<T, S, G, NS, 1, 1, reg_pairs<T, METHOD, G, NS>()>;
+    EV ev;
+    constexpr int SMEM = EV::SMEM_BYTES;   // (only CG on doubles parks k-vectors here)
     __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM > 0 && METHOD == K_CG ? SMEM : 16];
 #ifdef PMF_TIMING
     const unsigned long long t_kernel = __builtin_amdgcn_s_memtime();
 #endif
-    sweep_rows<RegEval<T, S, G, NS>, T, RegEval<T, S, G, NS>::NC, METHOD, 1>(a, ev, smem);
+    sweep_rows<EV, T, EV::NC, METHOD, 1>(a, ev, smem);
 #ifdef PMF_TIMING
     if (ev.lane == 0) atomicAdd(&g_pmf_timing[5], __builtin_amdgcn_s_memtime() - t_kernel);
 #endif

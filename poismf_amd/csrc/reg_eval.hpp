@@ -154,11 +154,21 @@ __device__ __forceinline__ unsigned long long gran_load(const unsigned long long
 // slowest: it needs everybody's granules of exchange n before it can publish n + 1, and everybody publishes n only after
 // reading n - 1).  Teams form in arrival order per XCD (poismf_hip.hip, half_sweep_team_kernel), so a team's members are
 // resident by construction and a launch makes progress with any two workgroups of an XCD on the chip.
-template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> struct RegEval {
+//
+// PAIR_ (fp32, G = 16, NS = 1, one wave): the tile is kept STEP-INTERLEAVED, register pair (t[2i][e], t[2i+1][e]) instead
+// of the slot's (t[s][e], t[s][e+1]).  The two halves of a packed op then belong to two different nonzeros: the dots of a
+// step pair are one v_pk_mul + three v_pk_fma with a[e] broadcast to both halves (4 instructions instead of 2 x (pk_mul +
+// pk_fma + add)), and the axpy accumulates (sum over even steps, sum over odd steps) in register pairs from the coefficient
+// pair (c_2i, c_2i+1), its halves added once per evaluation.  The gather keeps one 16-byte load per step and swaps the
+// registers of a step pair into place once per row.
+template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, bool PAIR_ = false> struct RegEval {
     using SA = typename Slot<T>::A;
     using SU = typename Slot<T>::U;
     static constexpr int SN = Slot<T>::N;
     static constexpr int G = G_, NS = NS_;
+    static constexpr bool PAIRED = PAIR_;
+    static_assert(!PAIR_ || (SN == 4 && G_ == 16 && NS_ == 1 && NW_ == 1 && M_ == 1 && S % 2 == 0), "step pairs: fp32 one-wave tiles of whole pairs");
+    typedef T V2 __attribute__((ext_vector_type(2)));
     static constexpr int JG = WAVE / G;           // nonzeros per step
     static constexpr int NC = NS * SN;            // elements per lane
     static constexpr int NB = (S + G - 1) / G;    // batches of G steps = 64 nonzeros
@@ -181,7 +191,8 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
     static_assert(M_ == 1 || (sizeof(T) == 8 && NW_ > 1 && NS_ * Slot<T>::N <= WAVE / G_), "teams: doubles, one element per group to publish");
     static_assert(G == 8 || G == 16, "a factor row is held by 8 or 16 lanes");
 
-    SA t[S][NS];    // the tile
+    SA t[PAIRED ? 1 : S][NS];    // the tile
+    V2 tp[PAIRED ? S / 2 : 1][SN];  // PAIRED: the tile, tp[i][e] = (t[2 i][0].v[e], t[2 i + 1][0].v[e])
     T a[NC];        // current point (this lane's slots)
     T xr[NB];       // x_j of the nonzero whose pred this lane finishes in batch b: j = 64 b + JG g + jg
     unsigned idx_n[NB];  // column indices of the row whose tile is requested next, same layout (fetch_meta -> gather)
@@ -584,6 +595,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
         unsigned lane_off[NS];
 #pragma unroll
         for (int n = 0; n < NS; n++) lane_off[n] = slot_on[n] ? (unsigned)((g + G * n) * 16) : 0u;
+        SU raw[PAIRED ? S : 1];   // PAIRED: the loads land here, all in flight before the first is waited for
         static_for<0, S>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             // index of nonzero JG s + jg sits in lane s % G of group jg
@@ -592,10 +604,26 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
             for (int n = 0; n < NS; n++) {
                 const unsigned off = __umul24(slot_on[n] ? c : zero_row, rowbytes) + lane_off[n];
                 const SU v = *(const SU*)((const char*)F + (size_t)off);
+                if constexpr (PAIRED) raw[s] = v;
+                else {
 #pragma unroll
-                for (int e = 0; e < SN; e++) t[s][n].v[e] = v.v[e];
+                    for (int e = 0; e < SN; e++) t[s][n].v[e] = v.v[e];
+                }
             }
         });
+        if constexpr (PAIRED) {
+            // steps x = 2i, y = 2i + 1 land as (x0 x1 x2 x3) (y0 y1 y2 y3); two swaps, x1 <-> y0 and x3 <-> y2, leave the register
+            // pairs (x0 y0) (x1 y1) (x2 y2) (x3 y3) in place
+#pragma unroll
+            for (int i = 0; i < S / 2; i++) {
+                T x1 = raw[2 * i].v[1], y0 = raw[2 * i + 1].v[0], x3 = raw[2 * i].v[3], y2 = raw[2 * i + 1].v[2];
+                asm("v_swap_b32 %0, %1\n\tv_swap_b32 %2, %3" : "+v"(x1), "+v"(y0), "+v"(x3), "+v"(y2));
+                tp[i][0] = (V2){ raw[2 * i].v[0], x1 };
+                tp[i][1] = (V2){ y0, raw[2 * i + 1].v[1] };
+                tp[i][2] = (V2){ raw[2 * i].v[2], x3 };
+                tp[i][3] = (V2){ y2, raw[2 * i + 1].v[3] };
+            }
+        }
     }
     __device__ __forceinline__ void set_point(const T (&x)[NC])
     {
@@ -627,6 +655,21 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
             }
             return p;
         }
+    }
+
+    // PAIRED: this lane's shares of steps 2i and 2i + 1 (lo, hi) from the step pair w = tp[i]
+    __device__ __forceinline__ V2 lane_dot2(const V2 (&w)[SN]) const
+    {
+        V2 p = w[0] * (V2){ a[0], a[0] };
+#pragma unroll
+        for (int e = 1; e < SN; e++) p = __builtin_elementwise_fma(w[e], (V2){ a[e], a[e] }, p);
+        return p;
+    }
+    // element e of step s of the tile, either layout
+    __device__ __forceinline__ T tile_at(int s, int m, int e) const
+    {
+        if constexpr (PAIRED) return tp[s / 2][e][s % 2];
+        else return t[s][m].v[e];
     }
 
     // N (1..G) lane-partials p[u] -> lane g holds the sum over its group of p[g] (lanes g >= N: unspecified)
@@ -698,6 +741,9 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
         T part[NC];
 #pragma unroll
         for (int i = 0; i < NC; i++) part[i] = (T)0;
+        V2 part2[PAIRED ? SN : 1];   // PAIRED: (even steps, odd steps)
+#pragma unroll
+        for (int i = 0; i < (PAIRED ? SN : 1); i++) part2[i] = (V2){ (T)0, (T)0 };
         static_for<0, NB>([&](auto bc) {
             constexpr int b = decltype(bc)::value;
             constexpr int n = (S - G * b) < G ? (S - G * b) : G;
@@ -705,8 +751,17 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
             if constexpr (FROM_CACHE && CACHED) pred = pv[b];
             else {
                 T p[G];
+                if constexpr (PAIRED) {
 #pragma unroll
-                for (int u = 0; u < G; u++) p[u] = u < n ? lane_dot(t[(G * b + u) < S ? (G * b + u) : 0]) : (T)0;
+                    for (int i = 0; i < G / 2; i++) {
+                        const V2 q = 2 * i < n ? lane_dot2(tp[(G * b + 2 * i) < S ? (G * b) / 2 + i : 0]) : (V2){ (T)0, (T)0 };
+                        p[2 * i] = q.x;
+                        p[2 * i + 1] = q.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < G; u++) p[u] = u < n ? lane_dot(t[(G * b + u) < S ? (G * b + u) : 0]) : (T)0;
+                }
                 if constexpr (b == 0) PMF_STAMP(*this, 1);
                 pred = transpose_sum<n>(p);
                 if constexpr (b == 0) PMF_STAMP(*this, 2);
@@ -721,18 +776,32 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
             if constexpr (WANT_G) {
                 const T coef = on ? coef_div(sgn * xj, pred) : (T)0;
                 if constexpr (b == 0) PMF_STAMP(*this, 3);
-                static_for<0, n>([&](auto uc) {
-                    constexpr int u = decltype(uc)::value;
-                    const T c = group_bcast<G, u>(coef);
+                if constexpr (PAIRED) {
+                    static_for<0, n / 2>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        const V2 c = { group_bcast<G, 2 * i>(coef), group_bcast<G, 2 * i + 1>(coef) };
 #pragma unroll
-                    for (int m = 0; m < NS; m++) {
+                        for (int e = 0; e < SN; e++) part2[e] = __builtin_elementwise_fma(c, tp[(G * b) / 2 + i][e], part2[e]);
+                    });
+                } else {
+                    static_for<0, n>([&](auto uc) {
+                        constexpr int u = decltype(uc)::value;
+                        const T c = group_bcast<G, u>(coef);
 #pragma unroll
-                        for (int e = 0; e < SN; e++) part[m * SN + e] = fma_t(c, t[G * b + u][m].v[e], part[m * SN + e]);
-                    }
-                });
+                        for (int m = 0; m < NS; m++) {
+#pragma unroll
+                            for (int e = 0; e < SN; e++) part[m * SN + e] = fma_t(c, t[G * b + u][m].v[e], part[m * SN + e]);
+                        }
+                    });
+                }
                 if constexpr (b == 0) PMF_STAMP(*this, 4);
             }
         });
+        if constexpr (PAIRED && WANT_G) {
+            // (asm: left alone, the compiler pairs these four adds into two v_pk_add_f32 and needs six moves to line up their operands)
+#pragma unroll
+            for (int e = 0; e < SN; e++) asm("v_add_f32 %0, %1, %2" : "=v"(part[e]) : "v"(part2[e].x), "v"(part2[e].y));
+        }
         PMF_STAMP(*this, 5);
         if constexpr (NW > 1 && !WANT_F && !WANT_G) {
             return 0.0;   // (the cached line search's q = T.d pass: predictions only, nothing to add up)
@@ -850,7 +919,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
     __device__ __forceinline__ void tile_touch(T (&acc)[NC])
     {
 #pragma unroll
-        for (int s = 0; s < S; s++) acc[0] += t[s][0].v[0] + t[s][NS - 1].v[SN - 1];
+        for (int s = 0; s < S; s++) acc[0] += tile_at(s, 0, 0) + tile_at(s, NS - 1, SN - 1);
     }
 #endif
     // acc_c += sum_j F[ind_j, c]  (adjustment_Bsum's gather pass, ref: src/poismf.c:108-110)
@@ -864,7 +933,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1> str
 #pragma unroll
             for (int m = 0; m < NS; m++) {
 #pragma unroll
-                for (int e = 0; e < SN; e++) part[m * SN + e] += t[s][m].v[e];   // steps past the row's end hold zeros
+                for (int e = 0; e < SN; e++) part[m * SN + e] += tile_at(s, m, e);   // steps past the row's end hold zeros
             }
         }
         if constexpr (NW > 1) {
