@@ -124,6 +124,32 @@ POISMF_HIP_API int topN(
     size_t n_top, size_t n, int nthreads);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1e. Poisson log-likelihood of fitted factors (the reference declares eval_llk, ref: src/poismf.h:258-269, and
+ *     defines it nowhere -- SURVEY quirk Q12; this is the definition).
+ *
+ * For factors A [dimA x k], B [dimB x k] and cells (i, j, x) -- duplicate (i, j) summed first, as for a fit --
+ * with yhat_ij = sum_c A[i,c] B[j,c] (products and sums in double, in both precisions):
+ *
+ *     llk = sum_cells [ x log(yhat) - lgamma(x + 1) * full_llk ] - M
+ *     M   = sum_cells yhat                                 include_missing = false
+ *     M   = sum_c (sum_i A[i,c]) (sum_j B[j,c])             include_missing = true (every cell of the dimA x dimB
+ *                                                           matrix, a missing cell counting as x = 0)
+ *
+ * A cell with x = 0 contributes only -yhat (no log is taken); yhat = 0 with x > 0 gives -inf; NaN factors give NaN.
+ * The log is the row kernels' own (the one the solvers take).  This is a likelihood, not the solvers' objective: the
+ * l1 / l2 terms and w_mult play no part.  The result is deterministic (fp64 partials over fixed ranges of nonzeros,
+ * summed in a fixed order) and does not depend on the device's size.
+ *
+ * eval_llk: same name and arguments as the reference's declaration.  Host arrays; the triplets are converted to a CSR
+ * on the device as in section 1c (requires nnz < 2^32, dimA and dimB < 2^31, 1 <= k <= 512).  `nthreads` is accepted and
+ * ignored.  On an invalid index or argument, or a device error, it prints to stderr and returns NaN.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API long double eval_llk(
+    real_t *A, real_t *B, sparse_ix ixA[], sparse_ix ixB[], real_t *X,
+    size_t nnz, int k, bool full_llk, bool include_missing,
+    size_t dimA, size_t dimB, int nthreads);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -251,6 +277,13 @@ POISMF_HIP_API int poismf_hip_session_predict(poismf_hip_session *s, const spars
 POISMF_HIP_API int poismf_hip_session_topn(poismf_hip_session *s, size_t user,
                           const sparse_ix *include_ix, size_t n_include, const sparse_ix *exclude_ix, size_t n_exclude,
                           sparse_ix *outp_ix, real_t *outp_score, size_t n_top);
+
+/* The log-likelihood of section 1e for the session's resident CSR shard (rows [rowA_begin,rowA_end) of A) under its resident
+ * factors; with include_missing, M covers the shard's rows of A times all of B.  No factor or matrix is copied: one double
+ * comes back in *out.  Ordered after the work already enqueued on the session stream; reads the compact factors, so writes
+ * through poismf_hip_session_A/B are seen whether or not factors_dirty was called yet.  On a single-GPU session the result has
+ * the same bits as eval_llk on the same matrix and factors.  Returns 0, or 1 on a device error. */
+POISMF_HIP_API int poismf_hip_session_llk(poismf_hip_session *s, int full_llk, int include_missing, double *out);
 
 /* Which row-kernel instances the most recent half-sweep of half `which` launched, as text ("kernel<instance> rows=N;"
  * per launch), NUL-terminated and truncated to cap bytes; returns the untruncated length.  Reporting only. */

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
-    "poismf_hip_session_partials_ready",
+    "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk",
 )
 
 
@@ -119,6 +119,10 @@ def load_library(use_float):
     lib.poismf_hip_half_sweep_segment.restype = i
     lib.poismf_hip_session_predict.argtypes = [vp, vp, vp, sz, vp]
     lib.poismf_hip_session_predict.restype = i
+    lib.eval_llk.argtypes = [vp] * 5 + [sz, i, C.c_bool, C.c_bool, sz, sz, i]
+    lib.eval_llk.restype = C.c_longdouble
+    lib.poismf_hip_session_llk.argtypes = [vp, i, i, C.POINTER(C.c_double)]
+    lib.poismf_hip_session_llk.restype = i
     lib.poismf_hip_session_topn.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, sz]
     lib.poismf_hip_session_topn.restype = i
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
@@ -379,6 +383,25 @@ class PoisMF:
         self.is_fitted = True
         return self
 
+    def eval_llk(self, X, full_llk=False, include_missing=False):
+        """Poisson log-likelihood of the fitted factors on the cells of X (include/poismf_hip.h section 1e; the reference
+        declares eval_llk in src/poismf.h:258-269 and defines it nowhere).  X: a SciPy sparse matrix or synth.Triplets whose
+        rows and columns index this model's users and items; duplicate cells are summed.  full_llk adds the -lgamma(x + 1)
+        terms; include_missing counts every cell of the users x items matrix, a missing one as x = 0.  No regularisation."""
+        if not self.is_fitted:
+            raise ValueError("Model has not been fitted.")
+        import scipy.sparse as sp
+        coo = sp.coo_matrix(X) if sp.issparse(X) else X
+        row, col, val = _coo_arrays(coo, self.use_float)
+        if len(val) and (int(row.max()) >= self.nusers or int(col.max()) >= self.nitems):
+            raise IndexError("a row / column index of X lies outside the fitted model's users / items")
+        dt = np.float32 if self.use_float else np.float64
+        A = np.ascontiguousarray(self.A, dtype=dt)
+        B = np.ascontiguousarray(self.B, dtype=dt)
+        lib = load_library(self.use_float)
+        return float(lib.eval_llk(_ptr(A), _ptr(B), _ptr(row), _ptr(col), _ptr(val), len(val), self.k, bool(full_llk),
+                                  bool(include_missing), self.nusers, self.nitems, self.nthreads_))
+
     def _fit(self, csr, csc):                                                        # ref: __init__.py:427-439
         _run_poismf(csr[0], csr[1], csr[2], csc[0], csc[1], csc[2], self.A, self.B, self.method,
                     self.limit_step, self.l2_reg_, self.l1_reg_, self.weight_mult, self.initial_step,
@@ -540,6 +563,14 @@ class Session:
     def run(self, params, niter, handle_interrupt=True):
         """run_poismf's whole loop on this session (return codes 0 / 1 / 2 as run_poismf)"""
         return self.lib.poismf_hip_session_run(self.h, C.byref(params), int(niter), int(bool(handle_interrupt)))
+
+    def llk(self, full_llk=False, include_missing=False):
+        """Poisson log-likelihood of this session's CSR shard under its resident factors (include/poismf_hip.h section 1e): the
+        same bits as PoisMF.eval_llk / eval_llk on the same matrix and factors for a single-GPU session"""
+        out = C.c_double(0)
+        if self.lib.poismf_hip_session_llk(self.h, int(bool(full_llk)), int(bool(include_missing)), C.byref(out)):
+            raise RuntimeError("poismf_hip_session_llk failed")
+        return out.value
 
     def stream(self):
         """the hipStream_t this session enqueues on, as an integer handle"""

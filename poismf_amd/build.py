@@ -4,7 +4,7 @@
 
 Six translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
 PG, CG and TNCG are the bulk of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the
-rocPRIM-based COO conversion and the serving kernels -- are compiled to object files side by side and linked.  Every object and
+rocPRIM-based COO conversion, the serving kernels and the likelihood (llk.hip) -- are compiled to object files side by side and linked.  Every object and
 library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
 digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full
 build takes ~2 minutes on 8 cores.
@@ -30,6 +30,7 @@ UNITS = {
     "poismf_hip_eval": (_ROW, ["-DPMF_TU=4"]),   # evaluation-only kernels behind poismf_hip_debug_row_eval (testing aid)
     "coo_convert": (["coo_convert.hip", "devmem.hpp"], []),
     "serve": (["serve.hip", "devmem.hpp"], []),
+    "llk": (["llk.hip", "devmem.hpp", "wave_ops.hpp"], []),
 }
 
 
@@ -85,7 +86,7 @@ def _units():
     """The -DPMF_TIMING development build keeps its phase timers in one device-side array, so it stays one translation unit."""
     if "-DPMF_TIMING" in os.environ.get("POISMF_HIP_EXTRA_FLAGS", "").split():
         return {"poismf_hip_host": UNITS["poismf_hip_host"], "poismf_hip_all": (_ROW, []), "coo_convert": UNITS["coo_convert"],
-                "serve": UNITS["serve"]}
+                "serve": UNITS["serve"], "llk": UNITS["llk"]}
     return UNITS
 
 

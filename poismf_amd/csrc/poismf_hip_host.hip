@@ -176,6 +176,11 @@ int poismf_hip_serve_predict(const real_t* dA, const real_t* dB, const sparse_ix
 int poismf_hip_serve_topn(const real_t* d_a, const real_t* dB, int k, const sparse_ix* include_ix, size_t n_include,
                           const sparse_ix* exclude_ix, size_t n_exclude, sparse_ix* outp_ix, real_t* outp_score, size_t n_top, size_t n);
 int poismf_hip_serve_topn_check(const sparse_ix*& include_ix, size_t n_include, const sparse_ix*& exclude_ix, size_t n_exclude, size_t n_top, size_t n);
+// llk.hip (the likelihood on device-resident data)
+size_t poismf_hip_llk_scratch(size_t nrows, size_t dimB, size_t k, size_t nnz);
+int poismf_hip_llk_enqueue(const real_t* A, const real_t* B, size_t nrows, size_t dimB, size_t k, const unsigned long long* indptr,
+                           const unsigned* col, const real_t* val, size_t nnz, int full_llk, int include_missing, double* scratch,
+                           hipStream_t stream);
 // coo_convert.hip (rocPRIM-based helpers)
 int poismf_hip_device_sort_rows(const unsigned long long* d_indptr, size_t nloc, unsigned base, unsigned* d_perm, unsigned* d_len_sorted,
                                 hipStream_t stream);
@@ -264,6 +269,8 @@ struct poismf_hip_session {
     std::vector<ProfRec> prof;
     std::vector<LaunchRec> lprof;
     std::string last_plan[2];         // the launches of the most recent half-sweep of each half, as text
+    double* d_llk = nullptr;          // scratch of poismf_hip_session_llk (allocated by its first call)
+    size_t llk_cap = 0;               // ... in doubles
 };
 
 namespace {
@@ -831,6 +838,7 @@ void poismf_hip_session_destroy(poismf_hip_session* s)
     pmf_free(s->d_arrive, s->stream);
     pmf_free(s->d_team_backup, s->stream);
     pmf_free(s->d_team_eval_backup, s->stream);
+    pmf_free(s->d_llk, s->stream);
     (void)hipStreamSynchronize(s->stream);   // the stream-ordered frees have run
     if (aux) release_stream(s->device, aux);
     if (own) release_stream(s->device, own);
@@ -1573,6 +1581,28 @@ int poismf_hip_session_predict(poismf_hip_session* s, const sparse_ix* ixA, cons
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return poismf_hip_serve_predict(s->dA, s->dB, ixA, ixB, n, (int)s->k, out, nullptr, nullptr);
+}
+
+// Poisson log-likelihood of the resident CSR shard under the resident (compact) factors -- the padded gather copies play no part,
+// so no write through the factor pointers can leave a stale value behind.  Ordered after everything enqueued on the session stream.
+int poismf_hip_session_llk(poismf_hip_session* s, int full_llk, int include_missing, double* out)
+{
+    HIP_TRY(hipSetDevice(s->device));
+    const Half& h = s->half[1];
+    const size_t nrows = h.row_end - h.row_begin;
+    const size_t need = poismf_hip_llk_scratch(nrows, s->dimB, s->k, h.nnz);
+    if (s->llk_cap < need) {
+        pmf_free(s->d_llk, s->stream);
+        s->d_llk = nullptr;
+        s->llk_cap = 0;
+        HIP_TRY(pmf_alloc(&s->d_llk, need * sizeof(double), s->stream));
+        s->llk_cap = need;
+    }
+    if (poismf_hip_llk_enqueue(s->dA + h.row_begin * s->k, s->dB, nrows, s->dimB, s->k, h.d_indptr, h.d_indices, h.d_values, h.nnz,
+                               full_llk, include_missing, s->d_llk, s->stream))
+        return 1;
+    HIP_TRY(pmf_download(out, s->d_llk, sizeof(double), s->stream));
+    return 0;
 }
 
 int poismf_hip_session_topn(poismf_hip_session* s, size_t user, const sparse_ix* include_ix, size_t n_include, const sparse_ix* exclude_ix,
