@@ -80,6 +80,17 @@ constexpr int POISMF_EVAL = 4;
 // One row of the sorted order: where its nonzeros start in the shard's CSR arrays, how many, and which row it is.
 struct RowDesc { unsigned p0_lo, p0_hi, nnz, lrow; };
 
+// A lane-engine instance (lane_eval.hpp, lane_shape_for below).  lv / la / ll: lane sets per wave in architectural registers / accumulator
+// registers / LDS; waves: per row; small: the two-waves-per-SIMD flavour (a few KB of LDS per wave); lp: nonzeros of a further, partial LDS
+// set; tx: rows of the LDS image the gradient is accumulated from (lane_eval.hpp, TX_)
+struct LaneShape {
+    int lv, la, ll, waves; int small; int lp = 0; int tx = 0;
+    bool operator==(const LaneShape& o) const
+    {
+        return lv == o.lv && la == o.la && ll == o.ll && waves == o.waves && small == o.small && lp == o.lp && tx == o.tx;
+    }
+};
+
 namespace {
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
@@ -135,20 +146,14 @@ unsigned regw_wave_nnz_max(int method)
     return (unsigned)(method == POISMF_PG ? REGW_WAVE_NNZ_MAX_PG : method == POISMF_CG ? REGW_WAVE_NNZ_MAX_CG : REGW_WAVE_NNZ_MAX_TNCG);
 }
 unsigned regw_nnz_max(int method) { return (unsigned)REG_NW_MAX * regw_wave_nnz_max(method); }
-// Sixteen waves per row (one 1024-thread workgroup, four waves per SIMD, <= 128 registers each: shares of <= 64
-// nonzeros) for rows of 513 .. 1024 nonzeros: measured and NOT adopted (-DPMF_REGW16=1 builds it).  One such row occupies
-// a CU either way and a SIMD gets four instruction streams instead of two, but the per-pass fixed work of a wave (point
-// update, group combine, reading 16 partial gradients, a 16-wave barrier) is paid twice as often: C4 matrix, PG(10), B half
-// 7.9 ms with eight waves per row, 13.9 ms with sixteen.
-#ifndef PMF_REGW16
-#define PMF_REGW16 0
-#endif
-constexpr int REGW16_WAVE_NNZ = 64;
-inline bool regw16_method(int method) { return PMF_REGW16 && method == POISMF_PG; }
-// the fewest waves (2, 4, 8) whose shares of a row of max_nnz nonzeros fit; 16 where that pays (see above)
+// (Sixteen waves per row -- one 1024-thread workgroup, four waves per SIMD, shares of <= 64 nonzeros -- for rows of 513 .. 1024
+// nonzeros was measured and NOT adopted; its build switch is gone.  One such row occupies a CU either way and a SIMD
+// gets four instruction streams instead of two, but the per-pass fixed work of a wave (point update, group combine, reading 16
+// partial gradients, a 16-wave barrier) is paid twice as often: C4 matrix, PG(10), B half 7.9 ms with eight waves per row, 13.9 ms
+// with sixteen.)
+// the fewest waves (2, 4, 8) whose shares of a row of max_nnz nonzeros fit
 int regw_waves_for(unsigned max_nnz, int method)
 {
-    if (regw16_method(method) && max_nnz > 8u * REGW16_WAVE_NNZ && max_nnz <= 16u * REGW16_WAVE_NNZ) return 16;
     for (int nw : { 2, 4, 8 })
         if (max_nnz <= (unsigned)nw * regw_wave_nnz_max(method)) return nw;
     return 0;
@@ -181,9 +186,6 @@ inline TeamShape team_shape_for(unsigned max_nnz)
 // shortest rows) and of 13 slots in floats (k = 49..52).  Lane sets (64 nonzeros each) per wave -- in architectural registers,
 // in accumulator registers, in LDS -- and waves per row for rows of a length class; waves 0 = not a row of this engine.
 // A function of the class bound (and the solver) alone, so a row's arithmetic does not depend on its shard.
-// lv / la / ll: lane sets per wave in architectural registers / accumulator registers / LDS; waves: per row; small: the two-waves-per-SIMD flavour (a few KB
-// of LDS per wave); lp: nonzeros of a further, partial LDS set; tx: rows of the LDS image the gradient is accumulated from (lane_eval.hpp, TX_)
-struct LaneShape { int lv, la, ll, waves; int small; int lp = 0; int tx = 0; };
 inline LaneShape lane_shape_for(unsigned cls, int s_load, int method)
 {
     if (sizeof(real_t) == 8) {
@@ -255,16 +257,26 @@ int slots_per_lane(size_t k)
 
 }  // namespace
 
+// The kernel family of a launch.  The planner (poismf_hip_host.hip, plan_half) picks one per row bin; launch_one_here dispatches on it
+// first, then on the solver and the instance.
+enum class Engine {
+    Reg,        // half_sweep_reg_kernel: one wave per row, the tile in registers (reg_eval.hpp)
+    RegW,       // half_sweep_regw_kernel: 2 / 4 / 8 waves per row, each its share of the tile in registers
+    RegTeam,    // half_sweep_team_kernel: one row over the registers of `team` CUs (reg_eval.hpp, M_ > 1)
+    Lane,       // half_sweep_lane_kernel: a lane per nonzero (lane_eval.hpp), `lane` names the instance
+    LaneTeam,   // half_sweep_lane_team_kernel: one row resident over `team` four-wave workgroups (lane_eval.hpp, TM_)
+    Lds,        // half_sweep_kernel, one wave per row: the tile in LDS, resident or streamed (row_eval.hpp)
+    LdsLong,    // half_sweep_kernel, LONG_NW waves per row, streamed
+    Giant,      // half_sweep_giant_kernel: one streamed row over a team of GT_M eight-wave workgroups (row_eval.hpp, TM)
+};
+
 // One row-bin launch: everything the planner decided, minus the solver (which selects the translation unit).
 struct OneLaunch {
-    int reg_S, nw, s_load, spl;   // register-engine steps (0: LDS engine), waves per row, slots per factor row, slots per lane
-    int team;                     // > 1: CUs per row (team launch)
-    int lane_LP;                  // lane engine: nonzeros of the partial LDS set per wave
-    int lane_small;               // lane engine: the two-waves-per-SIMD flavour (lane_eval.hpp, SMALL_)
-    int lane_tx;                  // lane engine: rows of the LDS image of the tile (lane_eval.hpp, TX_)
-    int lane_L, lane_A, lane_LL;  // lane_L > 0: lane-per-nonzero engine with this many lane sets per wave in VGPRs, AGPRs, LDS (nw waves per row)
-    bool generic_only;
-    hipStream_t main_stream, bin_stream, long_stream;
+    Engine engine;
+    int reg_S, nw, s_load, spl;   // register-engine steps, waves per row, slots per factor row, slots per lane
+    int team;                     // > 1: CUs per row (RegTeam, LaneTeam, Giant)
+    LaneShape lane;               // Lane, LaneTeam
+    hipStream_t stream;
     size_t lds;
     unsigned grid, grid_mult;
     int device, num_cu;

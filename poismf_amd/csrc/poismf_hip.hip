@@ -11,6 +11,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "plan.hpp"
 #include "reg_eval.hpp"
@@ -754,10 +755,10 @@ template <int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL = false
     } else return 1;
 }
 // lane teams: k = 100 fp64 TNCG rows of 385 .. 8192 nonzeros, M = a.team_members four-wave workgroups per row
-int launch_lane_team(hipStream_t stream, int method, int s_load, int lv, int la, int ll, int nw, int lp, const HalfArgs<real_t>& a, unsigned grid)
+int launch_lane_team(hipStream_t stream, int method, int s_load, const LaneShape& l, const HalfArgs<real_t>& a, unsigned grid)
 {
     if constexpr (tu_has(K_TNCG) && sizeof(real_t) == 8) {
-        if (method == POISMF_TNCG && s_load == 50 && lv == 1 && la == 0 && ll == 0 && nw == 4 && lp == 32) {
+        if (method == POISMF_TNCG && s_load == 50 && l.lv == 1 && l.la == 0 && l.ll == 0 && l.waves == 4 && l.lp == 32) {
             hipLaunchKernelGGL((half_sweep_lane_team_kernel<real_t, K_TNCG, 50, 1, 0, 0, 4, 32>), dim3(grid), dim3(WAVE * 4), 0, stream, a);
             HIP_TRY(hipGetLastError());
             return 0;
@@ -765,9 +766,10 @@ int launch_lane_team(hipStream_t stream, int method, int s_load, int lv, int la,
     }
     return 1;
 }
-template <int METHOD> int launch_lane_shape(hipStream_t stream, int s_load, int lv, int la, int ll, int nw, int small, int lp, int tx, const HalfArgs<real_t>& a, unsigned grid_mult)
+template <int METHOD> int launch_lane_shape(hipStream_t stream, int s_load, const LaneShape& l, const HalfArgs<real_t>& a, unsigned grid_mult)
 {
-    const int key = (((lv * 10 + la) * 10 + ll) * 10 + nw) * 10 + small + (lp > 0 ? 100000 : 0);
+    const int lp = l.lp, tx = l.tx;
+    const int key = (((l.lv * 10 + l.la) * 10 + l.ll) * 10 + l.waves) * 10 + l.small + (lp > 0 ? 100000 : 0);
     if constexpr (sizeof(real_t) == 8) {
         if constexpr (METHOD == K_PG) return 1;
         else if (s_load == 25) {
@@ -817,19 +819,18 @@ template <int METHOD> int launch_lane_shape(hipStream_t stream, int s_load, int 
 template <int S, int NS, int NW> int launch_regw_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
 {
     if constexpr (S * REG_JG < 32) return 1;
-    else if constexpr (NW == 16 && (S * REG_JG > REGW16_WAVE_NNZ || NS != 1)) return 1;
     else switch (method) {
         case POISMF_PG:
             if constexpr (tu_has(K_PG)) return launch_regw<K_PG, S, NS, NW>(stream, a, grid_mult);
             else return 1;
         case POISMF_CG:
-            if constexpr (tu_has(K_CG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG && NW <= 8) return launch_regw<K_CG, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_CG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG) return launch_regw<K_CG, S, NS, NW>(stream, a, grid_mult);
             else return 1;
         case POISMF_EVAL:
-            if constexpr (tu_has(K_EVAL) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG && NW <= 8) return launch_regw<K_EVAL, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_EVAL) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG) return launch_regw<K_EVAL, S, NS, NW>(stream, a, grid_mult);
             else return 1;
         default:
-            if constexpr (tu_has(K_TNCG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_TNCG && NW <= 8) return launch_regw<K_TNCG, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_TNCG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_TNCG) return launch_regw<K_TNCG, S, NS, NW>(stream, a, grid_mult);
             else return 1;
     }
 }
@@ -849,9 +850,6 @@ template <int NS> int launch_regw_steps(hipStream_t stream, int nw, int S, int m
         case 2: return launch_regw_steps_nw<NS, 2>(stream, S, method, a, grid_mult);
         case 4: return launch_regw_steps_nw<NS, 4>(stream, S, method, a, grid_mult);
         case 8: return launch_regw_steps_nw<NS, 8>(stream, S, method, a, grid_mult);
-        case 16:
-            if constexpr (PMF_REGW16) return launch_regw_steps_nw<NS, 16>(stream, S, method, a, grid_mult);
-            else return 1;
     }
     return 1;
 }
@@ -867,66 +865,60 @@ template <int NS> int launch_reg_steps(hipStream_t stream, int S, int method, co
 }
 
 
+// The BASELINE configs' slot counts have instances of their own (the LDS engine prefetches the next chunk only in those); every other k takes
+// the generic ones, by slots per lane (tests/test_gpu_regtile.py).  f(NC, SL) launches the instance.
+template <class F> int with_slots(const OneLaunch& o, F f)
+{
+    using std::integral_constant;
+    if (o.s_load == SPECIAL_SL_A) return f(integral_constant<int, SLOT_ELEMS>{}, integral_constant<int, SPECIAL_SL_A>{});
+    if (o.s_load == SPECIAL_SL_B) return f(integral_constant<int, SLOT_ELEMS>{}, integral_constant<int, SPECIAL_SL_B>{});
+    switch (o.spl) {
+        case 1: return f(integral_constant<int, 1 * SLOT_ELEMS>{}, integral_constant<int, 0>{});
+        case 2: return f(integral_constant<int, 2 * SLOT_ELEMS>{}, integral_constant<int, 0>{});
+    }
+    return 1;
+}
+
 int launch_one_here(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
 {
-    int rc = 1;
     t_device = o.device; t_num_cu = o.num_cu;
-    if (o.lane_L > 0) {
-        if (o.team > 1) return launch_lane_team(o.main_stream, method, o.s_load, o.lane_L, o.lane_A, o.lane_LL, o.nw, o.lane_LP, a, o.grid);
-        if (method == POISMF_PG) return launch_lane_shape<K_PG>(o.main_stream, o.s_load, o.lane_L, o.lane_A, o.lane_LL, o.nw, o.lane_small, o.lane_LP, o.lane_tx, a, o.grid_mult);
-        if (method == POISMF_CG) return launch_lane_shape<K_CG>(o.nw > 1 ? o.main_stream : o.bin_stream, o.s_load, o.lane_L, o.lane_A, o.lane_LL, o.nw, o.lane_small, o.lane_LP, o.lane_tx, a, o.grid_mult);
-        if (method == POISMF_TNCG) return launch_lane_shape<K_TNCG>(o.nw > 1 ? o.main_stream : o.bin_stream, o.s_load, o.lane_L, o.lane_A, o.lane_LL, o.nw, o.lane_small, o.lane_LP, o.lane_tx, a, o.grid_mult);
-        if (method == POISMF_EVAL) return launch_lane_shape<K_EVAL>(o.nw > 1 ? o.main_stream : o.bin_stream, o.s_load, o.lane_L, o.lane_A, o.lane_LL, o.nw, o.lane_small, o.lane_LP, o.lane_tx, a, o.grid_mult);
-        return 1;
-    }
-#ifdef PMF_LANE_ONLY   // development: compile the lane-per-nonzero kernels alone (seconds instead of minutes)
-    return rc;
+    const hipStream_t st = o.stream;
+    switch (o.engine) {
+        case Engine::LaneTeam: return launch_lane_team(st, method, o.s_load, o.lane, a, o.grid);
+        case Engine::Lane:
+            switch (method) {
+                case POISMF_PG: return launch_lane_shape<K_PG>(st, o.s_load, o.lane, a, o.grid_mult);
+                case POISMF_CG: return launch_lane_shape<K_CG>(st, o.s_load, o.lane, a, o.grid_mult);
+                case POISMF_TNCG: return launch_lane_shape<K_TNCG>(st, o.s_load, o.lane, a, o.grid_mult);
+                case POISMF_EVAL: return launch_lane_shape<K_EVAL>(st, o.s_load, o.lane, a, o.grid_mult);
+            }
+            return 1;
+#ifndef PMF_LANE_ONLY   // (development: compile the lane-per-nonzero kernels alone, seconds instead of minutes)
+        case Engine::RegTeam:
+            if (o.team == 2 && o.reg_S == 32) return launch_team<2, 32>(st, method, a);
+            if (o.team == 2 && o.reg_S == 36) return launch_team<2, 36>(st, method, a);
+            if (o.team == 3 && o.reg_S == 28) return launch_team<3, 28>(st, method, a);
+            if (o.team == 3 && o.reg_S == 32) return launch_team<3, 32>(st, method, a);
+            if (o.team == 4 && o.reg_S == 32) return launch_team<4, 32>(st, method, a);
+            return 1;
+        case Engine::Reg:
+            if constexpr (REG_NS_MAX == 1) return launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult);
+            else return o.s_load <= REG_G ? launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult) : launch_reg_steps<2>(st, o.reg_S, method, a, o.grid_mult);
+        case Engine::RegW:
+            if constexpr (REG_G == 16) return launch_regw_steps<1>(st, o.nw, o.reg_S, method, a, o.grid_mult);
+            else return o.s_load <= REG_G ? launch_regw_steps<1>(st, o.nw, o.reg_S, method, a, o.grid_mult)
+                                          : launch_regw_steps<2>(st, o.nw, o.reg_S, method, a, o.grid_mult);
+        case Engine::Giant:
+            return with_slots(o, [&](auto nc, auto sl) { return launch_giant_method<decltype(nc)::value, decltype(sl)::value>(st, method, a, o.lds, o.grid); });
+        case Engine::LdsLong:
+            return with_slots(o, [&](auto nc, auto sl) { return launch_method<decltype(nc)::value, decltype(sl)::value, LONG_NW>(st, method, a, o.lds, o.grid); });
+        case Engine::Lds:
+            return with_slots(o, [&](auto nc, auto sl) { return launch_method<decltype(nc)::value, decltype(sl)::value>(st, method, a, o.lds, o.grid); });
 #else
-    if (o.team > 1 && o.team != GT_M) {
-        if (o.team == 2 && o.reg_S == 32) return launch_team<2, 32>(o.main_stream, method, a);
-        if (o.team == 2 && o.reg_S == 36) return launch_team<2, 36>(o.main_stream, method, a);
-        if (o.team == 3 && o.reg_S == 28) return launch_team<3, 28>(o.main_stream, method, a);
-        if (o.team == 3 && o.reg_S == 32) return launch_team<3, 32>(o.main_stream, method, a);
-        if (o.team == 4 && o.reg_S == 32) return launch_team<4, 32>(o.main_stream, method, a);
-        return 1;
-    }
-    if (o.reg_S > 0) {
-        if (o.nw > 1) {
-            if constexpr (REG_G == 16) rc = launch_regw_steps<1>(o.main_stream, o.nw, o.reg_S, method, a, o.grid_mult);
-            else rc = o.s_load <= REG_G ? launch_regw_steps<1>(o.main_stream, o.nw, o.reg_S, method, a, o.grid_mult)
-                                        : launch_regw_steps<2>(o.main_stream, o.nw, o.reg_S, method, a, o.grid_mult);
-        } else if constexpr (REG_NS_MAX == 1) rc = launch_reg_steps<1>(o.bin_stream, o.reg_S, method, a, o.grid_mult);
-        else rc = o.s_load <= REG_G ? launch_reg_steps<1>(o.bin_stream, o.reg_S, method, a, o.grid_mult)
-                                    : launch_reg_steps<2>(o.bin_stream, o.reg_S, method, a, o.grid_mult);
-        return rc;
-    }
-    if (o.nw > 1 && o.team == GT_M) {   // giant-row teams (row_eval.hpp, TM)
-        if (!o.generic_only && o.s_load == SPECIAL_SL_A) return launch_giant_method<SLOT_ELEMS, SPECIAL_SL_A>(o.long_stream, method, a, o.lds, o.grid);
-        if (!o.generic_only && o.s_load == SPECIAL_SL_B) return launch_giant_method<SLOT_ELEMS, SPECIAL_SL_B>(o.long_stream, method, a, o.lds, o.grid);
-        switch (o.spl) {
-            case 1: return launch_giant_method<1 * SLOT_ELEMS, 0>(o.long_stream, method, a, o.lds, o.grid);
-            case 2: return launch_giant_method<2 * SLOT_ELEMS, 0>(o.long_stream, method, a, o.lds, o.grid);
-        }
-        return 1;
-    }
-    if (o.nw > 1) {
-        // (the long-row path takes the compile-time slot counts of the BASELINE configs too, and with them the prefetch of the next chunk)
-        if (!o.generic_only && o.s_load == SPECIAL_SL_A) rc = launch_method<SLOT_ELEMS, SPECIAL_SL_A, LONG_NW>(o.long_stream, method, a, o.lds, o.grid);
-        else if (!o.generic_only && o.s_load == SPECIAL_SL_B) rc = launch_method<SLOT_ELEMS, SPECIAL_SL_B, LONG_NW>(o.long_stream, method, a, o.lds, o.grid);
-        else switch (o.spl) {
-            case 1: rc = launch_method<1 * SLOT_ELEMS, 0, LONG_NW>(o.long_stream, method, a, o.lds, o.grid); break;
-            case 2: rc = launch_method<2 * SLOT_ELEMS, 0, LONG_NW>(o.long_stream, method, a, o.lds, o.grid); break;
-        }
-        return rc;
-    }
-    if (!o.generic_only && o.s_load == SPECIAL_SL_A) rc = launch_method<SLOT_ELEMS, SPECIAL_SL_A>(o.bin_stream, method, a, o.lds, o.grid);
-    else if (!o.generic_only && o.s_load == SPECIAL_SL_B) rc = launch_method<SLOT_ELEMS, SPECIAL_SL_B>(o.bin_stream, method, a, o.lds, o.grid);
-    else switch (o.spl) {
-        case 1: rc = launch_method<1 * SLOT_ELEMS, 0>(o.bin_stream, method, a, o.lds, o.grid); break;
-        case 2: rc = launch_method<2 * SLOT_ELEMS, 0>(o.bin_stream, method, a, o.lds, o.grid); break;
-    }
-    return rc;
+        default: return 1;
 #endif
+    }
+    return 1;
 }
 }  // namespace
 

@@ -253,7 +253,7 @@ struct poismf_hip_session {
     unsigned long long* d_team = nullptr;   // team launches (plan.hpp, TEAM_*): allocated by the first one
     unsigned long long* d_gt = nullptr;     // giant-row and lane-team launches (row_eval.hpp, GT_*): one GT_BUF_BYTES area PER LAUNCH of a half, zeroed together before the first
     size_t gt_areas = 0, team_areas = 0;    // areas d_gt / d_team hold
-    unsigned* d_arrive = nullptr;           // workgroups of the forked long-row launch that have started (half_sweep_impl)
+    unsigned* d_arrive = nullptr;           // workgroups of the forked long-row launches that have started (issue_half)
     unsigned long long gate_budget = 200000;   // ticks of the wall clock the hold-back gate waits at most: 2 ms (session_alloc)
     unsigned* d_team_err = nullptr;         // TEAM_ERR_WORDS words (above): give-ups so far, and an error word and a tally per team launch of the current half
     real_t* d_team_backup = nullptr;        // the rows the team launches of a half start from, launch after launch (restored before a re-run)
@@ -621,6 +621,487 @@ int colsum(poismf_hip_session* s, const real_t* M, size_t n, real_t l1, real_t s
         case 8: return launch_colsum<8>(s, M, n, l1, scale, nscale);
     }
     return 1;
+}
+
+// ---- a half-sweep: prologue, plan, team preparation, issue, epilogue ------------------------------------------------
+// The planner's run-time knobs (testing knobs), read once per process on first use.
+struct PlanKnobs {
+    bool no_reg, no_team, static_rows, no_lane, no_lane_teams, no_giant_teams, no_fork, no_ls_prune;
+    bool longrow_set;   // POISMF_HIP_LONGROW_NNZ was given: then it also holds for TNCG's streamed rows (plan_half)
+    unsigned longrow_nnz, giant_nnz, team_spin;
+};
+const PlanKnobs& plan_knobs()
+{
+    static const PlanKnobs kn = [] {
+        PlanKnobs k{};
+        k.no_reg = getenv("POISMF_HIP_NO_REGTILE") != nullptr;   // (the LDS engine for every row)
+        k.no_team = getenv("POISMF_HIP_NO_TEAM") != nullptr; k.static_rows = getenv("POISMF_HIP_STATIC_ROWS") != nullptr;
+        k.no_lane = getenv("POISMF_HIP_NO_LANE") != nullptr; k.no_lane_teams = getenv("POISMF_HIP_NO_LANE_TEAMS") != nullptr;
+        k.no_giant_teams = getenv("POISMF_HIP_NO_GIANT_TEAMS") != nullptr; k.no_fork = getenv("POISMF_HIP_NO_FORK") != nullptr;
+        k.no_ls_prune = getenv("POISMF_HIP_NO_LS_PRUNE") != nullptr;   // (evaluate every line-search trial)
+        const char* e = getenv("POISMF_HIP_LONGROW_NNZ");             // (a huge value: no eight-wave rows at all)
+        k.longrow_set = e != nullptr;
+        k.longrow_nnz = e != nullptr ? (unsigned)std::max(64, atoi(e)) : LONG_ROW_NNZ;
+        e = getenv("POISMF_HIP_GIANT_NNZ");
+        k.giant_nnz = e != nullptr ? (unsigned)std::max(64, atoi(e)) : LONG_ROW_NNZ;
+        e = getenv("POISMF_HIP_TEAM_SPIN_LIMIT");
+        k.team_spin = e != nullptr ? (unsigned)std::max(1, atoi(e)) : TEAM_SPIN_LIMIT;
+        return k;
+    }();
+    return kn;
+}
+
+// What plan_half decides from besides the bins: factor dimension, rows and row stride of the gathered factor; the solver as planned (POISMF_EVAL
+// plans like CG), PG with one pass over each row, limit_step; poismf_hip_session::teams_off; CUs.
+struct PlanCtx { size_t k, dimF, ldF; int pm; bool single_pass, limit_step, teams_off; int num_cu; };
+
+// A launch as planned: what launch_one_here needs, plus the rows it covers and their tile geometry.  The issue loop fills in the stream,
+// grid and LDS.
+struct PlannedLaunch : OneLaunch {
+    unsigned begin, count;      // range of the nnz-sorted permutation
+    unsigned long long nnz;
+    TileGeom geom;
+};
+
+// A team launch's share of the session's team buffers (prepare_teams), in launch order.
+struct TeamSlot { size_t backup_at, eval_at; int area; };
+// What a team launch becomes if it gives up: its rows on the streamed LDS kernel, gated on its error word, issued after the join.
+struct TeamRerun { HalfArgs<real_t> af; OneLaunch of; size_t slot; };
+
+bool is_team(Engine e) { return e == Engine::RegTeam || e == Engine::LaneTeam || e == Engine::Giant; }
+bool is_long(Engine e) { return e == Engine::LdsLong || e == Engine::Giant; }   // a workgroup of LONG_NW waves per row, on the long stream
+
+// The eight-wave streamed kernel's geometry for rows of geometry g: every wave streams its own chunks, sized so that LONG_NW
+// private tiles and the reduction scratch fit in one CU's LDS.
+TileGeom long_geom(TileGeom g)
+{
+    g.resident = 0; g.prefetch = prefetch_enabled() ? 1 : 0; g.pq_cap = 0;
+    for (int cap = 128;; cap -= 16) {
+        g.cap = cap;
+        if (cap <= 16 || lds_bytes_per_block(g, sizeof(real_t), LONG_NW) <= 150 * 1024) break;
+    }
+    return g;
+}
+
+// Row bins -> launches: an engine and an instance per bin; consecutive bins that can share an instance share a launch.
+std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx& c)
+{
+    const PlanKnobs& kn = plan_knobs();
+    const int pm = c.pm;
+    std::vector<PlannedLaunch> launches;
+    // The bin joins the previous launch if that launch has the same engine, ends where the bin begins and joins(previous) holds; else it opens one.
+    auto place = [&](const Bin& b, Engine e, const TileGeom& g, int nw, int S, int team, const LaneShape& lane, auto joins) {
+        if (!launches.empty() && launches.back().engine == e && launches.back().begin + launches.back().count == b.begin && joins(launches.back()))
+            { launches.back().count += b.count; launches.back().nnz += b.nnz; return; }
+        PlannedLaunch L{};
+        L.engine = e; L.nw = nw; L.reg_S = S; L.team = team; L.lane = lane; L.s_load = g.s_load; L.spl = slots_per_lane(c.k);
+        L.begin = b.begin; L.count = b.count; L.nnz = b.nnz; L.geom = g; L.geom.zero_row = (unsigned)c.dimF; L.geom.ldF = (int)c.ldF;
+        launches.push_back(L);
+    };
+    // (every team launch of a call gets a row-queue head, an error word and a buffer area of its own: no more than TEAM_LAUNCH_MAX of them; a bin
+    // that would open one more takes the path it has without teams -- asked before whether the bin would join the previous launch)
+    auto team_room = [&]() { return std::count_if(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_team(L.engine); }) < TEAM_LAUNCH_MAX - 1; };
+    // register engine: factor rows of at most 16 slots (32 for doubles, two slots per lane), and 24-bit row ids / 32-bit
+    // byte offsets into the factor
+    const int reg_ns = reg_slots_per_lane((c.k * sizeof(real_t) + 15) / 16);
+    const bool reg_ok = !kn.no_reg && reg_ns > 0 &&
+                        c.dimF < ((size_t)1 << 24) && (c.dimF + 1) * c.ldF * sizeof(real_t) + 16 < ((size_t)1 << 32);
+    // two slots per lane: single-wave rows only, and TNC's ~21 k-vectors leave room for 112 nonzeros of tile
+    const bool regw_ok = reg_ok && (reg_ns == 1 || REG_G == 8);
+    // (kernel-resource-usage: CG with 40 steps of two slots spills 360 bytes per lane even at one wave per SIMD, 36 steps 60)
+    const unsigned reg_max = reg_ns == 2 && REG_G == 16 ? (pm == POISMF_TNCG ? 112u : pm == POISMF_CG ? 144u : reg_nnz_max(pm))
+                                                        : reg_nnz_max(pm);
+    // (a bin of a few thousand rows is not worth a launch of its own: it rides along with the next longer size.  TNC keeps the tile size its
+    // length class names: in fp32 its results move in the last bits with the size of the instance -- 62 of 900 rows in tests/test_gpu_parity.py's
+    // segment test -- and a row must not depend on which other rows share its shard; PG and CG, and fp64 TNC, are bit-identical across instances)
+    const bool ride = pm != POISMF_TNCG || sizeof(real_t) == 8;
+    // teams: CG on doubles with two slots per lane (k = 50 fp64: 25 slots), rows handed out through the queue
+    const bool no_team = kn.no_team || c.teams_off;
+    const bool team_ok = !no_team && !kn.static_rows && reg_ok && reg_ns == 2 && REG_G == 16 && sizeof(real_t) == 8 && pm == POISMF_CG;
+    // lane-per-nonzero engine (lane_eval.hpp): 24-bit row ids and row strides, 32-bit byte offsets into the factor (as the register engine)
+    const bool lane_ok = !kn.no_lane && !c.single_pass && c.dimF < ((size_t)1 << 24) && c.ldF * sizeof(real_t) < ((size_t)1 << 24) &&
+                         (c.dimF + 1) * c.ldF * sizeof(real_t) + 16 < ((size_t)1 << 32);
+    const bool no_long = kn.longrow_nnz >= 0x40000000u;
+    for (const Bin& b : bins) {
+        TileGeom g = plan_geom(c.k, b.cls, c.single_pass, pm == POISMF_CG && c.limit_step);
+        if (c.single_pass) { g.resident = 0; g.prefetch = prefetch_enabled() ? 1 : 0; }  // one pass: "gather once" and "stream" are the same thing
+        if (lane_ok) {
+            LaneShape ls = lane_shape_for(b.cls, g.s_load, pm);
+            // k = 100 fp64 rows above 64 nonzeros on the B half: rounds 3-4 left them to the streamed launch (with only the 65 .. 128-nonzero rows
+            // taken out, that launch lost the short-row tail that kept its wave slots busy: B half 234.6 -> 296.0 ms); since round 5 every row up
+            // to 384 nonzeros has a resident instance and the streamed launch keeps the 3 k rows above.
+            // k = 100 fp64 under TNCG, rows of 385 .. 8192 nonzeros (round 5): a TEAM of ceil(class / 384) four-wave workgroups keeps the row
+            // RESIDENT (each member its 1/M of the nonzeros in one register set + a partial LDS set per wave, lane_eval.hpp TM_) and the members
+            // exchange their sums per evaluation -- instead of re-streaming 800 bytes per nonzero for each of ~70 evaluations (84 % of config C5's
+            // 697 GB per sweep).  The team size is a function of the row's length class alone.  POISMF_HIP_NO_LANE_TEAMS=1: the eight-wave
+            // streamed kernel (round 5a)
+            int lane_team = 0;
+            if (ls.waves == 0 && sizeof(real_t) == 8 && g.s_load == 50 && pm == POISMF_TNCG && !kn.no_lane_teams && !no_team && !kn.static_rows &&
+                b.cls > 384 && b.cls <= LONG_ROW_NNZ && team_room()) {
+                const int m = (int)((b.cls + 383u) / 384u);
+                if (m >= 2 && c.num_cu >= 2 * m) { ls = LaneShape{ 1, 0, 0, 4, 0, 32 }; lane_team = m; }
+            }
+            if (ls.waves > 0) {
+                place(b, lane_team ? Engine::LaneTeam : Engine::Lane, g, ls.waves, 0, lane_team, ls,
+                      [&](const PlannedLaunch& P) { return P.team == lane_team && P.lane == ls; });
+                continue;
+            }
+        }
+        if (reg_ok && b.cls <= reg_max) {
+            // short rows: the tile lives in registers (reg_eval.hpp); bins sharing a step count share a launch
+            const int S = reg_steps_for(ride ? b.max_nnz : b.cls);
+            place(b, Engine::Reg, g, 1, S, 0, LaneShape{},
+                  [&](const PlannedLaunch& P) { return P.reg_S >= S && (P.reg_S == S || (ride && b.count < 4096u)); });
+            continue;
+        }
+        if (regw_ok && b.cls <= regw_nnz_max(pm)) {
+            // medium rows: 2, 4 or 8 waves share a row, each keeps its part of the tile in registers
+            const int nw = regw_waves_for(b.cls, pm);
+            const int S = regw_steps_for(ride ? b.max_nnz : b.cls, nw);
+            place(b, Engine::RegW, g, nw, S, 0, LaneShape{},
+                  [&](const PlannedLaunch& P) { return P.nw == nw && P.reg_S >= S && (P.reg_S == S || (ride && b.count < 2048u)); });
+            continue;
+        }
+        if (team_ok) {
+            // rows whose tile fits the registers of two to four CUs, not of one: a team per row (reg_eval.hpp, M_ > 1) -- by the class bound,
+            // never by the longest row that happens to be in the bin: a row's share of the tile (my_share: C = ceil(nnz / (NW M))) -- and with it
+            // its summation order -- must not depend on its shard
+            const TeamShape ts = team_room() ? team_shape_for(b.cls) : TeamShape{};
+            if (ts.members > 0) {
+                place(b, Engine::RegTeam, g, TEAM_NW, ts.steps, ts.members, LaneShape{},
+                      [&](const PlannedLaunch& P) { return P.team == ts.members && P.reg_S == ts.steps; });
+                continue;
+            }
+        }
+        // TNCG streams a non-resident row once per evaluation (~70 of them): one wave keeps ~8 KB of gathers in flight (~4 GB/s), and once
+        // the lane engine holds every row up to 384 nonzeros the few thousand longer ones are a tail, not a crowd -- config C5, rows of
+        // 385 .. 8192 nonzeros on one wave each: 229 ms; on eight-wave workgroups: inside the 133 ms of the then-giant-row-bound launch.
+        // So TNCG's streamed rows always take the eight-wave kernel (POISMF_HIP_LONGROW_NNZ overrides; CG caches its line search, PG
+        // makes one gather per pass over the whole chip: they keep the one-wave streamed kernel below 8192 nonzeros).
+        const unsigned long_thr_here = (pm == POISMF_TNCG && !g.resident && !kn.longrow_set) ? 0u : kn.longrow_nnz;
+        const TileGeom gl = long_geom(g);
+        // (round 6: eight private tiles of even 16 nonzeros do not fit a CU's LDS once a factor row is ~1.2 KB -- k > 146 in fp64, > 292 in fp32 --
+        // and the launch failed with "invalid argument", i.e. rc 1 for a TNCG fit at k = 200 fp64 with any row past the resident limit, found by
+        // scripts/knob_matrix.sh under POISMF_HIP_LONGROW_NNZ=256: such rows keep the one-wave streamed kernel below)
+        const bool long_fits = lds_bytes_per_block(gl, sizeof(real_t), LONG_NW) <= LDS_PER_CU;
+        if (!no_long && long_fits && b.cls > long_thr_here) {
+            // TNCG re-streams such a row for every evaluation: a team of GT_M workgroups per row (row_eval.hpp, TM; POISMF_HIP_NO_GIANT_TEAMS=1:
+            // one workgroup per row, rounds 1-4).  Decided by the solver alone: a row's arithmetic must not depend on its shard.
+            const bool giant = !kn.no_giant_teams && !no_team && !kn.static_rows && pm == POISMF_TNCG && b.cls > kn.giant_nnz && team_room() &&
+                               c.num_cu >= 2 * GT_M;
+            place(b, giant ? Engine::Giant : Engine::LdsLong, gl, LONG_NW, 0, giant ? GT_M : 0, LaneShape{}, [](const PlannedLaunch&) { return true; });
+            continue;
+        }
+        place(b, Engine::Lds, g, 1, 0, 0, LaneShape{}, [&](const PlannedLaunch& P) {
+            return g.resident == 0 && P.geom.resident == 0 && g.pq_cap == 0 && P.geom.pq_cap == 0 && P.geom.cap == g.cap;
+        });
+    }
+    return launches;
+}
+
+// The kernel instance a launch runs, as plan() and the launch profile name it.
+std::string launch_name(int method, const PlannedLaunch& L)
+{
+    const char* m = method == POISMF_PG ? "pg" : method == POISMF_EVAL ? "eval" : method == POISMF_CG ? "cg" : "tncg";
+    const char* t = sizeof(real_t) == 4 ? "float" : "double";
+    const LaneShape& l = L.lane;
+    char txt[160] = "";
+    switch (L.engine) {
+        case Engine::LaneTeam: snprintf(txt, sizeof txt, "half_sweep_lane_team_kernel<%s,%s,KS=%d,V=%d,L=0+%d,NW=%d,M=%d>", t, m, L.geom.s_load, l.lv, l.lp, L.nw, L.team); break;
+        case Engine::Lane:
+            snprintf(txt, sizeof txt, "half_sweep_lane_kernel<%s,%s,KS=%d,V=%d,A=%d,L=%d%s,NW=%d%s%s>", t, m, L.geom.s_load, l.lv, l.la, l.ll,
+                     l.lp == 32 ? "+32" : l.lp ? "+16" : "", L.nw, l.small ? ",2/SIMD" : "", l.tx == 48 ? ",TX=48" : l.tx == 64 ? ",TX=64" : "");
+            break;
+        case Engine::Giant: snprintf(txt, sizeof txt, "half_sweep_giant_kernel<%s,%s,NW=%d,M=%d,streamed cap=%d>", t, m, L.nw, L.team, L.geom.cap); break;
+        case Engine::RegTeam: snprintf(txt, sizeof txt, "half_sweep_team_kernel<%s,%s,S=%d,NW=%d,M=%d>", t, m, L.reg_S, L.nw, L.team); break;
+        case Engine::Reg: snprintf(txt, sizeof txt, "half_sweep_reg_kernel<%s,%s,S=%d>", t, m, L.reg_S); break;
+        case Engine::RegW: snprintf(txt, sizeof txt, "half_sweep_regw_kernel<%s,%s,S=%d,NW=%d>", t, m, L.reg_S, L.nw); break;
+        case Engine::Lds:
+        case Engine::LdsLong:
+            snprintf(txt, sizeof txt, "half_sweep_kernel<%s,%s,NW=%d,%s cap=%d>", t, m, L.nw, L.geom.resident ? "resident" : "streamed", L.geom.cap);
+            break;
+    }
+    return txt;
+}
+
+// The stream a launch runs on: `bin` is the balanced stream of the one-wave bins, `longs` the one the long rows share.  (PG has no one-wave
+// Lane launch -- lane_shape_for gives it four-wave shapes only -- so every one-wave Lane launch is CG's, TNCG's or the evaluation kernels'.)
+hipStream_t launch_stream(const PlannedLaunch& L, hipStream_t main, hipStream_t bin, hipStream_t longs)
+{
+    switch (L.engine) {
+        case Engine::Reg: case Engine::Lds: return bin;
+        case Engine::Lane: return L.nw == 1 ? bin : main;
+        case Engine::RegW: case Engine::RegTeam: return main;
+        case Engine::LaneTeam: case Engine::LdsLong: case Engine::Giant: return longs;
+    }
+    return main;
+}
+
+// grows a session buffer to `need` units of `unit` bytes (growing frees it first, i.e. synchronises the device: only ever grown)
+template <class T> hipError_t grow_buffer(T*& buf, size_t& have, size_t need, size_t unit, hipStream_t stream)
+{
+    if (need <= have) return hipSuccess;
+    pmf_free(buf, stream); buf = nullptr; have = 0;
+    const hipError_t e = pmf_alloc(&buf, need * unit, stream);
+    if (e == hipSuccess) have = need;
+    return e;
+}
+
+// The half's prologue: column sums of the fixed factor (or the caller's k-vector), the padded gather copy, and the arguments every launch of
+// the half starts from.
+int half_prologue(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div, bool prologue, bool early_stop,
+                  const real_t* bsum_override, real_t neg_step_override, real_t neg_step2, HalfArgs<real_t>& a)
+{
+    Half& h = s->half[which];
+    real_t* M = which ? s->dA : s->dB;
+    const real_t* F = which ? s->dB : s->dA;
+    const size_t dimF = which ? s->dimB : s->dimA;
+    const bool is_pg = p->method == POISMF_PG;
+
+    // column sums of the fixed factor (+ l1), with the PG pre-scaling when w == 1:
+    //   B half: * (-step)            ref: src/poismf.c:523-524
+    //   A half: * (-step) twice      ref: src/poismf.c:573-577 (quirk Q1)
+    real_t neg_step = -step_size;
+    if (bsum_override != nullptr) {
+        s->partials_given = false;   // (declared for a half that computes its own sum: not for a later one)
+        neg_step = neg_step_override;
+        HIP_TRY(pmf_upload(s->d_bsum, bsum_override, s->k * sizeof(real_t), s->stream));
+    } else if (prologue) {
+        int nscale = 0;
+        if (is_pg && p->w_mult == (real_t)1.) nscale = which ? 2 : 1;
+        if (colsum(s, F, dimF, p->l1_reg, neg_step, nscale)) return 1;
+    }
+
+    // the gathers read the line-padded copy of the fixed factor when the session keeps one
+    const real_t* Fg = F;
+    real_t* Mp = nullptr;
+    if (s->ld != 0) {
+        // The padded copy of F is current only if this session's own previous half-sweep rewrote ALL of F (its row
+        // kernels store every updated row to both copies).  Anything else -- factors set by the caller, a shard
+        // exchange between GPUs writing into the compact factor -- is picked up by re-padding the whole factor.
+        real_t* Fp = which ? s->dBp : s->dAp;
+        if (prologue && !s->padded_fresh[which ? 0 : 1]) {
+            const size_t total = dimF * s->k;
+            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)s->num_cu * 16);
+            if (blocks > 0) hipLaunchKernelGGL((repad_kernel<real_t>), dim3(blocks), dim3(256), 0, s->stream, F, Fp, dimF, (int)s->k, (int)s->ld);
+            HIP_TRY(hipGetLastError());
+        }
+        Fg = Fp;
+        Mp = which ? s->dAp : s->dBp;
+        if (prologue) {
+            s->padded_fresh[which ? 0 : 1] = true;   // the copy of F was just re-derived (or was current)
+            s->padded_fresh[which ? 1 : 0] = h.row_begin == 0 && h.row_end == h.dimM;
+        }
+    }
+
+    a = HalfArgs<real_t>{};
+    a.M = M; a.F = Fg;
+    a.Mp = Mp; a.ldM = (int)s->ld;
+    a.indptr = h.d_indptr; a.indices = h.d_indices; a.values = h.d_values; a.perm = h.d_perm; a.desc = h.d_desc;
+    a.row_offset = (unsigned)h.row_begin;
+    a.bsum = s->d_bsum;
+    a.P.l2 = p->l2_reg; a.P.w = p->w_mult;
+    a.P.step = step_size * p->w_mult;  // ref: src/poismf.c:151
+    a.P.cnst_div = cnst_div;
+    a.P.neg_step = neg_step;
+    a.P.neg_step2 = neg_step2;
+    a.P.maxupd = (int)std::min<size_t>(p->maxupd, 0x7fffffff);
+    a.P.limit_step = p->limit_step;
+    a.P.max_cg_it = (int)std::max(1.0, std::min(50.0, (double)(real_t)s->k / 2.0));  // ref: src/poismf.c:342
+    // (w_mult > 0: the bound that lets a line search skip a trial needs the data term -w sum x log(.) to be CONVEX along the line;
+    // the reference's Python wrapper asserts weight_mult > 0, the C ABI does not)
+    a.P.x_pos = (h.x_positive && !plan_knobs().no_ls_prune && p->w_mult > (real_t)0) ? 1 : 0;
+    a.reuse_prev = p->reuse_prev;
+    a.early_stop = early_stop;
+    a.n_unchanged = s->d_counter;
+    a.stop = is_pg ? nullptr : (const unsigned*)g_stop_word;   // (pinned host memory, portable: the same address on every device)
+    a.eval_rows = s->profiling ? h.d_eval_rows : nullptr;
+    a.dec_rows = s->profiling ? h.d_dec_rows : nullptr;
+    a.team_err = s->d_team_err + 2;
+    a.team_spin = plan_knobs().team_spin;
+    a.team_members = 1;
+    if (a.early_stop && prologue) HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(unsigned), s->stream));
+    return 0;
+}
+
+// Everything the team launches of a half need, once, on the main stream, before anything of the half is on the chip: a zeroed buffer area,
+// row-queue head (+ one for the re-run), error word and tally per launch, and a copy of the rows they start from.
+int prepare_teams(poismf_hip_session* s, const Half& h, const HalfArgs<real_t>& base, const std::vector<PlannedLaunch>& launches,
+                  std::vector<TeamSlot>& tslots)
+{
+    size_t elems = 0, rows = 0;
+    int n_gt = 0, n_reg = 0;
+    for (const PlannedLaunch& L : launches) {
+        if (!is_team(L.engine)) continue;
+        const bool gt = L.engine != Engine::RegTeam;   // lane teams and giant rows share the GT_* layout
+        tslots.push_back({ elems, rows, gt ? n_gt++ : n_reg++ });
+        elems += (size_t)L.count * s->k;
+        rows += L.count;
+    }
+    if (tslots.empty()) return 0;
+    // (sized for the whole half at once)
+    HIP_TRY(grow_buffer(s->d_gt, s->gt_areas, (size_t)n_gt, (size_t)GT_BUF_BYTES, s->stream));
+    HIP_TRY(grow_buffer(s->d_team, s->team_areas, (size_t)n_reg, (size_t)TEAM_BUF_BYTES, s->stream));
+    HIP_TRY(grow_buffer(s->d_team_backup, s->team_backup_elems, elems, sizeof(real_t), s->stream));
+    if (base.eval_rows != nullptr) HIP_TRY(grow_buffer(s->d_team_eval_backup, s->team_eval_backup_rows, rows, sizeof(unsigned), s->stream));
+    // (a giant / lane team's area is used up to its teams' words: the whole areas are zeroed all the same -- n x 4.6 MB, microseconds on an
+    // empty chip, where round 5 zeroed one area per launch between persistent kernels)
+    if (n_gt) HIP_TRY(hipMemsetAsync(s->d_gt, 0, (size_t)n_gt * (size_t)GT_BUF_BYTES, s->stream));
+    if (n_reg) HIP_TRY(hipMemsetAsync(s->d_team, 0, (size_t)n_reg * (size_t)TEAM_BUF_BYTES, s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_queue + MAX_LAUNCHES, 0, sizeof(unsigned) * 2 * TEAM_LAUNCH_MAX, s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_team_err + 2, 0, sizeof(unsigned) * 2 * TEAM_LAUNCH_MAX, s->stream));
+    size_t ti = 0;
+    for (const PlannedLaunch& L : launches) {
+        if (!is_team(L.engine)) continue;
+        const size_t need = (size_t)L.count * s->k;
+        hipLaunchKernelGGL(team_save_rows_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, (size_t)s->num_cu * 8)), dim3(256), 0, s->stream,
+                           base.M, h.d_desc + L.begin, L.count, (unsigned)h.row_begin, (int)s->k, s->d_team_backup + tslots[ti].backup_at,
+                           (const unsigned*)base.eval_rows, base.eval_rows != nullptr ? s->d_team_eval_backup + tslots[ti].eval_at : nullptr);
+        ti++;
+    }
+    HIP_TRY(hipGetLastError());
+    s->team_launched = true;
+    return 0;
+}
+
+// If team launch `slot` (launched as o with arguments a) gives up: its rows back to where they started, the same rows on the streamed LDS
+// kernel -- one wave per row for register teams, eight for giant rows and lane teams -- after the join.
+TeamRerun team_rerun(const poismf_hip_session* s, const PlannedLaunch& L, const OneLaunch& o, const HalfArgs<real_t>& a, size_t slot)
+{
+    const bool eight = L.engine != Engine::RegTeam;
+    HalfArgs<real_t> af = a;
+    // (a.geom is the LDS engine's geometry for the launch's longest length class: what these rows take without teams -- but a lane team carries the
+    // one-wave geometry of its class: the eight-wave streamed kernel wants its own)
+    if (L.engine == Engine::LaneTeam) af.geom = long_geom(af.geom);
+    af.team_buf = nullptr; af.gate = a.team_err; af.arrive = nullptr; af.n_unchanged = s->d_counter;
+    af.queue = s->d_queue + MAX_LAUNCHES + TEAM_LAUNCH_MAX + slot;
+    OneLaunch of = o;
+    of.engine = eight ? Engine::LdsLong : Engine::Lds;
+    of.reg_S = 0; of.nw = eight ? LONG_NW : 1; of.team = 0; of.lane = LaneShape{};
+    of.s_load = af.geom.s_load; of.stream = s->stream;
+    of.lds = lds_bytes_per_block(af.geom, sizeof(real_t), of.nw);
+    of.grid = eight ? (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu)
+                    : (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu * std::max<size_t>(1, std::min<size_t>(16, LDS_PER_CU / of.lds)) * 2);
+    return { af, of, slot };
+}
+
+// Issues the half's launches in plan order: per launch its arguments, grid, stream, the hold-back gate behind a long-row launch and, in
+// profiling sessions, events around it.  The re-runs of the team launches are described in `reruns`, not issued.
+int issue_half(poismf_hip_session* s, int which, int method, const std::vector<PlannedLaunch>& launches, const HalfArgs<real_t>& base,
+               const std::vector<TeamSlot>& tslots, bool dynamic, bool forked, std::vector<TeamRerun>& reruns)
+{
+    // (two TEAM launches must never run beside each other: each waits for partners that need the CUs the other's partial teams hold -- giant rows
+    // and lane teams follow one another on the SECOND stream, beside the main stream's non-team bins)
+    const hipStream_t long_stream = forked ? s->aux_stream : s->stream;
+    double queued[2] = { 0.0, 0.0 };
+    unsigned arrive_goal = 0;
+    size_t team_no = 0;
+    for (size_t i = 0; i < launches.size(); i++) {
+        const PlannedLaunch& L = launches[i];
+        const std::string name = launch_name(method, L);
+        s->last_plan[which] += name + " rows=" + std::to_string(L.count) + ";";
+        HalfArgs<real_t> a = base;
+        a.perm_begin = L.begin; a.nrows = L.count; a.geom = L.geom;
+        a.team_members = (unsigned)std::max(1, L.team);
+        // Waves launched per resident wave slot.  Rows pulled from the queue balance themselves: 2 is enough.  Rows dealt
+        // out statically come in nnz-descending order, so wave 0 always gets the longest of each round; many short
+        // waves let the dispatcher even that out (measured on C2, PG(10): 2 -> 1.214 ms, 8 -> 1.165, 32 -> 1.146).
+        // The single-wave register kernels are always dealt out this way: with ~1 row per wave the hardware dispatcher IS
+        // the queue (CG fp32 on C2: 3.87 ms with tickets, 3.35 ms without).
+        const bool one_wave = L.engine == Engine::Reg || (L.engine == Engine::Lane && L.nw == 1);
+        a.queue = dynamic && !one_wave ? s->d_queue + i : nullptr;
+        unsigned grid_mult = one_wave ? 32 : 2;
+        // PG on the multi-wave lane kernel: ONE ROW PER WORKGROUP, the hardware dispatcher hands them out.  C4 matrix, PG(10), the 78 715 item
+        // rows of 513 .. 1024 nonzeros: persistent workgroups walking rows r, r + grid, .. at 2 / 4 / 8 / 16 / 64 workgroups per slot 4.28 /
+        // 4.13 / 4.08 / 4.09 / 4.39 ms; persistent workgroups on the queue 4.07; one row per workgroup 3.87 ms.  The queue's gain is balance
+        // (no workgroup owns a fixed share of the rows); what the dispatcher gains on top is measured, not explained (DESIGN.md section 6.0:
+        // neither the cross-row pipeline nor start delays account for it; the workgroup-wide ticket's two barriers per row remain).
+        // (Not for CG / TNCG, whose rows differ in cost and want the longest-first queue: CG fp32 B half 11.25 -> 13.17 ms; not for the
+        // eight-wave register kernel, one workgroup per CU: 1.83 -> 1.90.)
+        if (method == POISMF_PG && L.engine == Engine::Lane && L.nw > 1) grid_mult = 1u << 20;
+        const size_t lds = lds_bytes_per_block(a.geom, sizeof(real_t), L.nw);
+        const unsigned waves_per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(16, LDS_PER_CU / lds));
+        unsigned grid = (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu * waves_per_cu * grid_mult);
+        if (L.engine == Engine::Giant)   // whole teams only: as many as the chip holds at one workgroup per CU
+            grid = std::max(1u, std::min((unsigned)L.count, std::min((unsigned)GT_TEAMS_MAX, (unsigned)s->num_cu / (unsigned)GT_M))) * (unsigned)GT_M;
+        if (L.engine == Engine::LaneTeam)   // whole teams, one workgroup per CU
+            grid = std::max(1u, std::min((unsigned)L.count, (unsigned)s->num_cu / (unsigned)L.team)) * (unsigned)L.team;
+        a.arrive = forked && is_long(L.engine) ? s->d_arrive : nullptr;
+        const size_t slot = team_no;
+        if (is_team(L.engine)) {
+            // one dispatch: its queue head, buffer area, error word and tally are its own and were zeroed before the half began
+            team_no++;
+            a.queue = s->d_queue + MAX_LAUNCHES + slot;                     // teams always draw their rows from a queue
+            a.team_err = s->d_team_err + 2 + slot;
+            a.n_unchanged = s->d_team_err + 2 + TEAM_LAUNCH_MAX + slot;   // kept only if the launch's results are (team_fold_kernel)
+            a.team_buf = L.engine == Engine::RegTeam ? s->d_team + (size_t)tslots[slot].area * (size_t)(TEAM_BUF_BYTES / 8)
+                                                     : s->d_gt + (size_t)tslots[slot].area * (size_t)(GT_BUF_BYTES / 8);
+        }
+        // (with long rows on the second stream, the one-wave bins that follow go wherever less work is queued -- unless the half has TEAM launches:
+        // they follow one another on the second stream and are the half's critical path; round 6's timeline of a C5 sweep, profiles/r06/kt_c5_timeline.txt,
+        // showed the last one-wave bin queued behind all seven of them and running alone for 8 ms after the main stream had been idle for 33)
+        // (multi-wave launches count against the second stream wherever they are issued)
+        const int lane_stream = (forked && tslots.empty() && L.nw == 1 && queued[1] < queued[0]) ? 1 : 0;
+        queued[L.nw > 1 ? 1 : lane_stream] += (double)L.count * (double)std::max(16, L.reg_S > 0 ? L.reg_S * REG_JG : L.geom.cap);
+        OneLaunch o = L;
+        o.stream = launch_stream(L, s->stream, lane_stream ? s->aux_stream : s->stream, long_stream);
+        o.lds = lds; o.grid = grid; o.grid_mult = grid_mult;
+        o.device = s->device; o.num_cu = s->num_cu;
+        LaunchRec lr{};
+        if (s->profiling) {   // events around this launch, on its stream
+            HIP_TRY(hipEventCreate(&lr.t0));
+            HIP_TRY(hipEventCreate(&lr.t1));
+            lr.which = which; lr.name = name; lr.rows = L.count; lr.nnz = L.nnz;
+            HIP_TRY(hipEventRecord(lr.t0, o.stream));
+        }
+        const int rc = launch_one(method, o, a);
+        if (!rc && a.arrive != nullptr) {
+            arrive_goal += std::min<unsigned>(grid, (unsigned)s->num_cu);   // (one eight-wave workgroup per CU)
+            // (hold_back_gate_kernel: returns when that many workgroups are on the chip, or after 2 ms)
+            hipLaunchKernelGGL(hold_back_gate_kernel, dim3(1), dim3(1), 0, s->stream, s->d_arrive, arrive_goal, s->gate_budget);
+        }
+        if (!rc && is_team(L.engine)) reruns.push_back(team_rerun(s, L, o, a, slot));
+        if (s->profiling) {
+            HIP_TRY(hipEventRecord(lr.t1, o.stream));
+            s->lprof.push_back(lr);
+        }
+        if (rc) return 1;
+    }
+    return 0;
+}
+
+// The half's epilogue: the join; per team launch a restore and a streamed re-run that return at once unless the launch's error word is set,
+// then the fold -- on a chip that has nothing else resident; the early-stop counter.
+int half_epilogue(poismf_hip_session* s, const Half& h, int method, const HalfArgs<real_t>& base, bool forked, const std::vector<TeamSlot>& tslots,
+                  const std::vector<TeamRerun>& reruns, const ProfRec& rec, size_t* n_unchanged)
+{
+    if (forked) {
+        HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
+        HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_join, 0));
+    }
+    for (const TeamRerun& r : reruns) {
+        hipLaunchKernelGGL(team_restore_rows_kernel, dim3((unsigned)std::min<size_t>(((size_t)r.af.nrows * s->k + 255) / 256, (size_t)s->num_cu * 8)),
+                           dim3(256), 0, s->stream, base.M, base.Mp, (int)s->ld, h.d_desc + r.af.perm_begin, r.af.nrows, (unsigned)h.row_begin, (int)s->k,
+                           s->d_team_backup + tslots[r.slot].backup_at, s->d_team_err + 2 + r.slot, base.eval_rows,
+                           base.eval_rows != nullptr ? s->d_team_eval_backup + tslots[r.slot].eval_at : nullptr);
+#ifndef PMF_LANE_ONLY   // (development builds without the streamed kernels: no re-run)
+        if (launch_one(method, r.of, r.af)) return 1;
+#endif
+    }
+    if (!reruns.empty()) {
+        hipLaunchKernelGGL(team_fold_kernel, dim3(1), dim3(1), 0, s->stream, s->d_team_err, (int)tslots.size(), base.early_stop ? s->d_counter : nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (s->profiling) {
+        HIP_TRY(hipEventRecord(rec.t1, s->stream));
+        s->prof.push_back(rec);
+    }
+    if (base.early_stop && n_unchanged != nullptr) {
+        unsigned cnt = 0;
+        HIP_TRY(pmf_download(&cnt, s->d_counter, sizeof(unsigned), s->stream));
+        *n_unchanged = cnt;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1037,79 +1518,11 @@ static int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_pa
     HIP_TRY(hipSetDevice(s->device));
     which = which ? 1 : 0;
     Half& h = s->half[which];
-    real_t* M = which ? s->dA : s->dB;
-    const real_t* F = which ? s->dB : s->dA;
-    const size_t dimF = which ? s->dimB : s->dimA;
-    const bool is_pg = p->method == POISMF_PG;
-    const int pm = p->method == POISMF_EVAL ? POISMF_CG : p->method;   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
-    const bool weighted = p->w_mult != (real_t)1.;
     if (seg >= (int)h.segs.size()) return 1;
     const bool prologue = seg <= 0;
-
-    // column sums of the fixed factor (+ l1), with the PG pre-scaling when w == 1:
-    //   B half: * (-step)            ref: src/poismf.c:523-524
-    //   A half: * (-step) twice      ref: src/poismf.c:573-577 (quirk Q1)
-    real_t neg_step = -step_size;
-    if (bsum_override != nullptr) {
-        s->partials_given = false;   // (declared for a half that computes its own sum: not for a later one)
-        neg_step = neg_step_override;
-        HIP_TRY(pmf_upload(s->d_bsum, bsum_override, s->k * sizeof(real_t), s->stream));
-    } else if (prologue) {
-        int nscale = 0;
-        if (is_pg && !weighted) nscale = which ? 2 : 1;
-        if (colsum(s, F, dimF, p->l1_reg, neg_step, nscale)) return 1;
-    }
-
-    // the gathers read the line-padded copy of the fixed factor when the session keeps one
-    const real_t* Fg = F;
-    size_t ldF = s->k;
-    real_t* Mp = nullptr;
-    if (s->ld != 0) {
-        // The padded copy of F is current only if this session's own previous half-sweep rewrote ALL of F (its row
-        // kernels store every updated row to both copies).  Anything else -- factors set by the caller, a shard
-        // exchange between GPUs writing into the compact factor -- is picked up by re-padding the whole factor.
-        real_t* Fp = which ? s->dBp : s->dAp;
-        if (prologue && !s->padded_fresh[which ? 0 : 1]) {
-            const size_t total = dimF * s->k;
-            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)s->num_cu * 16);
-            if (blocks > 0) hipLaunchKernelGGL((repad_kernel<real_t>), dim3(blocks), dim3(256), 0, s->stream, F, Fp, dimF, (int)s->k, (int)s->ld);
-            HIP_TRY(hipGetLastError());
-        }
-        Fg = Fp;
-        ldF = s->ld;
-        Mp = which ? s->dAp : s->dBp;
-        if (prologue) {
-            s->padded_fresh[which ? 0 : 1] = true;   // the copy of F was just re-derived (or was current)
-            s->padded_fresh[which ? 1 : 0] = h.row_begin == 0 && h.row_end == h.dimM;
-        }
-    }
-
-    HalfArgs<real_t> a;
-    a.M = M; a.F = Fg;
-    a.Mp = Mp; a.ldM = (int)s->ld;
-    a.indptr = h.d_indptr; a.indices = h.d_indices; a.values = h.d_values; a.perm = h.d_perm; a.desc = h.d_desc;
-    a.row_offset = (unsigned)h.row_begin;
-    a.bsum = s->d_bsum;
-    a.P.l2 = p->l2_reg; a.P.w = p->w_mult;
-    a.P.step = step_size * p->w_mult;  // ref: src/poismf.c:151
-    a.P.cnst_div = cnst_div;
-    a.P.neg_step = neg_step;
-    a.P.neg_step2 = neg_step2;
-    a.P.maxupd = (int)std::min<size_t>(p->maxupd, 0x7fffffff);
-    a.P.limit_step = p->limit_step;
-    a.P.max_cg_it = (int)std::max(1.0, std::min(50.0, (double)(real_t)s->k / 2.0));  // ref: src/poismf.c:342
-    static const bool no_prune = getenv("POISMF_HIP_NO_LS_PRUNE") != nullptr;  // testing knob: evaluate every line-search trial
-    // (w_mult > 0: the bound that lets a line search skip a trial needs the data term -w sum x log(.) to be CONVEX along the line;
-    // the reference's Python wrapper asserts weight_mult > 0, the C ABI does not)
-    a.P.x_pos = (h.x_positive && !no_prune && p->w_mult > (real_t)0) ? 1 : 0;
-    a.reuse_prev = p->reuse_prev;
-    a.early_stop = (p->method == POISMF_TNCG) && p->early_stop && (n_unchanged != nullptr || seg >= 0);
-    a.n_unchanged = s->d_counter;
-    a.eval_rows = s->profiling ? h.d_eval_rows : nullptr;
-    a.dec_rows = s->profiling ? h.d_dec_rows : nullptr;
-    if (a.early_stop && prologue) HIP_TRY(hipMemsetAsync(s->d_counter, 0, sizeof(unsigned), s->stream));
-
-    const bool single_pass = is_pg && p->maxupd <= 1 && !weighted;
+    const bool early_stop = (p->method == POISMF_TNCG) && p->early_stop && (n_unchanged != nullptr || seg >= 0);
+    HalfArgs<real_t> base;
+    if (half_prologue(s, which, p, step_size, cnst_div, prologue, early_stop, bsum_override, neg_step_override, neg_step2, base)) return 1;
     ProfRec rec{};
     if (s->profiling) {
         HIP_TRY(hipEventCreate(&rec.t0));
@@ -1117,407 +1530,40 @@ static int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_pa
         rec.which = which;
         HIP_TRY(hipEventRecord(rec.t0, s->stream));
     }
-    // Consecutive bins that end up with the same tile geometry (all streamed bins; every bin of a single-pass
-    // solver) are merged into one launch.
-    struct Launch { unsigned begin, count; TileGeom geom; int nw; int reg_S; int team; unsigned long long nnz; int lane_L = 0, lane_A = 0, lane_LL = 0, lane_small = 0, lane_LP = 0, lane_tx = 0; };
-    std::vector<Launch> launches;
-    // (every team launch of a call gets a row-queue head, an error word and a buffer area of its own: no more than TEAM_LAUNCH_MAX of them; a bin
-    // that would open one more takes the path it has without teams)
-    auto n_team_launches = [&]() { int n = 0; for (const Launch& L : launches) n += L.team > 1; return n; };
-    static const bool no_reg = getenv("POISMF_HIP_NO_REGTILE") != nullptr;  // testing knob: LDS engine for every row
-    // register engine: factor rows of at most 16 slots (32 for doubles, two slots per lane), and 24-bit row ids / 32-bit
-    // byte offsets into the factor
-    const int reg_ns = reg_slots_per_lane((s->k * sizeof(real_t) + 15) / 16);
-    const bool reg_ok = !no_reg && reg_ns > 0 &&
-                        dimF < ((size_t)1 << 24) && (dimF + 1) * ldF * sizeof(real_t) + 16 < ((size_t)1 << 32);
-    // two slots per lane: single-wave rows only, and TNC's ~21 k-vectors leave room for 112 nonzeros of tile
-    const bool regw_ok = reg_ok && (reg_ns == 1 || REG_G == 8);
-    // (kernel-resource-usage: CG with 40 steps of two slots spills 360 bytes per lane even at one wave per SIMD, 36 steps 60)
-    const unsigned reg_max = reg_ns == 2 && REG_G == 16 ? (pm == POISMF_TNCG ? 112u : pm == POISMF_CG ? 144u : reg_nnz_max(pm))
-                                                        : reg_nnz_max(pm);
-    // teams: CG on doubles with two slots per lane (k = 50 fp64: 25 slots), rows handed out through the queue
-    static const bool no_team_env = getenv("POISMF_HIP_NO_TEAM") != nullptr;  // testing knob
-    const bool no_team = no_team_env || s->teams_off;
-    static const bool static_rows_ = getenv("POISMF_HIP_STATIC_ROWS") != nullptr;
-    const bool team_ok = !no_team && !static_rows_ && reg_ok && reg_ns == 2 && REG_G == 16 && sizeof(real_t) == 8 && pm == POISMF_CG;
-    // lane-per-nonzero engine (lane_eval.hpp): doubles with 25 / 50 slots per factor row, CG and TNCG; 24-bit row ids and
-    // row strides, 32-bit byte offsets into the factor (as the register engine)
-    static const bool no_lane = getenv("POISMF_HIP_NO_LANE") != nullptr;  // testing knob
-    const bool lane_ok = !no_lane && !single_pass && dimF < ((size_t)1 << 24) && ldF * sizeof(real_t) < ((size_t)1 << 24) &&
-                         (dimF + 1) * ldF * sizeof(real_t) + 16 < ((size_t)1 << 32);
-    unsigned long_thr = LONG_ROW_NNZ;
-    if (const char* e = getenv("POISMF_HIP_LONGROW_NNZ")) long_thr = (unsigned)std::max(64, atoi(e));  // testing knob (a huge value: no eight-wave rows at all)
-    const bool no_long = long_thr >= 0x40000000u;
+
     std::vector<Bin> bins;   // of the segments this call runs, in order
     for (size_t j = 0; j < h.segs.size(); j++)
         if (seg < 0 || (size_t)seg == j) bins.insert(bins.end(), h.segs[j].bins.begin(), h.segs[j].bins.end());
-    for (const Bin& b : bins) {
-        TileGeom g = plan_geom(s->k, b.cls, single_pass, pm == POISMF_CG && p->limit_step);
-        if (single_pass) { g.resident = 0; g.prefetch = prefetch_enabled() ? 1 : 0; }  // one pass: "gather once" and "stream" are the same thing
-        if (lane_ok) {
-            LaneShape ls = lane_shape_for(b.cls, g.s_load, pm);
-            // k = 100 fp64 rows above 64 nonzeros on the B half: rounds 3-4 left them to the streamed launch (with only the 65 .. 128-nonzero rows
-            // taken out, that launch lost the short-row tail that kept its wave slots busy: B half 234.6 -> 296.0 ms); since round 5 every row up
-            // to 384 nonzeros has a resident instance and the streamed launch keeps the 3 k rows above.
-            // k = 100 fp64 under TNCG, rows of 385 .. 8192 nonzeros (round 5): a TEAM of ceil(class / 384) four-wave workgroups keeps the row
-            // RESIDENT (each member its 1/M of the nonzeros in one register set + a partial LDS set per wave, lane_eval.hpp TM_) and the members
-            // exchange their sums per evaluation -- instead of re-streaming 800 bytes per nonzero for each of ~70 evaluations (84 % of config C5's
-            // 697 GB per sweep).  The team size is a function of the row's length class alone.  POISMF_HIP_NO_LANE_TEAMS=1: the eight-wave
-            // streamed kernel (round 5a)
-            int lane_team = 0;
-            static const bool no_lane_teams = getenv("POISMF_HIP_NO_LANE_TEAMS") != nullptr;
-            if (ls.waves == 0 && sizeof(real_t) == 8 && g.s_load == 50 && pm == POISMF_TNCG && !no_lane_teams && !no_team && !static_rows_ && b.cls > 384 &&
-                b.cls <= LONG_ROW_NNZ && n_team_launches() < TEAM_LAUNCH_MAX - 1) {
-                const int m = (int)((b.cls + 383u) / 384u);
-                if (m >= 2 && s->num_cu >= 2 * m) { ls = LaneShape{ 1, 0, 0, 4, 0, 32 }; lane_team = m; }
-            }
-            if (ls.waves > 0) {
-                if (!launches.empty() && launches.back().team == lane_team && launches.back().lane_L == ls.lv && launches.back().lane_A == ls.la && launches.back().lane_LL == ls.ll && launches.back().lane_small == ls.small && launches.back().lane_LP == ls.lp && launches.back().lane_tx == ls.tx &&
-                    launches.back().nw == ls.waves && launches.back().begin + launches.back().count == b.begin)
-                    { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-                else {
-                    launches.push_back({ b.begin, b.count, g, ls.waves, 0, lane_team, b.nnz });
-                    launches.back().lane_L = ls.lv; launches.back().lane_A = ls.la; launches.back().lane_LL = ls.ll; launches.back().lane_small = ls.small; launches.back().lane_LP = ls.lp; launches.back().lane_tx = ls.tx;
-                }
-                continue;
-            }
-        }
-        if (reg_ok && b.cls <= reg_max) {
-            // short rows: the tile lives in registers (reg_eval.hpp); bins sharing a step count share a launch
-            // (a bin of a few thousand rows is not worth a launch of its own: it rides along with the next longer size)
-            // (TNC keeps the tile size its length class names: in fp32 its results move in the last bits with the size of
-            // the instance -- 62 of 900 rows in tests/test_gpu_parity.py's segment test -- and a row must not depend on
-            // which other rows share its shard; PG and CG are bit-identical across instances and may ride along)
-            const bool ride = pm != POISMF_TNCG || sizeof(real_t) == 8;   // (fp64 TNC is bit-identical across instances too)
-            const int S = reg_steps_for(ride ? b.max_nnz : b.cls);
-            if (!launches.empty() && launches.back().lane_L == 0 && launches.back().nw == 1 && launches.back().reg_S >= S &&
-                (launches.back().reg_S == S || (ride && b.count < 4096u)) && launches.back().begin + launches.back().count == b.begin)
-                { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-            else
-                launches.push_back({ b.begin, b.count, g, 1, S, 0, b.nnz });
-            continue;
-        }
-        if (regw_ok && b.cls <= regw_nnz_max(pm)) {
-            // medium rows: 2, 4 or 8 waves share a row, each keeps its part of the tile in registers
-            const int nw = regw_waves_for(b.cls, pm);
-            const bool ride = pm != POISMF_TNCG || sizeof(real_t) == 8;   // (fp64 TNC is bit-identical across instances too)
-            const int S = regw_steps_for(ride ? b.max_nnz : b.cls, nw);
-            if (!launches.empty() && launches.back().lane_L == 0 && launches.back().nw == nw && launches.back().reg_S >= S &&
-                (launches.back().reg_S == S || (ride && b.count < 2048u)) && launches.back().begin + launches.back().count == b.begin)
-                { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-            else
-                launches.push_back({ b.begin, b.count, g, nw, S, 0, b.nnz });
-            continue;
-        }
-        if (team_ok) {
-            // rows whose tile fits the registers of two to four CUs, not of one: a team per row (reg_eval.hpp, M_ > 1)
-            const TeamShape ts = n_team_launches() < TEAM_LAUNCH_MAX - 1 ? team_shape_for(b.cls) : TeamShape{};   // by the class bound, never by the longest row that happens to be in the bin: a row's
-            // share of the tile (my_share: C = ceil(nnz / (NW M))) -- and with it its summation order -- must not depend on its shard
-            if (ts.members > 0) {
-                if (!launches.empty() && launches.back().team == ts.members && launches.back().reg_S == ts.steps &&
-                    launches.back().begin + launches.back().count == b.begin)
-                    { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-                else
-                    launches.push_back({ b.begin, b.count, g, TEAM_NW, ts.steps, ts.members, b.nnz });
-                continue;
-            }
-        }
-        // TNCG streams a non-resident row once per evaluation (~70 of them): one wave keeps ~8 KB of gathers in flight (~4 GB/s), and once
-        // the lane engine holds every row up to 384 nonzeros the few thousand longer ones are a tail, not a crowd -- config C5, rows of
-        // 385 .. 8192 nonzeros on one wave each: 229 ms; on eight-wave workgroups: inside the 133 ms of the then-giant-row-bound launch.
-        // So TNCG's streamed rows always take the eight-wave kernel (POISMF_HIP_LONGROW_NNZ overrides; CG caches its line search, PG
-        // makes one gather per pass over the whole chip: they keep the one-wave streamed kernel below 8192 nonzeros).
-        const unsigned long_thr_here = (pm == POISMF_TNCG && !g.resident && getenv("POISMF_HIP_LONGROW_NNZ") == nullptr) ? 0u : long_thr;
-        // a workgroup of LONG_NW waves per row; every wave streams its own chunks: size the chunk so that
-        // LONG_NW private tiles and the reduction scratch fit in one CU's LDS
-        TileGeom gl = g;
-        gl.resident = 0;
-        gl.prefetch = prefetch_enabled() ? 1 : 0;
-        gl.pq_cap = 0;
-        for (int cap = 128;; cap -= 16) {
-            gl.cap = cap;
-            if (cap <= 16 || lds_bytes_per_block(gl, sizeof(real_t), LONG_NW) <= 150 * 1024) break;
-        }
-        // (round 6: eight private tiles of even 16 nonzeros do not fit a CU's LDS once a factor row is ~1.2 KB -- k > 146 in fp64, > 292 in fp32 --
-        // and the launch failed with "invalid argument", i.e. rc 1 for a TNCG fit at k = 200 fp64 with any row past the resident limit, found by
-        // scripts/knob_matrix.sh under POISMF_HIP_LONGROW_NNZ=256: such rows keep the one-wave streamed kernel below)
-        const bool long_fits = lds_bytes_per_block(gl, sizeof(real_t), LONG_NW) <= LDS_PER_CU;
-        if (!no_long && long_fits && b.cls > long_thr_here) {
-            g = gl;
-            // TNCG re-streams such a row for every evaluation: a team of GT_M workgroups per row (row_eval.hpp, TM; POISMF_HIP_NO_GIANT_TEAMS=1:
-            // one workgroup per row, rounds 1-4).  Decided by the solver alone: a row's arithmetic must not depend on its shard.
-            static const bool no_giant = getenv("POISMF_HIP_NO_GIANT_TEAMS") != nullptr;
-            static const unsigned giant_thr = getenv("POISMF_HIP_GIANT_NNZ") ? (unsigned)std::max(64, atoi(getenv("POISMF_HIP_GIANT_NNZ"))) : LONG_ROW_NNZ;   // testing knob
-            const int giant = (!no_giant && !no_team && !static_rows_ && pm == POISMF_TNCG && b.cls > giant_thr && n_team_launches() < TEAM_LAUNCH_MAX - 1 &&
-                               s->num_cu >= 2 * GT_M) ? GT_M : 0;
-            if (!launches.empty() && launches.back().lane_L == 0 && launches.back().reg_S == 0 && launches.back().nw == LONG_NW && launches.back().team == giant &&
-                launches.back().begin + launches.back().count == b.begin)
-                { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-            else
-                launches.push_back({ b.begin, b.count, g, LONG_NW, 0, giant, b.nnz });
-            continue;
-        }
-        if (!launches.empty() && launches.back().lane_L == 0 && launches.back().reg_S == 0 && launches.back().geom.cap == g.cap &&
-            launches.back().geom.resident == g.resident && (g.resident == 0) && g.pq_cap == 0 && launches.back().geom.pq_cap == 0 && launches.back().nw == 1 &&
-            launches.back().begin + launches.back().count == b.begin)
-            { launches.back().count += b.count; launches.back().nnz += b.nnz; }
-        else
-            launches.push_back({ b.begin, b.count, g, 1, 0, 0, b.nnz });
-    }
-    static const bool static_rows = getenv("POISMF_HIP_STATIC_ROWS") != nullptr;  // testing knob
-    const bool dynamic = !is_pg && !static_rows && launches.size() <= (size_t)MAX_LAUNCHES;
-    // (PG's multi-wave lane launches take ONE ROW PER WORKGROUP, below; persistent workgroups on the queue or with static shares -- rounds 2-4a,
+    const bool is_pg = p->method == POISMF_PG;
+    const int pm = p->method == POISMF_EVAL ? POISMF_CG : p->method;   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
+    const bool single_pass = is_pg && p->maxupd <= 1 && p->w_mult == (real_t)1.;
+    const PlanCtx c{ s->k, which ? s->dimB : s->dimA, s->ld != 0 ? s->ld : s->k, pm, single_pass, p->limit_step != 0, s->teams_off, s->num_cu };
+    const std::vector<PlannedLaunch> launches = plan_half(bins, c);
+
+    const bool dynamic = !is_pg && !plan_knobs().static_rows && launches.size() <= (size_t)MAX_LAUNCHES;
+    // (PG's multi-wave lane launches take ONE ROW PER WORKGROUP, issue_half; persistent workgroups on the queue or with static shares -- rounds 2-4a,
     // POISMF_HIP_PG_LANE_ROWS -- lost to it, DESIGN.md 6.0, and went in round 6)
     if (dynamic) HIP_TRY(hipMemsetAsync(s->d_queue, 0, sizeof(unsigned) * MAX_LAUNCHES, s->stream));
-    // the few workgroup-per-row launches of the power-law tail occupy a few dozen CUs for a long time: run them on a
-    // second stream beside the other bins (fork after the column sums, join before anything reads the result)
-    static const bool no_fork = getenv("POISMF_HIP_NO_FORK") != nullptr;  // testing knob
-    bool any_long = false;
-    for (const Launch& L : launches) any_long = any_long || (L.nw > 1 && L.reg_S == 0 && L.lane_L == 0);
-    const bool forked = !no_fork && launches.size() > 1 && any_long;
-    // (two TEAM launches must never run beside each other: each waits for partners that need the CUs the other's partial teams hold -- giant rows
-    // and lane teams follow one another on the SECOND stream, beside the main stream's non-team bins)
-    hipStream_t long_stream = forked ? s->aux_stream : s->stream;
-    double queued[2] = { 0.0, 0.0 };
-    // The long rows go to the second stream to run NEXT TO the other bins, not after them.  The other bins' kernels are persistent
-    // (a workgroup keeps its CU until the bin's queue is empty): whichever kernel reaches the chip first fills it, and on config C5
-    // that was the mid-length bin -- the 60 giant rows then waited 260 ms for a CU and ran on their own afterwards (390 ms for what
-    // takes 150 alone).  So every workgroup of the long-row launch counts itself in when it starts, and the main stream waits for
-    // that count (a one-wave gate kernel with a time limit, above; rounds 3-4a: hipStreamWaitValue32) before it launches anything else.
-    // Arrivals only ever grow, so a chip that cannot hold the whole launch at once delays the main stream by the gate's 2 ms, no more.
-    const bool hold_back = forked && any_long;
-    if (hold_back) HIP_TRY(hipMemsetAsync(s->d_arrive, 0, sizeof(unsigned), s->stream));
-    // ---- everything the team launches of this call need, once, on the main stream, before anything of the half is on the chip: a zeroed
-    // buffer area, row-queue head (+ one for the re-run), error word and tally per launch, and a copy of the rows they start from
-    struct TeamSlot { size_t backup_at, eval_at; int area; };   // per team launch, in launch order
+    // The few workgroup-per-row launches of the power-law tail occupy a few dozen CUs for a long time: run them on a second stream beside the
+    // other bins (fork after the column sums, join before anything reads the result) -- NEXT TO the other bins, not after them.  The other bins'
+    // kernels are persistent (a workgroup keeps its CU until the bin's queue is empty): whichever kernel reaches the chip first fills it, and on
+    // config C5 that was the mid-length bin -- the 60 giant rows then waited 260 ms for a CU and ran on their own afterwards (390 ms for what
+    // takes 150 alone).  So every workgroup of a long-row launch counts itself in when it starts, and the main stream waits for that count (a
+    // one-wave gate kernel with a time limit; rounds 3-4a: hipStreamWaitValue32) before it launches anything else.  Arrivals only ever grow, so
+    // a chip that cannot hold the whole launch at once delays the main stream by the gate's 2 ms, no more.
+    const bool forked = !plan_knobs().no_fork && launches.size() > 1 &&
+                        std::any_of(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_long(L.engine); });
+    if (forked) HIP_TRY(hipMemsetAsync(s->d_arrive, 0, sizeof(unsigned), s->stream));
     std::vector<TeamSlot> tslots;
-    {
-        size_t elems = 0, rows = 0;
-        int n_gt = 0, n_reg = 0;
-        for (const Launch& L : launches) {
-            if (L.team <= 1) continue;
-            const bool gt = L.lane_L > 0 || (L.team == GT_M && L.reg_S == 0);   // lane teams and giant rows share the GT_* layout
-            tslots.push_back({ elems, rows, gt ? n_gt++ : n_reg++ });
-            elems += (size_t)L.count * s->k;
-            rows += L.count;
-        }
-        if (!tslots.empty()) {
-            // (growing a buffer frees it first, i.e. synchronises the device: sized for the whole half at once, and only ever grown)
-            if ((size_t)n_gt > s->gt_areas) {
-                pmf_free(s->d_gt, s->stream); s->d_gt = nullptr; s->gt_areas = 0;
-                HIP_TRY(pmf_alloc(&s->d_gt, (size_t)n_gt * (size_t)GT_BUF_BYTES, s->stream));
-                s->gt_areas = (size_t)n_gt;
-            }
-            if ((size_t)n_reg > s->team_areas) {
-                pmf_free(s->d_team, s->stream); s->d_team = nullptr; s->team_areas = 0;
-                HIP_TRY(pmf_alloc(&s->d_team, (size_t)n_reg * (size_t)TEAM_BUF_BYTES, s->stream));
-                s->team_areas = (size_t)n_reg;
-            }
-            if (elems > s->team_backup_elems) {
-                pmf_free(s->d_team_backup, s->stream); s->d_team_backup = nullptr; s->team_backup_elems = 0;
-                HIP_TRY(pmf_alloc(&s->d_team_backup, elems * sizeof(real_t), s->stream));
-                s->team_backup_elems = elems;
-            }
-            if (a.eval_rows != nullptr && rows > s->team_eval_backup_rows) {
-                pmf_free(s->d_team_eval_backup, s->stream); s->d_team_eval_backup = nullptr; s->team_eval_backup_rows = 0;
-                HIP_TRY(pmf_alloc(&s->d_team_eval_backup, rows * sizeof(unsigned), s->stream));
-                s->team_eval_backup_rows = rows;
-            }
-            // (a giant / lane team's area is used up to its teams' words: the whole areas are zeroed all the same -- n x 4.6 MB, microseconds on an
-            // empty chip, where round 5 zeroed one area per launch between persistent kernels)
-            if (n_gt) HIP_TRY(hipMemsetAsync(s->d_gt, 0, (size_t)n_gt * (size_t)GT_BUF_BYTES, s->stream));
-            if (n_reg) HIP_TRY(hipMemsetAsync(s->d_team, 0, (size_t)n_reg * (size_t)TEAM_BUF_BYTES, s->stream));
-            HIP_TRY(hipMemsetAsync(s->d_queue + MAX_LAUNCHES, 0, sizeof(unsigned) * 2 * TEAM_LAUNCH_MAX, s->stream));
-            HIP_TRY(hipMemsetAsync(s->d_team_err + 2, 0, sizeof(unsigned) * 2 * TEAM_LAUNCH_MAX, s->stream));
-            size_t ti = 0;
-            for (const Launch& L : launches) {
-                if (L.team <= 1) continue;
-                const size_t need = (size_t)L.count * s->k;
-                hipLaunchKernelGGL(team_save_rows_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, (size_t)s->num_cu * 8)), dim3(256), 0, s->stream,
-                                   M, h.d_desc + L.begin, L.count, (unsigned)h.row_begin, (int)s->k, s->d_team_backup + tslots[ti].backup_at,
-                                   (const unsigned*)a.eval_rows, a.eval_rows != nullptr ? s->d_team_eval_backup + tslots[ti].eval_at : nullptr);
-                ti++;
-            }
-            HIP_TRY(hipGetLastError());
-            s->team_launched = true;
-        }
-    }
-    struct TeamRerun { HalfArgs<real_t> af; OneLaunch of; unsigned begin, count; size_t slot; };
-    std::vector<TeamRerun> reruns;   // what each team launch becomes if it gives up (issued, gated, after the join)
-    size_t team_no = 0;
+    if (prepare_teams(s, h, base, launches, tslots)) return 1;
     if (forked) {
         HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
         HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
     }
-    int launch_no = 0;
-    unsigned arrive_goal = 0;
     if (prologue) s->last_plan[which].clear();
-    for (const Launch& L : launches) {
-        char lname[160];
-        {
-            char txt[192];
-            const char* m = is_pg ? "pg" : p->method == POISMF_EVAL ? "eval" : pm == POISMF_CG ? "cg" : "tncg";
-            const char* t = sizeof(real_t) == 4 ? "float" : "double";
-            if (L.lane_L > 0 && L.team > 1) snprintf(txt, sizeof txt, "half_sweep_lane_team_kernel<%s,%s,KS=%d,V=%d,L=0+%d,NW=%d,M=%d> rows=%u;", t, m, L.geom.s_load, L.lane_L, L.lane_LP, L.nw, L.team, L.count);
-            else if (L.lane_L > 0) snprintf(txt, sizeof txt, "half_sweep_lane_kernel<%s,%s,KS=%d,V=%d,A=%d,L=%d%s,NW=%d%s%s> rows=%u;", t, m, L.geom.s_load, L.lane_L, L.lane_A, L.lane_LL, L.lane_LP == 32 ? "+32" : L.lane_LP ? "+16" : "", L.nw, L.lane_small ? ",2/SIMD" : "", L.lane_tx == 48 ? ",TX=48" : L.lane_tx == 64 ? ",TX=64" : "", L.count);
-            else if (L.team == GT_M && L.reg_S == 0) snprintf(txt, sizeof txt, "half_sweep_giant_kernel<%s,%s,NW=%d,M=%d,streamed cap=%d> rows=%u;", t, m, L.nw, L.team, L.geom.cap, L.count);
-            else if (L.team > 1) snprintf(txt, sizeof txt, "half_sweep_team_kernel<%s,%s,S=%d,NW=%d,M=%d> rows=%u;", t, m, L.reg_S, L.nw, L.team, L.count);
-            else if (L.reg_S > 0 && L.nw == 1) snprintf(txt, sizeof txt, "half_sweep_reg_kernel<%s,%s,S=%d> rows=%u;", t, m, L.reg_S, L.count);
-            else if (L.reg_S > 0) snprintf(txt, sizeof txt, "half_sweep_regw_kernel<%s,%s,S=%d,NW=%d> rows=%u;", t, m, L.reg_S, L.nw, L.count);
-            else snprintf(txt, sizeof txt, "half_sweep_kernel<%s,%s,NW=%d,%s cap=%d> rows=%u;", t, m, L.nw, L.geom.resident ? "resident" : "streamed", L.geom.cap, L.count);
-            s->last_plan[which] += txt;
-            snprintf(lname, sizeof lname, "%s", txt);
-            if (char* sp = strstr(lname, " rows=")) *sp = 0;
-        }
-        a.queue = dynamic ? s->d_queue + launch_no : nullptr;
-        a.stop = is_pg ? nullptr : (const unsigned*)g_stop_word;   // (pinned host memory, portable: the same address on every device)
-        launch_no++;
-        a.perm_begin = L.begin;
-        a.nrows = L.count;
-        a.geom = L.geom;
-        a.geom.zero_row = (unsigned)dimF;
-        a.geom.ldF = (int)ldF;
-        const size_t lds = lds_bytes_per_block(a.geom, sizeof(real_t), L.nw);
-        const unsigned waves_per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(16, LDS_PER_CU / lds));
-        // Waves launched per resident wave slot.  Rows pulled from the queue balance themselves: 2 is enough.  Rows dealt
-        // out statically come in nnz-descending order, so wave 0 always gets the longest of each round; many short
-        // waves let the dispatcher even that out (measured on C2, PG(10): 2 -> 1.214 ms, 8 -> 1.165, 32 -> 1.146).
-        // The single-wave register kernels are always dealt out this way: with ~1 row per wave the hardware dispatcher IS
-        // the queue (CG fp32 on C2: 3.87 ms with tickets, 3.35 ms without).
-        const bool one_wave_reg = (L.reg_S > 0 || L.lane_L > 0) && L.nw == 1;
-        if (one_wave_reg) a.queue = nullptr;
-        a.team_buf = nullptr; a.team_err = s->d_team_err + 2;
-        a.n_unchanged = s->d_counter;
-        unsigned* terr = s->d_team_err + 2;
-        const bool giant = L.team == GT_M && L.reg_S == 0 && L.lane_L == 0;
-        const bool lane_team = L.team > 1 && L.lane_L > 0;
-        a.team_members = (unsigned)std::max(1, L.team);
-        // (a giant-row team launch lives on the stream the long rows run on)
-        hipStream_t tst = (giant || lane_team) ? long_stream : s->stream;
-        const size_t my_slot = team_no;
-        if (L.team > 1) {
-            // one dispatch: its queue head, buffer area, error word and tally are its own and were zeroed before the half began
-            team_no++;
-            a.queue = s->d_queue + MAX_LAUNCHES + my_slot;            // teams always draw their rows from a queue
-            terr = s->d_team_err + 2 + my_slot;
-            a.team_err = terr;
-            a.n_unchanged = s->d_team_err + 2 + TEAM_LAUNCH_MAX + my_slot;   // kept only if the launch's results are (team_fold_kernel)
-            a.team_buf = (giant || lane_team) ? s->d_gt + (size_t)tslots[my_slot].area * (size_t)(GT_BUF_BYTES / 8)
-                                              : s->d_team + (size_t)tslots[my_slot].area * (size_t)(TEAM_BUF_BYTES / 8);
-        }
-        a.gate = nullptr;
-        const bool is_long = L.nw > 1 && L.reg_S == 0 && L.lane_L == 0;
-        a.arrive = hold_back && is_long ? s->d_arrive : nullptr;
-        static const unsigned team_spin = getenv("POISMF_HIP_TEAM_SPIN_LIMIT") ? (unsigned)std::max(1, atoi(getenv("POISMF_HIP_TEAM_SPIN_LIMIT"))) : TEAM_SPIN_LIMIT;   // testing knob
-        a.team_spin = team_spin;
-        unsigned grid_mult = one_wave_reg ? 32 : 2;
-        // PG on the multi-wave lane kernel: ONE ROW PER WORKGROUP, the hardware dispatcher hands them out.  C4 matrix, PG(10), the 78 715 item
-        // rows of 513 .. 1024 nonzeros: persistent workgroups walking rows r, r + grid, .. at 2 / 4 / 8 / 16 / 64 workgroups per slot 4.28 /
-        // 4.13 / 4.08 / 4.09 / 4.39 ms; persistent workgroups on the queue 4.07; one row per workgroup 3.87 ms.  The queue's gain is balance
-        // (no workgroup owns a fixed share of the rows); what the dispatcher gains on top is measured, not explained (DESIGN.md section 6.0:
-        // neither the cross-row pipeline nor start delays account for it; the workgroup-wide ticket's two barriers per row remain).
-        // (Not for CG / TNCG, whose rows differ in cost and want the longest-first queue: CG fp32 B half 11.25 -> 13.17 ms; not for the
-        // eight-wave register kernel, one workgroup per CU: 1.83 -> 1.90.)
-        if (is_pg && L.lane_L > 0 && L.nw > 1) grid_mult = 1u << 20;
-        unsigned grid = (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu * waves_per_cu * grid_mult);
-        if (giant) {
-            // whole teams only: as many as the chip holds at one workgroup per CU
-            const unsigned teams = std::max(1u, std::min((unsigned)L.count, std::min((unsigned)GT_TEAMS_MAX, (unsigned)s->num_cu / (unsigned)GT_M)));
-            grid = teams * (unsigned)GT_M;
-        }
-        if (lane_team) grid = std::max(1u, std::min((unsigned)L.count, (unsigned)s->num_cu / (unsigned)L.team)) * (unsigned)L.team;   // whole teams, one workgroup per CU
-        int rc = 1;
-        // (with long rows on the second stream, the one-wave bins that follow go wherever less work is queued -- unless the half has TEAM launches:
-        // they follow one another on the second stream and are the half's critical path; round 6's timeline of a C5 sweep, profiles/r06/kt_c5_timeline.txt,
-        // showed the last one-wave bin queued behind all seven of them and running alone for 8 ms after the main stream had been idle for 33)
-        const int lane_stream = (forked && tslots.empty() && L.nw == 1 && queued[1] < queued[0]) ? 1 : 0;
-        hipStream_t bin_stream = lane_stream ? s->aux_stream : s->stream;
-        queued[L.nw > 1 ? 1 : lane_stream] += (double)L.count * (double)std::max(16, L.reg_S > 0 ? L.reg_S * REG_JG : L.geom.cap);
-        {
-            OneLaunch o;
-            o.reg_S = L.reg_S; o.nw = L.nw; o.team = L.team; o.lane_L = L.lane_L; o.lane_A = L.lane_A; o.lane_LL = L.lane_LL; o.lane_small = L.lane_small; o.lane_LP = L.lane_LP; o.lane_tx = L.lane_tx; o.s_load = a.geom.s_load; o.spl = slots_per_lane(s->k);
-            o.generic_only = false;   // (the generic slot-count kernels are what every k other than the BASELINE configs' takes: tests/test_gpu_regtile.py)
-            o.main_stream = lane_team ? tst : s->stream; o.bin_stream = bin_stream; o.long_stream = long_stream;
-            o.lds = lds; o.grid = grid; o.grid_mult = grid_mult;
-            o.device = s->device; o.num_cu = s->num_cu;
-            // profiling sessions: events around this launch, on the stream it goes to (launch_one_here's choice)
-            hipStream_t lst = giant ? o.long_stream : L.team > 1 || ((L.reg_S > 0 || L.lane_L > 0) && L.nw > 1) ? o.main_stream : (L.reg_S == 0 && L.lane_L == 0 && L.nw > 1 ? o.long_stream : o.bin_stream);
-            LaunchRec lr{};
-            if (s->profiling) {
-                HIP_TRY(hipEventCreate(&lr.t0));
-                HIP_TRY(hipEventCreate(&lr.t1));
-                lr.which = which; lr.name = lname; lr.rows = L.count; lr.nnz = L.nnz;
-                HIP_TRY(hipEventRecord(lr.t0, lst));
-            }
-            rc = launch_one(p->method, o, a);
-            if (!rc && a.arrive != nullptr) {
-                arrive_goal += std::min<unsigned>(grid, (unsigned)s->num_cu);   // (one eight-wave workgroup per CU)
-                // (hold_back_gate_kernel: returns when that many workgroups are on the chip, or after 2 ms)
-                hipLaunchKernelGGL(hold_back_gate_kernel, dim3(1), dim3(1), 0, s->stream, s->d_arrive, arrive_goal, s->gate_budget);
-            }
-            if (!rc && L.team > 1) {
-                // if the team launch gives up: rows back to where they started, the same rows on the streamed LDS kernel -- after the join (below)
-                HalfArgs<real_t> af = a;
-                // (a.geom is the LDS engine's geometry for the launch's longest length class: what these rows take without teams)
-                af.team_buf = nullptr;
-                af.gate = terr;
-                af.arrive = nullptr;
-                af.n_unchanged = s->d_counter;
-                af.queue = s->d_queue + MAX_LAUNCHES + TEAM_LAUNCH_MAX + my_slot;
-                if (lane_team) {   // (a lane launch carries the one-wave LDS geometry of its class: the eight-wave streamed kernel wants its own)
-                    af.geom.resident = 0;
-                    af.geom.prefetch = prefetch_enabled() ? 1 : 0;
-                    af.geom.pq_cap = 0;
-                    for (int cap = 128;; cap -= 16) {
-                        af.geom.cap = cap;
-                        if (cap <= 16 || lds_bytes_per_block(af.geom, sizeof(real_t), LONG_NW) <= 150 * 1024) break;
-                    }
-                }
-                OneLaunch of = o;
-                of.reg_S = 0; of.nw = (giant || lane_team) ? LONG_NW : 1; of.team = 0; of.lane_L = 0; of.lane_A = 0; of.lane_LL = 0; of.lane_small = 0; of.lane_LP = 0; of.lane_tx = 0;
-                of.s_load = af.geom.s_load;
-                of.main_stream = s->stream; of.bin_stream = s->stream; of.long_stream = s->stream;
-                of.lds = lds_bytes_per_block(af.geom, sizeof(real_t), of.nw);
-                of.grid = (giant || lane_team) ? (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu)
-                                : (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu * std::max<size_t>(1, std::min<size_t>(16, LDS_PER_CU / of.lds)) * 2);
-                reruns.push_back({ af, of, L.begin, L.count, my_slot });
-            }
-            if (s->profiling) {
-                HIP_TRY(hipEventRecord(lr.t1, lst));
-                s->lprof.push_back(lr);
-            }
-        }
-        if (rc) return 1;
-    }
-    if (forked) {
-        HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
-        HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_join, 0));
-    }
-    // the team launches' epilogue, on a chip that has nothing else resident: per launch a restore and a streamed re-run that return at once unless
-    // the launch's error word is set, then the fold
-    for (const TeamRerun& r : reruns) {
-        hipLaunchKernelGGL(team_restore_rows_kernel, dim3((unsigned)std::min<size_t>(((size_t)r.count * s->k + 255) / 256, (size_t)s->num_cu * 8)),
-                           dim3(256), 0, s->stream, M, Mp, (int)s->ld, h.d_desc + r.begin, r.count, (unsigned)h.row_begin, (int)s->k,
-                           s->d_team_backup + tslots[r.slot].backup_at, s->d_team_err + 2 + r.slot, a.eval_rows,
-                           a.eval_rows != nullptr ? s->d_team_eval_backup + tslots[r.slot].eval_at : nullptr);
-#ifndef PMF_LANE_ONLY   // (development builds without the streamed kernels: no re-run)
-        if (launch_one(p->method, r.of, r.af)) return 1;
-#endif
-    }
-    if (!reruns.empty()) {
-        hipLaunchKernelGGL(team_fold_kernel, dim3(1), dim3(1), 0, s->stream, s->d_team_err, (int)tslots.size(), a.early_stop ? s->d_counter : nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    if (s->profiling) {
-        HIP_TRY(hipEventRecord(rec.t1, s->stream));
-        s->prof.push_back(rec);
-    }
-    if (a.early_stop && n_unchanged != nullptr) {
-        unsigned cnt = 0;
-        HIP_TRY(pmf_download(&cnt, s->d_counter, sizeof(unsigned), s->stream));
-        *n_unchanged = cnt;
-    }
-    return 0;
+    std::vector<TeamRerun> reruns;
+    if (issue_half(s, which, p->method, launches, base, tslots, dynamic, forked, reruns)) return 1;
+    return half_epilogue(s, h, p->method, base, forked, tslots, reruns, rec, n_unchanged);
 }
 
 int poismf_hip_half_sweep(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div,

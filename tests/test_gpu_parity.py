@@ -27,11 +27,16 @@ def T(is_float, t64, t32):
     return t32 if is_float else t64
 
 
-def gpu_run(csr, csc, A0, B0, method, numiter, k, **kw):
+def run_args(method, numiter, k, **kw):
     l2, maxupd, niter = harness.auto_defaults(method, k)
     args = dict(l2_reg=l2, l1_reg=0.0, w_mult=1.0, step_size=1e-7, limit_step=True,
                 niter=niter if numiter == "default" else numiter, maxupd=maxupd, early_stop=True, reuse_prev=False)
     args.update(kw)
+    return args
+
+
+def gpu_run(csr, csc, A0, B0, method, numiter, k, **kw):
+    args = run_args(method, numiter, k, **kw)
     A, B = A0.copy(), B0.copy()
     rc = api._run_poismf(csr[0], csr[1], csr[2], csc[0], csc[1], csc[2], A, B, method, args["limit_step"],
                          args["l2_reg"], args["l1_reg"], args["w_mult"], args["step_size"], args["niter"],
@@ -359,20 +364,40 @@ def test_transform_matches_fit_rows(prec):
 
 
 # ------------------------------------------------------------------ long-row path: a workgroup of 8 waves per row
+LONG_ROW_CHILD = r"""
+import sys, numpy as np
+sys.path.insert(0, {root!r})
+from tests import helpers as H
+from tests.test_gpu_parity import gpu_run
+csr, csc, A0, B0 = H.small_problem(3000, 2000, 120000, {k}, {prec}, seed=5, powerlaw=True, empty_rows=(3, 2999))
+A, B, args = gpu_run(csr, csc, A0, B0, {method!r}, 1, {k}, **{kw!r})
+np.save({out!r}, np.concatenate([A.ravel(), B.ravel()]))
+"""
+
+
 @pytest.mark.parametrize("method,k", [("pg", 50), ("cg", 50), ("tncg", 50), ("cg", 100), ("pg", 7), ("tncg", 100)])
-def test_long_row_workgroup_path(prec, method, k, monkeypatch):
+def test_long_row_workgroup_path(prec, method, k, tmp_path):
     """POISMF_HIP_LONGROW_NNZ lowers the threshold above which one row is handled by 8 cooperating wavefronts
     (row_eval.hpp, NW > 1), so the path that the power-law tail of config C5 takes is exercised on a small matrix:
     rows with 65 .. ~10^4 nonzeros go through it, shorter ones through the wave-per-row kernel.  (tncg, k = 100) is config C5's own
     instance: half_sweep_kernel<double,tncg,NW=8,streamed> with the compile-time slot count of PMF_LONG_SPECIAL and the
-    hold-back of the other bins behind a bounded gate kernel (hold_back_gate_kernel; the long rows run on the second stream)."""
-    monkeypatch.setenv("POISMF_HIP_LONGROW_NNZ", "64")
+    hold-back of the other bins behind a bounded gate kernel (hold_back_gate_kernel; the long rows run on the second stream).
+    (The knob is read once per process: the fit runs in a child.)"""
+    import subprocess
+    import sys
     csr, csc, A0, B0 = H.small_problem(3000, 2000, 120000, k, prec, seed=5, powerlaw=True, empty_rows=(3, 2999))
     assert np.diff(csc[2].astype(np.int64)).max() > 2000
     # (tncg: enough evaluations for the fp64 rows to converge at k = 100 too -- a truncated run ends wherever its last accepted step
     # left it, see test_row_lengths_on_both_sides_of_every_hand_over)
     kw = dict(maxupd=60 if k == 50 else (60 if prec else 400)) if method == "tncg" else {}
-    A, B, args = gpu_run(csr, csc, A0, B0, method, 1, k, **kw)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "AB.npy")
+    env = dict(os.environ, POISMF_HIP_LONGROW_NNZ="64")
+    subprocess.run([sys.executable, "-c", LONG_ROW_CHILD.format(root=root, k=k, prec=prec, method=method, kw=kw, out=out)], check=True, env=env,
+                   cwd=root, timeout=900)
+    AB = np.load(out)
+    A, B = AB[:A0.size].reshape(A0.shape), AB[A0.size:].reshape(B0.shape)
+    args = run_args(method, 1, k, **kw)
     Ar, Br = oracle_run(prec, csr, csc, A0, B0, method, args)
     if method == "pg" and prec and np.isfinite(Ar).all():
         assert H.scaled_err(A, Ar) <= 1e-4 and H.scaled_err(B, Br) <= 1e-4
