@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- nonzeros/sec per full A+B sweep of the factor-update hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--method pg|cg|tncg] [--maxupd M] [--fp64] [--no-cpu] [--no-extra]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--method pg|cg|tncg] [--maxupd M] [--fp64] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-extra]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,24 +12,32 @@ included) on synthetic data that is already resident in HBM when the timed regio
 Workload (every N): the matrix BASELINE.json quotes the metric on -- uniform 1 000 000 x 100 000, 1e8 triplets
 (seed 1; ~9.995e7 nonzeros after duplicate summing), k = 50 (configs C3 / C4).  The headline line is method = pg,
 fp32, maxupd 10, with hyper-parameters that keep the factors alive (PG_LIVE: l2 1e3, step 1e-9) -- the reference's Python
-defaults (l2 1e9, step 1e-7) zero this matrix's factors within the first sweeps, so a run on them computes nothing; at N = 1
-`extra` carries the other points of the metric on the SAME matrix, each with its own roofline block: pg with maxupd = 1 (the
-bandwidth point, R's default), pg with the reference's defaults (same work per sweep), cg and tncg fp32 (the solvers config
+defaults (l2 1e9, step 1e-7) zero this matrix's factors within the first sweeps, so a run on them computes nothing; with --full
+at N = 1 `extra` carries the other points of the metric on the SAME matrix, each with its own roofline block: pg with
+maxupd = 1 (the bandwidth point, R's default), pg with the reference's defaults (same work per sweep), cg and tncg fp32 (the solvers config
 C4's matrix is not quoted on, for completeness), cg fp64 (config C3) -- and `tncg_f64_c5`: config C5's own matrix (Last.FM-shaped
 358 858 x 160 112, power-law item degrees, k = 100, tncg fp64, l2 1e3, maxupd 1500), steady-state sweeps.  `--steps K` is the
 number of timed sweeps of the headline and `ms_per_step` the wall time of one of them; `--dump-outputs DIR` writes the factors
-the headline's last timed sweep left (see dump_outputs): the inputs are seeded, so two builds can be compared output for output.  Every block carries the
-HBM roofline of SURVEY.md 8(d) AND a vector-ALU roofline (`roofline.valu`: the flops the reference's arithmetic needs for the
-decisions the solvers took, against the fp32 / fp64 vector peak) -- the multi-pass solvers are not HBM-bound.
+the headline's last timed sweep left (see dump_outputs): the inputs are seeded, so two builds can be compared output for output.
+Every block carries the HBM roofline of SURVEY.md 8(d); with --full also a vector-ALU roofline (`roofline.valu`: the flops
+the reference's arithmetic needs for the decisions the solvers took, against the fp32 / fp64 vector peak) -- the multi-pass
+solvers are not HBM-bound.
 N > 1 is STRONG scaling of that one matrix: A rows and B rows are cut into per-rank ranges with balanced nonzero
 counts, every rank builds its CSR / CSC shards on its GPU from the triplets, both factors are replicated, and
 after each half the updated rows go to every peer over RCCL (poismf_amd/dist.py).
 
 Rank 0 prints ONE JSON line (see the driver contract); `roofline` prices the row-update kernels against HBM
-peak with SURVEY.md 8(d)'s algorithmic bytes, `cpu_baseline` is the compiled reference (oracle/_ref, kind
-"reference") timed on this box's host cores on the same matrix (steady state: the difference of a 2-iteration
-and a 1-iteration run).  `roofline.by_config` / `cpu_baseline.by_config` put the three lines of the metric side by side:
-PG with hyper-parameters that keep the factors alive (the headline), PG with the reference's defaults, CG fp64.
+peak with SURVEY.md 8(d)'s algorithmic bytes.
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the K steps, writes the outputs if
+--dump-outputs is given and prints the line (the HBM roofline of the timed region included: it takes no run of its own).
+--full adds everything else, as one run: the factors' health (`results_finite`, `results_alive`), a profiled pass after the
+timed one (per-launch and vector-ALU rooflines, multi-GPU exchange times), the other lines of the metric and config C5
+(`extra`, `roofline.by_config`; --no-extra leaves them out), and at N = 1 `cpu_baseline`, the compiled reference (oracle/_ref,
+kind "reference") timed on the host's cores on the same matrix (steady state: the difference of a 2-iteration and a
+1-iteration run), with the drop-in call's timing (`extra.run_poismf_abi`; --no-cpu leaves both out).
+`roofline.by_config` / `cpu_baseline.by_config` put the three lines of the metric side by side: PG with hyper-parameters that
+keep the factors alive (the headline), PG with the reference's defaults, CG fp64.
 """
 import argparse
 import json
@@ -132,11 +140,12 @@ class Job:
         self.A0, self.B0 = harness.initialize_matrices(self.dimA, self.dimB, k, use_float, 1)
         self.nnz_local = (self.be.sess.nnz(0), self.be.sess.nnz(1))
 
-    def run(self, method, maxupd, steps, warmup, l2=None, step0=1e-7, profile_steps=None, keep_factors=False):
-        """warmup + `steps` timed sweeps with profiling OFF (the product configuration), then a separate profiled pass
-        (HIP events around the row-kernel launches of each half, per-row pass counters) of `profile_steps` sweeps from
-        the same starting point for the kernel time and the pass-weighted traffic.  keep_factors: the result also carries
-        `factors`, the host (A, B) the last timed sweep left."""
+    def run(self, method, maxupd, steps, warmup, l2=None, step0=1e-7, profile_steps=None, keep_factors=False, profile=True):
+        """warmup + `steps` timed sweeps with profiling OFF (the product configuration), then -- with `profile` -- a check of the
+        factors (`finite`, `alive`) and a separate profiled pass (HIP events around the row-kernel launches of each half, per-row pass
+        counters) of `profile_steps` sweeps from the same starting point for the kernel time and the pass-weighted traffic.  Without
+        `profile` the result carries the timing alone.  keep_factors: the result also carries `factors`, the host (A, B) the last
+        timed sweep left."""
         l2d, mu, _ = harness.auto_defaults(method, self.k)
         l2 = l2d if l2 is None else l2
         maxupd = mu if maxupd is None else maxupd
@@ -152,6 +161,9 @@ class Job:
         for _ in range(warmup):
             alt.sweep()
         dt = timed_sweeps(alt, steps, self.device)
+        if not profile:
+            return dict(method=method, maxupd=maxupd, l2=l2, step0=step0, steps=steps, seconds=dt,
+                        factors=sess.get_factors() if keep_factors else None)
         A, B = sess.get_factors()
         finite = bool(np.isfinite(A).all() and np.isfinite(B).all())
         # "finite" only says no NaN / inf; a factor the solver has driven to all zeros is finite too -- report how much is alive
@@ -187,21 +199,27 @@ def roofline_block(job, res, traffic_key=None):
     """HBM roofline of one run, this rank's launches.  `achieved` / `frac`: SURVEY.md 8(d)'s algorithmic bytes of the rank's two
     shards per sweep / the UNPROFILED time of a sweep (the timed region: row kernels + column sums, profiling off).  The
     row-kernel durations (`kernel_ms_*`, `frac_row_kernels`, `launches`) come from a separate profiled pass: HIP events on the
-    stream each launch is issued on, around every row-bin launch and around each half."""
+    stream each launch is issued on, around every row-bin launch and around each half.  A run without that pass (a plain run of
+    bench.py: no --full) gets the HBM roofline of its timed region alone."""
     s = 4 if job.use_float else 8
     K = job.k
     rA, rB = job.rangesA[job.rank], job.rangesB[job.rank]
     b_half = [algorithmic_bytes_half(job.nnz_local[0], rB[1] - rB[0], K, s), algorithmic_bytes_half(job.nnz_local[1], rA[1] - rA[0], K, s)]
-    k_ms_half = [res["kernel_ms"][w][0] / res["psteps"] for w in (0, 1)]
-    k_ms = sum(k_ms_half)
     sweep_ms = res["seconds"] / res["steps"] * 1e3
     achieved = sum(b_half) / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
+    traffic, traffic_source = traffic_from_profiles(traffic_key)
+    if "kernel_ms" not in res:
+        return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_source": traffic_source, "sweep_ms_unprofiled": sweep_ms, "algorithmic_bytes_per_sweep": int(sum(b_half)),
+                "note": "achieved / frac = algorithmic bytes of one sweep / the wall time of one timed sweep; the vector-ALU roofline, the "
+                        "row-kernel times and launches[] come from a profiled pass of their own (bench.py --full)"}
+    k_ms_half = [res["kernel_ms"][w][0] / res["psteps"] for w in (0, 1)]
+    k_ms = sum(k_ms_half)
     achieved_k = sum(b_half) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
     rows = (rA[1] - rA[0]) + (rB[1] - rB[0])
     passes = res["ev_stats"][0][0] + res["ev_stats"][1][0]
     nnzp = res["ev_stats"][0][1] + res["ev_stats"][1][1]
     gb = nnzp * K * s / res["psteps"] / 1e9
-    traffic, traffic_source = traffic_from_profiles(traffic_key)
     valu = valu_block(job, res, sweep_ms)
     # per launch: algorithmic bytes of the rows it covers / its average duration
     launches = []
@@ -462,16 +480,18 @@ def compact_line(full):
     out["roofline"] = {"bound": rf.get("bound"), "achieved": _r(rf.get("achieved")), "peak": rf.get("peak"), "unit": rf.get("unit"),
                        "frac": _r(rf.get("frac")), "traffic": _r(rf.get("traffic")),
                        "traffic_source": None if src is None else ("separate rocprofv3 --pmc run, profiles/hbm_traffic.json"
-                                                                   if rf.get("traffic") is not None else "stale: not quoted"),
-                       "dominant_kernel": {"kernel": dom.get("kernel"), "avg_ms": _r(dom.get("avg_ms")), "frac": _r(dom.get("frac"))},
-                       "valu": {"frac": _r((rf.get("valu") or {}).get("frac"))}}
+                                                                   if rf.get("traffic") is not None else "stale: not quoted")}
+    if "valu" in rf:   # (from the profiled pass of a --full run)
+        out["roofline"]["dominant_kernel"] = {"kernel": dom.get("kernel"), "avg_ms": _r(dom.get("avg_ms")), "frac": _r(dom.get("frac"))}
+        out["roofline"]["valu"] = {"frac": _r((rf.get("valu") or {}).get("frac"))}
     if cb:
         out["cpu_baseline"] = {"value": _r(cb.get("value")), "unit": "nnz/s", "cores": cb.get("cores"), "threads": cb.get("threads"),
                                "physical_cores": cb.get("physical_cores"), "kind": cb.get("kind"),
                                "seconds_per_sweep": _r(cb.get("seconds_per_sweep")),
                                "sample": "whole workload matrix, run_poismf 2 iters minus 1, bound OpenMP threads"}
-    alive = full.get("results_alive") or {}
-    out["results_alive"] = {k_: _r(alive.get(k_)) for k_ in ("A_nonzero_frac", "B_nonzero_frac")}
+    if "results_alive" in full:
+        alive = full["results_alive"] or {}
+        out["results_alive"] = {k_: _r(alive.get(k_)) for k_ in ("A_nonzero_frac", "B_nonzero_frac")}
     byc_cpu = cb.get("by_config") or {}
     byc = {}
     for name, b in (rf.get("by_config") or {}).items():
@@ -479,7 +499,8 @@ def compact_line(full):
         if name in byc_cpu:
             e["cpu_s"] = _r(byc_cpu[name].get("seconds_per_sweep"), 3)
         byc[name] = e
-    out["by_config"] = byc
+    if "by_config" in rf:
+        out["by_config"] = byc
     abi = (full.get("extra") or {}).get("run_poismf_abi")
     if abi:
         out["run_poismf_abi"] = {"first_iter_ms": _r(abi.get("abi_ms_first_iter")), "per_extra_iter_ms": _r(abi.get("abi_ms_per_extra_iter")),
@@ -587,8 +608,12 @@ def main():
     ap.add_argument("--fp64", action="store_true")
     ap.add_argument("--workload", default="C4", choices=sorted(WORKLOADS))
     ap.add_argument("--segments", type=int, default=None, help="segments of the A half (multi-GPU exchange / compute overlap)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the factors' health, a profiled pass (per-launch and "
+                         "vector-ALU rooflines, exchange times), the other lines of the metric, config C5, the CPU baselines and the "
+                         "drop-in call's timing")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines and the drop-in call's timing")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other lines of the metric and config C5")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the factors the headline's last timed sweep left as DIR/<name>.npy (at most 64 MB: a seeded row sample "
                          "of a factor that does not fit)")
@@ -641,7 +666,7 @@ def main():
     segA = a.segments if a.segments is not None else (4 if world > 1 else 1)
     job = Job(trip, rangesA, rangesB, rank, device, use_float, segA)
     hkw = PG_LIVE if a.method == "pg" else {}
-    res = job.run(a.method, a.maxupd, a.steps, a.warmup, keep_factors=bool(a.dump_outputs) and rank == 0, **hkw)
+    res = job.run(a.method, a.maxupd, a.steps, a.warmup, keep_factors=bool(a.dump_outputs) and rank == 0, profile=a.full, **hkw)
     prec = "f32" if use_float else "f64"
     if res["factors"] is not None:
         A, B = res.pop("factors")
@@ -662,7 +687,7 @@ def main():
     single = world == 1
     extra = {}
     c5 = None
-    if single and not a.no_extra:
+    if single and a.full and not a.no_extra:
         # the other points of the metric, same matrix, same session where the precision matches
         # (name, method, fp32?, maxupd, timed sweeps, warm-up sweeps, overrides): TNCG's first sweeps from the random start cost a
         # multiple of the later ones -- two warm-up sweeps, so that the timed ones are steady state
@@ -719,32 +744,33 @@ def main():
                        "setup_s": {"triplets": gen_s, "session_from_coo": headline_setup_s}},
             "roofline": headline_roofline,
             # multi-GPU: what the communicator reports (ranks a sum of ones reached -- over RCCL when the backend is nccl), every rank's
-            # nonzeros, and the device time of rank 0's exchanges per sweep in a separate profiled pass (on the stream each is issued on)
+            # nonzeros, and (--full) the device time of rank 0's exchanges per sweep in a separate profiled pass (on the stream each is issued on)
             "rccl_ranks": comm["rccl_ranks"] if comm else None,
-            "comm": dict(comm, exchange=res["exchange"]) if comm else None,
-            "results_finite": res["finite"],
-            "results_alive": dict(res["alive"], note="results_finite = no NaN / inf anywhere; it does NOT mean the factors are alive: with the "
-                                  "reference's Python defaults for pg (l2 1e9, step 1e-7) the reference's own arithmetic drives this matrix's "
-                                  "factors to exact zeros within the first sweeps (DESIGN.md 6.2) -- A/B_nonzero_frac say how much is left.  The "
-                                  "pg headline therefore runs with l2 1e3, step 1e-9 (same work per sweep, factors stay positive); "
-                                  "by_config.pg_maxupd10_f32_defaults times the same kernels on the defaults"),
+            "comm": dict(comm, exchange=res["exchange"]) if comm and a.full else comm,
         }
-        if extra:
-            out["extra"] = extra
-        # the lines of the metric side by side in the parsed line: PG with hyper-parameters that keep the factors alive (the
-        # headline), PG with the reference's defaults (same work per sweep), CG / TNCG fp32, CG fp64 (config C3), TNCG fp64 on
-        # config C5's matrix -- each with its two roofline fractions
-        head_name = f"{a.method}_maxupd{res['maxupd']}_{prec}_{'finite' if hkw else 'defaults'}"
-        byc = {head_name: {"value": out["value"], "ms_per_step": out["ms_per_step"], "frac": headline_roofline["frac"],
-                           "frac_valu": headline_roofline["valu"]["frac"],
-                           "frac_row_kernels": headline_roofline["frac_row_kernels"], "dominant_kernel": headline_roofline["dominant_kernel"]}}
-        for name, blk in extra.items():
-            byc[name] = {"value": blk["value"], "ms_per_step": blk["ms_per_step"], "frac": blk["roofline"]["frac"],
-                         "frac_valu": blk["roofline"]["valu"]["frac"],
-                         "frac_row_kernels": blk["roofline"]["frac_row_kernels"], "dominant_kernel": blk["roofline"]["dominant_kernel"]}
-        out["roofline"]["by_config"] = byc
+        if a.full:
+            out["results_finite"] = res["finite"]
+            out["results_alive"] = dict(res["alive"], note="results_finite = no NaN / inf anywhere; it does NOT mean the factors are alive: with "
+                                        "the reference's Python defaults for pg (l2 1e9, step 1e-7) the reference's own arithmetic drives this "
+                                        "matrix's factors to exact zeros within the first sweeps (DESIGN.md 6.2) -- A/B_nonzero_frac say how much "
+                                        "is left.  The pg headline therefore runs with l2 1e3, step 1e-9 (same work per sweep, factors stay "
+                                        "positive); by_config.pg_maxupd10_f32_defaults times the same kernels on the defaults")
+            if extra:
+                out["extra"] = extra
+            # the lines of the metric side by side in the parsed line: PG with hyper-parameters that keep the factors alive (the
+            # headline), PG with the reference's defaults (same work per sweep), CG / TNCG fp32, CG fp64 (config C3), TNCG fp64 on
+            # config C5's matrix -- each with its two roofline fractions
+            head_name = f"{a.method}_maxupd{res['maxupd']}_{prec}_{'finite' if hkw else 'defaults'}"
+            byc = {head_name: {"value": out["value"], "ms_per_step": out["ms_per_step"], "frac": headline_roofline["frac"],
+                               "frac_valu": headline_roofline["valu"]["frac"],
+                               "frac_row_kernels": headline_roofline["frac_row_kernels"], "dominant_kernel": headline_roofline["dominant_kernel"]}}
+            for name, blk in extra.items():
+                byc[name] = {"value": blk["value"], "ms_per_step": blk["ms_per_step"], "frac": blk["roofline"]["frac"],
+                             "frac_valu": blk["roofline"]["valu"]["frac"],
+                             "frac_row_kernels": blk["roofline"]["frac_row_kernels"], "dominant_kernel": blk["roofline"]["dominant_kernel"]}
+            out["roofline"]["by_config"] = byc
         final_line = out
-    if single and not a.no_cpu and rank == 0:
+    if single and a.full and not a.no_cpu and rank == 0:
         job.close()
         cb = cpu_baseline(trip, a.method, use_float, a.maxupd, **hkw)
         final_line["cpu_baseline"] = cb

@@ -7,8 +7,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
-# 1. the default command as the driver runs it
+B="python3 $R/bench.py --full"   # (the profiled pass, bench_full.json and the 2 x sweeps below need --full)
+# 1. the full bench command: every line of the metric, its profiled rooflines and the CPU legs
 $B > $OUT/bench_default.log 2>&1; grep '^{"metric"' $OUT/bench_default.log | tail -1 > $OUT/bench_line.json; cp $R/bench_full.json $OUT/bench_full.json
 # 2. one workload per command: kernel trace, then counters.  Each run makes warmup + steps timed sweeps and the same again
 #    with the session's own event timing on (the pass `roofline` is computed from): 2 x (1 + STEPS) sweeps per run.

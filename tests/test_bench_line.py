@@ -63,6 +63,33 @@ def test_compact_line_of_a_minimal_object():
     assert back["n_gpus"] == 8 and back["roofline"]["frac"] == 0.0125 and "cpu_baseline" not in back
 
 
+def test_plain_run_line_carries_the_headline_and_its_timed_roofline_only():
+    """A run without --full makes no profiled pass, checks nothing and runs no other line: roofline_block gives the HBM roofline of
+    the timed region alone, and the line carries the headline keys without the blocks only --full measures."""
+    b = _bench()
+
+    class J:
+        k, use_float, rank = 50, True, 0
+        rangesA, rangesB = [(0, 10 ** 6)], [(0, 10 ** 5)]
+        nnz_local = (99949803, 99949803)
+    res = dict(method="pg", maxupd=10, l2=1e3, step0=1e-9, steps=20, seconds=0.185, factors=None)
+    rf = b.roofline_block(J, res, None)
+    by = b.algorithmic_bytes_half(J.nnz_local[0], 10 ** 5, 50, 4) + b.algorithmic_bytes_half(J.nnz_local[1], 10 ** 6, 50, 4)
+    assert rf["algorithmic_bytes_per_sweep"] == int(by) and abs(rf["sweep_ms_unprofiled"] - 9.25) < 1e-9
+    assert abs(rf["achieved"] - by / 9.25e-3 / 1e9) < 1e-6 and abs(rf["frac"] - rf["achieved"] / 8000.0) < 1e-12
+    assert not {"valu", "dominant_kernel", "launches", "kernel_ms_per_sweep"} & set(rf)
+    full = {"metric": "nonzeros/sec per full A+B sweep", "value": 99949803 * 20 / 0.185, "unit": "nnz/s", "n_gpus": 1, "steps": 20,
+            "warmup": 5, "ms_per_step": 9.25, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic", "config": {"workload": "uniform 1000000x100000, ...", "baseline_config": "C4: x", "sharding": "none"},
+            "roofline": rf, "rccl_ranks": None, "comm": None}
+    back = json.loads(json.dumps(b.compact_line(full), separators=(",", ":")))
+    for key in CONTRACT:
+        assert (key in back) == (key != "cpu_baseline"), key
+    assert back["roofline"]["frac"] == b._r(rf["frac"]) and back["ms_per_step"] == 9.25
+    assert not {"dominant_kernel", "valu"} & set(back["roofline"])
+    assert not {"by_config", "results_alive", "run_poismf_abi", "extra"} & set(back)
+
+
 def test_main_prints_the_compact_line_last():
     src = open(os.path.join(ROOT, "bench.py")).read()
     tail = src[src.rindex("write_full(final_line)"):]

@@ -43,11 +43,12 @@ def test_two_processes_reproduce_the_single_process_result(method, prec, early, 
 def test_bench_gpus_2_launches_itself_and_prints_one_parseable_line():
     """`python3 bench.py --gpus 2` with no launcher around it (WORLD_SIZE unset): the parent starts two fresh ranks before any GPU call,
     relays rank 0's compact line as its LAST stdout line and returns the ranks' exit code.  Two ranks on the one GPU of the test box
-    (POISMF_BENCH_SHARE_GPUS=1, gloo: RCCL refuses two ranks on one device), the metric's matrix shrunk 10 x."""
+    (POISMF_BENCH_SHARE_GPUS=1, gloo: RCCL refuses two ranks on one device), the metric's matrix shrunk 10 x; --full for the exchange
+    times of the profiled pass."""
     import json
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(POISMF_BENCH_SHARE_GPUS="1", POISMF_BENCH_BACKEND="gloo", POISMF_BENCH_SCALE="10", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     last = res.stdout.strip().splitlines()[-1]
