@@ -337,6 +337,14 @@ POISMF_HIP_API size_t poismf_hip_set_device_cache_mb(size_t mb);
 POISMF_HIP_API int poismf_hip_debug_row_eval(real_t *G, double *f, real_t *B, real_t *Bsum, real_t *point, real_t *Xr,
                           sparse_ix *Xr_indptr, sparse_ix *Xr_indices, int k, size_t dimA, real_t l2_reg, real_t w_mult, int which);
 
+/* Testing aid: the planner alone, without a device (no HIP call is made).  A half of `nrows` rows with row_nnz[r] nonzeros each, gathering from a
+ * factor of dimF rows, is cut into nseg segments as poismf_hip_session_set_segments cuts it, each segment's rows sorted by length (longest
+ * first) and binned; buf receives the plan of one half-sweep call over segment `seg` (seg < 0: over all segments, as poismf_hip_half_sweep
+ * runs them) on a device of num_cu compute units, worded as poismf_hip_session_plan words it and in launch order.  method, maxupd, w_mult,
+ * limit_step: as in poismf_hip_params.  Same buffer convention as poismf_hip_session_plan. */
+POISMF_HIP_API size_t poismf_hip_debug_plan(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
+                          size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
+
 /* Number of nonzeros held by this session for half `which` (shard only). */
 POISMF_HIP_API size_t poismf_hip_session_nnz(poismf_hip_session *s, int which);
 

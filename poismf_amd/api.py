@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
-    "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk",
+    "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
 )
 
 
@@ -320,6 +320,21 @@ def debug_row_eval(B, Bsum, point, Xr_indptr, Xr_indices, Xr, l2_reg, w_mult=1.,
     if ret:
         raise MemoryError("poismf_hip_debug_row_eval failed")
     return f, G
+
+
+def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256):
+    """Testing aid (include/poismf_hip.h, poismf_hip_debug_plan): the launches the planner gives a half whose rows have row_nnz nonzeros,
+    cut into nseg segments, for one call over segment `seg` (< 0: all of them): [(kernel instance, rows), ...].  Needs no GPU."""
+    lib = load_library(use_float)
+    row_nnz = np.ascontiguousarray(row_nnz, dtype=np.uint32)
+    real = C.c_float if use_float else C.c_double
+    fn = lib.poismf_hip_debug_plan
+    fn.restype = C.c_size_t
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, real, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
+    buf = C.create_string_buffer(int(fn(*args, None, 0)) + 1)
+    fn(*args, buf, len(buf))
+    return [(name.strip(), int(rows)) for name, rows in (item.rsplit(" rows=", 1) for item in buf.value.decode().split(";") if item.strip())]
 
 
 class PoisMF:

@@ -192,13 +192,14 @@ int poismf_hip_device_coo_to_cs(const unsigned* d_major, const unsigned* d_minor
 namespace {
 
 constexpr size_t LDS_RESIDENT_LIMIT = 64 * 1024;  // largest tile a single wave may claim
-constexpr int TEAM_LAUNCH_MAX = 32;   // team launches per half-sweep call (one per team size: <= 22 lane-team sizes + the giant rows + the register teams' shapes)
+constexpr int TEAM_LAUNCH_MAX = 32;   // team launches per pass of a half-sweep (one per team shape of a segment: seven lane-team sizes + the giant rows, or the register
+                                      // teams' five shapes; half_sweep_impl refuses a plan with more)
 // layout of poismf_hip_session::d_team_err, in words: [0] team launches that gave up and were re-run since the word was last read, [1] spare,
 // [2 + i] set by team launch i of the current half when it gives up, [2 + TEAM_LAUNCH_MAX + i] rows launch i found unchanged (TNCG early stop:
 // added to the half's counter only when the launch's results are kept)
 constexpr int TEAM_ERR_WORDS = 2 + 2 * TEAM_LAUNCH_MAX;
-constexpr int MAX_LAUNCHES = 256;  // launches per half-sweep call that get a row-queue head: length classes are multiples of 16 up to 256, of 64
-                                   // up to 2048, then powers of two (<= 60 per segment); a call over several segments concatenates their bins
+constexpr int MAX_LAUNCHES = 256;  // launches per pass of a half-sweep that get a row-queue head: length classes are multiples of 16 up to 256, of 64
+                                   // up to 2048, then powers of two (<= 60 per segment, and a pass is one segment: plan_call)
 
 struct Bin {
     unsigned begin, count;  // range of the nnz-sorted permutation
@@ -380,6 +381,22 @@ unsigned length_class(unsigned n)
     return cls;
 }
 
+// first row of segment j when a shard of nloc rows is cut into nseg segments (== dist.segment_of)
+inline size_t segment_cut(size_t nloc, int j, int nseg) { return nloc * (size_t)j / (size_t)nseg; }
+
+// The length bins of one segment: len[lo .. hi) are its rows' lengths, sorted (longest first).
+std::vector<Bin> bins_of(const unsigned* len, size_t lo, size_t hi)
+{
+    std::vector<Bin> bins;
+    for (size_t i = lo; i < hi; i++) {
+        const unsigned cls = length_class(len[i]);
+        if (bins.empty() || cls != bins.back().cls) bins.push_back({ (unsigned)i, 0u, len[i], cls, 0ull });   // sorted: the first row of a bin is its longest
+        bins.back().count++;
+        bins.back().nnz += len[i];
+    }
+    return bins;
+}
+
 // h.d_indptr (shard-local, nloc + 1), h.d_indices, h.d_values are on the device: per segment, sort the rows by length
 // (longest first, equal lengths in row order), build the row descriptors on the device and the length bins on the host
 // (from the sorted lengths: 4 bytes per row come back over PCIe, the only host work left is one linear scan).
@@ -396,7 +413,7 @@ int finish_half_launch(Half& h, hipStream_t stream, HalfPending& pend, int nseg 
     if (nloc == 0) { for (int j = 0; j < nseg; j++) h.segs.push_back({ 0u, 0u, {} }); return 0; }
     HIP_TRY(pmf_alloc(&pend.d_len, sizeof(unsigned) * nloc, stream));
     for (int j = 0; j < nseg; j++) {
-        const size_t lo = nloc * (size_t)j / (size_t)nseg, hi = nloc * (size_t)(j + 1) / (size_t)nseg;   // == dist.segment_of
+        const size_t lo = segment_cut(nloc, j, nseg), hi = segment_cut(nloc, j + 1, nseg);
         h.segs.push_back({ (unsigned)lo, (unsigned)hi, {} });
         if (hi > lo && poismf_hip_device_sort_rows(h.d_indptr + lo, hi - lo, (unsigned)lo, h.d_perm + lo, pend.d_len + lo, stream)) {
             pmf_free(pend.d_len, stream);
@@ -426,14 +443,7 @@ int finish_half_collect(Half& h, hipStream_t stream, HalfPending& pend)
     pmf_free(pend.d_len, stream);
     pend = HalfPending();
     HIP_TRY(e);
-    for (auto& sg : h.segs) {
-        for (size_t i = sg.row_lo; i < sg.row_hi; i++) {
-            const unsigned cls = length_class(len[i]);
-            if (sg.bins.empty() || cls != sg.bins.back().cls) sg.bins.push_back({ (unsigned)i, 0u, len[i], cls, 0ull });   // sorted: the first row of a bin is its longest
-            sg.bins.back().count++;
-            sg.bins.back().nnz += len[i];
-        }
-    }
+    for (auto& sg : h.segs) sg.bins = bins_of(len.data(), sg.row_lo, sg.row_hi);
     return 0;
 }
 int finish_half(Half& h, hipStream_t stream, int nseg = 1)
@@ -651,9 +661,28 @@ const PlanKnobs& plan_knobs()
     return kn;
 }
 
+// Bytes of a factor row of k elements in the line-padded gather copies (== k * sizeof(real_t): the session keeps no such copy).
+size_t padded_row_bytes(size_t k)
+{
+    const size_t rowb = k * sizeof(real_t);
+    size_t padb = (rowb + 127) / 128 * 128;
+    static const bool no_pad = getenv("POISMF_HIP_NO_PAD") != nullptr;  // testing knob
+    const bool line_pad = !no_pad && padb != rowb && (double)padb <= 0.9 * (double)(rowb + 120);
+    // and a row that does not end on a 16-byte slot boundary is padded to one in any case: the gathers fetch whole
+    // slots and rely on the excess of the last one being zero
+    if (!line_pad) padb = (rowb + 15) / 16 * 16;
+    return padb;
+}
+
 // What plan_half decides from besides the bins: factor dimension, rows and row stride of the gathered factor; the solver as planned (POISMF_EVAL
 // plans like CG), PG with one pass over each row, limit_step; poismf_hip_session::teams_off; CUs.
 struct PlanCtx { size_t k, dimF, ldF; int pm; bool single_pass, limit_step, teams_off; int num_cu; };
+PlanCtx plan_ctx(size_t k, size_t dimF, int method, size_t maxupd, real_t w_mult, bool limit_step, bool teams_off, int num_cu)
+{
+    const int pm = method == POISMF_EVAL ? POISMF_CG : method;   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
+    const bool single_pass = method == POISMF_PG && maxupd <= 1 && w_mult == (real_t)1.;
+    return { k, dimF, padded_row_bytes(k) / sizeof(real_t), pm, single_pass, limit_step, teams_off, num_cu };
+}
 
 // A launch as planned: what launch_one_here needs, plus the rows it covers and their tile geometry.  The issue loop fills in the stream,
 // grid and LDS.
@@ -698,9 +727,6 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
         L.begin = b.begin; L.count = b.count; L.nnz = b.nnz; L.geom = g; L.geom.zero_row = (unsigned)c.dimF; L.geom.ldF = (int)c.ldF;
         launches.push_back(L);
     };
-    // (every team launch of a call gets a row-queue head, an error word and a buffer area of its own: no more than TEAM_LAUNCH_MAX of them; a bin
-    // that would open one more takes the path it has without teams -- asked before whether the bin would join the previous launch)
-    auto team_room = [&]() { return std::count_if(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_team(L.engine); }) < TEAM_LAUNCH_MAX - 1; };
     // register engine: factor rows of at most 16 slots (32 for doubles, two slots per lane), and 24-bit row ids / 32-bit
     // byte offsets into the factor
     const int reg_ns = reg_slots_per_lane((c.k * sizeof(real_t) + 15) / 16);
@@ -737,7 +763,7 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
             // streamed kernel (round 5a)
             int lane_team = 0;
             if (ls.waves == 0 && sizeof(real_t) == 8 && g.s_load == 50 && pm == POISMF_TNCG && !kn.no_lane_teams && !no_team && !kn.static_rows &&
-                b.cls > 384 && b.cls <= LONG_ROW_NNZ && team_room()) {
+                b.cls > 384 && b.cls <= LONG_ROW_NNZ) {
                 const int m = (int)((b.cls + 383u) / 384u);
                 if (m >= 2 && c.num_cu >= 2 * m) { ls = LaneShape{ 1, 0, 0, 4, 0, 32 }; lane_team = m; }
             }
@@ -766,7 +792,7 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
             // rows whose tile fits the registers of two to four CUs, not of one: a team per row (reg_eval.hpp, M_ > 1) -- by the class bound,
             // never by the longest row that happens to be in the bin: a row's share of the tile (my_share: C = ceil(nnz / (NW M))) -- and with it
             // its summation order -- must not depend on its shard
-            const TeamShape ts = team_room() ? team_shape_for(b.cls) : TeamShape{};
+            const TeamShape ts = team_shape_for(b.cls);
             if (ts.members > 0) {
                 place(b, Engine::RegTeam, g, TEAM_NW, ts.steps, ts.members, LaneShape{},
                       [&](const PlannedLaunch& P) { return P.team == ts.members && P.reg_S == ts.steps; });
@@ -787,8 +813,7 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
         if (!no_long && long_fits && b.cls > long_thr_here) {
             // TNCG re-streams such a row for every evaluation: a team of GT_M workgroups per row (row_eval.hpp, TM; POISMF_HIP_NO_GIANT_TEAMS=1:
             // one workgroup per row, rounds 1-4).  Decided by the solver alone: a row's arithmetic must not depend on its shard.
-            const bool giant = !kn.no_giant_teams && !no_team && !kn.static_rows && pm == POISMF_TNCG && b.cls > kn.giant_nnz && team_room() &&
-                               c.num_cu >= 2 * GT_M;
+            const bool giant = !kn.no_giant_teams && !no_team && !kn.static_rows && pm == POISMF_TNCG && b.cls > kn.giant_nnz && c.num_cu >= 2 * GT_M;
             place(b, giant ? Engine::Giant : Engine::LdsLong, gl, LONG_NW, 0, giant ? GT_M : 0, LaneShape{}, [](const PlannedLaunch&) { return true; });
             continue;
         }
@@ -822,6 +847,33 @@ std::string launch_name(int method, const PlannedLaunch& L)
             break;
     }
     return txt;
+}
+
+// ... and as poismf_hip_session_plan lists it
+std::string plan_item(int method, const PlannedLaunch& L) { return launch_name(method, L) + " rows=" + std::to_string(L.count) + ";"; }
+
+// The launches of one half-sweep call over segment `seg` of a half, or (seg < 0) over all of its segments, as the passes the call makes: one
+// per segment, each planned from that segment's bins alone and run as a call over that segment would run it.  So a row's launch -- its engine,
+// instance and team -- does not depend on which segments a call names, and the per-launch resources (row-queue heads, team areas and words)
+// are a segment's however many segments there are.
+std::vector<std::vector<PlannedLaunch>> plan_call(const std::vector<Half::Segment>& segs, int seg, const PlanCtx& c)
+{
+    std::vector<std::vector<PlannedLaunch>> passes;
+    for (size_t j = 0; j < segs.size(); j++)
+        if (seg < 0 || (size_t)seg == j) passes.push_back(plan_half(segs[j].bins, c));
+    if (passes.empty()) passes.emplace_back();   // (a half without segments: the prologue and the epilogue run all the same)
+    return passes;
+}
+
+// a text report into the caller's buffer: NUL-terminated, truncated to cap bytes; returns the untruncated length
+size_t copy_text(const std::string& t, char* buf, size_t cap)
+{
+    if (cap > 0) {
+        const size_t n = std::min(cap - 1, t.size());
+        memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return t.size();
 }
 
 // The stream a launch runs on: `bin` is the balanced stream of the one-wave bins, `longs` the one the long rows share.  (PG has no one-wave
@@ -999,7 +1051,7 @@ int issue_half(poismf_hip_session* s, int which, int method, const std::vector<P
     for (size_t i = 0; i < launches.size(); i++) {
         const PlannedLaunch& L = launches[i];
         const std::string name = launch_name(method, L);
-        s->last_plan[which] += name + " rows=" + std::to_string(L.count) + ";";
+        s->last_plan[which] += plan_item(method, L);
         HalfArgs<real_t> a = base;
         a.perm_begin = L.begin; a.nrows = L.count; a.geom = L.geom;
         a.team_members = (unsigned)std::max(1, L.team);
@@ -1070,10 +1122,10 @@ int issue_half(poismf_hip_session* s, int which, int method, const std::vector<P
     return 0;
 }
 
-// The half's epilogue: the join; per team launch a restore and a streamed re-run that return at once unless the launch's error word is set,
+// A pass's epilogue: the join; per team launch a restore and a streamed re-run that return at once unless the launch's error word is set,
 // then the fold -- on a chip that has nothing else resident; the early-stop counter.
 int half_epilogue(poismf_hip_session* s, const Half& h, int method, const HalfArgs<real_t>& base, bool forked, const std::vector<TeamSlot>& tslots,
-                  const std::vector<TeamRerun>& reruns, const ProfRec& rec, size_t* n_unchanged)
+                  const std::vector<TeamRerun>& reruns, const ProfRec* rec, size_t* n_unchanged)
 {
     if (forked) {
         HIP_TRY(hipEventRecord(s->ev_join, s->aux_stream));
@@ -1092,9 +1144,9 @@ int half_epilogue(poismf_hip_session* s, const Half& h, int method, const HalfAr
         hipLaunchKernelGGL(team_fold_kernel, dim3(1), dim3(1), 0, s->stream, s->d_team_err, (int)tslots.size(), base.early_stop ? s->d_counter : nullptr);
         HIP_TRY(hipGetLastError());
     }
-    if (s->profiling) {
-        HIP_TRY(hipEventRecord(rec.t1, s->stream));
-        s->prof.push_back(rec);
+    if (rec != nullptr) {   // (the call's last pass)
+        HIP_TRY(hipEventRecord(rec->t1, s->stream));
+        s->prof.push_back(*rec);
     }
     if (base.early_stop && n_unchanged != nullptr) {
         unsigned cnt = 0;
@@ -1171,13 +1223,7 @@ static poismf_hip_session* session_alloc(int device, void* stream, size_t dimA, 
     {
         // A gathered row of B bytes at an arbitrary 8-byte offset touches (B + 120) / 128 lines of 128 bytes on average;
         // in a copy whose rows start on line boundaries it touches ceil(B / 128).  k = 50 fp32: 2.5 -> 2 lines.
-        const size_t rowb = k * sizeof(real_t);
-        size_t padb = (rowb + 127) / 128 * 128;
-        static const bool no_pad = getenv("POISMF_HIP_NO_PAD") != nullptr;  // testing knob
-        const bool line_pad = !no_pad && padb != rowb && (double)padb <= 0.9 * (double)(rowb + 120);
-        // and a row that does not end on a 16-byte slot boundary is padded to one in any case: the gathers fetch whole
-        // slots and rely on the excess of the last one being zero
-        if (!line_pad) padb = (rowb + 15) / 16 * 16;
+        const size_t rowb = k * sizeof(real_t), padb = padded_row_bytes(k);
         if (padb != rowb) {
             s->ld = padb / sizeof(real_t);
             const size_t pslack = padb + 16;
@@ -1508,9 +1554,9 @@ int poismf_hip_session_decision_stats(poismf_hip_session* s, int which, unsigned
 
 // bsum_override != nullptr: use this HOST k-vector (already carrying l1 and any PG scaling) instead of the column
 // sums of the fixed factor; neg_step_override then replaces -step_size as the PG scale of the per-row Bsum_w.
-// seg < 0: every segment of the shard; seg >= 0: that segment only -- segment 0 then also runs the prologue (column sums,
-// refresh of the padded gather copy, reset of the early-stop counter), and the counter is read by whichever call passes
-// n_unchanged (the last segment).
+// seg < 0: every segment of the shard, one pass after the other (plan_call); seg >= 0: that segment only -- segment 0 then also runs the
+// prologue (column sums, refresh of the padded gather copy, reset of the early-stop counter), and the counter is read by whichever call
+// passes n_unchanged (the last segment).  Either way a segment's launches are the same launches.
 static int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div,
                            size_t* n_unchanged, const real_t* bsum_override, real_t neg_step_override, real_t neg_step2 = (real_t)1,
                            int seg = -1)
@@ -1519,51 +1565,55 @@ static int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_pa
     which = which ? 1 : 0;
     Half& h = s->half[which];
     if (seg >= (int)h.segs.size()) return 1;
-    const bool prologue = seg <= 0;
     const bool early_stop = (p->method == POISMF_TNCG) && p->early_stop && (n_unchanged != nullptr || seg >= 0);
-    HalfArgs<real_t> base;
-    if (half_prologue(s, which, p, step_size, cnst_div, prologue, early_stop, bsum_override, neg_step_override, neg_step2, base)) return 1;
-    ProfRec rec{};
-    if (s->profiling) {
-        HIP_TRY(hipEventCreate(&rec.t0));
-        HIP_TRY(hipEventCreate(&rec.t1));
-        rec.which = which;
-        HIP_TRY(hipEventRecord(rec.t0, s->stream));
-    }
-
-    std::vector<Bin> bins;   // of the segments this call runs, in order
-    for (size_t j = 0; j < h.segs.size(); j++)
-        if (seg < 0 || (size_t)seg == j) bins.insert(bins.end(), h.segs[j].bins.begin(), h.segs[j].bins.end());
     const bool is_pg = p->method == POISMF_PG;
-    const int pm = p->method == POISMF_EVAL ? POISMF_CG : p->method;   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
-    const bool single_pass = is_pg && p->maxupd <= 1 && p->w_mult == (real_t)1.;
-    const PlanCtx c{ s->k, which ? s->dimB : s->dimA, s->ld != 0 ? s->ld : s->k, pm, single_pass, p->limit_step != 0, s->teams_off, s->num_cu };
-    const std::vector<PlannedLaunch> launches = plan_half(bins, c);
-
-    const bool dynamic = !is_pg && !plan_knobs().static_rows && launches.size() <= (size_t)MAX_LAUNCHES;
-    // (PG's multi-wave lane launches take ONE ROW PER WORKGROUP, issue_half; persistent workgroups on the queue or with static shares -- rounds 2-4a,
-    // POISMF_HIP_PG_LANE_ROWS -- lost to it, DESIGN.md 6.0, and went in round 6)
-    if (dynamic) HIP_TRY(hipMemsetAsync(s->d_queue, 0, sizeof(unsigned) * MAX_LAUNCHES, s->stream));
-    // The few workgroup-per-row launches of the power-law tail occupy a few dozen CUs for a long time: run them on a second stream beside the
-    // other bins (fork after the column sums, join before anything reads the result) -- NEXT TO the other bins, not after them.  The other bins'
-    // kernels are persistent (a workgroup keeps its CU until the bin's queue is empty): whichever kernel reaches the chip first fills it, and on
-    // config C5 that was the mid-length bin -- the 60 giant rows then waited 260 ms for a CU and ran on their own afterwards (390 ms for what
-    // takes 150 alone).  So every workgroup of a long-row launch counts itself in when it starts, and the main stream waits for that count (a
-    // one-wave gate kernel with a time limit; rounds 3-4a: hipStreamWaitValue32) before it launches anything else.  Arrivals only ever grow, so
-    // a chip that cannot hold the whole launch at once delays the main stream by the gate's 2 ms, no more.
-    const bool forked = !plan_knobs().no_fork && launches.size() > 1 &&
-                        std::any_of(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_long(L.engine); });
-    if (forked) HIP_TRY(hipMemsetAsync(s->d_arrive, 0, sizeof(unsigned), s->stream));
-    std::vector<TeamSlot> tslots;
-    if (prepare_teams(s, h, base, launches, tslots)) return 1;
-    if (forked) {
-        HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
-        HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
+    const PlanCtx c = plan_ctx(s->k, which ? s->dimB : s->dimA, p->method, p->maxupd, p->w_mult, p->limit_step != 0, s->teams_off, s->num_cu);
+    const std::vector<std::vector<PlannedLaunch>> passes = plan_call(h.segs, seg, c);
+    ProfRec rec{};
+    for (size_t i = 0; i < passes.size(); i++) {
+        const std::vector<PlannedLaunch>& launches = passes[i];
+        const bool prologue = seg <= 0 && i == 0, last = i + 1 == passes.size();
+        HalfArgs<real_t> base;
+        if (half_prologue(s, which, p, step_size, cnst_div, prologue, early_stop, bsum_override, neg_step_override, neg_step2, base)) return 1;
+        if (s->profiling && i == 0) {
+            HIP_TRY(hipEventCreate(&rec.t0));
+            HIP_TRY(hipEventCreate(&rec.t1));
+            rec.which = which;
+            HIP_TRY(hipEventRecord(rec.t0, s->stream));
+        }
+        // (every team launch of a pass has a row-queue head, an error word, a tally and a buffer area of its own: the session holds
+        // TEAM_LAUNCH_MAX of each.  A segment has one team launch per team shape, eight at most; a plan with more is refused, never re-planned)
+        if (std::count_if(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_team(L.engine); }) > TEAM_LAUNCH_MAX) {
+            fprintf(stderr, "poismf_hip: a half-sweep pass with more than %d multi-CU row launches\n", TEAM_LAUNCH_MAX);
+            pmf_last_hip_error() = hipErrorInvalidValue;
+            return 1;
+        }
+        const bool dynamic = !is_pg && !plan_knobs().static_rows && launches.size() <= (size_t)MAX_LAUNCHES;
+        // (PG's multi-wave lane launches take ONE ROW PER WORKGROUP, issue_half; persistent workgroups on the queue or with static shares -- rounds 2-4a,
+        // POISMF_HIP_PG_LANE_ROWS -- lost to it, DESIGN.md 6.0, and went in round 6)
+        if (dynamic) HIP_TRY(hipMemsetAsync(s->d_queue, 0, sizeof(unsigned) * MAX_LAUNCHES, s->stream));
+        // The few workgroup-per-row launches of the power-law tail occupy a few dozen CUs for a long time: run them on a second stream beside the
+        // other bins (fork after the column sums, join before anything reads the result) -- NEXT TO the other bins, not after them.  The other bins'
+        // kernels are persistent (a workgroup keeps its CU until the bin's queue is empty): whichever kernel reaches the chip first fills it, and on
+        // config C5 that was the mid-length bin -- the 60 giant rows then waited 260 ms for a CU and ran on their own afterwards (390 ms for what
+        // takes 150 alone).  So every workgroup of a long-row launch counts itself in when it starts, and the main stream waits for that count (a
+        // one-wave gate kernel with a time limit; rounds 3-4a: hipStreamWaitValue32) before it launches anything else.  Arrivals only ever grow, so
+        // a chip that cannot hold the whole launch at once delays the main stream by the gate's 2 ms, no more.
+        const bool forked = !plan_knobs().no_fork && launches.size() > 1 &&
+                            std::any_of(launches.begin(), launches.end(), [](const PlannedLaunch& L) { return is_long(L.engine); });
+        if (forked) HIP_TRY(hipMemsetAsync(s->d_arrive, 0, sizeof(unsigned), s->stream));
+        std::vector<TeamSlot> tslots;
+        if (prepare_teams(s, h, base, launches, tslots)) return 1;
+        if (forked) {
+            HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
+            HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_fork, 0));
+        }
+        if (prologue) s->last_plan[which].clear();
+        std::vector<TeamRerun> reruns;
+        if (issue_half(s, which, p->method, launches, base, tslots, dynamic, forked, reruns)) return 1;
+        if (half_epilogue(s, h, p->method, base, forked, tslots, reruns, s->profiling && last ? &rec : nullptr, last ? n_unchanged : nullptr)) return 1;
     }
-    if (prologue) s->last_plan[which].clear();
-    std::vector<TeamRerun> reruns;
-    if (issue_half(s, which, p->method, launches, base, tslots, dynamic, forked, reruns)) return 1;
-    return half_epilogue(s, h, p->method, base, forked, tslots, reruns, rec, n_unchanged);
+    return 0;
 }
 
 int poismf_hip_half_sweep(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div,
@@ -1576,13 +1626,7 @@ int poismf_hip_half_sweep(poismf_hip_session* s, int which, const poismf_hip_par
 // truncated to cap bytes.  Returns the untruncated length.
 size_t poismf_hip_session_plan(poismf_hip_session* s, int which, char* buf, size_t cap)
 {
-    const std::string& t = s->last_plan[which ? 1 : 0];
-    if (cap > 0) {
-        const size_t n = std::min(cap - 1, t.size());
-        memcpy(buf, t.data(), n);
-        buf[n] = 0;
-    }
-    return t.size();
+    return copy_text(s->last_plan[which ? 1 : 0], buf, cap);
 }
 
 // Per-launch durations of half `which` since profile(1), launches of the same instance and row count added up:
@@ -1609,12 +1653,7 @@ size_t poismf_hip_session_launch_profile(poismf_hip_session* s, int which, char*
         snprintf(txt, sizeof txt, "%s rows=%u nnz=%llu calls=%u ms=%.6f;", g.name.c_str(), g.rows, g.nnz, g.calls, g.ms);
         t += txt;
     }
-    if (cap > 0) {
-        const size_t n = std::min(cap - 1, t.size());
-        memcpy(buf, t.data(), n);
-        buf[n] = 0;
-    }
-    return t.size();
+    return copy_text(t, buf, cap);
 }
 
 // Serving from the session's resident factors: predict_multiple (ref: src/pred.c:42-64) and topN for the
@@ -2242,6 +2281,28 @@ int poismf_hip_debug_row_eval(real_t* G, double* f, real_t* B, real_t* Bsum, rea
         memcpy(&f[r], &b, sizeof(double));
     }
     return 0;
+}
+// Testing aid: the planner without a device.  Rows of row_nnz[0 .. nrows) nonzeros, cut into nseg segments, sorted and binned as
+// finish_half_launch / finish_half_collect do it; then the plan of a half-sweep call over segment `seg` (< 0: over all of them), as
+// poismf_hip_session_plan words it.  No HIP call.
+size_t poismf_hip_debug_plan(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                             real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+{
+    std::string text;
+    nseg = std::max(nseg, 1);
+    if (k > 0 && slots_per_lane(k) != 0 && seg < nseg) {
+        std::vector<unsigned> len(row_nnz, row_nnz + nrows);
+        std::vector<Half::Segment> segs;
+        for (int j = 0; j < nseg; j++) {
+            const size_t lo = segment_cut(nrows, j, nseg), hi = segment_cut(nrows, j + 1, nseg);
+            std::stable_sort(len.begin() + lo, len.begin() + hi, std::greater<unsigned>());
+            segs.push_back({ (unsigned)lo, (unsigned)hi, bins_of(len.data(), lo, hi) });
+        }
+        const PlanCtx c = plan_ctx(k, dimF, method, maxupd, w_mult, limit_step != 0, false, num_cu);
+        for (const auto& pass : plan_call(segs, seg, c))
+            for (const PlannedLaunch& L : pass) text += plan_item(method, L);
+    }
+    return copy_text(text, buf, cap);
 }
 // Testing aid: factors_multiple that also hands back every row's solver decisions (2 words per row, see
 // poismf_hip_session_decisions) -- how the golden single-row fixtures pin the device's iteration / evaluation counts.
