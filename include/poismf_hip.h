@@ -150,6 +150,49 @@ POISMF_HIP_API long double eval_llk(
     size_t dimA, size_t dimB, int nthreads);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1f. Batched top-N: the best items of many users in one fused pass (no counterpart in the reference, whose topN serves
+ *     one user per call, ref: src/topN.c:112-284).
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), n_top, and per user an exclusion set E(u):
+ *
+ *   score(u, j)  the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t -- bit for bit what
+ *                predict_multiple / poismf_hip_session_predict return.  It is NOT the summation order of topN /
+ *                poismf_hip_session_topn (sixteen strided partial chains and a butterfly): the last bit of a batched score
+ *                may differ from theirs.  Factors are assumed finite; the result for a user with a NaN score is unspecified.
+ *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under the total order "score descending, then item index ascending".
+ *                It is a function of (A[u], B, E(u), n_top) alone: not of the other users in the batch, their order, or how
+ *                the library tiles users and items.
+ *   E(u)         the union of (a) with exclude_seen (session only): the items of row u of the session's resident CSR -- nothing
+ *                is uploaded; rows are binary-searched only when a check on the device (once per session) found every resident
+ *                row strictly ascending, as the COO conversion leaves them; rows in the caller's own order are scanned -- and
+ *                (b) an optional CSR-shaped list for the batch: excl_indptr [m + 1], excl_indices, host arrays, row i belonging
+ *                to u_i, indices strictly ascending within a row.  excl_indptr = NULL: no list.
+ *   output       out_ix [m x n_top] (row-major) and, unless NULL, out_score [m x n_top]; host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, when: a user index
+ * >= dimA; an item index >= dimB; an exclusion row not strictly ascending; n_top == 0; n_top > dimB - |E(u)| for some user;
+ * n_top > POISMF_HIP_TOPN_BATCH_MAX_N_TOP; k outside what a session supports (1..512 float, 1..256 double); exclude_seen on a
+ * session whose rows of A (rowA_begin..rowA_end) do not contain every requested user; one exclusion row longer than
+ * POISMF_HIP_TOPN_BATCH_BUDGET_MB / 8 Mi entries.  n_users == 0 is not an error (returns 0).  With exclude_seen the sizes of the
+ * resident rows are known on the device only: the row pointers are fetched once per session, and a user whose two lists
+ * together could leave fewer than n_top items has its resident row fetched and the union counted, before anything is written.
+ *
+ * Memory: the users x items scores are never materialised.  The batch is cut into chunks of users inside the call, and ONE
+ * scratch allocation per call (session: kept and reused) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB holds a chunk's user list,
+ * exclusion lists, partial results and results, for any n_users; poismf_hip_topn_batch_scratch_bytes (testing aid, no HIP call)
+ * is the size both entry points allocate.  poismf_hip_topn_batch's own copies of B and of A (all of A, or only the batch's
+ * rows when n_users < dimA) come on top of that.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_BATCH_MAX_N_TOP 128   /* largest n_top of the batched entry points */
+#define POISMF_HIP_TOPN_BATCH_BUDGET_MB 256   /* upper bound of their scratch allocation, MiB */
+/* host factors, copied up once per call (what a fitted PoisMF holds); users' rows of A only if that is less */
+POISMF_HIP_API int poismf_hip_topn_batch(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_batch_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -277,6 +320,12 @@ POISMF_HIP_API int poismf_hip_session_predict(poismf_hip_session *s, const spars
 POISMF_HIP_API int poismf_hip_session_topn(poismf_hip_session *s, size_t user,
                           const sparse_ix *include_ix, size_t n_include, const sparse_ix *exclude_ix, size_t n_exclude,
                           sparse_ix *outp_ix, real_t *outp_score, size_t n_top);
+
+/* Section 1f from the session-resident factors (and, with exclude_seen, the session's own CSR rows).  Ordered after the work already
+ * enqueued on the session stream; reads the compact factors, as poismf_hip_session_llk does. */
+POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
 
 /* The log-likelihood of section 1e for the session's resident CSR shard (rows [rowA_begin,rowA_end) of A) under its resident
  * factors; with include_missing, M covers the shard's rows of A times all of B.  No factor or matrix is copied: one double

@@ -48,7 +48,9 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
     "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
+    "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
 )
+TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -125,6 +127,12 @@ def load_library(use_float):
     lib.poismf_hip_session_llk.restype = i
     lib.poismf_hip_session_topn.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, sz]
     lib.poismf_hip_session_topn.restype = i
+    lib.poismf_hip_topn_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp]
+    lib.poismf_hip_topn_batch.restype = i
+    lib.poismf_hip_session_topn_batch.argtypes = [vp, vp, sz, sz, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_batch.restype = i
+    lib.poismf_hip_topn_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_topn_batch_scratch_bytes.restype = sz
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -441,6 +449,103 @@ def _transform(self, X):
 
 PoisMF.transform = _transform
 
+def _index_array(a, what):
+    """a 1-d index list as C-contiguous uint64; ValueError for a negative or non-integer entry"""
+    a = np.asarray(a)
+    if a.ndim != 1:
+        a = a.reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be integers")
+    if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
+        raise ValueError(f"{what}: negative index")
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _topn_batch_args(users, n, exclude, dimA, dimB):
+    """The argument checks of the batched top-N (include/poismf_hip.h section 1f) that need no device, as the library itself
+    makes them; returns (users, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if n > dimB:
+        raise ValueError("n is larger than the number of items")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if exclude is None:
+        return users, None, None
+    if isinstance(exclude, (tuple, list)) and len(exclude) == 2 and not hasattr(exclude, "tocsr"):
+        indptr, indices = _index_array(exclude[0], "exclude indptr"), _index_array(exclude[1], "exclude indices")
+    else:
+        import scipy.sparse as sp
+        csr = sp.csr_matrix(exclude)
+        if csr.shape[0] != m:
+            raise ValueError(f"exclude has {csr.shape[0]} rows for {m} users")
+        if csr.shape[1] > dimB:
+            raise ValueError("exclude has more columns than there are items")
+        csr.sum_duplicates()
+        csr.sort_indices()
+        indptr, indices = _index_array(csr.indptr, "exclude indptr"), _index_array(csr.indices, "exclude indices")
+    if len(indptr) != m + 1:
+        raise ValueError(f"exclude has {max(len(indptr) - 1, 0)} rows for {m} users")
+    if m:
+        if np.any(indptr[1:] < indptr[:-1]) or int(indptr[-1]) > len(indices):
+            raise ValueError("exclude: row pointers must not decrease and must stay inside the index list")
+        lo, hi = int(indptr[0]), int(indptr[-1])
+        seg = indices[lo:hi]
+        if len(seg) and int(seg.max()) >= dimB:
+            raise ValueError("an item index of exclude is out of range")
+        if len(seg) > 1:
+            bad = seg[1:] <= seg[:-1]
+            starts = indptr[1:-1].astype(np.int64) - lo - 1          # position (in bad) of each later row's first entry
+            starts = starts[(starts >= 0) & (starts < len(bad))]
+            bad[starts] = False
+            if np.any(bad):
+                raise ValueError("exclude: the item indices of a row must be strictly ascending")
+        lens = (indptr[1:] - indptr[:-1]).astype(np.int64)
+        if int(lens.max()) > dimB - n:
+            raise ValueError("n is larger than the number of items a user has left after exclusion")
+    return users, indptr, indices
+
+
+def _topn_batch_rc(rc):
+    if rc == 2:
+        raise ValueError("invalid arguments for the batched top-N (index out of range, unsorted exclusion row, or n against the items left)")
+    if rc:
+        raise MemoryError("batched top-N failed (no usable HIP device or out of memory)")
+
+
+def _topN_batch(self, users, n=10, exclude=None, output_score=False):
+    """The n best items of every user in `users` (rows of the fitted A) under "score descending, item index ascending", in one
+    fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
+    `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
+    does not keep X) or an (indptr, indices) pair with strictly ascending rows.  Returns (items uint64 [m x n], scores [m x n],
+    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    m, n = len(users), int(n)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    lib = load_library(self.use_float)
+    _topn_batch_rc(lib.poismf_hip_topn_batch(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
+                                             _ptr(indptr) if indptr is not None else None,
+                                             _ptr(indices) if indices is not None and len(indices) else None,
+                                             _ptr(ix), _ptr(sc) if output_score else None))
+    return ix, sc
+
+
+PoisMF.topN_batch = _topN_batch
+
+
 
 class _DevArray:
     """Minimal __cuda_array_interface__ carrier so torch can alias session-owned device memory."""
@@ -671,6 +776,26 @@ class Session:
             raise ValueError("invalid combination of include / exclude / top_n, or an index out of range")
         if rc:
             raise MemoryError("poismf_hip_session_topn failed")
+        return ix, sc
+
+    def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False):
+        """The top_n best items of every user in `users` from the resident factors, in one fused pass (include/poismf_hip.h section
+        1f): "score descending, item index ascending", scores bit for bit those of predict().  exclude_seen leaves out the items of
+        the user's row of the session's own CSR; exclude (a SciPy sparse matrix with one row per entry of `users`, or an
+        (indptr, indices) pair with strictly ascending rows) leaves out more.  Returns (items uint64 [m x top_n], scores [m x top_n],
+        empty unless output_score)."""
+        users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
+        m, n = len(users), int(top_n)
+        if exclude_seen and m and (int(users.min()) < self.shardA[0] or int(users.max()) >= self.shardA[1]):
+            raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
+        if m == 0:
+            return ix, sc
+        _topn_batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
+                                                              _ptr(indptr) if indptr is not None else None,
+                                                              _ptr(indices) if indices is not None and len(indices) else None,
+                                                              _ptr(ix), _ptr(sc) if output_score else None))
         return ix, sc
 
     def _text(self, fn, which):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "topn_batch.hpp"
 
 // the device-visible twin of the interrupt flag (pinned host memory; see on_sigint below): one word, allocated on first use, never freed
 static volatile unsigned* g_stop_word = nullptr;
@@ -272,6 +273,10 @@ struct poismf_hip_session {
     std::string last_plan[2];         // the launches of the most recent half-sweep of each half, as text
     double* d_llk = nullptr;          // scratch of poismf_hip_session_llk (allocated by its first call)
     size_t llk_cap = 0;               // ... in doubles
+    void* d_topn = nullptr;           // scratch of poismf_hip_session_topn_batch (allocated by its first call, grown when a call needs more)
+    size_t topn_cap = 0;              // ... in bytes
+    std::vector<unsigned long long> topn_indptr;   // exclude_seen: host copy of the CSR shard's row pointers (fetched by the first such call)
+    int csr_rows_sorted = -1;         // exclude_seen: -1 not checked yet, 0 some resident CSR row is not strictly ascending, 1 all are
 };
 
 namespace {
@@ -1366,6 +1371,7 @@ void poismf_hip_session_destroy(poismf_hip_session* s)
     pmf_free(s->d_team_backup, s->stream);
     pmf_free(s->d_team_eval_backup, s->stream);
     pmf_free(s->d_llk, s->stream);
+    pmf_free(s->d_topn, s->stream);
     (void)hipStreamSynchronize(s->stream);   // the stream-ordered frees have run
     if (aux) release_stream(s->device, aux);
     if (own) release_stream(s->device, own);
@@ -1703,6 +1709,24 @@ int poismf_hip_session_topn(poismf_hip_session* s, size_t user, const sparse_ix*
     HIP_TRY(hipStreamSynchronize(s->stream));
     return poismf_hip_serve_topn(s->dA + user * s->k, s->dB, (int)s->k, include_ix, n_include, exclude_ix, n_exclude, outp_ix, outp_score,
                                  n_top, s->dimB);
+}
+
+// Batched top-N from the resident (compact) factors (topn_batch.hip; include/poismf_hip.h section 1f).  Ordered after the work already
+// enqueued on the session stream; with exclude_seen the resident CSR shard's rows are the exclusion lists -- nothing of them is uploaded.
+int poismf_hip_session_topn_batch(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, int exclude_seen,
+                                  const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_batch_check(users, n_users, n_top, s->dimA, s->dimB, s->k, excl_indptr, excl_indices)) return rc;
+    const Half& h = s->half[1];
+    if (exclude_seen)
+        for (size_t i = 0; i < n_users; i++)
+            if ((size_t)users[i] < h.row_begin || (size_t)users[i] >= h.row_end) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
+    return poismf_hip_topn_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, exclude_seen ? &seen : nullptr,
+                                     excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
 #ifdef PMF_PROBE

@@ -1,0 +1,646 @@
+// topn_batch.hip -- batched top-N (include/poismf_hip.h, section 1f): for many users at once, the n_top best items of each under
+// the total order "score descending, item index ascending", minus per-user exclusion sets.
+//
+//   score(u, j) = the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t
+//
+// which is bit for bit what pair_dot_kernel (serve.hip: predict_multiple, poismf_hip_session_predict) computes.  It is NOT
+// score_kernel's order (sixteen strided partial chains and a butterfly), so the last bit may differ from topN's score.
+//
+// One kernel (topn_tile_kernel): a workgroup of four waves owns a tile of TB_TU = 64 users (wave w: users 16 w .. 16 w + 15) and a
+// slice of the items, which it walks TB_TJ = 64 items at a time.  The users' rows and the items' rows go through LDS in chunks of
+// TB_KC columns, zero padded to a multiple of four columns (fma(0, 0, s) = s for every s such a chain can hold: it starts at +0 and is
+// never -0).  fp32: v_mfma_f32_16x16x4_f32, whose result is the k-ordered fmaf chain from C = 0; four independent accumulators
+// (16 users x 64 items) per wave.  fp64: a VALU fma chain with the same register layout (one accumulator per (user, item), k
+// ascending) -- whether v_mfma_f64_16x16x4_f64 rounds as that chain does has not been measured, so it is not used.
+// Scores die in registers unless they beat the user's threshold (the n_top-th best so far, kept in LDS with its item index);
+// a survivor is then looked up in the exclusion lists (binary search; linear scan of a resident row not known to be sorted) and
+// appended to the user's candidate list in LDS through an LDS counter.  A list is pruned by its wave alone, by rank counting under
+// the total order, whenever fewer than 16 slots are left (a pass over 16 item columns can add 16 candidates to one user).
+// Arrival order in the list varies from run to run; ranks under a strict total order do not, so the output is deterministic.
+// Per (user, slice) the sorted best n_top go to scratch; topn_merge_kernel ranks the slices' lists of a user the same way.
+// No float atomics anywhere.
+//
+// The host side cuts the batch into chunks of users so that ONE scratch allocation of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB holds a
+// chunk's user list, exclusion lists, partial lists and results (TbLayout; poismf_hip_topn_batch_scratch_bytes reports its size).
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "../../include/poismf_hip.h"
+#include "devmem.hpp"
+#include "topn_batch.hpp"
+
+namespace {
+
+constexpr int TB_WG = 256;                                // threads per workgroup (four waves)
+constexpr int TB_TU = 64;                                 // users per workgroup
+constexpr int TB_TJ = 64;                                 // items per step
+constexpr int TB_KC = sizeof(real_t) == 4 ? 64 : 32;      // columns of the factors per LDS chunk
+constexpr int TB_KS = TB_KC + 4;                          // LDS row stride (fp32: lanes (row l & 15, column l >> 4) fall on 64 distinct banks)
+constexpr int TB_ROOM = 16;                               // free slots a list must have before a pass over 16 item columns
+constexpr int TB_PRUNE_Q = 3;                             // list entries per lane in a prune: lists hold <= 192 entries
+constexpr size_t TB_LDS_LIMIT = 156 * 1024;
+constexpr size_t TB_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many
+constexpr size_t TB_MERGE_MAX = 2048;                     // entries of one user's partial lists the merge kernel ranks in LDS
+constexpr size_t TB_CHUNK_USERS_MAX = 262144;
+constexpr size_t TB_N_TOP_MAX = POISMF_HIP_TOPN_BATCH_MAX_N_TOP;
+constexpr size_t TB_BUDGET = (size_t)POISMF_HIP_TOPN_BATCH_BUDGET_MB << 20;
+constexpr size_t TB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
+constexpr unsigned TB_NONE = 0xffffffffu;
+static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
+static_assert(TB_N_TOP_MAX >= 128, "the header promises at least 128");
+
+typedef float tb_f32x4 __attribute__((ext_vector_type(4)));
+
+struct TbArgs {
+    const real_t* A;                  // rows addressed by `users`
+    const real_t* B;                  // [dimB x k]
+    const unsigned* users;            // the chunk's rows of A
+    unsigned n_users, dimB;
+    int k;
+    unsigned n_top, cap;              // list capacity in LDS (n_top + TB_ROOM + slack)
+    unsigned nslices, tiles_per_slice;
+    const unsigned long long* seen_indptr;   // exclude_seen: the resident CSR (nullptr: off); local row = user - seen_row0
+    const unsigned* seen_indices;
+    unsigned seen_row0;
+    int seen_sorted;                  // its rows are strictly ascending (binary search) or not known to be (scan)
+    const unsigned* ex_indptr;        // the batch's own lists for this chunk (nullptr: none), strictly ascending rows
+    const unsigned* ex_indices;
+    real_t* part_score;               // [n_users][nslices][n_top]
+    unsigned* part_ix;
+};
+
+// the total order: (s1, j1) comes before (s2, j2)
+__device__ __forceinline__ bool tb_better(real_t s1, unsigned j1, real_t s2, unsigned j2) { return s1 > s2 || (s1 == s2 && j1 < j2); }
+
+__device__ __forceinline__ void tb_wave_sync()
+{
+    // LDS operations of one wave complete in order; this keeps the compiler from moving them across the point
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ bool tb_sorted_has(const unsigned* v, unsigned long long lo, unsigned long long hi, unsigned j)
+{
+    while (lo < hi) {
+        const unsigned long long mid = lo + (hi - lo) / 2;
+        const unsigned x = v[mid];
+        if (x == j) return true;
+        if (x < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// Rank-counts list `u` (c entries, c <= cap) under the total order, keeps the best min(c, n_top) in order and, when the list is full,
+// sets the user's threshold to its last entry.  Called by a whole wave with uniform arguments.
+__device__ __forceinline__ void tb_prune(real_t* ls, unsigned* li, unsigned c, unsigned n_top, unsigned* cnt_u, real_t* thr_s_u, unsigned* thr_j_u)
+{
+    const unsigned lane = threadIdx.x & 63;
+    real_t es[TB_PRUNE_Q];
+    unsigned ej[TB_PRUNE_Q], rk[TB_PRUNE_Q];
+#pragma unroll
+    for (int q = 0; q < TB_PRUNE_Q; q++) {
+        const unsigned e = lane + 64u * q;
+        es[q] = e < c ? ls[e] : (real_t)0;
+        ej[q] = e < c ? li[e] : TB_NONE;
+        rk[q] = 0;
+    }
+    for (unsigned i = 0; i < c; i++) {
+        const real_t si = ls[i];
+        const unsigned ji = li[i];
+#pragma unroll
+        for (int q = 0; q < TB_PRUNE_Q; q++) rk[q] += tb_better(si, ji, es[q], ej[q]) ? 1u : 0u;
+    }
+    tb_wave_sync();
+#pragma unroll
+    for (int q = 0; q < TB_PRUNE_Q; q++) {
+        const unsigned e = lane + 64u * q;
+        if (e < c && rk[q] < n_top) {
+            ls[rk[q]] = es[q];
+            li[rk[q]] = ej[q];
+            if (rk[q] == n_top - 1) { *thr_s_u = es[q]; *thr_j_u = ej[q]; }
+        }
+    }
+    if (lane == 0) *cnt_u = c < n_top ? c : n_top;
+    tb_wave_sync();
+}
+
+constexpr int TB_NL = TB_TU * TB_KC / TB_WG;   // elements of a [64 x TB_KC] tile per thread: element e = thread + i TB_WG is (row e / TB_KC, column e % TB_KC)
+
+// rows [64 x TB_KC columns] of a row-major [* x k] factor into registers: columns c0 .. c0 + len - 1, zero elsewhere
+template <class RowOf> __device__ __forceinline__ void tb_fetch(real_t (&v)[TB_NL], const real_t* src, int k, int c0, int len, RowOf row_of)
+{
+#pragma unroll
+    for (int i = 0; i < TB_NL; i++) {
+        const int e = (int)threadIdx.x + i * TB_WG;
+        const int row = e / TB_KC, col = e % TB_KC;
+        const long long r = row_of(row);   // < 0: no such row
+        v[i] = 0;
+        if (r >= 0 && col < len) v[i] = src[(size_t)r * (size_t)k + (size_t)(c0 + col)];
+    }
+}
+__device__ __forceinline__ void tb_store(real_t* dst, const real_t (&v)[TB_NL])
+{
+#pragma unroll
+    for (int i = 0; i < TB_NL; i++) {
+        const int e = (int)threadIdx.x + i * TB_WG;
+        dst[(e / TB_KC) * TB_KS + e % TB_KC] = v[i];
+    }
+}
+
+// acc[t][r] += sum over the chunk's columns, in ascending order, of As[user][c] Bs[item][c] for user 16 wave + 4 (lane >> 4) + r and
+// item 16 t + (lane & 15): one fused multiply-add per column
+template <class T, bool MFMA> __device__ __forceinline__ void tb_compute(T (&acc)[4][4], const T* As, const T* Bs, int len)
+{
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned col = lane & 15, quad = lane >> 4;
+    if constexpr (MFMA) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // A operand: user row (lane & 15), column 4 s + (lane >> 4); B operand: item row (lane & 15), same column;
+        // D: item column lane & 15, user row 4 (lane >> 4) + register
+        const int ksteps = (len + 3) / 4;
+        const T* ap = As + (16 * wave + col) * TB_KS + quad;
+        const T* bp = Bs + col * TB_KS + quad;
+        tb_f32x4 d0 = { acc[0][0], acc[0][1], acc[0][2], acc[0][3] }, d1 = { acc[1][0], acc[1][1], acc[1][2], acc[1][3] };
+        tb_f32x4 d2 = { acc[2][0], acc[2][1], acc[2][2], acc[2][3] }, d3 = { acc[3][0], acc[3][1], acc[3][2], acc[3][3] };
+#pragma unroll 4
+        for (int s = 0; s < ksteps; s++) {
+            const float av = ap[4 * s];
+            const float b0 = bp[4 * s], b1 = bp[16 * TB_KS + 4 * s], b2 = bp[32 * TB_KS + 4 * s], b3 = bp[48 * TB_KS + 4 * s];
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, d1, 0, 0, 0);
+            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b2, d2, 0, 0, 0);
+            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b3, d3, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) { acc[0][r] = d0[r]; acc[1][r] = d1[r]; acc[2][r] = d2[r]; acc[3][r] = d3[r]; }
+#endif
+    } else {
+        const T* ap = As + (16 * wave + 4 * quad) * TB_KS;
+        const T* bp = Bs + col * TB_KS;
+        for (int c = 0; c < len; c++) {
+            T av[4], bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) av[r] = ap[r * TB_KS + c];
+#pragma unroll
+            for (int t = 0; t < 4; t++) bv[t] = bp[16 * t * TB_KS + c];
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[t][r] = __builtin_fma(av[r], bv[t], acc[t][r]);
+        }
+    }
+}
+
+template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile_kernel(TbArgs a)
+{
+    extern __shared__ __align__(16) unsigned char tb_smem[];
+    static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
+    T* As = (T*)tb_smem;                                  // [TB_TU][TB_KS]
+    T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
+    T* Ls = Bs + TB_TJ * TB_KS;                           // [TB_TU][cap] candidate scores
+    unsigned* Li = (unsigned*)(Ls + (size_t)TB_TU * a.cap);   // [TB_TU][cap] candidate items
+    T* thr_s = (T*)(Li + (size_t)TB_TU * a.cap);          // [TB_TU] threshold: score ...
+    unsigned* thr_j = (unsigned*)(thr_s + TB_TU);         // ... and item
+    unsigned* cnt = thr_j + TB_TU;                        // [TB_TU] entries in the list
+    unsigned* uid = cnt + TB_TU;                          // [TB_TU] row of A, TB_NONE beyond the chunk
+
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned u_base = blockIdx.x * TB_TU;
+    if (tid < TB_TU) {
+        const unsigned u = u_base + tid;
+        uid[tid] = u < a.n_users ? a.users[u] : TB_NONE;
+        cnt[tid] = 0;
+        thr_s[tid] = -std::numeric_limits<T>::infinity();
+        thr_j[tid] = 0;
+    }
+    __syncthreads();
+
+    const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
+    const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
+    const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
+    const int nchunks = (a.k + TB_KC - 1) / TB_KC;
+    const unsigned col = lane & 15, quad = lane >> 4;
+    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
+    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
+    auto item_row = [&](unsigned j_base) { return [&a, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < a.dimB ? (long long)j : -1ll; }; };
+
+    // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
+    T thr_reg[4];
+    bool u_valid[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
+    bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
+
+    // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
+    T b_next[TB_NL];
+    if (nchunks == 1) {
+        tb_fetch(b_next, a.A, a.k, 0, a.k, user_row);
+        tb_store(As, b_next);
+        tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(tile0 * TB_TJ));
+    }
+
+    for (unsigned jt = tile0; jt < tile1; jt++) {
+        const unsigned j_base = jt * TB_TJ;
+        T acc[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) acc[t][r] = 0;
+        if (nchunks == 1) {
+            __syncthreads();   // every wave is done with the items' tile of the step before
+            tb_store(Bs, b_next);
+            __syncthreads();
+            if (jt + 1 < tile1) tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(j_base + TB_TJ));
+            tb_compute<T, MFMA>(acc, As, Bs, a.k);
+        } else {
+            for (int ch = 0; ch < nchunks; ch++) {
+                const int c0 = ch * TB_KC;
+                const int len = a.k - c0 < TB_KC ? a.k - c0 : TB_KC;
+                __syncthreads();   // every wave is done with the tiles of the step before
+                tb_fetch(b_next, a.A, a.k, c0, len, user_row);
+                tb_store(As, b_next);
+                tb_fetch(b_next, a.B, a.k, c0, len, item_row(j_base));
+                tb_store(Bs, b_next);
+                __syncthreads();
+                tb_compute<T, MFMA>(acc, As, Bs, len);
+            }
+        }
+
+        // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (dirty) {
+                const unsigned c_mine = cnt[16 * wave + col];
+                unsigned long long full = __ballot(quad == 0 && c_mine + TB_ROOM > a.cap);
+                if (full) {
+                    while (full) {
+                        const unsigned uu = 16 * wave + (unsigned)__builtin_ctzll(full);
+                        full &= full - 1;
+                        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r++) thr_reg[r] = thr_s[urow0 + r];
+                }
+                dirty = false;
+            }
+            const unsigned j = j_base + 16 * t + col;
+            bool appended = false;
+            if (j < a.dimB) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const unsigned uu = urow0 + r;
+                    const T s = acc[t][r];
+                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu])) {
+                        bool excluded = false;
+                        if (a.ex_indptr != nullptr) {
+                            const unsigned g = u_base + uu;
+                            excluded = tb_sorted_has(a.ex_indices, a.ex_indptr[g], a.ex_indptr[g + 1], j);
+                        }
+                        if (!excluded && a.seen_indptr != nullptr) {
+                            const unsigned row = uid[uu] - a.seen_row0;
+                            const unsigned long long p0 = a.seen_indptr[row], p1 = a.seen_indptr[row + 1];
+                            if (a.seen_sorted) excluded = tb_sorted_has(a.seen_indices, p0, p1, j);
+                            else
+                                for (unsigned long long p = p0; p < p1 && !excluded; p++) excluded = a.seen_indices[p] == j;
+                        }
+                        if (!excluded) {
+                            const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
+                            Ls[(size_t)uu * a.cap + pos] = s;
+                            Li[(size_t)uu * a.cap + pos] = j;
+                            appended = true;
+                        }
+                    }
+                }
+            }
+            if (__ballot(appended)) {
+                dirty = true;
+                tb_wave_sync();
+            }
+        }
+    }
+
+    // ---- the slice's answer per user: the best min(count, n_top) in order, the rest marked empty ----
+    for (unsigned q = 0; q < 16; q++) {
+        const unsigned uu = 16 * wave + q;
+        if (uid[uu] == TB_NONE) continue;   // (uniform over the wave)
+        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
+        const unsigned c = cnt[uu];
+        const size_t o = ((size_t)(u_base + uu) * a.nslices + blockIdx.y) * a.n_top;
+        for (unsigned i = lane; i < a.n_top; i += 64) {
+            a.part_score[o + i] = i < c ? Ls[(size_t)uu * a.cap + i] : -std::numeric_limits<T>::infinity();
+            a.part_ix[o + i] = i < c ? Li[(size_t)uu * a.cap + i] : TB_NONE;
+        }
+    }
+}
+
+// One wave per user: the best n_top of its nslices sorted partial lists, by rank counting under the total order.
+__global__ __launch_bounds__(64) void topn_merge_kernel(const real_t* part_score, const unsigned* part_ix, unsigned n_users, unsigned nslices,
+                                                        unsigned n_top, real_t* out_score, unsigned* out_ix)
+{
+    __shared__ real_t ms[TB_MERGE_MAX];
+    __shared__ unsigned mj[TB_MERGE_MAX];
+    const unsigned u = blockIdx.x, lane = threadIdx.x;
+    const unsigned m = nslices * n_top;
+    const size_t o = (size_t)u * m;
+    for (unsigned i = lane; i < m; i += 64) { ms[i] = part_score[o + i]; mj[i] = part_ix[o + i]; }
+    __syncthreads();
+    for (unsigned e = lane; e < m; e += 64) {
+        const real_t s = ms[e];
+        const unsigned j = mj[e];
+        if (j == TB_NONE) continue;
+        // entries after e in its own (sorted) list are worse; empty entries (-inf, TB_NONE) are worse than every real one
+        unsigned rk = e % n_top;
+        const unsigned own = e / n_top;
+        for (unsigned sl = 0; sl < nslices && rk < n_top; sl++) {
+            if (sl == own) continue;
+            for (unsigned i = sl * n_top; i < (sl + 1) * n_top; i++) {
+                if (!tb_better(ms[i], mj[i], s, j)) break;   // (sorted: nothing further in this list is better either)
+                rk++;
+            }
+        }
+        if (rk < n_top) { out_score[(size_t)u * n_top + rk] = s; out_ix[(size_t)u * n_top + rk] = j; }
+    }
+}
+
+// exclude_seen needs to know whether the resident rows may be binary-searched: flag[0] = 1 when some row is not strictly ascending
+__global__ __launch_bounds__(256) void topn_rows_sorted_kernel(const unsigned long long* indptr, const unsigned* indices, size_t nrows, unsigned* flag)
+{
+    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += (size_t)gridDim.x * blockDim.x) {
+        const unsigned long long p1 = indptr[r + 1];
+        for (unsigned long long p = indptr[r] + 1; p < p1; p++)
+            if (indices[p - 1] >= indices[p]) { flag[0] = 1u; break; }
+    }
+}
+
+size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+size_t round_up(size_t a, size_t b) { return ceil_div(a, b) * b; }
+
+// item slices for a chunk of `tiles` user tiles
+size_t tb_slices(size_t tiles, size_t n_top, size_t dimB)
+{
+    size_t s = tiles >= TB_TARGET_WGS ? 1 : ceil_div(TB_TARGET_WGS, tiles);
+    s = std::min(s, ceil_div(dimB, TB_TJ));
+    s = std::min(s, std::max<size_t>(1, TB_MERGE_MAX / n_top));
+    return std::max<size_t>(s, 1);
+}
+
+// The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
+struct TbLayout {
+    size_t chunk_users;      // users per chunk
+    size_t idx_cap;          // exclusion indices a chunk may carry
+    size_t part_entries;     // (user, slice, rank) entries of the partial lists
+    size_t users, ex_indptr, ex_indices, part_score, part_ix, out_score, out_ix, total;
+    TbLayout(size_t n_users, size_t n_top, size_t dimB)
+    {
+        const size_t R = sizeof(real_t);
+        n_users = std::max<size_t>(n_users, 1);
+        n_top = std::min(std::max<size_t>(n_top, 1), TB_N_TOP_MAX);
+        dimB = std::max<size_t>(dimB, 1);
+        const size_t first = std::min(n_users, TB_CHUNK_USERS_MAX);
+        idx_cap = std::min(TB_BUDGET / 2 / sizeof(unsigned), first * dimB);   // (no overflow: 2^18 x 2^31)
+        const size_t rest = TB_BUDGET - idx_cap * sizeof(unsigned) - 256;     // (256: alignment of the seven parts)
+        // partial lists: users x slices <= TB_TU x (TB_TARGET_WGS + tiles)  (tb_slices), results: users
+        const size_t fixed = 16 + (TB_TU * TB_TARGET_WGS + TB_TU) * n_top * (R + 4);
+        const size_t per_user = 8 + 2 * n_top * (R + 4);
+        size_t uc = (rest - fixed) / per_user;
+        uc = std::min(std::min(uc, TB_CHUNK_USERS_MAX), n_users);
+        if (uc > TB_TU) uc -= uc % TB_TU;
+        chunk_users = uc;
+        part_entries = (TB_TU * TB_TARGET_WGS + TB_TU + uc) * n_top;   // (every chunk of <= uc users fits, however it is sliced)
+        size_t o = 0;
+        auto take = [&o](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 32); return at; };
+        users = take(uc * sizeof(unsigned));
+        ex_indptr = take((uc + 1) * sizeof(unsigned));
+        ex_indices = take(idx_cap * sizeof(unsigned));
+        part_score = take(part_entries * R);
+        part_ix = take(part_entries * sizeof(unsigned));
+        out_score = take(uc * n_top * R);
+        out_ix = take(uc * n_top * sizeof(unsigned));
+        total = o;
+    }
+};
+
+size_t tb_lds_bytes(size_t cap) { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * cap * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12); }
+
+int pick_device()
+{
+    int device = 0;
+    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
+    return device;
+}
+
+#define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
+
+}  // namespace
+
+extern "C" size_t poismf_hip_topn_batch_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k)
+{
+    (void)k;   // (the factors' chunks live in LDS: no part of the scratch depends on k)
+    return TbLayout(n_users, n_top, dimB).total;
+}
+
+// The argument checks of both entry points: 0, or 2.  No device call.
+int poismf_hip_topn_batch_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                const sparse_ix* excl_indptr, const sparse_ix* excl_indices)
+{
+    if (n_top == 0 || n_top > TB_N_TOP_MAX || n_top > dimB) return 2;
+    if (k < 1 || k > TB_K_MAX || dimB > 0x7fffffffull || dimA > 0x7fffffffull) return 2;
+    if (users == nullptr) return 2;
+    for (size_t i = 0; i < n_users; i++)
+        if ((size_t)users[i] >= dimA) return 2;
+    if (excl_indptr != nullptr) {
+        const size_t idx_cap = TbLayout(n_users, n_top, dimB).idx_cap;
+        for (size_t i = 0; i < n_users; i++) {
+            const size_t p0 = (size_t)excl_indptr[i], p1 = (size_t)excl_indptr[i + 1];
+            if (p1 < p0) return 2;
+            const size_t len = p1 - p0;
+            if (len > dimB || n_top > dimB - len || len > idx_cap) return 2;
+            if (len > 0 && excl_indices == nullptr) return 2;
+            for (size_t p = p0; p < p1; p++) {
+                if ((size_t)excl_indices[p] >= dimB) return 2;
+                if (p > p0 && (size_t)excl_indices[p - 1] >= (size_t)excl_indices[p]) return 2;
+            }
+        }
+    }
+    return 0;
+}
+
+// exclude_seen (after poismf_hip_topn_batch_check): the shard must hold every user, and every user must keep n_top admissible items.
+// Row lengths come from a host copy of the row pointers (fetched once per session); only a user whose two lists together could
+// leave fewer than n_top items has its resident row fetched and the union counted.  0, 1 (device error) or 2.
+static int tb_check_seen(PmfTopnSeen& seen, const sparse_ix* users, size_t n_users, size_t n_top, size_t dimB, const sparse_ix* excl_indptr,
+                         const sparse_ix* excl_indices, hipStream_t stream)
+{
+    for (size_t i = 0; i < n_users; i++)
+        if ((size_t)users[i] < seen.row_begin || (size_t)users[i] >= seen.row_end) return 2;
+    const size_t nrows = seen.row_end - seen.row_begin;
+    std::vector<unsigned long long>& ip = *seen.h_indptr;
+    if (ip.size() != nrows + 1) {
+        ip.resize(nrows + 1);
+        TB_TRY(pmf_download(ip.data(), seen.d_indptr, (nrows + 1) * sizeof(unsigned long long), stream));
+    }
+    if (*seen.sorted < 0) {
+        unsigned* d_flag = nullptr;
+        unsigned flag = 0;
+        TB_TRY(pmf_alloc(&d_flag, sizeof(unsigned), stream));
+        hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), stream);
+        if (e == hipSuccess) {
+            const unsigned grid = (unsigned)std::min<size_t>(ceil_div(std::max<size_t>(nrows, 1), 256), 4096);
+            hipLaunchKernelGGL(topn_rows_sorted_kernel, dim3(grid), dim3(256), 0, stream, seen.d_indptr, seen.d_indices, nrows, d_flag);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = pmf_download(&flag, d_flag, sizeof(unsigned), stream);
+        pmf_free(d_flag, stream);
+        TB_TRY(e);
+        *seen.sorted = flag ? 0 : 1;
+    }
+    std::vector<unsigned> row;
+    for (size_t i = 0; i < n_users; i++) {
+        const size_t r = (size_t)users[i] - seen.row_begin;
+        const size_t len_s = (size_t)(ip[r + 1] - ip[r]);
+        const size_t len_e = excl_indptr ? (size_t)excl_indptr[i + 1] - (size_t)excl_indptr[i] : 0;
+        if (len_s + len_e <= dimB - n_top) continue;
+        row.resize(len_s);
+        TB_TRY(pmf_download(row.data(), seen.d_indices + ip[r], len_s * sizeof(unsigned), stream));
+        for (size_t p = 0; p < len_e; p++) row.push_back((unsigned)excl_indices[(size_t)excl_indptr[i] + p]);
+        std::sort(row.begin(), row.end());
+        const size_t uniq = (size_t)(std::unique(row.begin(), row.end()) - row.begin());
+        if (uniq > dimB - n_top) return 2;
+    }
+    return 0;
+}
+
+// ---- core on device-resident factors (the session and the drop-in below).  Arguments already checked. ----
+// dA rows are addressed by users[i], or by i itself when compact_A (the drop-in uploads only the batch's rows).  *d_scratch /
+// *scratch_cap: the caller's scratch, grown here when it is smaller than this call needs.  Returns 0, 1 or (exclude_seen) 2.
+int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                              const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                              const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score)
+{
+    if (seen != nullptr)
+        if (const int rc = tb_check_seen(*seen, users, n_users, n_top, dimB, excl_indptr, excl_indices, stream)) return rc;
+    const TbLayout L(n_users, n_top, dimB);
+    if (*scratch_cap < L.total) {
+        pmf_free(*d_scratch, stream);
+        *d_scratch = nullptr;
+        *scratch_cap = 0;
+        TB_TRY(pmf_alloc((unsigned char**)d_scratch, L.total, stream));
+        *scratch_cap = L.total;
+    }
+    unsigned char* base = (unsigned char*)*d_scratch;
+
+    size_t cap = n_top + TB_ROOM + std::min<size_t>(n_top, 32);
+    while (tb_lds_bytes(cap) > TB_LDS_LIMIT && cap > n_top + TB_ROOM) cap -= 16;
+    const size_t lds = tb_lds_bytes(cap);
+    auto kern = topn_tile_kernel<real_t, sizeof(real_t) == 4>;
+    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TB_LDS_LIMIT));
+
+    std::vector<unsigned> hu, hp, hx, hix;
+    for (size_t u0 = 0; u0 < n_users;) {
+        // the chunk: up to chunk_users users whose exclusion lists fit the index area together
+        size_t u1 = u0, nx = 0;
+        while (u1 < n_users && u1 - u0 < L.chunk_users) {
+            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
+            if (u1 > u0 && nx + len > L.idx_cap) break;
+            nx += len;
+            u1++;
+        }
+        const size_t nu = u1 - u0;
+        hu.resize(nu);
+        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
+        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
+        if (excl_indptr != nullptr) {
+            hp.resize(nu + 1);
+            hx.resize(nx);
+            const size_t p_base = (size_t)excl_indptr[u0];
+            for (size_t i = 0; i <= nu; i++) hp[i] = (unsigned)((size_t)excl_indptr[u0 + i] - p_base);
+            for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
+            TB_TRY(pmf_upload(base + L.ex_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream));
+            TB_TRY(pmf_upload(base + L.ex_indices, hx.data(), nx * sizeof(unsigned), stream));
+        }
+        const size_t tiles = ceil_div(nu, TB_TU);
+        const size_t item_tiles = ceil_div(dimB, TB_TJ);
+        const size_t tps = ceil_div(item_tiles, tb_slices(tiles, n_top, dimB));
+        const size_t nslices = ceil_div(item_tiles, tps);
+        if (nu * nslices * n_top > L.part_entries) return 1;   // (cannot happen: TbLayout sizes the lists for any slicing of a chunk)
+        TbArgs a;
+        a.A = dA;
+        a.B = dB;
+        a.users = (const unsigned*)(base + L.users);
+        a.n_users = (unsigned)nu;
+        a.dimB = (unsigned)dimB;
+        a.k = (int)k;
+        a.n_top = (unsigned)n_top;
+        a.cap = (unsigned)cap;
+        a.nslices = (unsigned)nslices;
+        a.tiles_per_slice = (unsigned)tps;
+        a.seen_indptr = seen ? seen->d_indptr : nullptr;
+        a.seen_indices = seen ? seen->d_indices : nullptr;
+        a.seen_row0 = seen ? (unsigned)seen->row_begin : 0u;
+        a.seen_sorted = seen ? *seen->sorted : 0;
+        a.ex_indptr = excl_indptr ? (const unsigned*)(base + L.ex_indptr) : nullptr;
+        a.ex_indices = (const unsigned*)(base + L.ex_indices);
+        // (one slice: its sorted lists are the results)
+        a.part_score = (real_t*)(base + (nslices == 1 ? L.out_score : L.part_score));
+        a.part_ix = (unsigned*)(base + (nslices == 1 ? L.out_ix : L.part_ix));
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nslices), dim3(TB_WG), lds, stream, a);
+        TB_TRY(hipGetLastError());
+        if (nslices > 1) {
+            hipLaunchKernelGGL(topn_merge_kernel, dim3((unsigned)nu), dim3(64), 0, stream, a.part_score, a.part_ix, (unsigned)nu, (unsigned)nslices,
+                               (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
+            TB_TRY(hipGetLastError());
+        }
+        hix.resize(nu * n_top);
+        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
+        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = (sparse_ix)hix[i];
+        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        u0 = u1;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int poismf_hip_topn_batch(const real_t* A, const real_t* B, int k, size_t dimA, size_t dimB, const sparse_ix* users, size_t n_users,
+                          size_t n_top, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (k < 1 || A == nullptr || B == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_batch_check(users, n_users, n_top, dimA, dimB, (size_t)k, excl_indptr, excl_indices)) return rc;
+    const int device = pick_device();
+    if (hipSetDevice(device) != hipSuccess) return 1;
+    const hipStream_t st = nullptr;
+    const size_t kk = (size_t)k;
+    const bool compact = n_users < dimA;   // only the batch's rows of A go up when that is less than all of A
+    real_t *dA = nullptr, *dB = nullptr;
+    void* d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    int rc = 1;
+    do {
+        const size_t rowsA = compact ? n_users : dimA;
+        if (pmf_alloc(&dA, rowsA * kk * sizeof(real_t) + 16, st) != hipSuccess || pmf_alloc(&dB, dimB * kk * sizeof(real_t) + 16, st) != hipSuccess) break;
+        if (compact) {
+            std::vector<real_t> rows;
+            try { rows.resize(n_users * kk); } catch (const std::bad_alloc&) { break; }
+            for (size_t i = 0; i < n_users; i++) memcpy(rows.data() + i * kk, A + (size_t)users[i] * kk, kk * sizeof(real_t));
+            if (pmf_upload_big(dA, rows.data(), rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        } else if (pmf_upload_big(dA, A, rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        if (pmf_upload_big(dB, B, dimB * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        rc = poismf_hip_topn_batch_run(st, dA, dB, dimB, kk, compact, users, n_users, n_top, nullptr, excl_indptr, excl_indices, &d_scratch,
+                                       &scratch_cap, out_ix, out_score);
+    } while (0);
+    pmf_free(dA, st);
+    pmf_free(dB, st);
+    pmf_free(d_scratch, st);
+    return rc;
+}
+
+}  // extern "C"
