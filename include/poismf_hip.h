@@ -193,6 +193,51 @@ POISMF_HIP_API int poismf_hip_topn_batch(const real_t *A, const real_t *B, int k
 POISMF_HIP_API size_t poismf_hip_topn_batch_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1g. Batched exact ranks: where each held-out item of many users stands in the user's COMPLETE ranked list, in one fused pass
+ *     (no counterpart in the reference, whose notebook gets ranking metrics from a CPU package that scores every user against
+ *     every item on the host).  poismf_amd/metrics.py turns the ranks into P@K, AP@K, NDCG@K, Hit@K, RR@K and AUC.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), per user an exclusion set E(u) defined exactly as in
+ * section 1f (exclude_seen on a session and / or the CSR-shaped host list excl_indptr / excl_indices), and per user a held-out
+ * list T(u): CSR-shaped host arrays test_indptr [m + 1], test_indices, item indices strictly ascending within a row.  Only
+ * indices: every listed cell is a positive.
+ *
+ *   score(u, j)  section 1f's score, bit for bit what predict_multiple / poismf_hip_session_predict return.
+ *   C(u), N(u)   C(u) = {0..dimB-1} \ E(u), N(u) = |C(u)|.
+ *   rank(u, t)   for t in T(u) and not in E(u): the number of j in C(u) that come before t under the total order of section 1f
+ *                (score(u,j) > score(u,t), or equal and j < t): t's 0-based position in the user's complete ranked list.  The
+ *                batched top-N with the same E(u) and n_top > rank lists t at index rank.  Other held-out items count like any
+ *                other item.  A rank is a function of (A[u], B, E(u), t) alone: not of the other users, the other held-out
+ *                items, the batch order, or how the library tiles users and items.  All counting is in integers.
+ *   excluded     a cell whose item is in E(u) gets POISMF_HIP_RANK_EXCLUDED; it is not an error (train / test overlaps are
+ *                common in real splits).
+ *   output       out_rank: one unsigned int per entry of test_indices, in the caller's order; out_n_adm [m]: N(u) (with
+ *                exclude_seen and a list together, |E(u)| is the size of the union).  Host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, when: a user index
+ * >= dimA; an item index >= dimB; a test or exclusion row not strictly ascending; row pointers that decrease; k outside what a
+ * session supports (1..512 float, 1..256 double); exclude_seen on a session whose rows of A do not contain every requested
+ * user; one exclusion row longer than POISMF_HIP_RANK_BATCH_BUDGET_MB / 8 Mi entries; one held-out row longer than
+ * POISMF_HIP_RANK_BATCH_MAX_ROW entries (a user's held-out scores are put in order on the device by counting, which is quadratic
+ * in the row's length).  n_users == 0 is not an error (returns 0); a user with an empty T(u) is valid.  Factors are assumed finite.
+ *
+ * Memory: the users x items scores are never materialised.  The batch is cut into chunks of users inside the call, and ONE
+ * scratch allocation per call (session: kept and reused) of at most POISMF_HIP_RANK_BATCH_BUDGET_MB MiB holds a chunk's users,
+ * lists, thresholds, counts and results, for any n_users and any total number of held-out cells;
+ * poismf_hip_rank_batch_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate.  poismf_hip_rank_batch's
+ * own copies of B and of A (all of A, or only the batch's rows when n_users < dimA) come on top of that.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_RANK_EXCLUDED 0xffffffffu   /* out_rank of a held-out cell whose item is in E(u) */
+#define POISMF_HIP_RANK_BATCH_BUDGET_MB 256    /* upper bound of the scratch allocation, MiB */
+#define POISMF_HIP_RANK_BATCH_MAX_ROW 65536    /* most held-out items of one user */
+POISMF_HIP_API int poismf_hip_rank_batch(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
+POISMF_HIP_API size_t poismf_hip_rank_batch_scratch_bytes(size_t n_users, size_t n_cells, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -326,6 +371,12 @@ POISMF_HIP_API int poismf_hip_session_topn(poismf_hip_session *s, size_t user,
 POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1g from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_rank_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
 
 /* The log-likelihood of section 1e for the session's resident CSR shard (rows [rowA_begin,rowA_end) of A) under its resident
  * factors; with include_missing, M covers the shard's rows of A times all of B.  No factor or matrix is copied: one double

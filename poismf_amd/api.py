@@ -49,8 +49,12 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
     "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
+    "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
+RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
+RANK_BATCH_MAX_ROW = 65536   # of include/poismf_hip.h section 1g (tests/test_rank_batch_cpu.py compares them with the header)
+RANK_BATCH_BUDGET_MB = 256
 
 
 def load_library(use_float):
@@ -133,6 +137,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_batch.restype = i
     lib.poismf_hip_topn_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_batch_scratch_bytes.restype = sz
+    lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_rank_batch.restype = i
+    lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_rank_batch.restype = i
+    lib.poismf_hip_rank_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_rank_batch_scratch_bytes.restype = sz
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -546,6 +556,156 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False):
 PoisMF.topN_batch = _topN_batch
 
 
+def _csr_list(lst, m, dimB, what, row_max=None):
+    """A per-user item list of the batched entry points -- a SciPy sparse matrix with one row per user (its stored columns;
+    explicit zeros dropped, duplicates merged) or an (indptr, indices) pair -- checked as the library checks it: m rows, indices
+    below dimB and strictly ascending within a row.  Returns (indptr, indices) as uint64 arrays starting at 0."""
+    if isinstance(lst, (tuple, list)) and len(lst) == 2 and not hasattr(lst, "tocsr"):
+        indptr, indices = _index_array(lst[0], what + " indptr"), _index_array(lst[1], what + " indices")
+    else:
+        import scipy.sparse as sp
+        if not sp.issparse(lst):
+            raise ValueError(f"{what} must be a SciPy sparse matrix or an (indptr, indices) pair")
+        csr = sp.csr_matrix(lst)
+        if csr.shape[0] != m:
+            raise ValueError(f"{what} has {csr.shape[0]} rows for {m} users")
+        if csr.shape[1] > dimB:
+            raise ValueError(f"{what} has more columns than there are items")
+        csr.sum_duplicates()
+        csr.eliminate_zeros()
+        csr.sort_indices()
+        indptr, indices = _index_array(csr.indptr, what + " indptr"), _index_array(csr.indices, what + " indices")
+    if len(indptr) != m + 1:
+        raise ValueError(f"{what} has {max(len(indptr) - 1, 0)} rows for {m} users")
+    if np.any(indptr[1:] < indptr[:-1]) or int(indptr[-1]) > len(indices):
+        raise ValueError(f"{what}: row pointers must not decrease and must stay inside the index list")
+    lo, hi = int(indptr[0]), int(indptr[-1])
+    seg = indices[lo:hi]
+    if len(seg) and int(seg.max()) >= dimB:
+        raise ValueError(f"an item index of {what} is out of range")
+    if len(seg) > 1:
+        bad = seg[1:] <= seg[:-1]
+        starts = indptr[1:-1].astype(np.int64) - lo - 1          # position (in bad) of each later row's first entry
+        starts = starts[(starts >= 0) & (starts < len(bad))]
+        bad[starts] = False
+        if np.any(bad):
+            raise ValueError(f"{what}: the item indices of a row must be strictly ascending")
+    if row_max is not None and m and int((indptr[1:] - indptr[:-1]).max()) > row_max:
+        raise ValueError(f"{what}: a row is longer than {row_max}")
+    return np.ascontiguousarray(indptr - indptr[0]), np.ascontiguousarray(seg)
+
+
+def _rank_batch_args(users, test, exclude, dimA, dimB, k):
+    """The argument checks of the batched ranks (include/poismf_hip.h section 1g) that need no device, as the library itself makes
+    them; returns (users, test_indptr, test_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if not 1 <= int(k) <= 512:
+        raise ValueError("the number of factors is outside what the batched entry points support")
+    if test is None:
+        raise ValueError("the held-out list is missing")
+    tp, ti = _csr_list(test, m, dimB, "test", RANK_BATCH_MAX_ROW)
+    if exclude is None:
+        return users, tp, ti, None, None
+    ep, ei = _csr_list(exclude, m, dimB, "exclude", (RANK_BATCH_BUDGET_MB << 20) // 8)
+    return users, tp, ti, ep, ei
+
+
+def _rank_batch_rc(rc):
+    if rc == 2:
+        raise ValueError("invalid arguments for the batched ranks (index out of range, unsorted row, or a row too long)")
+    if rc:
+        raise MemoryError("batched ranks failed (no usable HIP device or out of memory)")
+
+
+def _opt_ptr(a):
+    return _ptr(a) if a is not None and len(a) else None
+
+
+def rank_batch(A, B, users, test, exclude=None):
+    """poismf_hip_rank_batch on host factors A [dimA x k], B [dimB x k] (float32 or float64, both alike): for every cell of `test`
+    (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with strictly ascending rows) the
+    0-based position of its item in the user's complete ranked list, exclusion set left out (include/poismf_hip.h section 1g).
+    Returns (ranks uint32, one per cell in row order, RANK_EXCLUDED where the item is in the user's `exclude` row; n_adm uint32
+    [m], the admissible items of each user)."""
+    A, B = np.asarray(A), np.asarray(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
+        raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
+    use_float = A.dtype == np.float32
+    users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, A.shape[0], B.shape[0], A.shape[1])
+    m = len(users)
+    ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
+    if m == 0:
+        return ranks, n_adm
+    A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
+    lib = load_library(use_float)
+    _rank_batch_rc(lib.poismf_hip_rank_batch(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
+                                             _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)))
+    return ranks, n_adm
+
+
+def _eval_ranking_args(X_test, exclude, users, k, dimA, dimB):
+    """eval_ranking's inputs, given for the whole matrix, cut down to the batch: (users, the (indptr, indices) of their held-out rows,
+    their exclude rows or None, k)"""
+    import scipy.sparse as sp
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    if not sp.issparse(X_test):
+        raise ValueError("X_test must be a SciPy sparse matrix")
+    if X_test.shape != (dimA, dimB):
+        raise ValueError(f"X_test has shape {X_test.shape}, the model {(dimA, dimB)}")
+    csr = sp.csr_matrix(X_test)
+    csr.sum_duplicates()
+    csr.eliminate_zeros()
+    if users is None:
+        users = np.flatnonzero(np.diff(csr.indptr)).astype(np.uint64)
+    else:
+        users = _index_array(users, "users")
+        if len(users) and int(users.max()) >= dimA:
+            raise ValueError("a user index is out of range")
+    rows = users.astype(np.int64)
+    if exclude is not None and sp.issparse(exclude):
+        if exclude.shape != (dimA, dimB):
+            raise ValueError(f"exclude has shape {exclude.shape}, the model {(dimA, dimB)}")
+        exclude = sp.csr_matrix(exclude)[rows]
+    test = csr[rows]
+    test.sort_indices()
+    return users, (np.asarray(test.indptr, np.uint64), np.asarray(test.indices, np.uint64)), exclude, k
+
+
+def _ranking_result(tp, ranks, n_adm, k, per_user):
+    from . import metrics
+    each = metrics.metrics_from_ranks(tp, ranks, n_adm, k)
+    out = metrics.mean_metrics(each)
+    if per_user:
+        out["per_user"] = each
+        out["ranks"], out["n_adm"], out["test_indptr"] = ranks, n_adm, tp
+    return out
+
+
+def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False):
+    """Held-out ranking metrics of the fitted model, from exact ranks computed in one fused pass on the GPU (include/poismf_hip.h
+    section 1g; the definitions are those of poismf_amd/metrics.py).  X_test: a SciPy sparse matrix with the model's shape whose
+    stored cells are the held-out positives (values play no part; explicit zeros dropped, duplicates merged).  users: the rows to
+    evaluate, by default every row of X_test with a stored cell.  exclude: None, or a sparse matrix with the model's shape whose
+    stored cells leave the ranking (the training matrix; its rows for `users` are taken here), or an (indptr, indices) pair with
+    one strictly ascending row per entry of `users`; a held-out cell that is excluded takes no part in any metric.  Returns a dict
+    of the means of hit, precision, recall, ap, ndcg, rr, auc at cut-off k over the users that counted, plus n_users; with per_user
+    also "per_user" (the same names, one value per user), "ranks", "n_adm" and "test_indptr"."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude)
+    return _ranking_result(test[0], ranks, n_adm, k, per_user)
+
+
+PoisMF.eval_ranking = _eval_ranking
+
+
 
 class _DevArray:
     """Minimal __cuda_array_interface__ carrier so torch can alias session-owned device memory."""
@@ -797,6 +957,29 @@ class Session:
                                                               _ptr(indices) if indices is not None and len(indices) else None,
                                                               _ptr(ix), _ptr(sc) if output_score else None))
         return ix, sc
+
+    def rank_batch(self, users, test, exclude_seen=False, exclude=None):
+        """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with
+        strictly ascending rows) the 0-based position of its item in the user's complete ranked list from the resident factors
+        (include/poismf_hip.h section 1g); exclude_seen / exclude as in topn_batch.  Returns (ranks uint32, one per cell in row
+        order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m], the admissible items of each user)."""
+        users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, self.dimA, self.dimB, self.k)
+        m = len(users)
+        if exclude_seen and m and (int(users.min()) < self.shardA[0] or int(users.max()) >= self.shardA[1]):
+            raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+        ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
+        if m == 0:
+            return ranks, n_adm
+        _rank_batch_rc(self.lib.poismf_hip_session_rank_batch(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), int(bool(exclude_seen)),
+                                                              _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)))
+        return ranks, n_adm
+
+    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False):
+        """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
+        CSR (nothing is uploaded), exclude leaves out more."""
+        users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.dimA, self.dimB)
+        ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude)
+        return _ranking_result(test[0], ranks, n_adm, k, per_user)
 
     def _text(self, fn, which):
         """a text report of the library, whole: ask for the length first (a fixed buffer cut long plans mid-item)"""

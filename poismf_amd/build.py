@@ -2,9 +2,9 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Nine translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
+Ten translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
 PG, CG and TNCG are the bulk of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the
-rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip) and the batched top-N (topn_batch.hip) -- are compiled to object files side by side and linked.  Every object and
+rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip) -- are compiled to object files side by side and linked.  Every object and
 library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
 digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full
 build takes ~2 minutes on 8 cores.
@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "poismf_hip.h")
 _ROW = ["poismf_hip.hip", "plan.hpp", "devmem.hpp", "solvers.hpp", "row_eval.hpp", "reg_eval.hpp", "lane_eval.hpp", "wave_ops.hpp"]
-_HOST = ["poismf_hip_host.hip", "plan.hpp", "devmem.hpp", "row_eval.hpp", "wave_ops.hpp", "topn_batch.hpp"]
+_HOST = ["poismf_hip_host.hip", "plan.hpp", "devmem.hpp", "row_eval.hpp", "wave_ops.hpp", "topn_batch.hpp", "rank_batch.hpp"]
 # unit -> (source files, first is the one compiled; extra flags).  poismf_hip.hip is compiled four times: one
 # translation unit per inner solver (its row kernels are the bulk of the compile time); the host side is its own file.
 UNITS = {
@@ -31,7 +31,8 @@ UNITS = {
     "coo_convert": (["coo_convert.hip", "devmem.hpp"], []),
     "serve": (["serve.hip", "devmem.hpp"], []),
     "llk": (["llk.hip", "devmem.hpp", "wave_ops.hpp"], []),
-    "topn_batch": (["topn_batch.hip", "topn_batch.hpp", "devmem.hpp"], []),
+    "topn_batch": (["topn_batch.hip", "topn_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
+    "rank_batch": (["rank_batch.hip", "rank_batch.hpp", "topn_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
 }
 
 
@@ -87,7 +88,7 @@ def _units():
     """The -DPMF_TIMING development build keeps its phase timers in one device-side array, so it stays one translation unit."""
     if "-DPMF_TIMING" in os.environ.get("POISMF_HIP_EXTRA_FLAGS", "").split():
         return {"poismf_hip_host": UNITS["poismf_hip_host"], "poismf_hip_all": (_ROW, []), "coo_convert": UNITS["coo_convert"],
-                "serve": UNITS["serve"], "llk": UNITS["llk"], "topn_batch": UNITS["topn_batch"]}
+                "serve": UNITS["serve"], "llk": UNITS["llk"], "topn_batch": UNITS["topn_batch"], "rank_batch": UNITS["rank_batch"]}
     return UNITS
 
 

@@ -23,6 +23,7 @@
 
 #include "plan.hpp"
 #include "topn_batch.hpp"
+#include "rank_batch.hpp"
 
 // the device-visible twin of the interrupt flag (pinned host memory; see on_sigint below): one word, allocated on first use, never freed
 static volatile unsigned* g_stop_word = nullptr;
@@ -273,7 +274,7 @@ struct poismf_hip_session {
     std::string last_plan[2];         // the launches of the most recent half-sweep of each half, as text
     double* d_llk = nullptr;          // scratch of poismf_hip_session_llk (allocated by its first call)
     size_t llk_cap = 0;               // ... in doubles
-    void* d_topn = nullptr;           // scratch of poismf_hip_session_topn_batch (allocated by its first call, grown when a call needs more)
+    void* d_topn = nullptr;           // scratch of poismf_hip_session_topn_batch and _rank_batch (allocated by its first call, grown when a call needs more)
     size_t topn_cap = 0;              // ... in bytes
     std::vector<unsigned long long> topn_indptr;   // exclude_seen: host copy of the CSR shard's row pointers (fetched by the first such call)
     int csr_rows_sorted = -1;         // exclude_seen: -1 not checked yet, 0 some resident CSR row is not strictly ascending, 1 all are
@@ -1727,6 +1728,26 @@ int poismf_hip_session_topn_batch(poismf_hip_session* s, const sparse_ix* users,
     PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
     return poismf_hip_topn_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, exclude_seen ? &seen : nullptr,
                                      excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
+}
+
+// Batched exact ranks from the resident (compact) factors (rank_batch.hip; include/poismf_hip.h section 1g), ordered as the call above.
+// The scratch is the batched top-N's: either call grows it to what it needs and neither keeps anything in it between calls.
+int poismf_hip_session_rank_batch(poismf_hip_session* s, const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr,
+                                  const sparse_ix* test_indices, int exclude_seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                  unsigned int* out_rank, unsigned int* out_n_adm)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
+    if (const int rc = poismf_hip_rank_batch_check(users, n_users, s->dimA, s->dimB, s->k, test_indptr, test_indices, excl_indptr, excl_indices))
+        return rc;
+    const Half& h = s->half[1];
+    if (exclude_seen)
+        for (size_t i = 0; i < n_users; i++)
+            if ((size_t)users[i] < h.row_begin || (size_t)users[i] >= h.row_end) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
+    return poismf_hip_rank_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, test_indptr, test_indices,
+                                     exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_rank, out_n_adm);
 }
 
 #ifdef PMF_PROBE

@@ -1,0 +1,660 @@
+// rank_batch.hip -- batched exact ranks (include/poismf_hip.h, section 1g): for many users at once, the 0-based position of each
+// held-out item in the user's complete ranked list under the total order "score descending, item index ascending", exclusion sets
+// left out.  score(u, j) is section 1f's: the k-ordered fused chain, bit for bit what pair_dot_kernel (serve.hip) computes.
+//
+// rank(u, t) = #{j in 0..dimB-1 before t} - #{e in E(u) before t}: a dense count over every item and a sparse correction.
+//
+//   rank_threshold_kernel  one thread per held-out cell: its score with the scalar chain (the "threshold"), and whether it is in E(u).
+//   rank_order_kernel      one thread per cell: its position among the user's cells (valid ones best first under the total order, cells
+//                          in E(u) behind them), by counting -- quadratic in a row's length, hence POISMF_HIP_RANK_BATCH_MAX_ROW.
+//   rank_tile_kernel       the users x items tile of tb_tile.hpp with a counting epilogue.  A row of the tile is a GROUP: up to RB_G
+//                          consecutive thresholds of one user (a user with more occupies several rows; ranks of different thresholds
+//                          are independent).  LDS holds the groups' thresholds and RB_G integer bins per row, registers the group's
+//                          best and worst threshold.  A score that does not come before the worst threshold dies in registers; one
+//                          before the best adds to a register counter; one in between is compared with the thresholds between them
+//                          (read from LDS once for the lane's four scores of that row) and adds 1 to the bin of the first threshold
+//                          it comes before (LDS integer add).  At the end a row's running sum over its bins
+//                          is the slice's count for each threshold; slices add theirs with integer atomics (order cannot matter).
+//                          The tile's score of item t has the bits of t's threshold (tests/test_gpu_rank_batch.py), so t never
+//                          comes before itself.
+//   rank_excl_kernel       one wave per user over E(u) (the batch's list, then the resident row minus what the list already had):
+//                          the item's score with the scalar chain, a binary search in the user's ordered thresholds, +1 in a
+//                          difference array at the first threshold it comes before; and N(u) = dimB - |E(u)|.
+//   rank_finish_kernel     one thread per user: rank = dense count - running sum of the difference array, written at the cell's
+//                          place in the caller's order; POISMF_HIP_RANK_EXCLUDED for cells in E(u).
+//
+// All counting is in integers; no float atomics.  The host side cuts the batch into chunks of users so that ONE scratch allocation of
+// at most POISMF_HIP_RANK_BATCH_BUDGET_MB holds a chunk (RbLayout; poismf_hip_rank_batch_scratch_bytes reports its size).
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <limits>
+#include <vector>
+
+#include "../../include/poismf_hip.h"
+#include "devmem.hpp"
+#include "tb_tile.hpp"
+#include "rank_batch.hpp"
+
+namespace {
+
+constexpr int RB_G = 32;                                  // thresholds per row of the tile
+constexpr int RB_GS = RB_G + 1;                           // LDS row stride of thresholds and bins (rows 4 apart fall on banks 4 apart)
+constexpr size_t RB_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many
+constexpr size_t RB_CHUNK_USERS_MAX = 262144;
+constexpr size_t RB_BUDGET = (size_t)POISMF_HIP_RANK_BATCH_BUDGET_MB << 20;
+constexpr size_t RB_ROW_MAX = POISMF_HIP_RANK_BATCH_MAX_ROW;
+constexpr size_t RB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
+constexpr unsigned RB_EXCLUDED = POISMF_HIP_RANK_EXCLUDED;
+
+struct RbArgs {
+    const real_t* A;                  // rows addressed by `arow`
+    const real_t* B;                  // [dimB x k]
+    int k;
+    unsigned dimB, n_users, n_cells;
+    const unsigned* arow;             // [n_users] the chunk's rows of A
+    const unsigned* tptr;             // [n_users + 1] the chunk's held-out rows, from 0
+    const unsigned* cell_row;         // [n_cells] chunk user of a cell
+    const unsigned* cell_item;        // [n_cells]
+    real_t* cell_score;               // [n_cells] thresholds in the caller's order
+    unsigned* cell_excl;              // [n_cells] 1: the item is in E(u)
+    real_t* s_score;                  // [n_cells] per user: valid thresholds best first, then the excluded cells
+    unsigned* s_item;
+    unsigned* s_origin;               // the cell an ordered entry came from
+    unsigned* nvalid;                 // [n_users] cells not in E(u)
+    unsigned* dense;                  // [n_cells] (ordered) items of 0..dimB-1 before the threshold
+    unsigned* corr;                   // [n_cells] (ordered) difference array: items of E(u) whose first beaten threshold this is
+    unsigned* rank;                   // [n_cells] (caller's order)
+    unsigned* n_adm;                  // [n_users]
+    const unsigned* grow;             // [ngroups] chunk user of a group
+    const unsigned* gstart;           // [ngroups] its first ordered entry
+    unsigned ngroups, nslices, tiles_per_slice;
+    const unsigned long long* seen_indptr;   // exclude_seen: the resident CSR (nullptr: off); local row = arow - seen_row0
+    const unsigned* seen_indices;
+    unsigned seen_row0;
+    int seen_sorted;
+    const unsigned* ex_indptr;        // the batch's own lists for this chunk (nullptr: none), strictly ascending rows
+    const unsigned* ex_indices;
+};
+
+__device__ __forceinline__ float rb_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double rb_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// the k-ordered fused chain of pair_dot_kernel
+__device__ __forceinline__ real_t rb_dot(const real_t* A, const real_t* B, int k, unsigned u, unsigned j)
+{
+    const real_t* p = A + (size_t)u * (size_t)k;
+    const real_t* q = B + (size_t)j * (size_t)k;
+    real_t s = 0;
+    for (int c = 0; c < k; c++) s = rb_fma(p[c], q[c], s);
+    return s;
+}
+
+__device__ __forceinline__ bool rb_sorted_has(const unsigned* v, unsigned long long lo, unsigned long long hi, unsigned j)
+{
+    while (lo < hi) {
+        const unsigned long long mid = lo + (hi - lo) / 2;
+        const unsigned x = v[mid];
+        if (x == j) return true;
+        if (x < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// item j is in E(chunk user i)
+__device__ __forceinline__ bool rb_excluded(const RbArgs& a, unsigned i, unsigned j)
+{
+    if (a.ex_indptr != nullptr && rb_sorted_has(a.ex_indices, a.ex_indptr[i], a.ex_indptr[i + 1], j)) return true;
+    if (a.seen_indptr != nullptr) {
+        const unsigned row = a.arow[i] - a.seen_row0;
+        const unsigned long long p0 = a.seen_indptr[row], p1 = a.seen_indptr[row + 1];
+        if (a.seen_sorted) return rb_sorted_has(a.seen_indices, p0, p1, j);
+        for (unsigned long long p = p0; p < p1; p++)
+            if (a.seen_indices[p] == j) return true;
+    }
+    return false;
+}
+
+// the first of n thresholds ordered best first that (s, j) comes before; n when there is none
+__device__ __forceinline__ unsigned rb_first_beaten(const real_t* ts, const unsigned* tj, unsigned n, real_t s, unsigned j)
+{
+    unsigned lo = 0, hi = n;
+    while (lo < hi) {
+        const unsigned mid = lo + (hi - lo) / 2;
+        if (tb_better(s, j, ts[mid], tj[mid])) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void rank_threshold_kernel(RbArgs a)
+{
+    const unsigned c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const unsigned i = a.cell_row[c], j = a.cell_item[c];
+    a.cell_score[c] = rb_dot(a.A, a.B, a.k, a.arow[i], j);
+    a.cell_excl[c] = rb_excluded(a, i, j) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void rank_order_kernel(RbArgs a)
+{
+    const unsigned c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const unsigned i = a.cell_row[c];
+    const unsigned p0 = a.tptr[i], p1 = a.tptr[i + 1];
+    const real_t s = a.cell_score[c];
+    const unsigned j = a.cell_item[c];
+    const bool valid = a.cell_excl[c] == 0;
+    unsigned pos = 0, nv = 0;
+    for (unsigned q = p0; q < p1; q++) {
+        const bool vq = a.cell_excl[q] == 0;
+        nv += vq ? 1u : 0u;
+        bool first;   // cell q stands before cell c
+        if (vq && valid) first = tb_better(a.cell_score[q], a.cell_item[q], s, j);
+        else if (vq != valid) first = vq;
+        else first = q < c;
+        pos += first ? 1u : 0u;
+    }
+    a.s_score[p0 + pos] = s;
+    a.s_item[p0 + pos] = j;
+    a.s_origin[p0 + pos] = c;
+    if (c == p0) a.nvalid[i] = nv;
+}
+
+template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile_kernel(RbArgs a)
+{
+    extern __shared__ __align__(16) unsigned char rb_smem[];
+    static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
+    T* As = (T*)rb_smem;                                  // [TB_TU][TB_KS]
+    T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
+    T* Ts = Bs + TB_TJ * TB_KS;                           // [TB_TU][RB_GS] a group's thresholds, best first: score ...
+    unsigned* Tj = (unsigned*)(Ts + TB_TU * RB_GS);       // ... and item
+    unsigned* bins = Tj + TB_TU * RB_GS;                  // [TB_TU][RB_GS] scores whose first beaten threshold is this one
+    unsigned* uid = bins + TB_TU * RB_GS;                 // [TB_TU] row of A, TB_NONE for a row without thresholds
+    unsigned* gn = uid + TB_TU;                           // [TB_TU] thresholds in the group
+    unsigned* gs = gn + TB_TU;                            // [TB_TU] its first ordered entry
+
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned g_base = blockIdx.x * TB_TU;
+    if (tid < TB_TU) {
+        const unsigned g = g_base + tid;
+        unsigned u = TB_NONE, n = 0, st = 0;
+        if (g < a.ngroups) {
+            const unsigned row = a.grow[g];
+            st = a.gstart[g];
+            const unsigned off = st - a.tptr[row], nv = a.nvalid[row];
+            if (nv > off) n = nv - off < (unsigned)RB_G ? nv - off : (unsigned)RB_G;
+            if (n > 0) u = a.arow[row];
+        }
+        uid[tid] = u;
+        gn[tid] = n;
+        gs[tid] = st;
+    }
+    __syncthreads();
+    for (unsigned e = tid; e < (unsigned)(TB_TU * RB_G); e += TB_WG) {
+        const unsigned row = e / RB_G, i = e % RB_G;
+        const bool in = i < gn[row];
+        Ts[row * RB_GS + i] = in ? a.s_score[gs[row] + i] : (T)0;
+        Tj[row * RB_GS + i] = in ? a.s_item[gs[row] + i] : 0u;
+        bins[row * RB_GS + i] = 0;
+    }
+    __syncthreads();
+
+    const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
+    const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
+    const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
+    const int nchunks = (a.k + TB_KC - 1) / TB_KC;
+    const unsigned col = lane & 15, quad = lane >> 4;
+    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four rows are urow0 .. urow0 + 3
+    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
+    auto item_row = [&](unsigned j_base) { return [&a, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < a.dimB ? (long long)j : -1ll; }; };
+
+    // best and worst threshold of this lane's four rows; a row without thresholds has a worst one nothing comes before
+    T best_s[4], worst_s[4];
+    unsigned best_j[4], worst_j[4], n_r[4], all_r[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const unsigned n = gn[urow0 + r];
+        n_r[r] = n;
+        all_r[r] = 0;
+        best_s[r] = Ts[(urow0 + r) * RB_GS];
+        best_j[r] = Tj[(urow0 + r) * RB_GS];
+        worst_s[r] = n > 0 ? Ts[(urow0 + r) * RB_GS + n - 1] : std::numeric_limits<T>::infinity();
+        worst_j[r] = n > 0 ? Tj[(urow0 + r) * RB_GS + n - 1] : 0u;
+    }
+
+    // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
+    T b_next[TB_NL];
+    if (nchunks == 1) {
+        tb_fetch(b_next, a.A, a.k, 0, a.k, user_row);
+        tb_store(As, b_next);
+        tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(tile0 * TB_TJ));
+    }
+
+    for (unsigned jt = tile0; jt < tile1; jt++) {
+        const unsigned j_base = jt * TB_TJ;
+        T acc[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) acc[t][r] = 0;
+        if (nchunks == 1) {
+            __syncthreads();   // every wave is done with the items' tile of the step before
+            tb_store(Bs, b_next);
+            __syncthreads();
+            if (jt + 1 < tile1) tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(j_base + TB_TJ));
+            tb_compute<T, MFMA>(acc, As, Bs, a.k);
+        } else {
+            for (int ch = 0; ch < nchunks; ch++) {
+                const int c0 = ch * TB_KC;
+                const int len = a.k - c0 < TB_KC ? a.k - c0 : TB_KC;
+                __syncthreads();   // every wave is done with the tiles of the step before
+                tb_fetch(b_next, a.A, a.k, c0, len, user_row);
+                tb_store(As, b_next);
+                tb_fetch(b_next, a.B, a.k, c0, len, item_row(j_base));
+                tb_store(Bs, b_next);
+                __syncthreads();
+                tb_compute<T, MFMA>(acc, As, Bs, len);
+            }
+        }
+
+        // ---- counting: the bins of rows 16 wave .. 16 wave + 15 are touched by this wave alone ----
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            bool some[4], any = false;   // comes before some threshold: before the worst one
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const unsigned j = j_base + 16 * t + col;
+                some[t] = j < a.dimB && tb_better(acc[t][r], j, worst_s[r], worst_j[r]);
+                any = any || some[t];
+            }
+            if (__ballot(any) == 0) continue;       // (uniform over the wave) every score of this pass died in registers
+            bool mid[4], any_mid = false;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const bool all = some[t] && tb_better(acc[t][r], j_base + 16 * t + col, best_s[r], best_j[r]);   // before all of them
+                all_r[r] += all ? 1u : 0u;
+                mid[t] = some[t] && !all;
+                any_mid = any_mid || mid[t];
+            }
+            if (__ballot(any_mid) == 0) continue;   // (uniform) the survivors counted in registers
+            // before the worst threshold, not before the best: how many of thresholds 1 .. n - 2 it comes before besides.  The row's
+            // thresholds are read once for the lane's four scores (the same address for the 16 lanes of a row: a broadcast); the
+            // item indices are only looked at when some lane of the wave meets an equal score.
+            const T* ts = Ts + (urow0 + r) * RB_GS;
+            const unsigned* tj = Tj + (urow0 + r) * RB_GS;
+            const unsigned n = n_r[r];
+            unsigned beaten[4] = { 1, 1, 1, 1 };
+            for (unsigned i = 1; i + 1 < n; i++) {
+                const T ti = ts[i];
+#pragma unroll
+                for (int t = 0; t < 4; t++) beaten[t] += acc[t][r] > ti ? 1u : 0u;
+                const bool tie = acc[0][r] == ti || acc[1][r] == ti || acc[2][r] == ti || acc[3][r] == ti;
+                if (__ballot(tie) != 0) {
+                    const unsigned ji = tj[i];
+#pragma unroll
+                    for (int t = 0; t < 4; t++) beaten[t] += acc[t][r] == ti && j_base + 16 * t + col < ji ? 1u : 0u;
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                if (mid[t]) atomicAdd(&bins[(urow0 + r) * RB_GS + n - beaten[t]], 1u);   // (LDS, integer) the first threshold it comes before
+        }
+    }
+
+    // ---- the slice's counts: a score before the best threshold is before every one of the group ----
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+        if (all_r[r]) atomicAdd(&bins[(urow0 + r) * RB_GS], all_r[r]);
+    __syncthreads();
+    if (tid < TB_TU) {
+        const unsigned n = gn[tid];
+        unsigned run = 0;
+        for (unsigned i = 0; i < n; i++) {
+            run += bins[tid * RB_GS + i];
+            if (run) atomicAdd(&a.dense[gs[tid] + i], run);   // (global, integer: the slices' counts add up in any order)
+        }
+    }
+}
+
+// one wave per chunk user
+__global__ __launch_bounds__(256) void rank_excl_kernel(RbArgs a)
+{
+    const unsigned i = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= a.n_users) return;   // (uniform over the wave)
+    const unsigned p0 = a.tptr[i], nv = a.nvalid[i], u = a.arow[i];
+    const real_t* ts = a.s_score + p0;
+    const unsigned* tj = a.s_item + p0;
+    unsigned n_excl = 0;
+    auto subtract = [&](unsigned j) {
+        if (nv == 0) return;
+        const unsigned pos = rb_first_beaten(ts, tj, nv, rb_dot(a.A, a.B, a.k, u, j), j);
+        if (pos < nv) atomicAdd(&a.corr[p0 + pos], 1u);
+    };
+    unsigned long long e0 = 0, e1 = 0;
+    if (a.ex_indptr != nullptr) {
+        e0 = a.ex_indptr[i];
+        e1 = a.ex_indptr[i + 1];
+        for (unsigned long long e = e0 + lane; e < e1; e += 64) subtract(a.ex_indices[e]);
+        n_excl = (unsigned)(e1 - e0);
+    }
+    if (a.seen_indptr != nullptr) {
+        const unsigned row = u - a.seen_row0;
+        const unsigned long long s0 = a.seen_indptr[row], s1 = a.seen_indptr[row + 1];
+        for (unsigned long long base = s0; base < s1; base += 64) {
+            const unsigned long long p = base + lane;
+            bool mine = p < s1;
+            unsigned j = 0;
+            if (mine) {
+                j = a.seen_indices[p];
+                if (a.ex_indptr != nullptr && rb_sorted_has(a.ex_indices, e0, e1, j)) mine = false;   // the list had it
+                if (mine && !a.seen_sorted)   // a row in the caller's own order may name an item twice: the first one counts
+                    for (unsigned long long q = s0; q < p && mine; q++) mine = a.seen_indices[q] != j;
+            }
+            if (mine) subtract(j);
+            n_excl += (unsigned)__popcll(__ballot(mine));
+        }
+    }
+    if (lane == 0) a.n_adm[i] = a.dimB - n_excl;
+}
+
+__global__ __launch_bounds__(256) void rank_finish_kernel(RbArgs a)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n_users) return;
+    const unsigned p0 = a.tptr[i], p1 = a.tptr[i + 1], nv = a.nvalid[i];
+    unsigned run = 0;
+    for (unsigned p = p0; p < p1; p++) {
+        if (p - p0 < nv) {
+            run += a.corr[p];
+            a.rank[a.s_origin[p]] = a.dense[p] - run;
+        } else
+            a.rank[a.s_origin[p]] = RB_EXCLUDED;
+    }
+}
+
+size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+size_t round_up(size_t a, size_t b) { return ceil_div(a, b) * b; }
+
+// The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
+struct RbLayout {
+    size_t chunk_users;      // users per chunk
+    size_t cell_cap;         // held-out cells a chunk may carry
+    size_t idx_cap;          // exclusion indices a chunk may carry
+    size_t group_cap;
+    size_t arow, tptr, ex_indptr, nvalid, n_adm, cell_row, cell_item, cell_score, cell_excl, s_score, s_item, s_origin, dense, corr, rank, grow,
+        gstart, ex_indices, total;
+    RbLayout(size_t n_users, size_t n_cells, size_t dimB)
+    {
+        const size_t R = sizeof(real_t), U = sizeof(unsigned);
+        n_users = std::max<size_t>(n_users, 1);
+        n_cells = std::max<size_t>(n_cells, 1);
+        dimB = std::max<size_t>(dimB, 1);
+        const size_t uc = std::min(n_users, RB_CHUNK_USERS_MAX);
+        idx_cap = std::min(RB_BUDGET / 2 / U, uc * dimB);   // (no overflow: 2^18 x 2^31)
+        const size_t rest = RB_BUDGET - idx_cap * U - 32 * 20;   // (32: alignment of each of the parts)
+        const size_t per_user = 5 * U + 2 * U + 2 * U;           // five per-user arrays (two of uc + 1), a group of its own
+        const size_t per_cell = 8 * U + 2 * R + 1;               // eight index arrays, two of scores, 2 U / RB_G for the groups
+        cell_cap = std::min((rest - per_user * uc - 64) / per_cell, n_cells);   // (>= RB_ROW_MAX whatever the arguments: see the static_assert)
+        chunk_users = uc;
+        group_cap = uc + cell_cap / RB_G + 1;
+        size_t o = 0;
+        auto take = [&o](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 32); return at; };
+        arow = take(uc * U);
+        tptr = take((uc + 1) * U);
+        ex_indptr = take((uc + 1) * U);
+        nvalid = take(uc * U);
+        n_adm = take(uc * U);
+        cell_row = take(cell_cap * U);
+        cell_item = take(cell_cap * U);
+        cell_score = take(cell_cap * R);
+        cell_excl = take(cell_cap * U);
+        s_score = take(cell_cap * R);
+        s_item = take(cell_cap * U);
+        s_origin = take(cell_cap * U);
+        dense = take(cell_cap * U);
+        corr = take(cell_cap * U);
+        rank = take(cell_cap * U);
+        grow = take(group_cap * U);
+        gstart = take(group_cap * U);
+        ex_indices = take(idx_cap * U);
+        total = o;
+    }
+};
+// the least a chunk's cells get (every exclusion index and every user of a chunk present) holds the longest row a call accepts
+static_assert((RB_BUDGET / 2 - 32 * 20 - 9 * sizeof(unsigned) * RB_CHUNK_USERS_MAX - 64) / (8 * sizeof(unsigned) + 2 * sizeof(real_t) + 1) >= RB_ROW_MAX,
+              "one held-out row fits a chunk");
+
+size_t rb_lds_bytes() { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * RB_GS * (sizeof(real_t) + 8) + (size_t)TB_TU * 12; }
+// two workgroups per CU (160 KB of LDS), as topn_tile_kernel at its usual list sizes
+static_assert(2 * (2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * RB_GS * (sizeof(real_t) + 8) + (size_t)TB_TU * 12) <= 160 * 1024,
+              "two workgroups of rank_tile_kernel per CU");
+
+int pick_device()
+{
+    int device = 0;
+    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
+    return device;
+}
+
+#define RB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
+
+}  // namespace
+
+extern "C" size_t poismf_hip_rank_batch_scratch_bytes(size_t n_users, size_t n_cells, size_t dimB, size_t k)
+{
+    (void)k;   // (the factors' chunks live in LDS: no part of the scratch depends on k)
+    return RbLayout(n_users, n_cells, dimB).total;
+}
+
+// The argument checks of both entry points: 0, or 2.  No device call.
+int poismf_hip_rank_batch_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
+                                const sparse_ix* test_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices)
+{
+    if (k < 1 || k > RB_K_MAX || dimB < 1 || dimB > 0x7fffffffull || dimA > 0x7fffffffull) return 2;
+    if (users == nullptr || test_indptr == nullptr) return 2;
+    for (size_t i = 0; i < n_users; i++)
+        if ((size_t)users[i] >= dimA) return 2;
+    // a CSR-shaped list: rows strictly ascending, indices below dimB, no row longer than row_max
+    auto rows_ok = [&](const sparse_ix* indptr, const sparse_ix* indices, size_t row_max) {
+        if ((long long)indptr[0] < 0) return false;
+        for (size_t i = 0; i < n_users; i++) {
+            if (indptr[i + 1] < indptr[i]) return false;
+            const size_t p0 = (size_t)indptr[i], p1 = (size_t)indptr[i + 1];
+            if (p1 - p0 > dimB || p1 - p0 > row_max) return false;
+            if (p1 > p0 && indices == nullptr) return false;
+            for (size_t p = p0; p < p1; p++) {
+                if ((long long)indices[p] < 0 || (size_t)indices[p] >= dimB) return false;
+                if (p > p0 && (size_t)indices[p - 1] >= (size_t)indices[p]) return false;
+            }
+        }
+        return true;
+    };
+    if (!rows_ok(test_indptr, test_indices, RB_ROW_MAX)) return 2;
+    if (excl_indptr != nullptr && !rows_ok(excl_indptr, excl_indices, RbLayout(n_users, 1, dimB).idx_cap)) return 2;
+    return 0;
+}
+
+// ---- core on device-resident factors (the session and the drop-in below).  Arguments already checked. ----
+// dA rows are addressed by users[i], or by i itself when compact_A (the drop-in uploads only the batch's rows).  *d_scratch /
+// *scratch_cap: the caller's scratch, grown here when it is smaller than this call needs.  Returns 0 or 1.
+int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                              const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices,
+                              PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
+                              size_t* scratch_cap, unsigned int* out_rank, unsigned int* out_n_adm)
+{
+    if (seen != nullptr && poismf_hip_topn_seen_sorted(*seen, stream)) return 1;
+    const size_t n_cells = (size_t)test_indptr[n_users] - (size_t)test_indptr[0];
+    const RbLayout L(n_users, n_cells, dimB);
+    if (*scratch_cap < L.total) {
+        pmf_free(*d_scratch, stream);
+        *d_scratch = nullptr;
+        *scratch_cap = 0;
+        RB_TRY(pmf_alloc((unsigned char**)d_scratch, L.total, stream));
+        *scratch_cap = L.total;
+    }
+    unsigned char* base = (unsigned char*)*d_scratch;
+    const size_t lds = rb_lds_bytes();
+    auto kern = rank_tile_kernel<real_t, sizeof(real_t) == 4>;
+    RB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+
+    std::vector<unsigned> hu, htp, hrow, hitem, hgrow, hgstart, hp, hx;
+    for (size_t u0 = 0; u0 < n_users;) {
+        // the chunk: up to chunk_users users whose held-out cells and exclusion lists fit their areas together
+        size_t u1 = u0, nc = 0, nx = 0;
+        while (u1 < n_users && u1 - u0 < L.chunk_users) {
+            const size_t cells = (size_t)test_indptr[u1 + 1] - (size_t)test_indptr[u1];
+            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
+            if (u1 > u0 && (nc + cells > L.cell_cap || nx + len > L.idx_cap)) break;
+            nc += cells;
+            nx += len;
+            u1++;
+        }
+        const size_t nu = u1 - u0;
+        if (nc > L.cell_cap || nx > L.idx_cap) return 1;   // (cannot happen: the checks bound a single row by both)
+        const size_t c_base = (size_t)test_indptr[u0];
+        hu.resize(nu);
+        htp.resize(nu + 1);
+        hrow.resize(nc);
+        hitem.resize(nc);
+        hgrow.clear();
+        hgstart.clear();
+        for (size_t i = 0; i < nu; i++) {
+            hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
+            const size_t p0 = (size_t)test_indptr[u0 + i] - c_base, p1 = (size_t)test_indptr[u0 + i + 1] - c_base;
+            htp[i] = (unsigned)p0;
+            for (size_t p = p0; p < p1; p++) {
+                hrow[p] = (unsigned)i;
+                hitem[p] = (unsigned)test_indices[c_base + p];
+            }
+            for (size_t p = p0; p < p1; p += RB_G) {
+                hgrow.push_back((unsigned)i);
+                hgstart.push_back((unsigned)p);
+            }
+        }
+        htp[nu] = (unsigned)nc;
+        const size_t ng = hgrow.size();
+        if (ng > L.group_cap) return 1;   // (cannot happen: a user adds at most one partial group)
+        RB_TRY(pmf_upload(base + L.arow, hu.data(), nu * sizeof(unsigned), stream));
+        RB_TRY(pmf_upload(base + L.tptr, htp.data(), (nu + 1) * sizeof(unsigned), stream));
+        RB_TRY(pmf_upload(base + L.cell_row, hrow.data(), nc * sizeof(unsigned), stream));
+        RB_TRY(pmf_upload(base + L.cell_item, hitem.data(), nc * sizeof(unsigned), stream));
+        RB_TRY(pmf_upload(base + L.grow, hgrow.data(), ng * sizeof(unsigned), stream));
+        RB_TRY(pmf_upload(base + L.gstart, hgstart.data(), ng * sizeof(unsigned), stream));
+        if (excl_indptr != nullptr) {
+            hp.resize(nu + 1);
+            hx.resize(nx);
+            const size_t p_base = (size_t)excl_indptr[u0];
+            for (size_t i = 0; i <= nu; i++) hp[i] = (unsigned)((size_t)excl_indptr[u0 + i] - p_base);
+            for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
+            RB_TRY(pmf_upload(base + L.ex_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream));
+            RB_TRY(pmf_upload(base + L.ex_indices, hx.data(), nx * sizeof(unsigned), stream));
+        }
+        RB_TRY(hipMemsetAsync(base + L.nvalid, 0, nu * sizeof(unsigned), stream));
+        if (nc > 0) {
+            RB_TRY(hipMemsetAsync(base + L.dense, 0, nc * sizeof(unsigned), stream));
+            RB_TRY(hipMemsetAsync(base + L.corr, 0, nc * sizeof(unsigned), stream));
+        }
+
+        const size_t tiles = ceil_div(std::max<size_t>(ng, 1), TB_TU);
+        const size_t item_tiles = ceil_div(dimB, TB_TJ);
+        const size_t want = std::min(tiles >= RB_TARGET_WGS ? 1 : ceil_div(RB_TARGET_WGS, tiles), item_tiles);
+        const size_t tps = ceil_div(item_tiles, want);
+        const size_t nslices = ceil_div(item_tiles, tps);
+        RbArgs a;
+        a.A = dA;
+        a.B = dB;
+        a.k = (int)k;
+        a.dimB = (unsigned)dimB;
+        a.n_users = (unsigned)nu;
+        a.n_cells = (unsigned)nc;
+        a.arow = (const unsigned*)(base + L.arow);
+        a.tptr = (const unsigned*)(base + L.tptr);
+        a.cell_row = (const unsigned*)(base + L.cell_row);
+        a.cell_item = (const unsigned*)(base + L.cell_item);
+        a.cell_score = (real_t*)(base + L.cell_score);
+        a.cell_excl = (unsigned*)(base + L.cell_excl);
+        a.s_score = (real_t*)(base + L.s_score);
+        a.s_item = (unsigned*)(base + L.s_item);
+        a.s_origin = (unsigned*)(base + L.s_origin);
+        a.nvalid = (unsigned*)(base + L.nvalid);
+        a.dense = (unsigned*)(base + L.dense);
+        a.corr = (unsigned*)(base + L.corr);
+        a.rank = (unsigned*)(base + L.rank);
+        a.n_adm = (unsigned*)(base + L.n_adm);
+        a.grow = (const unsigned*)(base + L.grow);
+        a.gstart = (const unsigned*)(base + L.gstart);
+        a.ngroups = (unsigned)ng;
+        a.nslices = (unsigned)nslices;
+        a.tiles_per_slice = (unsigned)tps;
+        a.seen_indptr = seen ? seen->d_indptr : nullptr;
+        a.seen_indices = seen ? seen->d_indices : nullptr;
+        a.seen_row0 = seen ? (unsigned)seen->row_begin : 0u;
+        a.seen_sorted = seen ? *seen->sorted : 0;
+        a.ex_indptr = excl_indptr ? (const unsigned*)(base + L.ex_indptr) : nullptr;
+        a.ex_indices = (const unsigned*)(base + L.ex_indices);
+        if (nc > 0) {
+            const unsigned cell_blocks = (unsigned)ceil_div(nc, 256);
+            hipLaunchKernelGGL(rank_threshold_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
+            RB_TRY(hipGetLastError());
+            hipLaunchKernelGGL(rank_order_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
+            RB_TRY(hipGetLastError());
+            hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nslices), dim3(TB_WG), lds, stream, a);
+            RB_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)ceil_div(nu, 4)), dim3(256), 0, stream, a);
+        RB_TRY(hipGetLastError());
+        if (nc > 0) {
+            hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)ceil_div(nu, 256)), dim3(256), 0, stream, a);
+            RB_TRY(hipGetLastError());
+            RB_TRY(pmf_download(out_rank + c_base, base + L.rank, nc * sizeof(unsigned), stream));
+        }
+        RB_TRY(pmf_download(out_n_adm + u0, base + L.n_adm, nu * sizeof(unsigned), stream));
+        u0 = u1;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int poismf_hip_rank_batch(const real_t* A, const real_t* B, int k, size_t dimA, size_t dimB, const sparse_ix* users, size_t n_users,
+                          const sparse_ix* test_indptr, const sparse_ix* test_indices, const sparse_ix* excl_indptr,
+                          const sparse_ix* excl_indices, unsigned int* out_rank, unsigned int* out_n_adm)
+{
+    if (n_users == 0) return 0;
+    if (k < 1 || A == nullptr || B == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
+    if (const int rc = poismf_hip_rank_batch_check(users, n_users, dimA, dimB, (size_t)k, test_indptr, test_indices, excl_indptr, excl_indices))
+        return rc;
+    const int device = pick_device();
+    if (hipSetDevice(device) != hipSuccess) return 1;
+    const hipStream_t st = nullptr;
+    const size_t kk = (size_t)k;
+    const bool compact = n_users < dimA;   // only the batch's rows of A go up when that is less than all of A
+    real_t *dA = nullptr, *dB = nullptr;
+    void* d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    int rc = 1;
+    do {
+        const size_t rowsA = compact ? n_users : dimA;
+        if (pmf_alloc(&dA, rowsA * kk * sizeof(real_t) + 16, st) != hipSuccess || pmf_alloc(&dB, dimB * kk * sizeof(real_t) + 16, st) != hipSuccess) break;
+        if (compact) {
+            std::vector<real_t> rows;
+            try { rows.resize(n_users * kk); } catch (const std::bad_alloc&) { break; }
+            for (size_t i = 0; i < n_users; i++) memcpy(rows.data() + i * kk, A + (size_t)users[i] * kk, kk * sizeof(real_t));
+            if (pmf_upload_big(dA, rows.data(), rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        } else if (pmf_upload_big(dA, A, rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        if (pmf_upload_big(dB, B, dimB * kk * sizeof(real_t), device, st) != hipSuccess) break;
+        rc = poismf_hip_rank_batch_run(st, dA, dB, dimB, kk, compact, users, n_users, test_indptr, test_indices, nullptr, excl_indptr, excl_indices,
+                                       &d_scratch, &scratch_cap, out_rank, out_n_adm);
+    } while (0);
+    pmf_free(dA, st);
+    pmf_free(dB, st);
+    pmf_free(d_scratch, st);
+    return rc;
+}
+
+}  // extern "C"

@@ -1,0 +1,92 @@
+// tb_tile.hpp -- the users x items score tile shared by the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip):
+// a workgroup of four waves owns TB_TU = 64 rows of users (wave w: rows 16 w .. 16 w + 15) and walks the items TB_TJ = 64 at a time; the
+// users' rows and the items' rows go through LDS in chunks of TB_KC columns, zero padded to a multiple of four columns.  tb_compute gives
+// each (user, item) the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  -- fp32 on v_mfma_f32_16x16x4_f32, fp64
+// on a VALU chain with the same register layout -- bit for bit what pair_dot_kernel (serve.hip) computes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/poismf_hip.h"
+
+namespace {
+
+constexpr int TB_WG = 256;                                // threads per workgroup (four waves)
+constexpr int TB_TU = 64;                                 // users per workgroup
+constexpr int TB_TJ = 64;                                 // items per step
+constexpr int TB_KC = sizeof(real_t) == 4 ? 64 : 32;      // columns of the factors per LDS chunk
+constexpr int TB_KS = TB_KC + 4;                          // LDS row stride (fp32: lanes (row l & 15, column l >> 4) fall on 64 distinct banks)
+constexpr unsigned TB_NONE = 0xffffffffu;
+
+typedef float tb_f32x4 __attribute__((ext_vector_type(4)));
+
+// the total order: (s1, j1) comes before (s2, j2)
+__device__ __forceinline__ bool tb_better(real_t s1, unsigned j1, real_t s2, unsigned j2) { return s1 > s2 || (s1 == s2 && j1 < j2); }
+
+constexpr int TB_NL = TB_TU * TB_KC / TB_WG;   // elements of a [64 x TB_KC] tile per thread: element e = thread + i TB_WG is (row e / TB_KC, column e % TB_KC)
+
+// rows [64 x TB_KC columns] of a row-major [* x k] factor into registers: columns c0 .. c0 + len - 1, zero elsewhere
+template <class RowOf> __device__ __forceinline__ void tb_fetch(real_t (&v)[TB_NL], const real_t* src, int k, int c0, int len, RowOf row_of)
+{
+#pragma unroll
+    for (int i = 0; i < TB_NL; i++) {
+        const int e = (int)threadIdx.x + i * TB_WG;
+        const int row = e / TB_KC, col = e % TB_KC;
+        const long long r = row_of(row);   // < 0: no such row
+        v[i] = 0;
+        if (r >= 0 && col < len) v[i] = src[(size_t)r * (size_t)k + (size_t)(c0 + col)];
+    }
+}
+__device__ __forceinline__ void tb_store(real_t* dst, const real_t (&v)[TB_NL])
+{
+#pragma unroll
+    for (int i = 0; i < TB_NL; i++) {
+        const int e = (int)threadIdx.x + i * TB_WG;
+        dst[(e / TB_KC) * TB_KS + e % TB_KC] = v[i];
+    }
+}
+
+// acc[t][r] += sum over the chunk's columns, in ascending order, of As[user][c] Bs[item][c] for user 16 wave + 4 (lane >> 4) + r and
+// item 16 t + (lane & 15): one fused multiply-add per column
+template <class T, bool MFMA> __device__ __forceinline__ void tb_compute(T (&acc)[4][4], const T* As, const T* Bs, int len)
+{
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned col = lane & 15, quad = lane >> 4;
+    if constexpr (MFMA) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // A operand: user row (lane & 15), column 4 s + (lane >> 4); B operand: item row (lane & 15), same column;
+        // D: item column lane & 15, user row 4 (lane >> 4) + register
+        const int ksteps = (len + 3) / 4;
+        const T* ap = As + (16 * wave + col) * TB_KS + quad;
+        const T* bp = Bs + col * TB_KS + quad;
+        tb_f32x4 d0 = { acc[0][0], acc[0][1], acc[0][2], acc[0][3] }, d1 = { acc[1][0], acc[1][1], acc[1][2], acc[1][3] };
+        tb_f32x4 d2 = { acc[2][0], acc[2][1], acc[2][2], acc[2][3] }, d3 = { acc[3][0], acc[3][1], acc[3][2], acc[3][3] };
+#pragma unroll 4
+        for (int s = 0; s < ksteps; s++) {
+            const float av = ap[4 * s];
+            const float b0 = bp[4 * s], b1 = bp[16 * TB_KS + 4 * s], b2 = bp[32 * TB_KS + 4 * s], b3 = bp[48 * TB_KS + 4 * s];
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, d1, 0, 0, 0);
+            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b2, d2, 0, 0, 0);
+            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b3, d3, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) { acc[0][r] = d0[r]; acc[1][r] = d1[r]; acc[2][r] = d2[r]; acc[3][r] = d3[r]; }
+#endif
+    } else {
+        const T* ap = As + (16 * wave + 4 * quad) * TB_KS;
+        const T* bp = Bs + col * TB_KS;
+        for (int c = 0; c < len; c++) {
+            T av[4], bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) av[r] = ap[r * TB_KS + c];
+#pragma unroll
+            for (int t = 0; t < 4; t++) bv[t] = bp[16 * t * TB_KS + c];
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc[t][r] = __builtin_fma(av[r], bv[t], acc[t][r]);
+        }
+    }
+}
+
+}  // namespace

@@ -34,15 +34,11 @@
 
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
+#include "tb_tile.hpp"
 #include "topn_batch.hpp"
 
 namespace {
 
-constexpr int TB_WG = 256;                                // threads per workgroup (four waves)
-constexpr int TB_TU = 64;                                 // users per workgroup
-constexpr int TB_TJ = 64;                                 // items per step
-constexpr int TB_KC = sizeof(real_t) == 4 ? 64 : 32;      // columns of the factors per LDS chunk
-constexpr int TB_KS = TB_KC + 4;                          // LDS row stride (fp32: lanes (row l & 15, column l >> 4) fall on 64 distinct banks)
 constexpr int TB_ROOM = 16;                               // free slots a list must have before a pass over 16 item columns
 constexpr int TB_PRUNE_Q = 3;                             // list entries per lane in a prune: lists hold <= 192 entries
 constexpr size_t TB_LDS_LIMIT = 156 * 1024;
@@ -52,11 +48,8 @@ constexpr size_t TB_CHUNK_USERS_MAX = 262144;
 constexpr size_t TB_N_TOP_MAX = POISMF_HIP_TOPN_BATCH_MAX_N_TOP;
 constexpr size_t TB_BUDGET = (size_t)POISMF_HIP_TOPN_BATCH_BUDGET_MB << 20;
 constexpr size_t TB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
-constexpr unsigned TB_NONE = 0xffffffffu;
 static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
 static_assert(TB_N_TOP_MAX >= 128, "the header promises at least 128");
-
-typedef float tb_f32x4 __attribute__((ext_vector_type(4)));
 
 struct TbArgs {
     const real_t* A;                  // rows addressed by `users`
@@ -75,9 +68,6 @@ struct TbArgs {
     real_t* part_score;               // [n_users][nslices][n_top]
     unsigned* part_ix;
 };
-
-// the total order: (s1, j1) comes before (s2, j2)
-__device__ __forceinline__ bool tb_better(real_t s1, unsigned j1, real_t s2, unsigned j2) { return s1 > s2 || (s1 == s2 && j1 < j2); }
 
 __device__ __forceinline__ void tb_wave_sync()
 {
@@ -130,73 +120,6 @@ __device__ __forceinline__ void tb_prune(real_t* ls, unsigned* li, unsigned c, u
     }
     if (lane == 0) *cnt_u = c < n_top ? c : n_top;
     tb_wave_sync();
-}
-
-constexpr int TB_NL = TB_TU * TB_KC / TB_WG;   // elements of a [64 x TB_KC] tile per thread: element e = thread + i TB_WG is (row e / TB_KC, column e % TB_KC)
-
-// rows [64 x TB_KC columns] of a row-major [* x k] factor into registers: columns c0 .. c0 + len - 1, zero elsewhere
-template <class RowOf> __device__ __forceinline__ void tb_fetch(real_t (&v)[TB_NL], const real_t* src, int k, int c0, int len, RowOf row_of)
-{
-#pragma unroll
-    for (int i = 0; i < TB_NL; i++) {
-        const int e = (int)threadIdx.x + i * TB_WG;
-        const int row = e / TB_KC, col = e % TB_KC;
-        const long long r = row_of(row);   // < 0: no such row
-        v[i] = 0;
-        if (r >= 0 && col < len) v[i] = src[(size_t)r * (size_t)k + (size_t)(c0 + col)];
-    }
-}
-__device__ __forceinline__ void tb_store(real_t* dst, const real_t (&v)[TB_NL])
-{
-#pragma unroll
-    for (int i = 0; i < TB_NL; i++) {
-        const int e = (int)threadIdx.x + i * TB_WG;
-        dst[(e / TB_KC) * TB_KS + e % TB_KC] = v[i];
-    }
-}
-
-// acc[t][r] += sum over the chunk's columns, in ascending order, of As[user][c] Bs[item][c] for user 16 wave + 4 (lane >> 4) + r and
-// item 16 t + (lane & 15): one fused multiply-add per column
-template <class T, bool MFMA> __device__ __forceinline__ void tb_compute(T (&acc)[4][4], const T* As, const T* Bs, int len)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned col = lane & 15, quad = lane >> 4;
-    if constexpr (MFMA) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        // A operand: user row (lane & 15), column 4 s + (lane >> 4); B operand: item row (lane & 15), same column;
-        // D: item column lane & 15, user row 4 (lane >> 4) + register
-        const int ksteps = (len + 3) / 4;
-        const T* ap = As + (16 * wave + col) * TB_KS + quad;
-        const T* bp = Bs + col * TB_KS + quad;
-        tb_f32x4 d0 = { acc[0][0], acc[0][1], acc[0][2], acc[0][3] }, d1 = { acc[1][0], acc[1][1], acc[1][2], acc[1][3] };
-        tb_f32x4 d2 = { acc[2][0], acc[2][1], acc[2][2], acc[2][3] }, d3 = { acc[3][0], acc[3][1], acc[3][2], acc[3][3] };
-#pragma unroll 4
-        for (int s = 0; s < ksteps; s++) {
-            const float av = ap[4 * s];
-            const float b0 = bp[4 * s], b1 = bp[16 * TB_KS + 4 * s], b2 = bp[32 * TB_KS + 4 * s], b3 = bp[48 * TB_KS + 4 * s];
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, d1, 0, 0, 0);
-            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b2, d2, 0, 0, 0);
-            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b3, d3, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) { acc[0][r] = d0[r]; acc[1][r] = d1[r]; acc[2][r] = d2[r]; acc[3][r] = d3[r]; }
-#endif
-    } else {
-        const T* ap = As + (16 * wave + 4 * quad) * TB_KS;
-        const T* bp = Bs + col * TB_KS;
-        for (int c = 0; c < len; c++) {
-            T av[4], bv[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) av[r] = ap[r * TB_KS + c];
-#pragma unroll
-            for (int t = 0; t < 4; t++) bv[t] = bp[16 * t * TB_KS + c];
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) acc[t][r] = __builtin_fma(av[r], bv[t], acc[t][r]);
-        }
-    }
 }
 
 template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile_kernel(TbArgs a)
@@ -473,6 +396,27 @@ int poismf_hip_topn_batch_check(const sparse_ix* users, size_t n_users, size_t n
     return 0;
 }
 
+// exclude_seen: finds out, once per session, whether the resident rows are strictly ascending (*seen.sorted); 0, or 1 on a device error
+int poismf_hip_topn_seen_sorted(PmfTopnSeen& seen, hipStream_t stream)
+{
+    if (*seen.sorted >= 0) return 0;
+    const size_t nrows = seen.row_end - seen.row_begin;
+    unsigned* d_flag = nullptr;
+    unsigned flag = 0;
+    TB_TRY(pmf_alloc(&d_flag, sizeof(unsigned), stream));
+    hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), stream);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)std::min<size_t>(ceil_div(std::max<size_t>(nrows, 1), 256), 4096);
+        hipLaunchKernelGGL(topn_rows_sorted_kernel, dim3(grid), dim3(256), 0, stream, seen.d_indptr, seen.d_indices, nrows, d_flag);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = pmf_download(&flag, d_flag, sizeof(unsigned), stream);
+    pmf_free(d_flag, stream);
+    TB_TRY(e);
+    *seen.sorted = flag ? 0 : 1;
+    return 0;
+}
+
 // exclude_seen (after poismf_hip_topn_batch_check): the shard must hold every user, and every user must keep n_top admissible items.
 // Row lengths come from a host copy of the row pointers (fetched once per session); only a user whose two lists together could
 // leave fewer than n_top items has its resident row fetched and the union counted.  0, 1 (device error) or 2.
@@ -487,21 +431,7 @@ static int tb_check_seen(PmfTopnSeen& seen, const sparse_ix* users, size_t n_use
         ip.resize(nrows + 1);
         TB_TRY(pmf_download(ip.data(), seen.d_indptr, (nrows + 1) * sizeof(unsigned long long), stream));
     }
-    if (*seen.sorted < 0) {
-        unsigned* d_flag = nullptr;
-        unsigned flag = 0;
-        TB_TRY(pmf_alloc(&d_flag, sizeof(unsigned), stream));
-        hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), stream);
-        if (e == hipSuccess) {
-            const unsigned grid = (unsigned)std::min<size_t>(ceil_div(std::max<size_t>(nrows, 1), 256), 4096);
-            hipLaunchKernelGGL(topn_rows_sorted_kernel, dim3(grid), dim3(256), 0, stream, seen.d_indptr, seen.d_indices, nrows, d_flag);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = pmf_download(&flag, d_flag, sizeof(unsigned), stream);
-        pmf_free(d_flag, stream);
-        TB_TRY(e);
-        *seen.sorted = flag ? 0 : 1;
-    }
+    if (poismf_hip_topn_seen_sorted(seen, stream)) return 1;
     std::vector<unsigned> row;
     for (size_t i = 0; i < n_users; i++) {
         const size_t r = (size_t)users[i] - seen.row_begin;

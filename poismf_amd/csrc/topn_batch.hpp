@@ -16,6 +16,7 @@ struct PmfTopnSeen {
     int* sorted;                                 // -1 not checked yet, 0 some row is not strictly ascending, 1 all are
 };
 
+int poismf_hip_topn_seen_sorted(PmfTopnSeen& seen, hipStream_t stream);
 int poismf_hip_topn_batch_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
                                 const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
 int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
