@@ -471,100 +471,16 @@ def _index_array(a, what):
     return np.ascontiguousarray(a, dtype=np.uint64)
 
 
-def _topn_batch_args(users, n, exclude, dimA, dimB):
-    """The argument checks of the batched top-N (include/poismf_hip.h section 1f) that need no device, as the library itself
-    makes them; returns (users, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if n > dimB:
-        raise ValueError("n is larger than the number of items")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if exclude is None:
-        return users, None, None
-    if isinstance(exclude, (tuple, list)) and len(exclude) == 2 and not hasattr(exclude, "tocsr"):
-        indptr, indices = _index_array(exclude[0], "exclude indptr"), _index_array(exclude[1], "exclude indices")
-    else:
-        import scipy.sparse as sp
-        csr = sp.csr_matrix(exclude)
-        if csr.shape[0] != m:
-            raise ValueError(f"exclude has {csr.shape[0]} rows for {m} users")
-        if csr.shape[1] > dimB:
-            raise ValueError("exclude has more columns than there are items")
-        csr.sum_duplicates()
-        csr.sort_indices()
-        indptr, indices = _index_array(csr.indptr, "exclude indptr"), _index_array(csr.indices, "exclude indices")
-    if len(indptr) != m + 1:
-        raise ValueError(f"exclude has {max(len(indptr) - 1, 0)} rows for {m} users")
-    if m:
-        if np.any(indptr[1:] < indptr[:-1]) or int(indptr[-1]) > len(indices):
-            raise ValueError("exclude: row pointers must not decrease and must stay inside the index list")
-        lo, hi = int(indptr[0]), int(indptr[-1])
-        seg = indices[lo:hi]
-        if len(seg) and int(seg.max()) >= dimB:
-            raise ValueError("an item index of exclude is out of range")
-        if len(seg) > 1:
-            bad = seg[1:] <= seg[:-1]
-            starts = indptr[1:-1].astype(np.int64) - lo - 1          # position (in bad) of each later row's first entry
-            starts = starts[(starts >= 0) & (starts < len(bad))]
-            bad[starts] = False
-            if np.any(bad):
-                raise ValueError("exclude: the item indices of a row must be strictly ascending")
-        lens = (indptr[1:] - indptr[:-1]).astype(np.int64)
-        if int(lens.max()) > dimB - n:
-            raise ValueError("n is larger than the number of items a user has left after exclusion")
-    return users, indptr, indices
-
-
-def _topn_batch_rc(rc):
-    if rc == 2:
-        raise ValueError("invalid arguments for the batched top-N (index out of range, unsorted exclusion row, or n against the items left)")
-    if rc:
-        raise MemoryError("batched top-N failed (no usable HIP device or out of memory)")
-
-
-def _topN_batch(self, users, n=10, exclude=None, output_score=False):
-    """The n best items of every user in `users` (rows of the fitted A) under "score descending, item index ascending", in one
-    fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
-    `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
-    does not keep X) or an (indptr, indices) pair with strictly ascending rows.  Returns (items uint64 [m x n], scores [m x n],
-    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
-    dt = np.float32 if self.use_float else np.float64
-    m, n = len(users), int(n)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
-    if m == 0:
-        return ix, sc
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    lib = load_library(self.use_float)
-    _topn_batch_rc(lib.poismf_hip_topn_batch(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
-                                             _ptr(indptr) if indptr is not None else None,
-                                             _ptr(indices) if indices is not None and len(indices) else None,
-                                             _ptr(ix), _ptr(sc) if output_score else None))
-    return ix, sc
-
-
-PoisMF.topN_batch = _topN_batch
-
-
-def _csr_list(lst, m, dimB, what, row_max=None):
-    """A per-user item list of the batched entry points -- a SciPy sparse matrix with one row per user (its stored columns;
-    explicit zeros dropped, duplicates merged) or an (indptr, indices) pair -- checked as the library checks it: m rows, indices
-    below dimB and strictly ascending within a row.  Returns (indptr, indices) as uint64 arrays starting at 0."""
+def _csr_list(lst, m, dimB, what, row_max=None, dense_ok=False, keep_zeros=False):
+    """A per-user item list of the batched entry points -- a SciPy sparse matrix with one row per user (its stored columns,
+    duplicates merged; cells stored as zero dropped unless keep_zeros), with dense_ok anything scipy.sparse.csr_matrix() accepts,
+    or an (indptr, indices) pair -- checked as the library checks it: m rows, indices below dimB and strictly ascending within a
+    row.  Returns (indptr, indices) as uint64 arrays starting at 0."""
     if isinstance(lst, (tuple, list)) and len(lst) == 2 and not hasattr(lst, "tocsr"):
         indptr, indices = _index_array(lst[0], what + " indptr"), _index_array(lst[1], what + " indices")
     else:
         import scipy.sparse as sp
-        if not sp.issparse(lst):
+        if not dense_ok and not sp.issparse(lst):
             raise ValueError(f"{what} must be a SciPy sparse matrix or an (indptr, indices) pair")
         csr = sp.csr_matrix(lst)
         if csr.shape[0] != m:
@@ -572,7 +488,8 @@ def _csr_list(lst, m, dimB, what, row_max=None):
         if csr.shape[1] > dimB:
             raise ValueError(f"{what} has more columns than there are items")
         csr.sum_duplicates()
-        csr.eliminate_zeros()
+        if not keep_zeros:
+            csr.eliminate_zeros()
         csr.sort_indices()
         indptr, indices = _index_array(csr.indptr, what + " indptr"), _index_array(csr.indices, what + " indices")
     if len(indptr) != m + 1:
@@ -595,6 +512,72 @@ def _csr_list(lst, m, dimB, what, row_max=None):
     return np.ascontiguousarray(indptr - indptr[0]), np.ascontiguousarray(seg)
 
 
+def _topn_batch_args(users, n, exclude, dimA, dimB):
+    """The argument checks of the batched top-N (include/poismf_hip.h section 1f) that need no device, as the library itself
+    makes them; returns (users, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if n > dimB:
+        raise ValueError("n is larger than the number of items")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if exclude is None:
+        return users, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    if m and int((indptr[1:] - indptr[:-1]).max()) > dimB - n:
+        raise ValueError("n is larger than the number of items a user has left after exclusion")
+    return users, indptr, indices
+
+
+def _opt_ptr(a):
+    return _ptr(a) if a is not None and len(a) else None
+
+
+def _batch_rc(rc, what):
+    if rc == 2:
+        raise ValueError(f"invalid arguments for the batched {what} (an index out of range, an unsorted or overlong row, or too few items left)")
+    if rc:
+        raise MemoryError(f"batched {what} failed (no usable HIP device or out of memory)")
+
+
+def _outside_shard(users, shardA):
+    """exclude_seen of a session's batched calls: its CSR holds the rows shardA of A only"""
+    if len(users) and (int(users.min()) < shardA[0] or int(users.max()) >= shardA[1]):
+        raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+
+
+def _topN_batch(self, users, n=10, exclude=None, output_score=False):
+    """The n best items of every user in `users` (rows of the fitted A) under "score descending, item index ascending", in one
+    fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
+    `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
+    does not keep X) or an (indptr, indices) pair with strictly ascending rows.  Returns (items uint64 [m x n], scores [m x n],
+    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    m, n = len(users), int(n)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    lib = load_library(self.use_float)
+    _batch_rc(lib.poismf_hip_topn_batch(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
+                                        _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+    return ix, sc
+
+
+PoisMF.topN_batch = _topN_batch
+
+
 def _rank_batch_args(users, test, exclude, dimA, dimB, k):
     """The argument checks of the batched ranks (include/poismf_hip.h section 1g) that need no device, as the library itself makes
     them; returns (users, test_indptr, test_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
@@ -611,17 +594,6 @@ def _rank_batch_args(users, test, exclude, dimA, dimB, k):
         return users, tp, ti, None, None
     ep, ei = _csr_list(exclude, m, dimB, "exclude", (RANK_BATCH_BUDGET_MB << 20) // 8)
     return users, tp, ti, ep, ei
-
-
-def _rank_batch_rc(rc):
-    if rc == 2:
-        raise ValueError("invalid arguments for the batched ranks (index out of range, unsorted row, or a row too long)")
-    if rc:
-        raise MemoryError("batched ranks failed (no usable HIP device or out of memory)")
-
-
-def _opt_ptr(a):
-    return _ptr(a) if a is not None and len(a) else None
 
 
 def rank_batch(A, B, users, test, exclude=None):
@@ -641,8 +613,8 @@ def rank_batch(A, B, users, test, exclude=None):
         return ranks, n_adm
     A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
     lib = load_library(use_float)
-    _rank_batch_rc(lib.poismf_hip_rank_batch(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
-                                             _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)))
+    _batch_rc(lib.poismf_hip_rank_batch(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
+                                        _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
     return ranks, n_adm
 
 
@@ -946,16 +918,15 @@ class Session:
         empty unless output_score)."""
         users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
         m, n = len(users), int(top_n)
-        if exclude_seen and m and (int(users.min()) < self.shardA[0] or int(users.max()) >= self.shardA[1]):
-            raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
         ix = np.empty((m, n), np.uint64)
         sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
         if m == 0:
             return ix, sc
-        _topn_batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
-                                                              _ptr(indptr) if indptr is not None else None,
-                                                              _ptr(indices) if indices is not None and len(indices) else None,
-                                                              _ptr(ix), _ptr(sc) if output_score else None))
+        _batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
+                                                         _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                                         _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None):
@@ -965,13 +936,13 @@ class Session:
         order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m], the admissible items of each user)."""
         users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, self.dimA, self.dimB, self.k)
         m = len(users)
-        if exclude_seen and m and (int(users.min()) < self.shardA[0] or int(users.max()) >= self.shardA[1]):
-            raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
         ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
         if m == 0:
             return ranks, n_adm
-        _rank_batch_rc(self.lib.poismf_hip_session_rank_batch(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), int(bool(exclude_seen)),
-                                                              _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)))
+        _batch_rc(self.lib.poismf_hip_session_rank_batch(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), int(bool(exclude_seen)),
+                                                         _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
         return ranks, n_adm
 
     def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False):

@@ -4,8 +4,9 @@
 
 Ten translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
 PG, CG and TNCG are the bulk of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the
-rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip) -- are compiled to object files side by side and linked.  Every object and
-library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
+rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip) and the
+batched ranks (rank_batch.hip; the pair shares tb_tile.hpp and tb_batch.hpp) -- are compiled to object files side by
+side and linked.  Every object and library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
 digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full
 build takes ~2 minutes on 8 cores.
 """
@@ -19,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "poismf_hip.h")
 _ROW = ["poismf_hip.hip", "plan.hpp", "devmem.hpp", "solvers.hpp", "row_eval.hpp", "reg_eval.hpp", "lane_eval.hpp", "wave_ops.hpp"]
-_HOST = ["poismf_hip_host.hip", "plan.hpp", "devmem.hpp", "row_eval.hpp", "wave_ops.hpp", "topn_batch.hpp", "rank_batch.hpp"]
+_HOST = ["poismf_hip_host.hip", "plan.hpp", "devmem.hpp", "row_eval.hpp", "wave_ops.hpp", "tb_batch.hpp", "tb_tile.hpp"]
 # unit -> (source files, first is the one compiled; extra flags).  poismf_hip.hip is compiled four times: one
 # translation unit per inner solver (its row kernels are the bulk of the compile time); the host side is its own file.
 UNITS = {
@@ -31,8 +32,8 @@ UNITS = {
     "coo_convert": (["coo_convert.hip", "devmem.hpp"], []),
     "serve": (["serve.hip", "devmem.hpp"], []),
     "llk": (["llk.hip", "devmem.hpp", "wave_ops.hpp"], []),
-    "topn_batch": (["topn_batch.hip", "topn_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
-    "rank_batch": (["rank_batch.hip", "rank_batch.hpp", "topn_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
+    "topn_batch": (["topn_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
+    "rank_batch": (["rank_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
 }
 
 

@@ -185,8 +185,7 @@ int poismf_hip_coo_to_csr_csc(const sparse_ix* row, const sparse_ix* col, const 
                               sparse_ix* csc_indices, sparse_ix* csc_indptr, size_t* nnz_out)
 {
     if (n == 0 || n > 0xffffffffull || dimA > 0x7fffffffull || dimB > 0x7fffffffull) return 1;
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
+    const int device = pmf_env_device();
     HIP_TRY(hipSetDevice(device));
     hipStream_t stream = nullptr;
     unsigned *d_row = nullptr, *d_col = nullptr, *d_minor = nullptr;

@@ -41,6 +41,16 @@ inline void pmf_tl(const char* what)
     last = t;
 }
 
+// the device of the one-shot entry points (a session is told its device): POISMF_HIP_DEVICE, 0 when it is not set
+inline int pmf_env_device()
+{
+    const char* e = getenv("POISMF_HIP_DEVICE");
+    return e ? atoi(e) : 0;
+}
+
+inline size_t pmf_ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+inline size_t pmf_round_up(size_t a, size_t b) { return pmf_ceil_div(a, b) * b; }
+
 // ---- the device arrays of finished sessions are kept for the next one (round 4) ---------------------------------------------------
 // run_poismf is a one-shot call: 2.5 GB of device arrays allocated, filled, used and freed per fit.  On this stack the freeing and
 // allocating is not only 2.5 ms of calls: it also leaves the copy engines busy behind the call's back (scripts/probes/stage_probe2.hip --
@@ -193,6 +203,16 @@ inline void pmf_free(void* p, hipStream_t stream)
         }
     }
     (void)hipFree(p);   // waits for the device: nothing can still be using the block
+}
+
+// grows a buffer to `need` units of `unit` bytes (growing frees it first, i.e. synchronises the device: only ever grown)
+template <class T> hipError_t grow_buffer(T*& buf, size_t& have, size_t need, size_t unit, hipStream_t stream)
+{
+    if (need <= have) return hipSuccess;
+    pmf_free(buf, stream); buf = nullptr; have = 0;
+    const hipError_t e = pmf_alloc(&buf, need * unit, stream);
+    if (e == hipSuccess) have = need;
+    return e;
 }
 
 // Host <-> device copies of CALLER-OWNED (pageable) memory: drain the stream, then copy synchronously; kernels launched

@@ -199,15 +199,13 @@ __global__ __launch_bounds__(LLK_WG) void llk_final_kernel(const double* __restr
     }
 }
 
-size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-
 struct Layout {   // the scratch array of poismf_hip_llk_enqueue, in doubles
     size_t nranges, nbA, nbB, part, lg, colA, colB, sA, sB, total;
     Layout(size_t nrows, size_t dimB, size_t k, size_t nnz)
     {
-        nranges = ceil_div(nnz, LLK_RANGE);
-        nbA = ceil_div(nrows, LLK_COL_ROWS);
-        nbB = ceil_div(dimB, LLK_COL_ROWS);
+        nranges = pmf_ceil_div(nnz, LLK_RANGE);
+        nbA = pmf_ceil_div(nrows, LLK_COL_ROWS);
+        nbB = pmf_ceil_div(dimB, LLK_COL_ROWS);
         part = 1;                       // [0]: the result
         lg = part + nranges;
         colA = lg + nranges;
@@ -226,13 +224,6 @@ void launch_ranges(size_t nranges, hipStream_t stream, const real_t* A, const re
                        (unsigned long long)nnz, k, include_missing, partial);
 }
 
-int pick_device()
-{
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
-    return device;
-}
-
 }  // namespace
 
 // ---- core on device-resident data (the session and the drop-in below) ----
@@ -249,7 +240,7 @@ int poismf_hip_llk_enqueue(const real_t* A, const real_t* B, size_t nrows, size_
     const Layout L(nrows, dimB, k, nnz);
     const int ki = (int)k;
     if (L.nranges > 0) {
-        const size_t kpl = ceil_div(k, LLK_G);
+        const size_t kpl = pmf_ceil_div(k, LLK_G);
         double* part = scratch + L.part;
         if (kpl <= 1) launch_ranges<1>(L.nranges, stream, A, B, indptr, nrows, col, val, nnz, ki, include_missing, part);
         else if (kpl <= 2) launch_ranges<2>(L.nranges, stream, A, B, indptr, nrows, col, val, nnz, ki, include_missing, part);
@@ -299,7 +290,7 @@ long double eval_llk(real_t* A, real_t* B, sparse_ix ixA[], sparse_ix ixB[], rea
         hr[i] = (unsigned)ixA[i];
         hc[i] = (unsigned)ixB[i];
     }
-    const int device = pick_device();
+    const int device = pmf_env_device();
     if (hipSetDevice(device) != hipSuccess) {
         fprintf(stderr, "eval_llk: no usable HIP device\n");
         return nan;

@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "plan.hpp"
-#include "topn_batch.hpp"
-#include "rank_batch.hpp"
+#include "tb_batch.hpp"
 
 // the device-visible twin of the interrupt flag (pinned host memory; see on_sigint below): one word, allocated on first use, never freed
 static volatile unsigned* g_stop_word = nullptr;
@@ -895,16 +894,6 @@ hipStream_t launch_stream(const PlannedLaunch& L, hipStream_t main, hipStream_t 
     return main;
 }
 
-// grows a session buffer to `need` units of `unit` bytes (growing frees it first, i.e. synchronises the device: only ever grown)
-template <class T> hipError_t grow_buffer(T*& buf, size_t& have, size_t need, size_t unit, hipStream_t stream)
-{
-    if (need <= have) return hipSuccess;
-    pmf_free(buf, stream); buf = nullptr; have = 0;
-    const hipError_t e = pmf_alloc(&buf, need * unit, stream);
-    if (e == hipSuccess) have = need;
-    return e;
-}
-
 // The half's prologue: column sums of the fixed factor (or the caller's k-vector), the padded gather copy, and the arguments every launch of
 // the half starts from.
 int half_prologue(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div, bool prologue, bool early_stop,
@@ -1683,13 +1672,7 @@ int poismf_hip_session_llk(poismf_hip_session* s, int full_llk, int include_miss
     const Half& h = s->half[1];
     const size_t nrows = h.row_end - h.row_begin;
     const size_t need = poismf_hip_llk_scratch(nrows, s->dimB, s->k, h.nnz);
-    if (s->llk_cap < need) {
-        pmf_free(s->d_llk, s->stream);
-        s->d_llk = nullptr;
-        s->llk_cap = 0;
-        HIP_TRY(pmf_alloc(&s->d_llk, need * sizeof(double), s->stream));
-        s->llk_cap = need;
-    }
+    HIP_TRY(grow_buffer(s->d_llk, s->llk_cap, need, sizeof(double), s->stream));
     if (poismf_hip_llk_enqueue(s->dA + h.row_begin * s->k, s->dB, nrows, s->dimB, s->k, h.d_indptr, h.d_indices, h.d_values, h.nnz,
                                full_llk, include_missing, s->d_llk, s->stream))
         return 1;
@@ -1712,6 +1695,16 @@ int poismf_hip_session_topn(poismf_hip_session* s, size_t user, const sparse_ix*
                                  n_top, s->dimB);
 }
 
+// exclude_seen of the two batched calls below: the session's resident CSR shard as their exclusion lists; false when a user lies outside it
+static bool session_seen(poismf_hip_session* s, const sparse_ix* users, size_t n_users, PmfTopnSeen& seen)
+{
+    const Half& h = s->half[1];
+    for (size_t i = 0; i < n_users; i++)
+        if ((size_t)users[i] < h.row_begin || (size_t)users[i] >= h.row_end) return false;
+    seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
+    return true;
+}
+
 // Batched top-N from the resident (compact) factors (topn_batch.hip; include/poismf_hip.h section 1f).  Ordered after the work already
 // enqueued on the session stream; with exclude_seen the resident CSR shard's rows are the exclusion lists -- nothing of them is uploaded.
 int poismf_hip_session_topn_batch(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, int exclude_seen,
@@ -1720,12 +1713,9 @@ int poismf_hip_session_topn_batch(poismf_hip_session* s, const sparse_ix* users,
     if (n_users == 0) return 0;
     if (s == nullptr || out_ix == nullptr) return 2;
     if (const int rc = poismf_hip_topn_batch_check(users, n_users, n_top, s->dimA, s->dimB, s->k, excl_indptr, excl_indices)) return rc;
-    const Half& h = s->half[1];
-    if (exclude_seen)
-        for (size_t i = 0; i < n_users; i++)
-            if ((size_t)users[i] < h.row_begin || (size_t)users[i] >= h.row_end) return 2;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
     HIP_TRY(hipSetDevice(s->device));
-    PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
     return poismf_hip_topn_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, exclude_seen ? &seen : nullptr,
                                      excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
@@ -1740,12 +1730,9 @@ int poismf_hip_session_rank_batch(poismf_hip_session* s, const sparse_ix* users,
     if (s == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
     if (const int rc = poismf_hip_rank_batch_check(users, n_users, s->dimA, s->dimB, s->k, test_indptr, test_indices, excl_indptr, excl_indices))
         return rc;
-    const Half& h = s->half[1];
-    if (exclude_seen)
-        for (size_t i = 0; i < n_users; i++)
-            if ((size_t)users[i] < h.row_begin || (size_t)users[i] >= h.row_end) return 2;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
     HIP_TRY(hipSetDevice(s->device));
-    PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &s->topn_indptr, &s->csr_rows_sorted };
     return poismf_hip_rank_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, test_indptr, test_indices,
                                      exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_rank, out_n_adm);
 }
@@ -2227,8 +2214,7 @@ int run_poismf(real_t* A, real_t* Xr, sparse_ix* Xr_indptr, sparse_ix* Xr_indice
 
     int ret_code = 0;
     poismf_hip_session* s = nullptr;
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
+    int device = pmf_env_device();
 
     poismf_hip_params p;
     p.l2_reg = l2_reg; p.l1_reg = l1_reg; p.w_mult = w_mult; p.step_size = step_size;
@@ -2375,8 +2361,7 @@ static int factors_multiple_impl(real_t* A, real_t* B, real_t* Bsum, real_t* Ame
     size_t dimB = 0;  // the reference never needs the number of items; the device copy of B needs the rows in use
     for (size_t i = 0; i < nnz; i++) dimB = std::max(dimB, (size_t)Xr_indices[i] + 1);
 
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
+    const int device = pmf_env_device();
     poismf_hip_session* s = nullptr;
     int rc = 0;
     std::vector<real_t> bs(ks);

@@ -37,7 +37,7 @@
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
 #include "tb_tile.hpp"
-#include "rank_batch.hpp"
+#include "tb_batch.hpp"
 
 namespace {
 
@@ -47,7 +47,6 @@ constexpr size_t RB_TARGET_WGS = 768;                     // items are split ove
 constexpr size_t RB_CHUNK_USERS_MAX = 262144;
 constexpr size_t RB_BUDGET = (size_t)POISMF_HIP_RANK_BATCH_BUDGET_MB << 20;
 constexpr size_t RB_ROW_MAX = POISMF_HIP_RANK_BATCH_MAX_ROW;
-constexpr size_t RB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
 constexpr unsigned RB_EXCLUDED = POISMF_HIP_RANK_EXCLUDED;
 
 struct RbArgs {
@@ -72,12 +71,7 @@ struct RbArgs {
     const unsigned* grow;             // [ngroups] chunk user of a group
     const unsigned* gstart;           // [ngroups] its first ordered entry
     unsigned ngroups, nslices, tiles_per_slice;
-    const unsigned long long* seen_indptr;   // exclude_seen: the resident CSR (nullptr: off); local row = arow - seen_row0
-    const unsigned* seen_indices;
-    unsigned seen_row0;
-    int seen_sorted;
-    const unsigned* ex_indptr;        // the batch's own lists for this chunk (nullptr: none), strictly ascending rows
-    const unsigned* ex_indices;
+    TbExcl excl;                      // E(u) of the chunk's users
 };
 
 __device__ __forceinline__ float rb_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -91,32 +85,6 @@ __device__ __forceinline__ real_t rb_dot(const real_t* A, const real_t* B, int k
     real_t s = 0;
     for (int c = 0; c < k; c++) s = rb_fma(p[c], q[c], s);
     return s;
-}
-
-__device__ __forceinline__ bool rb_sorted_has(const unsigned* v, unsigned long long lo, unsigned long long hi, unsigned j)
-{
-    while (lo < hi) {
-        const unsigned long long mid = lo + (hi - lo) / 2;
-        const unsigned x = v[mid];
-        if (x == j) return true;
-        if (x < j) lo = mid + 1;
-        else hi = mid;
-    }
-    return false;
-}
-
-// item j is in E(chunk user i)
-__device__ __forceinline__ bool rb_excluded(const RbArgs& a, unsigned i, unsigned j)
-{
-    if (a.ex_indptr != nullptr && rb_sorted_has(a.ex_indices, a.ex_indptr[i], a.ex_indptr[i + 1], j)) return true;
-    if (a.seen_indptr != nullptr) {
-        const unsigned row = a.arow[i] - a.seen_row0;
-        const unsigned long long p0 = a.seen_indptr[row], p1 = a.seen_indptr[row + 1];
-        if (a.seen_sorted) return rb_sorted_has(a.seen_indices, p0, p1, j);
-        for (unsigned long long p = p0; p < p1; p++)
-            if (a.seen_indices[p] == j) return true;
-    }
-    return false;
 }
 
 // the first of n thresholds ordered best first that (s, j) comes before; n when there is none
@@ -137,7 +105,7 @@ __global__ __launch_bounds__(256) void rank_threshold_kernel(RbArgs a)
     if (c >= a.n_cells) return;
     const unsigned i = a.cell_row[c], j = a.cell_item[c];
     a.cell_score[c] = rb_dot(a.A, a.B, a.k, a.arow[i], j);
-    a.cell_excl[c] = rb_excluded(a, i, j) ? 1u : 0u;
+    a.cell_excl[c] = tb_excluded(a.excl, i, a.arow[i], j) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(256) void rank_order_kernel(RbArgs a)
@@ -168,7 +136,6 @@ __global__ __launch_bounds__(256) void rank_order_kernel(RbArgs a)
 template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile_kernel(RbArgs a)
 {
     extern __shared__ __align__(16) unsigned char rb_smem[];
-    static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
     T* As = (T*)rb_smem;                                  // [TB_TU][TB_KS]
     T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
     T* Ts = Bs + TB_TJ * TB_KS;                           // [TB_TU][RB_GS] a group's thresholds, best first: score ...
@@ -207,11 +174,9 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile
     const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
     const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
     const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
-    const int nchunks = (a.k + TB_KC - 1) / TB_KC;
     const unsigned col = lane & 15, quad = lane >> 4;
     const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four rows are urow0 .. urow0 + 3
     auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
-    auto item_row = [&](unsigned j_base) { return [&a, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < a.dimB ? (long long)j : -1ll; }; };
 
     // best and worst threshold of this lane's four rows; a row without thresholds has a worst one nothing comes before
     T best_s[4], worst_s[4];
@@ -227,41 +192,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile
         worst_j[r] = n > 0 ? Tj[(urow0 + r) * RB_GS + n - 1] : 0u;
     }
 
-    // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
-    T b_next[TB_NL];
-    if (nchunks == 1) {
-        tb_fetch(b_next, a.A, a.k, 0, a.k, user_row);
-        tb_store(As, b_next);
-        tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(tile0 * TB_TJ));
-    }
-
-    for (unsigned jt = tile0; jt < tile1; jt++) {
-        const unsigned j_base = jt * TB_TJ;
-        T acc[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) acc[t][r] = 0;
-        if (nchunks == 1) {
-            __syncthreads();   // every wave is done with the items' tile of the step before
-            tb_store(Bs, b_next);
-            __syncthreads();
-            if (jt + 1 < tile1) tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(j_base + TB_TJ));
-            tb_compute<T, MFMA>(acc, As, Bs, a.k);
-        } else {
-            for (int ch = 0; ch < nchunks; ch++) {
-                const int c0 = ch * TB_KC;
-                const int len = a.k - c0 < TB_KC ? a.k - c0 : TB_KC;
-                __syncthreads();   // every wave is done with the tiles of the step before
-                tb_fetch(b_next, a.A, a.k, c0, len, user_row);
-                tb_store(As, b_next);
-                tb_fetch(b_next, a.B, a.k, c0, len, item_row(j_base));
-                tb_store(Bs, b_next);
-                __syncthreads();
-                tb_compute<T, MFMA>(acc, As, Bs, len);
-            }
-        }
-
+    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, a.dimB, tile0, tile1, user_row, [&](T (&acc)[4][4], unsigned j_base) {
         // ---- counting: the bins of rows 16 wave .. 16 wave + 15 are touched by this wave alone ----
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -304,7 +235,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile
             for (int t = 0; t < 4; t++)
                 if (mid[t]) atomicAdd(&bins[(urow0 + r) * RB_GS + n - beaten[t]], 1u);   // (LDS, integer) the first threshold it comes before
         }
-    }
+    });
 
     // ---- the slice's counts: a score before the best threshold is before every one of the group ----
 #pragma unroll
@@ -336,24 +267,25 @@ __global__ __launch_bounds__(256) void rank_excl_kernel(RbArgs a)
         if (pos < nv) atomicAdd(&a.corr[p0 + pos], 1u);
     };
     unsigned long long e0 = 0, e1 = 0;
-    if (a.ex_indptr != nullptr) {
-        e0 = a.ex_indptr[i];
-        e1 = a.ex_indptr[i + 1];
-        for (unsigned long long e = e0 + lane; e < e1; e += 64) subtract(a.ex_indices[e]);
+    const TbExcl& x = a.excl;
+    if (x.ex_indptr != nullptr) {
+        e0 = x.ex_indptr[i];
+        e1 = x.ex_indptr[i + 1];
+        for (unsigned long long e = e0 + lane; e < e1; e += 64) subtract(x.ex_indices[e]);
         n_excl = (unsigned)(e1 - e0);
     }
-    if (a.seen_indptr != nullptr) {
-        const unsigned row = u - a.seen_row0;
-        const unsigned long long s0 = a.seen_indptr[row], s1 = a.seen_indptr[row + 1];
+    if (x.seen_indptr != nullptr) {
+        const unsigned row = u - x.seen_row0;
+        const unsigned long long s0 = x.seen_indptr[row], s1 = x.seen_indptr[row + 1];
         for (unsigned long long base = s0; base < s1; base += 64) {
             const unsigned long long p = base + lane;
             bool mine = p < s1;
             unsigned j = 0;
             if (mine) {
-                j = a.seen_indices[p];
-                if (a.ex_indptr != nullptr && rb_sorted_has(a.ex_indices, e0, e1, j)) mine = false;   // the list had it
-                if (mine && !a.seen_sorted)   // a row in the caller's own order may name an item twice: the first one counts
-                    for (unsigned long long q = s0; q < p && mine; q++) mine = a.seen_indices[q] != j;
+                j = x.seen_indices[p];
+                if (x.ex_indptr != nullptr && tb_sorted_has(x.ex_indices, e0, e1, j)) mine = false;   // the list had it
+                if (mine && !x.seen_sorted)   // a row in the caller's own order may name an item twice: the first one counts
+                    for (unsigned long long q = s0; q < p && mine; q++) mine = x.seen_indices[q] != j;
             }
             if (mine) subtract(j);
             n_excl += (unsigned)__popcll(__ballot(mine));
@@ -377,9 +309,6 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(RbArgs a)
     }
 }
 
-size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-size_t round_up(size_t a, size_t b) { return ceil_div(a, b) * b; }
-
 // The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
 struct RbLayout {
     size_t chunk_users;      // users per chunk
@@ -402,8 +331,7 @@ struct RbLayout {
         cell_cap = std::min((rest - per_user * uc - 64) / per_cell, n_cells);   // (>= RB_ROW_MAX whatever the arguments: see the static_assert)
         chunk_users = uc;
         group_cap = uc + cell_cap / RB_G + 1;
-        size_t o = 0;
-        auto take = [&o](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 32); return at; };
+        TbTake take;
         arow = take(uc * U);
         tptr = take((uc + 1) * U);
         ex_indptr = take((uc + 1) * U);
@@ -422,7 +350,7 @@ struct RbLayout {
         grow = take(group_cap * U);
         gstart = take(group_cap * U);
         ex_indices = take(idx_cap * U);
-        total = o;
+        total = take.o;
     }
 };
 // the least a chunk's cells get (every exclusion index and every user of a chunk present) holds the longest row a call accepts
@@ -433,15 +361,6 @@ size_t rb_lds_bytes() { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (siz
 // two workgroups per CU (160 KB of LDS), as topn_tile_kernel at its usual list sizes
 static_assert(2 * (2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * RB_GS * (sizeof(real_t) + 8) + (size_t)TB_TU * 12) <= 160 * 1024,
               "two workgroups of rank_tile_kernel per CU");
-
-int pick_device()
-{
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
-    return device;
-}
-
-#define RB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 }  // namespace
 
@@ -455,33 +374,16 @@ extern "C" size_t poismf_hip_rank_batch_scratch_bytes(size_t n_users, size_t n_c
 int poismf_hip_rank_batch_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
                                 const sparse_ix* test_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices)
 {
-    if (k < 1 || k > RB_K_MAX || dimB < 1 || dimB > 0x7fffffffull || dimA > 0x7fffffffull) return 2;
+    if (k < 1 || k > TB_K_MAX || dimB < 1 || dimB > 0x7fffffffull || dimA > 0x7fffffffull) return 2;
     if (users == nullptr || test_indptr == nullptr) return 2;
     for (size_t i = 0; i < n_users; i++)
         if ((size_t)users[i] >= dimA) return 2;
-    // a CSR-shaped list: rows strictly ascending, indices below dimB, no row longer than row_max
-    auto rows_ok = [&](const sparse_ix* indptr, const sparse_ix* indices, size_t row_max) {
-        if ((long long)indptr[0] < 0) return false;
-        for (size_t i = 0; i < n_users; i++) {
-            if (indptr[i + 1] < indptr[i]) return false;
-            const size_t p0 = (size_t)indptr[i], p1 = (size_t)indptr[i + 1];
-            if (p1 - p0 > dimB || p1 - p0 > row_max) return false;
-            if (p1 > p0 && indices == nullptr) return false;
-            for (size_t p = p0; p < p1; p++) {
-                if ((long long)indices[p] < 0 || (size_t)indices[p] >= dimB) return false;
-                if (p > p0 && (size_t)indices[p - 1] >= (size_t)indices[p]) return false;
-            }
-        }
-        return true;
-    };
-    if (!rows_ok(test_indptr, test_indices, RB_ROW_MAX)) return 2;
-    if (excl_indptr != nullptr && !rows_ok(excl_indptr, excl_indices, RbLayout(n_users, 1, dimB).idx_cap)) return 2;
+    if (!tb_rows_ok(test_indptr, test_indices, n_users, dimB, RB_ROW_MAX)) return 2;
+    if (excl_indptr != nullptr && !tb_rows_ok(excl_indptr, excl_indices, n_users, dimB, RbLayout(n_users, 1, dimB).idx_cap)) return 2;
     return 0;
 }
 
-// ---- core on device-resident factors (the session and the drop-in below).  Arguments already checked. ----
-// dA rows are addressed by users[i], or by i itself when compact_A (the drop-in uploads only the batch's rows).  *d_scratch /
-// *scratch_cap: the caller's scratch, grown here when it is smaller than this call needs.  Returns 0 or 1.
+// ---- core on device-resident factors (tb_batch.hpp) ----
 int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
                               const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices,
                               PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
@@ -490,18 +392,13 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
     if (seen != nullptr && poismf_hip_topn_seen_sorted(*seen, stream)) return 1;
     const size_t n_cells = (size_t)test_indptr[n_users] - (size_t)test_indptr[0];
     const RbLayout L(n_users, n_cells, dimB);
-    if (*scratch_cap < L.total) {
-        pmf_free(*d_scratch, stream);
-        *d_scratch = nullptr;
-        *scratch_cap = 0;
-        RB_TRY(pmf_alloc((unsigned char**)d_scratch, L.total, stream));
-        *scratch_cap = L.total;
-    }
+    TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
     unsigned char* base = (unsigned char*)*d_scratch;
     const size_t lds = rb_lds_bytes();
     auto kern = rank_tile_kernel<real_t, sizeof(real_t) == 4>;
-    RB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
+    RbArgs a;
     std::vector<unsigned> hu, htp, hrow, hitem, hgrow, hgstart, hp, hx;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose held-out cells and exclusion lists fit their areas together
@@ -539,33 +436,22 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
         htp[nu] = (unsigned)nc;
         const size_t ng = hgrow.size();
         if (ng > L.group_cap) return 1;   // (cannot happen: a user adds at most one partial group)
-        RB_TRY(pmf_upload(base + L.arow, hu.data(), nu * sizeof(unsigned), stream));
-        RB_TRY(pmf_upload(base + L.tptr, htp.data(), (nu + 1) * sizeof(unsigned), stream));
-        RB_TRY(pmf_upload(base + L.cell_row, hrow.data(), nc * sizeof(unsigned), stream));
-        RB_TRY(pmf_upload(base + L.cell_item, hitem.data(), nc * sizeof(unsigned), stream));
-        RB_TRY(pmf_upload(base + L.grow, hgrow.data(), ng * sizeof(unsigned), stream));
-        RB_TRY(pmf_upload(base + L.gstart, hgstart.data(), ng * sizeof(unsigned), stream));
-        if (excl_indptr != nullptr) {
-            hp.resize(nu + 1);
-            hx.resize(nx);
-            const size_t p_base = (size_t)excl_indptr[u0];
-            for (size_t i = 0; i <= nu; i++) hp[i] = (unsigned)((size_t)excl_indptr[u0 + i] - p_base);
-            for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
-            RB_TRY(pmf_upload(base + L.ex_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream));
-            RB_TRY(pmf_upload(base + L.ex_indices, hx.data(), nx * sizeof(unsigned), stream));
-        }
-        RB_TRY(hipMemsetAsync(base + L.nvalid, 0, nu * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.arow, hu.data(), nu * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.tptr, htp.data(), (nu + 1) * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.cell_row, hrow.data(), nc * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.cell_item, hitem.data(), nc * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.grow, hgrow.data(), ng * sizeof(unsigned), stream));
+        TB_TRY(pmf_upload(base + L.gstart, hgstart.data(), ng * sizeof(unsigned), stream));
+        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
+                             hx, stream));
+        TB_TRY(hipMemsetAsync(base + L.nvalid, 0, nu * sizeof(unsigned), stream));
         if (nc > 0) {
-            RB_TRY(hipMemsetAsync(base + L.dense, 0, nc * sizeof(unsigned), stream));
-            RB_TRY(hipMemsetAsync(base + L.corr, 0, nc * sizeof(unsigned), stream));
+            TB_TRY(hipMemsetAsync(base + L.dense, 0, nc * sizeof(unsigned), stream));
+            TB_TRY(hipMemsetAsync(base + L.corr, 0, nc * sizeof(unsigned), stream));
         }
 
-        const size_t tiles = ceil_div(std::max<size_t>(ng, 1), TB_TU);
-        const size_t item_tiles = ceil_div(dimB, TB_TJ);
-        const size_t want = std::min(tiles >= RB_TARGET_WGS ? 1 : ceil_div(RB_TARGET_WGS, tiles), item_tiles);
-        const size_t tps = ceil_div(item_tiles, want);
-        const size_t nslices = ceil_div(item_tiles, tps);
-        RbArgs a;
+        const size_t tiles = pmf_ceil_div(std::max<size_t>(ng, 1), TB_TU);
+        const TbSlices sl = tb_slices(tiles, dimB, RB_TARGET_WGS);
         a.A = dA;
         a.B = dB;
         a.k = (int)k;
@@ -589,31 +475,25 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
         a.grow = (const unsigned*)(base + L.grow);
         a.gstart = (const unsigned*)(base + L.gstart);
         a.ngroups = (unsigned)ng;
-        a.nslices = (unsigned)nslices;
-        a.tiles_per_slice = (unsigned)tps;
-        a.seen_indptr = seen ? seen->d_indptr : nullptr;
-        a.seen_indices = seen ? seen->d_indices : nullptr;
-        a.seen_row0 = seen ? (unsigned)seen->row_begin : 0u;
-        a.seen_sorted = seen ? *seen->sorted : 0;
-        a.ex_indptr = excl_indptr ? (const unsigned*)(base + L.ex_indptr) : nullptr;
-        a.ex_indices = (const unsigned*)(base + L.ex_indices);
+        a.nslices = (unsigned)sl.nslices;
+        a.tiles_per_slice = (unsigned)sl.tiles_per_slice;
         if (nc > 0) {
-            const unsigned cell_blocks = (unsigned)ceil_div(nc, 256);
+            const unsigned cell_blocks = (unsigned)pmf_ceil_div(nc, 256);
             hipLaunchKernelGGL(rank_threshold_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
-            RB_TRY(hipGetLastError());
+            TB_TRY(hipGetLastError());
             hipLaunchKernelGGL(rank_order_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
-            RB_TRY(hipGetLastError());
-            hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nslices), dim3(TB_WG), lds, stream, a);
-            RB_TRY(hipGetLastError());
+            TB_TRY(hipGetLastError());
+            hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)sl.nslices), dim3(TB_WG), lds, stream, a);
+            TB_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)ceil_div(nu, 4)), dim3(256), 0, stream, a);
-        RB_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)pmf_ceil_div(nu, 4)), dim3(256), 0, stream, a);
+        TB_TRY(hipGetLastError());
         if (nc > 0) {
-            hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)ceil_div(nu, 256)), dim3(256), 0, stream, a);
-            RB_TRY(hipGetLastError());
-            RB_TRY(pmf_download(out_rank + c_base, base + L.rank, nc * sizeof(unsigned), stream));
+            hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)pmf_ceil_div(nu, 256)), dim3(256), 0, stream, a);
+            TB_TRY(hipGetLastError());
+            TB_TRY(pmf_download(out_rank + c_base, base + L.rank, nc * sizeof(unsigned), stream));
         }
-        RB_TRY(pmf_download(out_n_adm + u0, base + L.n_adm, nu * sizeof(unsigned), stream));
+        TB_TRY(pmf_download(out_n_adm + u0, base + L.n_adm, nu * sizeof(unsigned), stream));
         u0 = u1;
     }
     return 0;
@@ -629,32 +509,11 @@ int poismf_hip_rank_batch(const real_t* A, const real_t* B, int k, size_t dimA, 
     if (k < 1 || A == nullptr || B == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
     if (const int rc = poismf_hip_rank_batch_check(users, n_users, dimA, dimB, (size_t)k, test_indptr, test_indices, excl_indptr, excl_indices))
         return rc;
-    const int device = pick_device();
-    if (hipSetDevice(device) != hipSuccess) return 1;
-    const hipStream_t st = nullptr;
-    const size_t kk = (size_t)k;
-    const bool compact = n_users < dimA;   // only the batch's rows of A go up when that is less than all of A
-    real_t *dA = nullptr, *dB = nullptr;
-    void* d_scratch = nullptr;
-    size_t scratch_cap = 0;
-    int rc = 1;
-    do {
-        const size_t rowsA = compact ? n_users : dimA;
-        if (pmf_alloc(&dA, rowsA * kk * sizeof(real_t) + 16, st) != hipSuccess || pmf_alloc(&dB, dimB * kk * sizeof(real_t) + 16, st) != hipSuccess) break;
-        if (compact) {
-            std::vector<real_t> rows;
-            try { rows.resize(n_users * kk); } catch (const std::bad_alloc&) { break; }
-            for (size_t i = 0; i < n_users; i++) memcpy(rows.data() + i * kk, A + (size_t)users[i] * kk, kk * sizeof(real_t));
-            if (pmf_upload_big(dA, rows.data(), rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        } else if (pmf_upload_big(dA, A, rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        if (pmf_upload_big(dB, B, dimB * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        rc = poismf_hip_rank_batch_run(st, dA, dB, dimB, kk, compact, users, n_users, test_indptr, test_indices, nullptr, excl_indptr, excl_indices,
-                                       &d_scratch, &scratch_cap, out_rank, out_n_adm);
-    } while (0);
-    pmf_free(dA, st);
-    pmf_free(dB, st);
-    pmf_free(d_scratch, st);
-    return rc;
+    return tb_dropin(A, B, (size_t)k, dimA, dimB, users, n_users,
+                     [&](hipStream_t st, const real_t* dA, const real_t* dB, bool compact, void** d_scratch, size_t* scratch_cap) {
+                         return poismf_hip_rank_batch_run(st, dA, dB, dimB, (size_t)k, compact, users, n_users, test_indptr, test_indices, nullptr,
+                                                          excl_indptr, excl_indices, d_scratch, scratch_cap, out_rank, out_n_adm);
+                     });
 }
 
 }  // extern "C"

@@ -65,13 +65,6 @@ struct DevBuf {
     template <class U> U* as() { return (U*)p; }
 };
 
-int pick_device()
-{
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
-    return device;
-}
-
 bool upload_u32(DevBuf& d, const sparse_ix* h, size_t n, size_t* maxv)
 {
     std::vector<unsigned> t(n ? n : 1);
@@ -157,7 +150,7 @@ void predict_multiple(real_t* out, real_t* A, real_t* B, sparse_ix* ixA, sparse_
         fprintf(stderr, "Error: out of memory.\n");
         for (size_t i = 0; i < n; i++) out[i] = std::numeric_limits<real_t>::quiet_NaN();
     };
-    if (hipSetDevice(pick_device()) != hipSuccess) return fail();
+    if (hipSetDevice(pmf_env_device()) != hipSuccess) return fail();
     size_t ma = 0, mb = 0;
     for (size_t i = 0; i < n; i++) { ma = std::max(ma, (size_t)ixA[i]); mb = std::max(mb, (size_t)ixB[i]); }
     DevBuf dA, dB;
@@ -174,7 +167,7 @@ int topN(real_t* a_vec, real_t* B, int k, sparse_ix* include_ix, size_t n_includ
     (void)nthreads;
     const sparse_ix *inc = include_ix, *exc = exclude_ix;
     if (const int rc = poismf_hip_serve_topn_check(inc, n_include, exc, n_exclude, n_top, n)) return rc;   // ref: :126-130
-    if (hipSetDevice(pick_device()) != hipSuccess) return 1;
+    if (hipSetDevice(pmf_env_device()) != hipSuccess) return 1;
     size_t maxrow = n - 1;
     if (inc) { maxrow = 0; for (size_t i = 0; i < n_include; i++) maxrow = std::max(maxrow, (size_t)inc[i]); }
     const size_t nrowsB = inc ? maxrow + 1 : n;

@@ -1,0 +1,138 @@
+// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip) have in common, and what the
+// session (poismf_hip_host.hip) hands to the two cores
+#pragma once
+#include <cstddef>
+#include <cstring>
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/poismf_hip.h"
+#include "devmem.hpp"
+#include "tb_tile.hpp"
+
+// exclude_seen: the session's resident CSR shard, and what the session remembers about it between calls
+struct PmfTopnSeen {
+    const unsigned long long* d_indptr;          // [row_end - row_begin + 1], from 0
+    const unsigned* d_indices;
+    size_t row_begin, row_end;                   // the shard's rows of A
+    std::vector<unsigned long long>* h_indptr;   // host copy of d_indptr (empty until the first call needs it)
+    int* sorted;                                 // -1 not checked yet, 0 some row is not strictly ascending, 1 all are
+};
+
+// (topn_batch.hip) finds out, once per session, whether the resident rows are strictly ascending (*seen.sorted); 0, or 1 on a device error
+int poismf_hip_topn_seen_sorted(PmfTopnSeen& seen, hipStream_t stream);
+
+// The argument checks of an entry point: 0, or 2.  No device call.
+int poismf_hip_topn_batch_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_rank_batch_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
+                                const sparse_ix* test_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+
+// The cores on device-resident factors (the session and the drop-in).  Arguments already checked.  dA rows are addressed by users[i], or
+// by i itself when compact_A (the drop-in uploads only the batch's rows).  *d_scratch / *scratch_cap: the caller's scratch, grown when it
+// is smaller than the call needs.  Return 0, 1 or (top-N with exclude_seen) 2.
+int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                              const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                              const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
+int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                              const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices,
+                              PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
+                              size_t* scratch_cap, unsigned int* out_rank, unsigned int* out_n_adm);
+
+#define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
+
+namespace {
+
+constexpr size_t TB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
+
+// the parts of a scratch layout, one after the other: take(bytes) is where the next part starts; `o` ends as the total
+struct TbTake {
+    size_t o = 0;
+    size_t operator()(size_t bytes) { const size_t at = o; o = pmf_round_up(o + bytes, 32); return at; }
+};
+
+// A CSR-shaped list with one row per user: row pointers from a non-negative start that never decrease, no row longer than row_max (or
+// dimB), indices below dimB and strictly ascending within a row.
+inline bool tb_rows_ok(const sparse_ix* indptr, const sparse_ix* indices, size_t n_users, size_t dimB, size_t row_max)
+{
+    if ((long long)indptr[0] < 0) return false;
+    for (size_t i = 0; i < n_users; i++) {
+        if (indptr[i + 1] < indptr[i]) return false;
+        const size_t p0 = (size_t)indptr[i], p1 = (size_t)indptr[i + 1];
+        if (p1 - p0 > dimB || p1 - p0 > row_max) return false;
+        if (p1 > p0 && indices == nullptr) return false;
+        for (size_t p = p0; p < p1; p++) {
+            if ((long long)indices[p] < 0 || (size_t)indices[p] >= dimB) return false;
+            if (p > p0 && (size_t)indices[p - 1] >= (size_t)indices[p]) return false;
+        }
+    }
+    return true;
+}
+
+// The items cut into slices for `row_tiles` tiles of users: about target_wgs workgroups in all, at most `cap` slices.
+struct TbSlices { size_t tiles_per_slice, nslices; };
+inline TbSlices tb_slices(size_t row_tiles, size_t dimB, size_t target_wgs, size_t cap = (size_t)-1)
+{
+    const size_t item_tiles = pmf_ceil_div(dimB, TB_TJ);
+    const size_t want = std::max<size_t>(std::min({ row_tiles >= target_wgs ? 1 : pmf_ceil_div(target_wgs, row_tiles), item_tiles, cap }), 1);
+    const size_t tps = pmf_ceil_div(item_tiles, want);
+    return { tps, pmf_ceil_div(item_tiles, tps) };
+}
+
+// The exclusion test of a chunk of users u0 .. u0 + nu - 1 whose lists hold nx indices: the lists go to d_indptr / d_indices rebased to
+// the chunk (hp, hx: staging the caller keeps between chunks), the resident rows are `seen`'s.
+inline hipError_t tb_stage_excl(TbExcl& x, const PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, size_t u0,
+                                size_t nu, size_t nx, unsigned* d_indptr, unsigned* d_indices, std::vector<unsigned>& hp,
+                                std::vector<unsigned>& hx, hipStream_t stream)
+{
+    x.seen_indptr = seen ? seen->d_indptr : nullptr;
+    x.seen_indices = seen ? seen->d_indices : nullptr;
+    x.seen_row0 = seen ? (unsigned)seen->row_begin : 0u;
+    x.seen_sorted = seen ? *seen->sorted : 0;
+    x.ex_indptr = excl_indptr ? d_indptr : nullptr;
+    x.ex_indices = d_indices;
+    if (excl_indptr == nullptr) return hipSuccess;
+    hp.resize(nu + 1);
+    hx.resize(nx);
+    const size_t p_base = (size_t)excl_indptr[u0];
+    for (size_t i = 0; i <= nu; i++) hp[i] = (unsigned)((size_t)excl_indptr[u0 + i] - p_base);
+    for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
+    const hipError_t e = pmf_upload(d_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream);
+    return e != hipSuccess ? e : pmf_upload(d_indices, hx.data(), nx * sizeof(unsigned), stream);
+}
+
+// The drop-in entry points: B and either all of A or (when that is less) the batch's rows go to the device of POISMF_HIP_DEVICE,
+// run(stream, dA, dB, compact, &d_scratch, &scratch_cap) gives the return code, and everything is freed again.
+template <class Run>
+int tb_dropin(const real_t* A, const real_t* B, size_t k, size_t dimA, size_t dimB, const sparse_ix* users, size_t n_users, Run run)
+{
+    const int device = pmf_env_device();
+    if (hipSetDevice(device) != hipSuccess) return 1;
+    const hipStream_t st = nullptr;
+    const bool compact = n_users < dimA;
+    real_t *dA = nullptr, *dB = nullptr;
+    void* d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    int rc = 1;
+    do {
+        const size_t rowsA = compact ? n_users : dimA;
+        if (pmf_alloc(&dA, rowsA * k * sizeof(real_t) + 16, st) != hipSuccess || pmf_alloc(&dB, dimB * k * sizeof(real_t) + 16, st) != hipSuccess) break;
+        if (compact) {
+            std::vector<real_t> rows;
+            try { rows.resize(n_users * k); } catch (const std::bad_alloc&) { break; }
+            for (size_t i = 0; i < n_users; i++) memcpy(rows.data() + i * k, A + (size_t)users[i] * k, k * sizeof(real_t));
+            if (pmf_upload_big(dA, rows.data(), rowsA * k * sizeof(real_t), device, st) != hipSuccess) break;
+        } else if (pmf_upload_big(dA, A, rowsA * k * sizeof(real_t), device, st) != hipSuccess) break;
+        if (pmf_upload_big(dB, B, dimB * k * sizeof(real_t), device, st) != hipSuccess) break;
+        rc = run(st, dA, dB, compact, &d_scratch, &scratch_cap);
+    } while (0);
+    pmf_free(dA, st);
+    pmf_free(dB, st);
+    pmf_free(d_scratch, st);
+    return rc;
+}
+
+}  // namespace

@@ -2,7 +2,8 @@
 // a workgroup of four waves owns TB_TU = 64 rows of users (wave w: rows 16 w .. 16 w + 15) and walks the items TB_TJ = 64 at a time; the
 // users' rows and the items' rows go through LDS in chunks of TB_KC columns, zero padded to a multiple of four columns.  tb_compute gives
 // each (user, item) the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  -- fp32 on v_mfma_f32_16x16x4_f32, fp64
-// on a VALU chain with the same register layout -- bit for bit what pair_dot_kernel (serve.hip) computes.
+// on a VALU chain with the same register layout -- bit for bit what pair_dot_kernel (serve.hip) computes.  tb_walk is that walk with the
+// kernel's epilogue as a functor; tb_excluded is the pair's one test "is item j in E(u)?".
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +88,90 @@ template <class T, bool MFMA> __device__ __forceinline__ void tb_compute(T (&acc
                 for (int r = 0; r < 4; r++) acc[t][r] = __builtin_fma(av[r], bv[t], acc[t][r]);
         }
     }
+}
+
+// The walk of one workgroup over the item tiles tile0 .. tile1 - 1: acc[t][r] = the whole chain for user 16 wave + 4 (lane >> 4) + r and item
+// j_base + 16 t + (lane & 15), then epilogue(acc, j_base).  As / Bs: [TB_TU][TB_KS] each in LDS; user_row(row) is the tile row's row of A (< 0: none).
+template <class T, bool MFMA, class UserRow, class Epilogue>
+__device__ __forceinline__ void tb_walk(T* As, T* Bs, const T* A, const T* B, int k, unsigned dimB, unsigned tile0, unsigned tile1, UserRow user_row,
+                                        Epilogue epilogue)
+{
+    static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
+    const int nchunks = (k + TB_KC - 1) / TB_KC;
+    auto item_row = [dimB](unsigned j_base) { return [dimB, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < dimB ? (long long)j : -1ll; }; };
+
+    // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
+    T b_next[TB_NL];
+    if (nchunks == 1) {
+        tb_fetch(b_next, A, k, 0, k, user_row);
+        tb_store(As, b_next);
+        tb_fetch(b_next, B, k, 0, k, item_row(tile0 * TB_TJ));
+    }
+
+    for (unsigned jt = tile0; jt < tile1; jt++) {
+        const unsigned j_base = jt * TB_TJ;
+        T acc[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) acc[t][r] = 0;
+        if (nchunks == 1) {
+            __syncthreads();   // every wave is done with the items' tile of the step before
+            tb_store(Bs, b_next);
+            __syncthreads();
+            if (jt + 1 < tile1) tb_fetch(b_next, B, k, 0, k, item_row(j_base + TB_TJ));
+            tb_compute<T, MFMA>(acc, As, Bs, k);
+        } else {
+            for (int ch = 0; ch < nchunks; ch++) {
+                const int c0 = ch * TB_KC;
+                const int len = k - c0 < TB_KC ? k - c0 : TB_KC;
+                __syncthreads();   // every wave is done with the tiles of the step before
+                tb_fetch(b_next, A, k, c0, len, user_row);
+                tb_store(As, b_next);
+                tb_fetch(b_next, B, k, c0, len, item_row(j_base));
+                tb_store(Bs, b_next);
+                __syncthreads();
+                tb_compute<T, MFMA>(acc, As, Bs, len);
+            }
+        }
+        epilogue(acc, j_base);
+    }
+}
+
+// ---- "is item j in E(u)?" ----
+struct TbExcl {
+    const unsigned long long* seen_indptr;   // exclude_seen: the resident CSR (nullptr: off); local row = row of A - seen_row0
+    const unsigned* seen_indices;
+    unsigned seen_row0;
+    int seen_sorted;                         // its rows are strictly ascending (binary search) or not known to be (scan)
+    const unsigned* ex_indptr;               // the batch's own lists for this chunk (nullptr: none), strictly ascending rows
+    const unsigned* ex_indices;
+};
+
+__device__ __forceinline__ bool tb_sorted_has(const unsigned* v, unsigned long long lo, unsigned long long hi, unsigned j)
+{
+    while (lo < hi) {
+        const unsigned long long mid = lo + (hi - lo) / 2;
+        const unsigned x = v[mid];
+        if (x == j) return true;
+        if (x < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// item j is in E(chunk user i, whose row of A is arow): the batch's list first, then the resident row
+__device__ __forceinline__ bool tb_excluded(const TbExcl& x, unsigned i, unsigned arow, unsigned j)
+{
+    if (x.ex_indptr != nullptr && tb_sorted_has(x.ex_indices, x.ex_indptr[i], x.ex_indptr[i + 1], j)) return true;
+    if (x.seen_indptr != nullptr) {
+        const unsigned row = arow - x.seen_row0;
+        const unsigned long long p0 = x.seen_indptr[row], p1 = x.seen_indptr[row + 1];
+        if (x.seen_sorted) return tb_sorted_has(x.seen_indices, p0, p1, j);
+        for (unsigned long long p = p0; p < p1; p++)
+            if (x.seen_indices[p] == j) return true;
+    }
+    return false;
 }
 
 }  // namespace

@@ -35,7 +35,7 @@
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
 #include "tb_tile.hpp"
-#include "topn_batch.hpp"
+#include "tb_batch.hpp"
 
 namespace {
 
@@ -47,7 +47,6 @@ constexpr size_t TB_MERGE_MAX = 2048;                     // entries of one user
 constexpr size_t TB_CHUNK_USERS_MAX = 262144;
 constexpr size_t TB_N_TOP_MAX = POISMF_HIP_TOPN_BATCH_MAX_N_TOP;
 constexpr size_t TB_BUDGET = (size_t)POISMF_HIP_TOPN_BATCH_BUDGET_MB << 20;
-constexpr size_t TB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
 static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
 static_assert(TB_N_TOP_MAX >= 128, "the header promises at least 128");
 
@@ -59,12 +58,7 @@ struct TbArgs {
     int k;
     unsigned n_top, cap;              // list capacity in LDS (n_top + TB_ROOM + slack)
     unsigned nslices, tiles_per_slice;
-    const unsigned long long* seen_indptr;   // exclude_seen: the resident CSR (nullptr: off); local row = user - seen_row0
-    const unsigned* seen_indices;
-    unsigned seen_row0;
-    int seen_sorted;                  // its rows are strictly ascending (binary search) or not known to be (scan)
-    const unsigned* ex_indptr;        // the batch's own lists for this chunk (nullptr: none), strictly ascending rows
-    const unsigned* ex_indices;
+    TbExcl excl;                      // E(u) of the chunk's users
     real_t* part_score;               // [n_users][nslices][n_top]
     unsigned* part_ix;
 };
@@ -74,18 +68,6 @@ __device__ __forceinline__ void tb_wave_sync()
     // LDS operations of one wave complete in order; this keeps the compiler from moving them across the point
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ bool tb_sorted_has(const unsigned* v, unsigned long long lo, unsigned long long hi, unsigned j)
-{
-    while (lo < hi) {
-        const unsigned long long mid = lo + (hi - lo) / 2;
-        const unsigned x = v[mid];
-        if (x == j) return true;
-        if (x < j) lo = mid + 1;
-        else hi = mid;
-    }
-    return false;
 }
 
 // Rank-counts list `u` (c entries, c <= cap) under the total order, keeps the best min(c, n_top) in order and, when the list is full,
@@ -125,7 +107,6 @@ __device__ __forceinline__ void tb_prune(real_t* ls, unsigned* li, unsigned c, u
 template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile_kernel(TbArgs a)
 {
     extern __shared__ __align__(16) unsigned char tb_smem[];
-    static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
     T* As = (T*)tb_smem;                                  // [TB_TU][TB_KS]
     T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
     T* Ls = Bs + TB_TJ * TB_KS;                           // [TB_TU][cap] candidate scores
@@ -149,11 +130,9 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
     const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
     const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
-    const int nchunks = (a.k + TB_KC - 1) / TB_KC;
     const unsigned col = lane & 15, quad = lane >> 4;
     const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
     auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
-    auto item_row = [&](unsigned j_base) { return [&a, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < a.dimB ? (long long)j : -1ll; }; };
 
     // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
     T thr_reg[4];
@@ -162,41 +141,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
     bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
 
-    // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
-    T b_next[TB_NL];
-    if (nchunks == 1) {
-        tb_fetch(b_next, a.A, a.k, 0, a.k, user_row);
-        tb_store(As, b_next);
-        tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(tile0 * TB_TJ));
-    }
-
-    for (unsigned jt = tile0; jt < tile1; jt++) {
-        const unsigned j_base = jt * TB_TJ;
-        T acc[4][4];
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) acc[t][r] = 0;
-        if (nchunks == 1) {
-            __syncthreads();   // every wave is done with the items' tile of the step before
-            tb_store(Bs, b_next);
-            __syncthreads();
-            if (jt + 1 < tile1) tb_fetch(b_next, a.B, a.k, 0, a.k, item_row(j_base + TB_TJ));
-            tb_compute<T, MFMA>(acc, As, Bs, a.k);
-        } else {
-            for (int ch = 0; ch < nchunks; ch++) {
-                const int c0 = ch * TB_KC;
-                const int len = a.k - c0 < TB_KC ? a.k - c0 : TB_KC;
-                __syncthreads();   // every wave is done with the tiles of the step before
-                tb_fetch(b_next, a.A, a.k, c0, len, user_row);
-                tb_store(As, b_next);
-                tb_fetch(b_next, a.B, a.k, c0, len, item_row(j_base));
-                tb_store(Bs, b_next);
-                __syncthreads();
-                tb_compute<T, MFMA>(acc, As, Bs, len);
-            }
-        }
-
+    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, a.dimB, tile0, tile1, user_row, [&](T (&acc)[4][4], unsigned j_base) {
         // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
 #pragma unroll
         for (int t = 0; t < 4; t++) {
@@ -221,25 +166,11 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
                 for (int r = 0; r < 4; r++) {
                     const unsigned uu = urow0 + r;
                     const T s = acc[t][r];
-                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu])) {
-                        bool excluded = false;
-                        if (a.ex_indptr != nullptr) {
-                            const unsigned g = u_base + uu;
-                            excluded = tb_sorted_has(a.ex_indices, a.ex_indptr[g], a.ex_indptr[g + 1], j);
-                        }
-                        if (!excluded && a.seen_indptr != nullptr) {
-                            const unsigned row = uid[uu] - a.seen_row0;
-                            const unsigned long long p0 = a.seen_indptr[row], p1 = a.seen_indptr[row + 1];
-                            if (a.seen_sorted) excluded = tb_sorted_has(a.seen_indices, p0, p1, j);
-                            else
-                                for (unsigned long long p = p0; p < p1 && !excluded; p++) excluded = a.seen_indices[p] == j;
-                        }
-                        if (!excluded) {
-                            const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
-                            Ls[(size_t)uu * a.cap + pos] = s;
-                            Li[(size_t)uu * a.cap + pos] = j;
-                            appended = true;
-                        }
+                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu]) && !tb_excluded(a.excl, u_base + uu, uid[uu], j)) {
+                        const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
+                        Ls[(size_t)uu * a.cap + pos] = s;
+                        Li[(size_t)uu * a.cap + pos] = j;
+                        appended = true;
                     }
                 }
             }
@@ -248,7 +179,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
                 tb_wave_sync();
             }
         }
-    }
+    });
 
     // ---- the slice's answer per user: the best min(count, n_top) in order, the rest marked empty ----
     for (unsigned q = 0; q < 16; q++) {
@@ -303,18 +234,6 @@ __global__ __launch_bounds__(256) void topn_rows_sorted_kernel(const unsigned lo
     }
 }
 
-size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-size_t round_up(size_t a, size_t b) { return ceil_div(a, b) * b; }
-
-// item slices for a chunk of `tiles` user tiles
-size_t tb_slices(size_t tiles, size_t n_top, size_t dimB)
-{
-    size_t s = tiles >= TB_TARGET_WGS ? 1 : ceil_div(TB_TARGET_WGS, tiles);
-    s = std::min(s, ceil_div(dimB, TB_TJ));
-    s = std::min(s, std::max<size_t>(1, TB_MERGE_MAX / n_top));
-    return std::max<size_t>(s, 1);
-}
-
 // The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
 struct TbLayout {
     size_t chunk_users;      // users per chunk
@@ -338,8 +257,7 @@ struct TbLayout {
         if (uc > TB_TU) uc -= uc % TB_TU;
         chunk_users = uc;
         part_entries = (TB_TU * TB_TARGET_WGS + TB_TU + uc) * n_top;   // (every chunk of <= uc users fits, however it is sliced)
-        size_t o = 0;
-        auto take = [&o](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 32); return at; };
+        TbTake take;
         users = take(uc * sizeof(unsigned));
         ex_indptr = take((uc + 1) * sizeof(unsigned));
         ex_indices = take(idx_cap * sizeof(unsigned));
@@ -347,20 +265,11 @@ struct TbLayout {
         part_ix = take(part_entries * sizeof(unsigned));
         out_score = take(uc * n_top * R);
         out_ix = take(uc * n_top * sizeof(unsigned));
-        total = o;
+        total = take.o;
     }
 };
 
 size_t tb_lds_bytes(size_t cap) { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * cap * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12); }
-
-int pick_device()
-{
-    int device = 0;
-    if (const char* e = getenv("POISMF_HIP_DEVICE")) device = atoi(e);
-    return device;
-}
-
-#define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 }  // namespace
 
@@ -380,18 +289,9 @@ int poismf_hip_topn_batch_check(const sparse_ix* users, size_t n_users, size_t n
     for (size_t i = 0; i < n_users; i++)
         if ((size_t)users[i] >= dimA) return 2;
     if (excl_indptr != nullptr) {
-        const size_t idx_cap = TbLayout(n_users, n_top, dimB).idx_cap;
-        for (size_t i = 0; i < n_users; i++) {
-            const size_t p0 = (size_t)excl_indptr[i], p1 = (size_t)excl_indptr[i + 1];
-            if (p1 < p0) return 2;
-            const size_t len = p1 - p0;
-            if (len > dimB || n_top > dimB - len || len > idx_cap) return 2;
-            if (len > 0 && excl_indices == nullptr) return 2;
-            for (size_t p = p0; p < p1; p++) {
-                if ((size_t)excl_indices[p] >= dimB) return 2;
-                if (p > p0 && (size_t)excl_indices[p - 1] >= (size_t)excl_indices[p]) return 2;
-            }
-        }
+        if (!tb_rows_ok(excl_indptr, excl_indices, n_users, dimB, TbLayout(n_users, n_top, dimB).idx_cap)) return 2;
+        for (size_t i = 0; i < n_users; i++)
+            if (n_top > dimB - ((size_t)excl_indptr[i + 1] - (size_t)excl_indptr[i])) return 2;   // n_top items must remain
     }
     return 0;
 }
@@ -406,7 +306,7 @@ int poismf_hip_topn_seen_sorted(PmfTopnSeen& seen, hipStream_t stream)
     TB_TRY(pmf_alloc(&d_flag, sizeof(unsigned), stream));
     hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(unsigned), stream);
     if (e == hipSuccess) {
-        const unsigned grid = (unsigned)std::min<size_t>(ceil_div(std::max<size_t>(nrows, 1), 256), 4096);
+        const unsigned grid = (unsigned)std::min<size_t>(pmf_ceil_div(std::max<size_t>(nrows, 1), 256), 4096);
         hipLaunchKernelGGL(topn_rows_sorted_kernel, dim3(grid), dim3(256), 0, stream, seen.d_indptr, seen.d_indices, nrows, d_flag);
         e = hipGetLastError();
     }
@@ -448,9 +348,7 @@ static int tb_check_seen(PmfTopnSeen& seen, const sparse_ix* users, size_t n_use
     return 0;
 }
 
-// ---- core on device-resident factors (the session and the drop-in below).  Arguments already checked. ----
-// dA rows are addressed by users[i], or by i itself when compact_A (the drop-in uploads only the batch's rows).  *d_scratch /
-// *scratch_cap: the caller's scratch, grown here when it is smaller than this call needs.  Returns 0, 1 or (exclude_seen) 2.
+// ---- core on device-resident factors (tb_batch.hpp) ----
 int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
                               const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
                               const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score)
@@ -458,13 +356,7 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
     if (seen != nullptr)
         if (const int rc = tb_check_seen(*seen, users, n_users, n_top, dimB, excl_indptr, excl_indices, stream)) return rc;
     const TbLayout L(n_users, n_top, dimB);
-    if (*scratch_cap < L.total) {
-        pmf_free(*d_scratch, stream);
-        *d_scratch = nullptr;
-        *scratch_cap = 0;
-        TB_TRY(pmf_alloc((unsigned char**)d_scratch, L.total, stream));
-        *scratch_cap = L.total;
-    }
+    TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
     unsigned char* base = (unsigned char*)*d_scratch;
 
     size_t cap = n_top + TB_ROOM + std::min<size_t>(n_top, 32);
@@ -473,6 +365,7 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
     auto kern = topn_tile_kernel<real_t, sizeof(real_t) == 4>;
     TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TB_LDS_LIMIT));
 
+    TbArgs a;
     std::vector<unsigned> hu, hp, hx, hix;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose exclusion lists fit the index area together
@@ -487,21 +380,12 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
         hu.resize(nu);
         for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
         TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
-        if (excl_indptr != nullptr) {
-            hp.resize(nu + 1);
-            hx.resize(nx);
-            const size_t p_base = (size_t)excl_indptr[u0];
-            for (size_t i = 0; i <= nu; i++) hp[i] = (unsigned)((size_t)excl_indptr[u0 + i] - p_base);
-            for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
-            TB_TRY(pmf_upload(base + L.ex_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream));
-            TB_TRY(pmf_upload(base + L.ex_indices, hx.data(), nx * sizeof(unsigned), stream));
-        }
-        const size_t tiles = ceil_div(nu, TB_TU);
-        const size_t item_tiles = ceil_div(dimB, TB_TJ);
-        const size_t tps = ceil_div(item_tiles, tb_slices(tiles, n_top, dimB));
-        const size_t nslices = ceil_div(item_tiles, tps);
+        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
+                             hx, stream));
+        const size_t tiles = pmf_ceil_div(nu, TB_TU);
+        const TbSlices sl = tb_slices(tiles, dimB, TB_TARGET_WGS, std::max<size_t>(1, TB_MERGE_MAX / n_top));   // (the merge kernel's LDS bounds them)
+        const size_t nslices = sl.nslices;
         if (nu * nslices * n_top > L.part_entries) return 1;   // (cannot happen: TbLayout sizes the lists for any slicing of a chunk)
-        TbArgs a;
         a.A = dA;
         a.B = dB;
         a.users = (const unsigned*)(base + L.users);
@@ -511,13 +395,7 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
         a.n_top = (unsigned)n_top;
         a.cap = (unsigned)cap;
         a.nslices = (unsigned)nslices;
-        a.tiles_per_slice = (unsigned)tps;
-        a.seen_indptr = seen ? seen->d_indptr : nullptr;
-        a.seen_indices = seen ? seen->d_indices : nullptr;
-        a.seen_row0 = seen ? (unsigned)seen->row_begin : 0u;
-        a.seen_sorted = seen ? *seen->sorted : 0;
-        a.ex_indptr = excl_indptr ? (const unsigned*)(base + L.ex_indptr) : nullptr;
-        a.ex_indices = (const unsigned*)(base + L.ex_indices);
+        a.tiles_per_slice = (unsigned)sl.tiles_per_slice;
         // (one slice: its sorted lists are the results)
         a.part_score = (real_t*)(base + (nslices == 1 ? L.out_score : L.part_score));
         a.part_ix = (unsigned*)(base + (nslices == 1 ? L.out_ix : L.part_ix));
@@ -545,32 +423,11 @@ int poismf_hip_topn_batch(const real_t* A, const real_t* B, int k, size_t dimA, 
     if (n_users == 0) return 0;
     if (k < 1 || A == nullptr || B == nullptr || out_ix == nullptr) return 2;
     if (const int rc = poismf_hip_topn_batch_check(users, n_users, n_top, dimA, dimB, (size_t)k, excl_indptr, excl_indices)) return rc;
-    const int device = pick_device();
-    if (hipSetDevice(device) != hipSuccess) return 1;
-    const hipStream_t st = nullptr;
-    const size_t kk = (size_t)k;
-    const bool compact = n_users < dimA;   // only the batch's rows of A go up when that is less than all of A
-    real_t *dA = nullptr, *dB = nullptr;
-    void* d_scratch = nullptr;
-    size_t scratch_cap = 0;
-    int rc = 1;
-    do {
-        const size_t rowsA = compact ? n_users : dimA;
-        if (pmf_alloc(&dA, rowsA * kk * sizeof(real_t) + 16, st) != hipSuccess || pmf_alloc(&dB, dimB * kk * sizeof(real_t) + 16, st) != hipSuccess) break;
-        if (compact) {
-            std::vector<real_t> rows;
-            try { rows.resize(n_users * kk); } catch (const std::bad_alloc&) { break; }
-            for (size_t i = 0; i < n_users; i++) memcpy(rows.data() + i * kk, A + (size_t)users[i] * kk, kk * sizeof(real_t));
-            if (pmf_upload_big(dA, rows.data(), rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        } else if (pmf_upload_big(dA, A, rowsA * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        if (pmf_upload_big(dB, B, dimB * kk * sizeof(real_t), device, st) != hipSuccess) break;
-        rc = poismf_hip_topn_batch_run(st, dA, dB, dimB, kk, compact, users, n_users, n_top, nullptr, excl_indptr, excl_indices, &d_scratch,
-                                       &scratch_cap, out_ix, out_score);
-    } while (0);
-    pmf_free(dA, st);
-    pmf_free(dB, st);
-    pmf_free(d_scratch, st);
-    return rc;
+    return tb_dropin(A, B, (size_t)k, dimA, dimB, users, n_users,
+                     [&](hipStream_t st, const real_t* dA, const real_t* dB, bool compact, void** d_scratch, size_t* scratch_cap) {
+                         return poismf_hip_topn_batch_run(st, dA, dB, dimB, (size_t)k, compact, users, n_users, n_top, nullptr, excl_indptr,
+                                                          excl_indices, d_scratch, scratch_cap, out_ix, out_score);
+                     });
 }
 
 }  // extern "C"

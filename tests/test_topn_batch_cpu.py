@@ -104,6 +104,43 @@ def test_scipy_exclude_with_wrong_row_count_raises():
         _fake_fitted(True).topN_batch([0, 1], 5, exclude=X)
 
 
+def _with_stored_zero():
+    """two rows of `exclude`, out of order, with a repeated cell and a stored zero: row 0 = {7, 2 (twice), 5 (value 0)}, row 1 = {9}"""
+    data = np.array([1.0, 1.0, 1.0, 0.0, 1.0])
+    cols = np.array([7, 2, 2, 5, 9])
+    return sp.csr_matrix((data, cols, np.array([0, 4, 5])), shape=(2, NITEMS))
+
+
+def test_topn_exclude_takes_what_csr_matrix_takes_and_keeps_stored_zeros():
+    """the top-N side of `exclude`: anything scipy.sparse.csr_matrix() accepts; duplicates merged, rows sorted, and a cell stored
+    with the value zero stays excluded"""
+    X = _with_stored_zero()
+    _, indptr, indices = api._topn_batch_args([0, 1], 5, X, NUSERS, NITEMS)
+    assert indptr.dtype == np.uint64 and indices.dtype == np.uint64
+    assert indptr.tolist() == [0, 3, 4] and indices.tolist() == [2, 5, 7, 9]
+    dense = np.zeros((2, NITEMS))
+    dense[0, [7, 2]] = 1.0
+    dense[1, 9] = 3.0
+    _, indptr, indices = api._topn_batch_args([0, 1], 5, dense, NUSERS, NITEMS)
+    assert indptr.tolist() == [0, 2, 3] and indices.tolist() == [2, 7, 9]
+    with pytest.raises(ValueError):   # the row count still counts
+        api._topn_batch_args([0, 1, 2], 5, dense, NUSERS, NITEMS)
+
+
+def test_rank_lists_need_a_sparse_matrix_or_a_pair_and_drop_stored_zeros():
+    """the rank side of the same argument: a dense array is refused, and a cell stored with the value zero is no cell"""
+    X = _with_stored_zero()
+    _, tp, ti, ep, ei = api._rank_batch_args([0, 1], X, X, NUSERS, NITEMS, K)
+    assert tp.tolist() == [0, 2, 3] and ti.tolist() == [2, 7, 9]
+    assert ep.tolist() == [0, 2, 3] and ei.tolist() == [2, 7, 9]
+    dense = np.zeros((2, NITEMS))
+    dense[0, 7] = 1.0
+    with pytest.raises(ValueError, match="must be a SciPy sparse matrix"):
+        api._rank_batch_args([0, 1], dense, None, NUSERS, NITEMS, K)
+    with pytest.raises(ValueError, match="must be a SciPy sparse matrix"):
+        api._rank_batch_args([0, 1], X, dense, NUSERS, NITEMS, K)
+
+
 class _NoDeviceSession(api.Session):
     """the Python half of a session, never connected to a device: any library call would fail on the missing handle"""
 
