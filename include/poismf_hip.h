@@ -444,6 +444,14 @@ POISMF_HIP_API int poismf_hip_debug_row_eval(real_t *G, double *f, real_t *B, re
  * limit_step: as in poismf_hip_params.  Same buffer convention as poismf_hip_session_plan. */
 POISMF_HIP_API size_t poismf_hip_debug_plan(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
                           size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
+/* The same plan; a lane launch whose instance is specialised on the used width of its factor rows (fp32 PG at k = 50: 50 elements of the 13
+ * slots' 52) carries "[KU=<width>]" behind its name. */
+POISMF_HIP_API size_t poismf_hip_debug_plan_widths(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
+                          size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
+/* Testing aid: full != 0 -- the lane launches this process plans from now on take the instances that carry every element of their slots, also
+ * where one specialised on the used width exists (the two agree bit for bit; a -DPMF_LANE_KU50=0 build never selects the latter); 0 -- the
+ * default again.  Returns the previous setting. */
+POISMF_HIP_API int poismf_hip_debug_lane_full_width(int full);
 
 /* Number of nonzeros held by this session for half `which` (shard only). */
 POISMF_HIP_API size_t poismf_hip_session_nnz(poismf_hip_session *s, int which);

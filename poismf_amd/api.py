@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
     "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
+    "poismf_hip_debug_plan_widths", "poismf_hip_debug_lane_full_width",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
 )
@@ -340,19 +341,28 @@ def debug_row_eval(B, Bsum, point, Xr_indptr, Xr_indices, Xr, l2_reg, w_mult=1.,
     return f, G
 
 
-def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256):
+def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256, widths=False):
     """Testing aid (include/poismf_hip.h, poismf_hip_debug_plan): the launches the planner gives a half whose rows have row_nnz nonzeros,
-    cut into nseg segments, for one call over segment `seg` (< 0: all of them): [(kernel instance, rows), ...].  Needs no GPU."""
+    cut into nseg segments, for one call over segment `seg` (< 0: all of them): [(kernel instance, rows), ...].  Needs no GPU.
+    widths: poismf_hip_debug_plan_widths -- a lane instance specialised on the used width of its factor rows is marked "[KU=<width>]"."""
     lib = load_library(use_float)
     row_nnz = np.ascontiguousarray(row_nnz, dtype=np.uint32)
     real = C.c_float if use_float else C.c_double
-    fn = lib.poismf_hip_debug_plan
+    fn = lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan
     fn.restype = C.c_size_t
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, real, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
     buf = C.create_string_buffer(int(fn(*args, None, 0)) + 1)
     fn(*args, buf, len(buf))
     return [(name.strip(), int(rows)) for name, rows in (item.rsplit(" rows=", 1) for item in buf.value.decode().split(";") if item.strip())]
+
+
+def lane_full_width(use_float, full):
+    """Testing aid (poismf_hip_debug_lane_full_width): full -- the lane launches this process plans from now on carry every element of their
+    slots, also where an instance specialised on the used width exists; not full -- the default again.  Returns the previous setting."""
+    fn = load_library(use_float).poismf_hip_debug_lane_full_width
+    fn.restype, fn.argtypes = C.c_int, [C.c_int]
+    return bool(fn(int(bool(full))))
 
 
 class PoisMF:

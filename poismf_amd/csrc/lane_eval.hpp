@@ -151,10 +151,16 @@ __device__ __forceinline__ unsigned acc_get(unsigned a)
 // nothing per dimension, the reference's own summation order.  The dots read the same image (lane j its own row, one ds_read_b128
 // per slot, row stride 816 bytes = conflict-free), so NO tile lives in registers: the solver's state has the 256 architectural
 // registers to itself and the v_accvgpr traffic is gone.  TX_ = rows of the image: 48 (39 KB: four rows per CU) or 64 (52 KB: three).
-template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool SMALL_ = false, int LP_ = 0, int TX_ = 0, bool TM_ = false> struct LaneEval {
+// KU_ (round 8; floats, the PG instances of four register sets): the USED width of a factor row, KU_ <= KP elements, known at compile time.  The
+// elements KU_ .. KP - 1 of a row are the padding of its last slot -- zeros in F, zeros in the point -- and the instances specialised on the slot count
+// carry them all the same: registers of the tile, multiply-adds of the dots and of the gradient's chains, inputs of the last batch's folds.  With
+// KU_ = 50 (k = 50: KP = 52) a set is 50 registers, the dots and the chains stop at dimension 49 and the last batch folds two partials, not four.
+// Every surviving sum keeps its operands and their order (DESIGN.md 4.4 goes through the chains one by one): the same bits as with KU_ = 0 (= KP).
+template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool SMALL_ = false, int LP_ = 0, int TX_ = 0, bool TM_ = false, int KU_ = 0> struct LaneEval {
     using SA = typename Slot<T>::A;
     static constexpr int SN = Slot<T>::N;                 // elements per 16-byte slot
     static constexpr int KP = KS * SN;                    // elements of a factor row, padded to whole slots
+    static constexpr int KU = KU_ > 0 ? KU_ : KP;         // elements of a factor row that have a register (the others: padding, never read)
     static constexpr int NC = (KP + WAVE - 1) / WAVE;     // elements of a k-vector per lane
     static constexpr int LP = LP_;                                                  // nonzeros of the partial LDS set (0: none)
     static constexpr int LLT = LL_ + (LP_ > 0 ? 1 : 0);                              // sets read from LDS (the partial one last)
@@ -250,12 +256,13 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     static constexpr bool PIPELINED = true;
     static constexpr int PIPE_MW = NW_ > 1 ? PMF_LANE_PIPE_MW : 1;   // (one-wave rows: always)
     static constexpr bool PARKS = false;
+    static constexpr bool COLD_CONSTANTS = KU < KP;   // (poismf_hip.hip, solve_row: constants of the row loop are built where they are used)
     static constexpr bool CACHED = true, MAY_CACHE = true, CACHED_GRAD = true;
     static constexpr int LS_BATCH = 1;
     static_assert(KS >= 13 && KP <= 2 * WAVE, "25 or 50 slots");
     static_assert(LV_ >= 1, "at least one set in architectural registers");
 
-    T t[LV][KP];                          // the sets in architectural registers
+    T t[LV][KU];                          // the sets in architectural registers
     static constexpr int AW = (int)sizeof(T) / 4;   // 32-bit words per element
     typedef unsigned U4 __attribute__((ext_vector_type(4)));
     typedef unsigned UE __attribute__((ext_vector_type(sizeof(T) / 4)));
@@ -288,6 +295,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     unsigned n_eval;
     unsigned char* stage;   // this wave's NBUF staging buffers
     unsigned char* part;    // this wave's partial LDS set (LP_ > 0): NCH chunk images of LP_ rows
+    unsigned char* smem0;   // the workgroup's LDS (wave w: WAVE_BYTES from smem0 + w WAVE_BYTES)
     unsigned char* red;     // this wave's transpose scratch
     SA* avec;               // this wave's copy of the current point, as slots
     unsigned char* tximg;   // TX_ > 0: this wave's LDS image of the tile
@@ -313,6 +321,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
         holds_dim = lane_on;
         F = F_;
         k = geo.k; ldF = geo.ldF; zero_row = geo.zero_row;
+        smem0 = smem;
         unsigned char* p = smem + (size_t)wid * WAVE_BYTES;
         stage = p;
         part = p + NBUF * STAGE_BYTES;
@@ -508,6 +517,10 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
             // solver, i.e. in scratch)
             unsigned lane_here = (unsigned)lane;
             asm volatile("" : "+v"(lane_here));
+            // KU < KP: in IMAGE order every register of a set holds real elements in some lane (lane l of load i has slot (64 i + l) % W), so
+            // the loads and the image's writes take all KP -- the elements past KU in registers that live only until the set has been through the
+            // image; the read-back in "one nonzero per lane" order keeps the KU elements that exist
+            T hi[LV][KP > KU ? KP - KU : 1];
             auto request_set = [&](auto sc) {
                 constexpr int s2 = decltype(sc)::value;
                 unsigned j4 = (lane_here / (unsigned)W) * 4u;            // byte address of the row's index for ds_bpermute
@@ -517,8 +530,11 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                     const unsigned c = (unsigned)__builtin_amdgcn_ds_bpermute((int)j4, (int)idx[s2]);
                     const unsigned off = __umul24(c, rowbytes) + q16;
                     const typename Slot<T>::U v = *(const typename Slot<T>::U*)((const char*)F + (size_t)off);
-#pragma unroll
-                    for (int e = 0; e < SN; e++) t[s2][i * SN + e] = v.v[e];
+                    static_for<0, SN>([&](auto ec) {
+                        constexpr int C = i * SN + decltype(ec)::value;
+                        if constexpr (C < KU) t[s2][C] = v.v[C % SN];
+                        else hi[s2][C - KU] = v.v[C % SN];
+                    });
                     j4 += (unsigned)(WAVE / W) * 4u;
                     q16 += (unsigned)(WAVE % W) * 16u;
                     const bool wrap = q16 >= (unsigned)(W * 16);
@@ -533,8 +549,10 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                 static_for<0, W>([&](auto qc) {
                     constexpr int q = decltype(qc)::value;
                     const SA v = rd[q];
-#pragma unroll
-                    for (int e = 0; e < SN; e++) t[s2][q * SN + e] = v.v[e];
+                    static_for<0, SN>([&](auto ec) {
+                        constexpr int C = q * SN + decltype(ec)::value;
+                        if constexpr (C < KU) t[s2][C] = v.v[C % SN];   // (past KU: the padding of the row's last slot, not kept)
+                    });
                 });
                 wave_lds_fence();
             };
@@ -544,8 +562,11 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                 static_for<0, W>([&](auto ic) {
                     constexpr int i = decltype(ic)::value;
                     SA v;
-#pragma unroll
-                    for (int e = 0; e < SN; e++) v.v[e] = t[s2][i * SN + e];
+                    static_for<0, SN>([&](auto ec) {
+                        constexpr int C = i * SN + decltype(ec)::value;
+                        if constexpr (C < KU) v.v[C % SN] = t[s2][C];
+                        else v.v[C % SN] = hi[s2][C - KU];
+                    });
                     wr[i * WAVE] = v;
                 });
                 wave_lds_fence();
@@ -624,9 +645,14 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     template <int Q0> __device__ __forceinline__ void dma_chunk_part(unsigned idx, int c)
     {
         const unsigned rowbytes = (unsigned)ldF * (unsigned)sizeof(T);
-        unsigned j4 = (unsigned)(lane / W) * 4u;
-        unsigned q16 = (unsigned)(lane % W) * 16u;
-        unsigned char* dst = part + c * PART_BYTES;
+        // (floats: the (row, slot) pairs of a lane and the image's address are the same for every row of the launch; from opaque copies of the lane
+        // and wave numbers they are recomputed here instead of being kept across the solver -- in the PG instance: in nine dwords of scratch -- as
+        // in the coalesced gather.  The fp64 instances stay as they were.)
+        unsigned lane_here = (unsigned)lane, wid_here = (unsigned)wid;
+        if constexpr (sizeof(T) == 4) asm volatile("" : "+v"(lane_here), "+v"(wid_here));
+        unsigned j4 = (lane_here / (unsigned)W) * 4u;
+        unsigned q16 = (lane_here % (unsigned)W) * 16u;
+        unsigned char* dst = (sizeof(T) == 4 ? smem0 + wid_here * (unsigned)WAVE_BYTES + NBUF * STAGE_BYTES : part) + c * PART_BYTES;
         constexpr int NI = (LP * W + WAVE - 1) / WAVE;
         static_for<0, NI>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
@@ -666,8 +692,11 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     {
         SA v;
         if constexpr (S < LV) {
-#pragma unroll
-            for (int e = 0; e < SN; e++) v.v[e] = t[S][Q * SN + e];
+            static_for<0, SN>([&](auto ec) {
+                constexpr int C = Q * SN + decltype(ec)::value;
+                if constexpr (C < KU) v.v[C % SN] = t[S][C];
+                else v.v[C % SN] = (T)0;
+            });
         } else if constexpr (S < LR) {
 #pragma unroll
             for (int e = 0; e < SN; e++) v.v[e] = acc_elem(tae[S - LV][Q * SN + e]);
@@ -681,8 +710,10 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     // element C of this lane's nonzero in set S
     template <int S, int C> __device__ __forceinline__ T tile_elem() const
     {
-        if constexpr (S < LV) return t[S][C];
-        else if constexpr (S < LR) return acc_elem(tae[S - LV][C]);
+        if constexpr (S < LV) {
+            if constexpr (C < KU) return t[S][C];
+            else return (T)0;   // (KU < KP: the padding has no register; no instance with a used width comes here)
+        } else if constexpr (S < LR) return acc_elem(tae[S - LV][C]);
         else {
             constexpr int q = C / SN, c = slot_chunk(q);
             if constexpr (S - LR < LL) return *((const T*)(stage + ((S - LR) * NCH + c) * STAGE_BYTES) + (lane * W + (q - chunk_start(c))) * SN + C % SN);
@@ -712,7 +743,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     template <int B, int COL, int R> __device__ __forceinline__ T partial(const T (&coef)[LT], const T (&tl)[4][LLX]) const
     {
         constexpr int C = DB * B + COL + CW * R;
-        T v = coef[0] * t[0][C];
+        T v = coef[0] * tile_elem<0, C>();
         static_for<1, LR>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             v = fma_t(coef[s], tile_elem<s, C>(), v);
@@ -736,6 +767,10 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                              // always done (reg_eval.hpp): PG(10) item rows 3.45 -> 3.15 ms.  (The instances of fewer sets read the point from LDS: packed there
                              // too, TNCG fp32 110.8 -> 109.9 ms, CG fp32 18.3 -> 18.0 for another order of their sums -- not kept.)
 #endif
+    // a used width below KP: only where every user of the tile is written for it -- the coalesced gather, the scalar-operand packed dots, the
+    // DPP butterfly with packed chains; whole pairs of dimensions, and only the last slot is cut
+    static_assert(KU == KP || (COAL && SPOINT && PMF_LANE_XPOSE == 2 && PMF_LANE_PK && PMF_LANE_PK_DOTS && KU % 2 == 0 && KU > KP - SN && KU < KP),
+                  "a used width: floats, four and more register sets, the last slot's upper pair");
     template <int W_> __device__ __forceinline__ T fold(T a, T b) const
     {
         return swap_fold<W_>(a, b);   // (the folds through the LDS crossbar, ds_bpermute + two selects, lost everywhere: DESIGN.md 4.4)
@@ -758,11 +793,28 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
             // total of dimension l.  ~160 VALU instructions for 52 dimensions, dependent chains of six operations.
             static_assert(B == 0 && KP <= WAVE, "one element per lane");
             const bool c8 = (lane & 8) != 0, c4 = (lane & 4) != 0, c2 = (lane & 2) != 0, c1 = (lane & 1) != 0;
-            constexpr int NBATCH = (KP + 15) / 16;
+            constexpr int NBATCH = (KU + 15) / 16;
             T rowsum[4] = { (T)0, (T)0, (T)0, (T)0 };
+            // The partial LDS set's slots, half a batch at a time (half h of batch b: slots 4 b + h and 4 b + h + 2, the dimensions of its eight chains),
+            // requested ONE HALF AHEAD: as soon as the previous half's multiply-adds have taken theirs, so that the round trip runs under that half's
+            // folds and this half's register chains -- 8 registers in flight.  (Left to the scheduler each read sat directly in front of the multiply-add
+            // that takes it, an s_waitcnt lgkmcnt between the two, four slots at a time: round 8)
+            SA lsh[2];
+            auto request_half = [&](auto bc, auto hc) {
+                constexpr int b = decltype(bc)::value, h = decltype(hc)::value;
+                if constexpr (LLT > 0 && b < NBATCH) {
+                    constexpr int N = KU - 16 * b < 16 ? KU - 16 * b : 16;
+                    static_for<0, 2>([&](auto gc2) {
+                        constexpr int g2 = decltype(gc2)::value;
+                        if constexpr (4 * h + 8 * g2 < N) lsh[g2] = tile_slot<LR, 4 * b + h + 2 * g2>();
+                    });
+                    pin_here();
+                }
+            };
+            request_half(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
             static_for<0, NBATCH>([&](auto bc) {
                 constexpr int b = decltype(bc)::value;
-                constexpr int N = KP - 16 * b < 16 ? KP - 16 * b : 16;        // partials of this batch
+                constexpr int N = KU - 16 * b < 16 ? KU - 16 * b : 16;        // partials of this batch (KU < KP: the padding has none)
                 T q[8], r[4], s2[2];
                 constexpr int N8 = N < 8 ? N : 8;
                 {
@@ -772,7 +824,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                         constexpr int h = decltype(hc)::value;
                         T u[8];
                         // chain j: dimension 16 b + 4 h + j / 2 + 8 (j % 2)   (the two inputs of fold 4 h + j / 2)
-                        static_assert(LLT == 0 || (sizeof(T) == 4 && PMF_LANE_PK && N % 4 == 0 && LV >= 2 && LV == LR), "a partial LDS set rides in the packed chains only");
+                        static_assert(LLT == 0 || (sizeof(T) == 4 && PMF_LANE_PK && N % 2 == 0 && LV >= 2 && LV == LR), "a partial LDS set rides in the packed chains only");
                         if constexpr (sizeof(T) == 4 && PMF_LANE_PK && N % 2 == 0 && LV >= 2) {   // (one set: the lone multiply is contracted with the fold's add by the compiler -- kept as it is, bit for bit)
                             // floats: the chains of two NEIGHBOURING dimensions in one v_pk_fma_f32 (the tile's elements C, C + 1 sit in neighbouring
                             // registers: they arrive four to a 16-byte load) -- the same multiply-adds in the same order, half the instructions
@@ -797,12 +849,18 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                                 static_for<0, 2>([&](auto gc2) {
                                     constexpr int g2 = decltype(gc2)::value;
                                     if constexpr (4 * h + 8 * g2 < N) {
-                                        const SA ls = tile_slot<LR, 4 * b + h + 2 * g2>();
+                                        const SA ls = lsh[g2];
                                         const v2f cc = { (float)coef[LR], (float)coef[LR] };
                                         u2[2 * g2] = __builtin_elementwise_fma(cc, v2f{ (float)ls.v[0], (float)ls.v[1] }, u2[2 * g2]);
-                                        u2[2 * g2 + 1] = __builtin_elementwise_fma(cc, v2f{ (float)ls.v[2], (float)ls.v[3] }, u2[2 * g2 + 1]);
+                                        if constexpr (4 * h + 8 * g2 + 2 < N)   // (the upper pair of a cut last slot: no chain)
+                                            u2[2 * g2 + 1] = __builtin_elementwise_fma(cc, v2f{ (float)ls.v[2], (float)ls.v[3] }, u2[2 * g2 + 1]);
                                     }
                                 });
+                                if constexpr (4 * h < N) {   // (a half without chains took nothing: its successor is on its way already)
+                                    pin_here();
+                                    if constexpr (h == 0 && 4 < N) request_half(std::integral_constant<int, b>{}, std::integral_constant<int, 1>{});
+                                    else request_half(std::integral_constant<int, b + 1>{}, std::integral_constant<int, 0>{});
+                                }
                             }
                             static_for<0, 4>([&](auto pc) {
                                 constexpr int p = decltype(pc)::value;
@@ -862,8 +920,8 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                 SA v;
                 static_for<0, SN>([&](auto ec) {
                     constexpr int C = q * SN + decltype(ec)::value;
-                    T u = coef[0] * t[0][C];
-                    static_for<1, LV>([&](auto sc) { u = fma_t(coef[decltype(sc)::value], t[decltype(sc)::value][C], u); });
+                    T u = coef[0] * tile_elem<0, C>();
+                    static_for<1, LV>([&](auto sc) { u = fma_t(coef[decltype(sc)::value], tile_elem<decltype(sc)::value, C>(), u); });
                     v.v[C % SN] = u;
                 });
                 img[q * XP_QS] = v;
@@ -966,9 +1024,29 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
     }
 
     // NW > 1: add up the NW waves' results (fixed order; every wave ends with the same bits)
-    __device__ __forceinline__ void combine_waves(T (&tot)[NC], double& lsum, bool vec = true)
+    // (WITH_L = false: no scalar rides along -- lsum is neither written nor read, and no 0.0 is kept in a register pair for it)
+    template <bool WITH_L = true> __device__ __forceinline__ void combine_waves(T (&tot)[NC], double& lsum, bool vec = true)
     {
-        if constexpr (NW > 1) {
+        if constexpr (NW > 1 && !WITH_L && !TM_) {
+            T* xv = (T*)(xw_base + xw_sel * XW_BYTES);
+            xw_sel ^= 1;
+#pragma unroll
+            for (int i = 0; i < NC; i++) xv[(wid * NC + i) * WAVE + lane] = tot[i];
+            __syncthreads();
+            T part[NW][NC];
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+#pragma unroll
+                for (int i = 0; i < NC; i++) part[w][i] = xv[(w * NC + i) * WAVE + lane];
+            }
+#pragma unroll
+            for (int i = 0; i < NC; i++) {
+                T s = part[0][i];
+#pragma unroll
+                for (int w = 1; w < NW; w++) s += part[w][i];
+                tot[i] = s;
+            }
+        } else if constexpr (NW > 1) {
             T* xv = (T*)(xw_base + xw_sel * XW_BYTES);
             double* xl = (double*)(xw_base + xw_sel * XW_BYTES + NW * WAVE * NC * (int)sizeof(T));
             xw_sel ^= 1;
@@ -1055,7 +1133,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                 T ac[GS];
                 static_for<0, GS>([&](auto ic) {
                     constexpr int c = c0 + decltype(ic)::value;
-                    if constexpr (c < KP) {
+                    if constexpr (c < KU) {
                         ac[c - c0] = read_lane(xcur, XPOSE ? c : (c % CW) + 16 * (c / CW));
                         asm volatile("" : "+s"(ac[c - c0]));   // here, not sunk next to its use
                     }
@@ -1063,6 +1141,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                 if constexpr (PKD) {
                     static_for<0, GS / 2>([&](auto hc) {
                         constexpr int c = c0 + 2 * decltype(hc)::value;
+                        if constexpr (c < KU) {
                         const v2f a2 = { (float)ac[c - c0], (float)ac[c - c0 + 1] };
                         static_for<0, LT>([&](auto sc) {
                             constexpr int s2 = decltype(sc)::value;
@@ -1072,6 +1151,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
                             if constexpr (c == 0) pred2[s2] = t2 * a2;
                             else pred2[s2] = __builtin_elementwise_fma(t2, a2, pred2[s2]);
                         });
+                        }
                     });
                 } else
                 static_for<0, GS>([&](auto ic) {
@@ -1235,7 +1315,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
         } else if constexpr (NW > 1) {
             double lsum = 0.0;
             if constexpr (WANT_F) lsum = wave_sum(lpart);
-            combine_waves(tot, lsum, WANT_G);
+            combine_waves<WANT_F || KU == KP>(tot, lsum, WANT_G);   // (the instances with a used width: the gradient alone where no value is wanted)
             PMF_STAMP(*this, 4);
             if constexpr (WANT_G) {
 #pragma unroll
@@ -1327,7 +1407,7 @@ template <class T, int KS, int LV_, int LA_ = 0, int LL_ = 0, int NW_ = 1, bool 
         });
         if constexpr (NW > 1) {
             double unused = 0.0;
-            combine_waves(tot, unused);
+            combine_waves<KU == KP>(tot, unused);
         }
 #pragma unroll
         for (int i = 0; i < NC; i++) acc[i] += tot[i];

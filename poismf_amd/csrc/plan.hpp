@@ -82,12 +82,13 @@ struct RowDesc { unsigned p0_lo, p0_hi, nnz, lrow; };
 
 // A lane-engine instance (lane_eval.hpp, lane_shape_for below).  lv / la / ll: lane sets per wave in architectural registers / accumulator
 // registers / LDS; waves: per row; small: the two-waves-per-SIMD flavour (a few KB of LDS per wave); lp: nonzeros of a further, partial LDS
-// set; tx: rows of the LDS image the gradient is accumulated from (lane_eval.hpp, TX_)
+// set; tx: rows of the LDS image the gradient is accumulated from (lane_eval.hpp, TX_); ku: the used width of a factor row where the instance
+// is specialised on it (lane_eval.hpp, KU_; lane_used_width below), 0 = all elements of its slots
 struct LaneShape {
-    int lv, la, ll, waves; int small; int lp = 0; int tx = 0;
+    int lv, la, ll, waves; int small; int lp = 0; int tx = 0; int ku = 0;
     bool operator==(const LaneShape& o) const
     {
-        return lv == o.lv && la == o.la && ll == o.ll && waves == o.waves && small == o.small && lp == o.lp && tx == o.tx;
+        return lv == o.lv && la == o.la && ll == o.ll && waves == o.waves && small == o.small && lp == o.lp && tx == o.tx && ku == o.ku;
     }
 };
 
@@ -241,6 +242,27 @@ inline LaneShape lane_shape_for(unsigned cls, int s_load, int method)
         if (cls <= 1536) return { 3, 0, 0, 8, 1 };
     }
     return { 0, 0, 0, 0, 0 };
+}
+
+// The used width (lane_eval.hpp, KU_) the instance of shape `ls` is specialised on for factors of k columns: the float PG instances of four
+// register sets at k = 50 -- the BASELINE configs' k, whose 13 slots end in two elements of padding -- carry 50 elements per factor row, not 52.
+// Every other k, solver and precision: 0, the instances that carry every element of their slots.  A function of k and the shape alone.
+// -DPMF_LANE_KU50=0 builds a library without them (the comparison build: same bits expected) -- as does every variant build
+// that switches off a path of the lane engine they are written for (lane_eval.hpp: the DPP butterfly, the coalesced gather, the scalar-operand
+// dots, the packed chains).
+#ifndef PMF_LANE_KU50
+#if (defined(PMF_LANE_XPOSE) && PMF_LANE_XPOSE != 2) || (defined(PMF_LANE_COAL) && PMF_LANE_COAL == 0) || (defined(PMF_LANE_SPOINT) && PMF_LANE_SPOINT == 0) || \
+    (defined(PMF_LANE_PK) && PMF_LANE_PK == 0) || (defined(PMF_LANE_PK_DOTS) && PMF_LANE_PK_DOTS == 0) || (defined(PMF_LANE_DIRECT) && PMF_LANE_DIRECT == 0)
+#define PMF_LANE_KU50 0
+#else
+#define PMF_LANE_KU50 1
+#endif
+#endif
+constexpr int LANE_KU_50 = 50;
+inline int lane_used_width(size_t k, int s_load, int method, const LaneShape& ls)
+{
+    if (PMF_LANE_KU50 && sizeof(real_t) == 4 && method == POISMF_PG && s_load == 13 && k == (size_t)LANE_KU_50 && ls.lv == 4 && ls.waves == 4) return LANE_KU_50;
+    return 0;
 }
 
 // Long-row path: rows above this many nonzeros get a whole workgroup of LONG_NW waves (row_eval.hpp, NW > 1).

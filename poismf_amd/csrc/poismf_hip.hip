@@ -26,6 +26,11 @@
 #endif
 constexpr bool tu_has(int kmethod) { return PMF_TU == -1 || PMF_TU == kmethod; }
 
+// An engine with `static constexpr bool COLD_CONSTANTS = true` has no register to spare for constants that are used once per row: solve_row
+// builds those where they are used (lane_eval.hpp: the instances with a used width).
+template <class EV, class = void> struct cold_constants : std::false_type {};
+template <class EV> struct cold_constants<EV, std::void_t<decltype(EV::COLD_CONSTANTS)>> : std::integral_constant<bool, EV::COLD_CONSTANTS> {};
+
 // Everything after the row's tile has been requested: starting point, per-row constant term, inner solver, store.
 template <class EV, class T, int NC, int METHOD>
 __device__ __forceinline__ void solve_row(const HalfArgs<T>& a, EV& ev, const T (&bs)[NC], unsigned lrow, unsigned nnz)
@@ -115,8 +120,12 @@ __device__ __forceinline__ void solve_row(const HalfArgs<T>& a, EV& ev, const T 
 #endif
     // the solver's decisions for this row (tests/test_gpu_decisions.py): { iterations | rc << 24, evaluations as the reference counts them }
     if (a.dec_rows != nullptr && ev.lane == 0 && ev.wid == 0 && ev.member == 0) {
-        a.dec_rows[2 * (size_t)lrow] = (unsigned)st.niter | ((unsigned)st.rc << 24);
-        a.dec_rows[2 * (size_t)lrow + 1] = (unsigned)st.nfeval;
+        unsigned d0 = (unsigned)st.niter | ((unsigned)st.rc << 24), d1 = (unsigned)st.nfeval;
+        // (PG decides nothing: two zeros, which as invariants of the row loop sit in a register pair for the whole kernel -- in the lane instance
+        // with a partial LDS set: in its last eight bytes of scratch.  Engines that say so get them built here, as the zeros at the top are.)
+        if constexpr (cold_constants<EV>::value) asm volatile("" : "+v"(d0), "+v"(d1));
+        a.dec_rows[2 * (size_t)lrow] = d0;
+        a.dec_rows[2 * (size_t)lrow + 1] = d1;
     }
 }
 
@@ -602,10 +611,11 @@ __global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(1))) v
 // (SMALL: one register set, 14 KB of LDS per wave) two.
 // (lane_two: instances compiled for two waves per SIMD -- the SMALL ones)
 template <bool SMALL> constexpr bool lane_two() { return SMALL; }
-template <class T, int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL, int LP = 0, int TX = 0>
+// (KU: the used width of a factor row where it is below the KS slots' elements, lane_eval.hpp KU_; 0 = all of them)
+template <class T, int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL, int LP = 0, int TX = 0, int KU = 0>
 __global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(lane_two<SMALL>() ? 2 : 1, lane_two<SMALL>() ? 2 : 1))) void half_sweep_lane_kernel(const HalfArgs<T> a)
 {
-    using EV = LaneEval<T, KS, LV, LA, LL, NW, SMALL, LP, TX>;
+    using EV = LaneEval<T, KS, LV, LA, LL, NW, SMALL, LP, TX, false, KU>;
     __shared__ __attribute__((aligned(16))) unsigned char smem[EV::SMEM_BYTES];
     EV ev;
     sweep_rows<EV, T, EV::NC, METHOD, NW>(a, ev, smem);
@@ -741,11 +751,11 @@ template <int M, int S> int launch_team(hipStream_t stream, int method, const Ha
 }
 
 // lane-per-nonzero launches
-template <int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL = false, int LP = 0, int TX = 0> int launch_lane(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
+template <int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL = false, int LP = 0, int TX = 0, int KU = 0> int launch_lane(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
 {
     if constexpr (tu_has(METHOD)) {
-        using EV = LaneEval<real_t, KS, LV, LA, LL, NW, SMALL, LP, TX>;
-        auto kern = half_sweep_lane_kernel<real_t, METHOD, KS, LV, LA, LL, NW, SMALL, LP, TX>;
+        using EV = LaneEval<real_t, KS, LV, LA, LL, NW, SMALL, LP, TX, false, KU>;
+        auto kern = half_sweep_lane_kernel<real_t, METHOD, KS, LV, LA, LL, NW, SMALL, LP, TX, KU>;
         // workgroups per CU: one (SMALL: two) waves per SIMD, and the LDS each takes
         const int occ = std::max(1, std::min((lane_two<SMALL>() ? 8 : 4) / NW, (int)(LDS_PER_CU / (size_t)EV::SMEM_BYTES)));
         const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
@@ -797,11 +807,19 @@ template <int METHOD> int launch_lane_shape(hipStream_t stream, int s_load, cons
     } else {
         if (s_load == 13) {
             if constexpr (METHOD == K_PG) {
-                switch (key) {
-                    case 40041: return launch_lane<METHOD, 13, 4, 0, 0, 4, true>(stream, a, grid_mult);
-                    case 140041: if (lp == 16) return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 16>(stream, a, grid_mult); break;
+                // (l.ku: the planner names the used width, lane_used_width -- 50 at k = 50, else 0 = every element of the 13 slots)
+                if (l.ku == LANE_KU_50) {
+                    if constexpr (PMF_LANE_KU50 != 0) switch (key) {
+                        case 40041: return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 0, 0, LANE_KU_50>(stream, a, grid_mult);
+                        case 140041: if (lp == 16) return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 16, 0, LANE_KU_50>(stream, a, grid_mult); break;
+                    }
+                } else if (l.ku == 0) {
+                    switch (key) {
+                        case 40041: return launch_lane<METHOD, 13, 4, 0, 0, 4, true>(stream, a, grid_mult);
+                        case 140041: if (lp == 16) return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 16>(stream, a, grid_mult); break;
+                    }
                 }
-            } else {
+            } else if (l.ku == 0) {
                 switch (key) {
                     case 10011: return launch_lane<METHOD, 13, 1, 0, 0, 1, true>(stream, a, grid_mult);
                     case 20011: return launch_lane<METHOD, 13, 2, 0, 0, 1, true>(stream, a, grid_mult);

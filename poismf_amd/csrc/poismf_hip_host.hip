@@ -666,6 +666,10 @@ const PlanKnobs& plan_knobs()
     return kn;
 }
 
+// poismf_hip_debug_lane_full_width (testing aid): != 0 -- the lane launches planned from now on carry every element of their slots, also where an
+// instance specialised on the used width exists (plan.hpp, lane_used_width): the two must agree bit for bit (tests/test_gpu_lane_width.py)
+std::atomic<int> g_lane_full_width{0};
+
 // Bytes of a factor row of k elements in the line-padded gather copies (== k * sizeof(real_t): the session keeps no such copy).
 size_t padded_row_bytes(size_t k)
 {
@@ -758,6 +762,7 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
         if (c.single_pass) { g.resident = 0; g.prefetch = prefetch_enabled() ? 1 : 0; }  // one pass: "gather once" and "stream" are the same thing
         if (lane_ok) {
             LaneShape ls = lane_shape_for(b.cls, g.s_load, pm);
+            if (ls.waves > 0 && g_lane_full_width.load(std::memory_order_relaxed) == 0) ls.ku = lane_used_width(c.k, g.s_load, pm, ls);
             // k = 100 fp64 rows above 64 nonzeros on the B half: rounds 3-4 left them to the streamed launch (with only the 65 .. 128-nonzero rows
             // taken out, that launch lost the short-row tail that kept its wave slots busy: B half 234.6 -> 296.0 ms); since round 5 every row up
             // to 384 nonzeros has a resident instance and the streamed launch keeps the 3 k rows above.
@@ -854,8 +859,14 @@ std::string launch_name(int method, const PlannedLaunch& L)
     return txt;
 }
 
-// ... and as poismf_hip_session_plan lists it
-std::string plan_item(int method, const PlannedLaunch& L) { return launch_name(method, L) + " rows=" + std::to_string(L.count) + ";"; }
+// ... and as poismf_hip_session_plan lists it (widths: a lane launch specialised on the used width says so behind its name, "...>[KU=50]" --
+// poismf_hip_debug_plan_widths; the names themselves are what they were before such instances existed)
+std::string plan_item(int method, const PlannedLaunch& L, bool widths = false)
+{
+    std::string name = launch_name(method, L);
+    if (widths && L.engine == Engine::Lane && L.lane.ku > 0) name += "[KU=" + std::to_string(L.lane.ku) + "]";
+    return name + " rows=" + std::to_string(L.count) + ";";
+}
 
 // The launches of one half-sweep call over segment `seg` of a half, or (seg < 0) over all of its segments, as the passes the call makes: one
 // per segment, each planned from that segment's bins alone and run as a call over that segment would run it.  So a row's launch -- its engine,
@@ -2316,8 +2327,8 @@ int poismf_hip_debug_row_eval(real_t* G, double* f, real_t* B, real_t* Bsum, rea
 // Testing aid: the planner without a device.  Rows of row_nnz[0 .. nrows) nonzeros, cut into nseg segments, sorted and binned as
 // finish_half_launch / finish_half_collect do it; then the plan of a half-sweep call over segment `seg` (< 0: over all of them), as
 // poismf_hip_session_plan words it.  No HIP call.
-size_t poismf_hip_debug_plan(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
-                             real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+static size_t debug_plan_impl(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                              real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap, bool widths)
 {
     std::string text;
     nseg = std::max(nseg, 1);
@@ -2331,10 +2342,24 @@ size_t poismf_hip_debug_plan(const unsigned* row_nnz, size_t nrows, int nseg, in
         }
         const PlanCtx c = plan_ctx(k, dimF, method, maxupd, w_mult, limit_step != 0, false, num_cu);
         for (const auto& pass : plan_call(segs, seg, c))
-            for (const PlannedLaunch& L : pass) text += plan_item(method, L);
+            for (const PlannedLaunch& L : pass) text += plan_item(method, L, widths);
     }
     return copy_text(text, buf, cap);
 }
+size_t poismf_hip_debug_plan(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                             real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+{
+    return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, false);
+}
+// The same plan, every lane launch that is specialised on the used width of its factor rows marked "[KU=<width>]" behind its name.
+size_t poismf_hip_debug_plan_widths(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                                    real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+{
+    return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, true);
+}
+// Testing aid: != 0 -- from now on this process plans its lane launches on the instances that carry every element of their slots (what a
+// -DPMF_LANE_KU50=0 build always does); 0 -- the default again.  Returns the previous setting.
+int poismf_hip_debug_lane_full_width(int full) { return g_lane_full_width.exchange(full != 0 ? 1 : 0); }
 // Testing aid: factors_multiple that also hands back every row's solver decisions (2 words per row, see
 // poismf_hip_session_decisions) -- how the golden single-row fixtures pin the device's iteration / evaluation counts.
 int poismf_hip_factors_multiple_decisions(real_t* A, real_t* B, real_t* Bsum, real_t* Amean, real_t* Xr, sparse_ix* Xr_indptr,
