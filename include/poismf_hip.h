@@ -238,6 +238,53 @@ POISMF_HIP_API int poismf_hip_rank_batch(const real_t *A, const real_t *B, int k
 POISMF_HIP_API size_t poismf_hip_rank_batch_scratch_bytes(size_t n_users, size_t n_cells, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1h. Batched top-N over per-user candidate lists: the best items of many users, each among a list of its own, in one fused
+ *     pass (the batched form of the reference's topN(..., include_ix), ref: src/topN.c:112-284, which serves one user per call).
+ *     Only the listed rows of B are read: the cost follows the lists' lengths, not dimB.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), n_top, and per user
+ *
+ *   I(u)         an include list: CSR-shaped host arrays incl_indptr [m + 1], incl_indices; row i belongs to u_i, indices are
+ *                < dimB and strictly ascending within a row.  Rows may be empty.
+ *   E(u)         an exclusion set exactly as in section 1f: exclude_seen on a session and / or the CSR-shaped host list
+ *                excl_indptr / excl_indices (excl_indptr = NULL: no list).
+ *   score(u, j)  section 1f's score,  s = +0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t: bit for bit what
+ *                predict_multiple / poismf_hip_session_predict and the batched top-N of section 1f return.
+ *   answer(u)    the first n_top of I(u) \ E(u) under section 1f's total order (score descending, then item index ascending).
+ *                It is a function of (A[u], B, I(u), E(u), n_top) alone: not of the other users, the batch order, how a list
+ *                is cut into slices or how the batch is cut into chunks.  Where |I(u) \ E(u)| >= n_top it therefore equals
+ *                section 1f's answer for the exclusion set E(u) united with {0..dimB-1} \ I(u).
+ *   short rows   are not an error: when only c < n_top items are admissible, entries c .. n_top-1 of the row are
+ *                POISMF_HIP_TOPN_NONE in out_ix (all bits of sparse_ix set) and -inf in out_score.  With exclude_seen the
+ *                admissible count is known on the device only, and candidate slates that lose items to "already seen" are
+ *                the normal case: no per-user pre-check as in section 1f is made.
+ *   output       out_ix [m x n_top] (row-major) and, unless NULL, out_score [m x n_top]; host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, when: a user index
+ * >= dimA; an item index >= dimB; an include or exclusion row not strictly ascending, or row pointers that decrease;
+ * incl_indptr == NULL; n_top == 0 or n_top > POISMF_HIP_TOPN_BATCH_MAX_N_TOP; k outside 1..512 float / 1..256 double;
+ * exclude_seen for a user outside the session's rows of A; an exclusion row over section 1f's limit; an include row longer than
+ * POISMF_HIP_TOPN_INCLUDE_MAX_ROW (the 32-bit indices a quarter of the scratch budget holds; a list near catalogue size belongs
+ * on the dense path of section 1f with its complement).  n_users == 0 is not an error (returns 0).  Factors are assumed finite.
+ *
+ * Memory: ONE scratch allocation per call (session: the one the calls of sections 1f and 1g share) of at most
+ * POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB, for any number of users and candidates; the batch is cut into chunks of users whose
+ * lists fit.  poismf_hip_topn_include_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate for a
+ * batch whose lists hold n_cells indices in all.  poismf_hip_topn_include_slice (testing aid, no HIP call) is the number of
+ * candidates per slice the host plan gives a list of `len` candidates: one wave scores one slice, a fixed minimum grown only so
+ * that no user has more slices than the merge step ranks at once.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_NONE (~(sparse_ix)0)             /* out_ix of an entry past a short row's last admissible item */
+#define POISMF_HIP_TOPN_INCLUDE_MAX_ROW 16777216         /* longest include row: 2^24 */
+POISMF_HIP_API int poismf_hip_topn_include(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_include_scratch_bytes(size_t n_users, size_t n_cells, size_t n_top, size_t dimB, size_t k);
+POISMF_HIP_API size_t poismf_hip_topn_include_slice(size_t len, size_t n_top);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -369,6 +416,12 @@ POISMF_HIP_API int poismf_hip_session_topn(poismf_hip_session *s, size_t user,
 /* Section 1f from the session-resident factors (and, with exclude_seen, the session's own CSR rows).  Ordered after the work already
  * enqueued on the session stream; reads the compact factors, as poismf_hip_session_llk does. */
 POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1h from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 

@@ -51,11 +51,14 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_debug_plan_widths", "poismf_hip_debug_lane_full_width",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
+    "poismf_hip_topn_include", "poismf_hip_session_topn_include", "poismf_hip_topn_include_scratch_bytes", "poismf_hip_topn_include_slice",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
 RANK_BATCH_MAX_ROW = 65536   # of include/poismf_hip.h section 1g (tests/test_rank_batch_cpu.py compares them with the header)
 RANK_BATCH_BUDGET_MB = 256
+TOPN_NONE = 2**64 - 1               # POISMF_HIP_TOPN_NONE and POISMF_HIP_TOPN_INCLUDE_MAX_ROW of include/poismf_hip.h section 1h
+TOPN_INCLUDE_MAX_ROW = 16777216     # (tests/test_topn_include_cpu.py compares them with the header)
 
 
 def load_library(use_float):
@@ -144,6 +147,14 @@ def load_library(use_float):
     lib.poismf_hip_session_rank_batch.restype = i
     lib.poismf_hip_rank_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_rank_batch_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_include.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_include.restype = i
+    lib.poismf_hip_session_topn_include.argtypes = [vp, vp, sz, sz, vp, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_include.restype = i
+    lib.poismf_hip_topn_include_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_topn_include_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
+    lib.poismf_hip_topn_include_slice.restype = sz
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -544,6 +555,26 @@ def _topn_batch_args(users, n, exclude, dimA, dimB):
     return users, indptr, indices
 
 
+def _topn_include_args(users, n, include, exclude, dimA, dimB):
+    """The argument checks of the batched top-N over include lists (include/poismf_hip.h section 1h) that need no device, as the
+    library itself makes them: n may exceed what a user has left (short rows are padded).  Returns (users, incl_indptr,
+    incl_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    ip, ii = _csr_list(include, m, dimB, "include", TOPN_INCLUDE_MAX_ROW, keep_zeros=True)
+    if exclude is None:
+        return users, ip, ii, None, None
+    ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, ip, ii, ep, ei
+
+
 def _opt_ptr(a):
     return _ptr(a) if a is not None and len(a) else None
 
@@ -561,15 +592,21 @@ def _outside_shard(users, shardA):
         raise ValueError("exclude_seen: a user lies outside this session's rows of A")
 
 
-def _topN_batch(self, users, n=10, exclude=None, output_score=False):
+def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=None):
     """The n best items of every user in `users` (rows of the fitted A) under "score descending, item index ascending", in one
     fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
     `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
     does not keep X) or an (indptr, indices) pair with strictly ascending rows.  Returns (items uint64 [m x n], scores [m x n],
-    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A."""
+    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A.
+    include: a candidate list per user, in the same two forms (a sparse matrix's stored columns): each user is ranked among its
+    own list only and only those rows of B are read (section 1h).  n may then exceed what a user has left: the row is padded
+    with TOPN_NONE and -inf."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
-    users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
+    if include is not None:
+        users, ip, ii, indptr, indices = _topn_include_args(users, n, include, exclude, self.nusers, self.nitems)
+    else:
+        users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
     dt = np.float32 if self.use_float else np.float64
     m, n = len(users), int(n)
     ix = np.empty((m, n), np.uint64)
@@ -579,6 +616,11 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False):
     A = np.ascontiguousarray(self.A, dtype=dt)
     B = np.ascontiguousarray(self.B, dtype=dt)
     lib = load_library(self.use_float)
+    if include is not None:
+        _batch_rc(lib.poismf_hip_topn_include(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii),
+                                              _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                              _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
     _batch_rc(lib.poismf_hip_topn_batch(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
                                         _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
                                         _ptr(ix), _ptr(sc) if output_score else None), "top-N")
@@ -920,19 +962,29 @@ class Session:
             raise MemoryError("poismf_hip_session_topn failed")
         return ix, sc
 
-    def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False):
+    def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False, include=None):
         """The top_n best items of every user in `users` from the resident factors, in one fused pass (include/poismf_hip.h section
         1f): "score descending, item index ascending", scores bit for bit those of predict().  exclude_seen leaves out the items of
         the user's row of the session's own CSR; exclude (a SciPy sparse matrix with one row per entry of `users`, or an
         (indptr, indices) pair with strictly ascending rows) leaves out more.  Returns (items uint64 [m x top_n], scores [m x top_n],
-        empty unless output_score)."""
-        users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
+        empty unless output_score).  include (same two forms) gives every user a candidate list of its own: it is ranked among
+        that list only, and only those rows of B are read (section 1h); top_n may then exceed what a user has left, and the row
+        is padded with TOPN_NONE and -inf."""
+        if include is not None:
+            users, ip, ii, indptr, indices = _topn_include_args(users, top_n, include, exclude, self.dimA, self.dimB)
+        else:
+            users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
         m, n = len(users), int(top_n)
         if exclude_seen:
             _outside_shard(users, self.shardA)
         ix = np.empty((m, n), np.uint64)
         sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
         if m == 0:
+            return ix, sc
+        if include is not None:
+            _batch_rc(self.lib.poismf_hip_session_topn_include(self.h, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii), int(bool(exclude_seen)),
+                                                               _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                                               _ptr(ix), _ptr(sc) if output_score else None), "top-N")
             return ix, sc
         _batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
                                                          _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),

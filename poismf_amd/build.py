@@ -2,10 +2,10 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Ten translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
+Eleven translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
 PG, CG and TNCG are the bulk of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the
-rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip) and the
-batched ranks (rank_batch.hip; the pair shares tb_tile.hpp and tb_batch.hpp) -- are compiled to object files side by
+rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip), the
+batched ranks (rank_batch.hip) and the batched top-N over include lists (topn_include.hip; the three share tb_tile.hpp and tb_batch.hpp) -- are compiled to object files side by
 side and linked.  Every object and library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
 digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full
 build takes ~2 minutes on 8 cores.
@@ -34,6 +34,7 @@ UNITS = {
     "llk": (["llk.hip", "devmem.hpp", "wave_ops.hpp"], []),
     "topn_batch": (["topn_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
     "rank_batch": (["rank_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
+    "topn_include": (["topn_include.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
 }
 
 
@@ -89,7 +90,8 @@ def _units():
     """The -DPMF_TIMING development build keeps its phase timers in one device-side array, so it stays one translation unit."""
     if "-DPMF_TIMING" in os.environ.get("POISMF_HIP_EXTRA_FLAGS", "").split():
         return {"poismf_hip_host": UNITS["poismf_hip_host"], "poismf_hip_all": (_ROW, []), "coo_convert": UNITS["coo_convert"],
-                "serve": UNITS["serve"], "llk": UNITS["llk"], "topn_batch": UNITS["topn_batch"], "rank_batch": UNITS["rank_batch"]}
+                "serve": UNITS["serve"], "llk": UNITS["llk"], "topn_batch": UNITS["topn_batch"], "rank_batch": UNITS["rank_batch"],
+                "topn_include": UNITS["topn_include"]}
     return UNITS
 
 

@@ -42,11 +42,23 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
                               PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
                               size_t* scratch_cap, unsigned int* out_rank, unsigned int* out_n_adm);
 
+// (topn_include.hip; section 1h) the same pair for the top-N over include lists: the check makes no device call, the core returns 0 or 1
+int poismf_hip_topn_include_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                  const sparse_ix* incl_indptr, const sparse_ix* incl_indices, const sparse_ix* excl_indptr,
+                                  const sparse_ix* excl_indices);
+int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* incl_indptr,
+                                const sparse_ix* incl_indices, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                                const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
+
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 namespace {
 
 constexpr size_t TB_K_MAX = sizeof(real_t) == 4 ? 512 : 256;   // what a session supports
+constexpr size_t TB_CHUNK_USERS_MAX = 262144;
+constexpr size_t TB_N_TOP_MAX = POISMF_HIP_TOPN_BATCH_MAX_N_TOP;
+constexpr size_t TB_BUDGET = (size_t)POISMF_HIP_TOPN_BATCH_BUDGET_MB << 20;
 
 // the parts of a scratch layout, one after the other: take(bytes) is where the next part starts; `o` ends as the total
 struct TbTake {

@@ -174,4 +174,76 @@ __device__ __forceinline__ bool tb_excluded(const TbExcl& x, unsigned i, unsigne
     return false;
 }
 
+// ---- candidate lists in LDS: pruning and merging by rank counting under the total order (the batched top-N, dense and by include list) ----
+constexpr int TB_PRUNE_Q = 3;                             // list entries per lane in a prune: lists hold <= 192 entries
+constexpr size_t TB_MERGE_MAX = 2048;                     // entries of one user's partial lists the merge kernel ranks in LDS
+
+__device__ __forceinline__ void tb_wave_sync()
+{
+    // LDS operations of one wave complete in order; this keeps the compiler from moving them across the point
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Rank-counts list `u` (c entries, c <= cap) under the total order, keeps the best min(c, n_top) in order and, when the list is full,
+// sets the user's threshold to its last entry.  Called by a whole wave with uniform arguments.
+__device__ __forceinline__ void tb_prune(real_t* ls, unsigned* li, unsigned c, unsigned n_top, unsigned* cnt_u, real_t* thr_s_u, unsigned* thr_j_u)
+{
+    const unsigned lane = threadIdx.x & 63;
+    real_t es[TB_PRUNE_Q];
+    unsigned ej[TB_PRUNE_Q], rk[TB_PRUNE_Q];
+#pragma unroll
+    for (int q = 0; q < TB_PRUNE_Q; q++) {
+        const unsigned e = lane + 64u * q;
+        es[q] = e < c ? ls[e] : (real_t)0;
+        ej[q] = e < c ? li[e] : TB_NONE;
+        rk[q] = 0;
+    }
+    for (unsigned i = 0; i < c; i++) {
+        const real_t si = ls[i];
+        const unsigned ji = li[i];
+#pragma unroll
+        for (int q = 0; q < TB_PRUNE_Q; q++) rk[q] += tb_better(si, ji, es[q], ej[q]) ? 1u : 0u;
+    }
+    tb_wave_sync();
+#pragma unroll
+    for (int q = 0; q < TB_PRUNE_Q; q++) {
+        const unsigned e = lane + 64u * q;
+        if (e < c && rk[q] < n_top) {
+            ls[rk[q]] = es[q];
+            li[rk[q]] = ej[q];
+            if (rk[q] == n_top - 1) { *thr_s_u = es[q]; *thr_j_u = ej[q]; }
+        }
+    }
+    if (lane == 0) *cnt_u = c < n_top ? c : n_top;
+    tb_wave_sync();
+}
+
+// One wave: the best n_top of nslices sorted partial lists of n_top entries each (part_*: the first of them), by rank counting under the
+// total order, to out_*[0 .. n_top); ranks no real entry reaches are left as they were.  ms / mj: TB_MERGE_MAX entries of LDS.
+__device__ __forceinline__ void tb_merge_lists(real_t* ms, unsigned* mj, const real_t* part_score, const unsigned* part_ix, unsigned nslices,
+                                               unsigned n_top, real_t* out_score, unsigned* out_ix)
+{
+    const unsigned lane = threadIdx.x;
+    const unsigned m = nslices * n_top;
+    for (unsigned i = lane; i < m; i += 64) { ms[i] = part_score[i]; mj[i] = part_ix[i]; }
+    __syncthreads();
+    for (unsigned e = lane; e < m; e += 64) {
+        const real_t s = ms[e];
+        const unsigned j = mj[e];
+        if (j == TB_NONE) continue;
+        // entries after e in its own (sorted) list are worse; empty entries (-inf, TB_NONE) are worse than every real one
+        unsigned rk = e % n_top;
+        const unsigned own = e / n_top;
+        for (unsigned sl = 0; sl < nslices && rk < n_top; sl++) {
+            if (sl == own) continue;
+            for (unsigned i = sl * n_top; i < (sl + 1) * n_top; i++) {
+                if (!tb_better(ms[i], mj[i], s, j)) break;   // (sorted: nothing further in this list is better either)
+                rk++;
+            }
+        }
+        if (rk < n_top) { out_score[rk] = s; out_ix[rk] = j; }
+    }
+}
+
 }  // namespace

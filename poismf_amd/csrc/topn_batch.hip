@@ -40,13 +40,8 @@
 namespace {
 
 constexpr int TB_ROOM = 16;                               // free slots a list must have before a pass over 16 item columns
-constexpr int TB_PRUNE_Q = 3;                             // list entries per lane in a prune: lists hold <= 192 entries
 constexpr size_t TB_LDS_LIMIT = 156 * 1024;
 constexpr size_t TB_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many
-constexpr size_t TB_MERGE_MAX = 2048;                     // entries of one user's partial lists the merge kernel ranks in LDS
-constexpr size_t TB_CHUNK_USERS_MAX = 262144;
-constexpr size_t TB_N_TOP_MAX = POISMF_HIP_TOPN_BATCH_MAX_N_TOP;
-constexpr size_t TB_BUDGET = (size_t)POISMF_HIP_TOPN_BATCH_BUDGET_MB << 20;
 static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
 static_assert(TB_N_TOP_MAX >= 128, "the header promises at least 128");
 
@@ -62,47 +57,6 @@ struct TbArgs {
     real_t* part_score;               // [n_users][nslices][n_top]
     unsigned* part_ix;
 };
-
-__device__ __forceinline__ void tb_wave_sync()
-{
-    // LDS operations of one wave complete in order; this keeps the compiler from moving them across the point
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Rank-counts list `u` (c entries, c <= cap) under the total order, keeps the best min(c, n_top) in order and, when the list is full,
-// sets the user's threshold to its last entry.  Called by a whole wave with uniform arguments.
-__device__ __forceinline__ void tb_prune(real_t* ls, unsigned* li, unsigned c, unsigned n_top, unsigned* cnt_u, real_t* thr_s_u, unsigned* thr_j_u)
-{
-    const unsigned lane = threadIdx.x & 63;
-    real_t es[TB_PRUNE_Q];
-    unsigned ej[TB_PRUNE_Q], rk[TB_PRUNE_Q];
-#pragma unroll
-    for (int q = 0; q < TB_PRUNE_Q; q++) {
-        const unsigned e = lane + 64u * q;
-        es[q] = e < c ? ls[e] : (real_t)0;
-        ej[q] = e < c ? li[e] : TB_NONE;
-        rk[q] = 0;
-    }
-    for (unsigned i = 0; i < c; i++) {
-        const real_t si = ls[i];
-        const unsigned ji = li[i];
-#pragma unroll
-        for (int q = 0; q < TB_PRUNE_Q; q++) rk[q] += tb_better(si, ji, es[q], ej[q]) ? 1u : 0u;
-    }
-    tb_wave_sync();
-#pragma unroll
-    for (int q = 0; q < TB_PRUNE_Q; q++) {
-        const unsigned e = lane + 64u * q;
-        if (e < c && rk[q] < n_top) {
-            ls[rk[q]] = es[q];
-            li[rk[q]] = ej[q];
-            if (rk[q] == n_top - 1) { *thr_s_u = es[q]; *thr_j_u = ej[q]; }
-        }
-    }
-    if (lane == 0) *cnt_u = c < n_top ? c : n_top;
-    tb_wave_sync();
-}
 
 template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile_kernel(TbArgs a)
 {
@@ -195,33 +149,15 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     }
 }
 
-// One wave per user: the best n_top of its nslices sorted partial lists, by rank counting under the total order.
+// One wave per user: the best n_top of its nslices sorted partial lists, [user][nslices][n_top].
 __global__ __launch_bounds__(64) void topn_merge_kernel(const real_t* part_score, const unsigned* part_ix, unsigned n_users, unsigned nslices,
                                                         unsigned n_top, real_t* out_score, unsigned* out_ix)
 {
     __shared__ real_t ms[TB_MERGE_MAX];
     __shared__ unsigned mj[TB_MERGE_MAX];
-    const unsigned u = blockIdx.x, lane = threadIdx.x;
-    const unsigned m = nslices * n_top;
-    const size_t o = (size_t)u * m;
-    for (unsigned i = lane; i < m; i += 64) { ms[i] = part_score[o + i]; mj[i] = part_ix[o + i]; }
-    __syncthreads();
-    for (unsigned e = lane; e < m; e += 64) {
-        const real_t s = ms[e];
-        const unsigned j = mj[e];
-        if (j == TB_NONE) continue;
-        // entries after e in its own (sorted) list are worse; empty entries (-inf, TB_NONE) are worse than every real one
-        unsigned rk = e % n_top;
-        const unsigned own = e / n_top;
-        for (unsigned sl = 0; sl < nslices && rk < n_top; sl++) {
-            if (sl == own) continue;
-            for (unsigned i = sl * n_top; i < (sl + 1) * n_top; i++) {
-                if (!tb_better(ms[i], mj[i], s, j)) break;   // (sorted: nothing further in this list is better either)
-                rk++;
-            }
-        }
-        if (rk < n_top) { out_score[(size_t)u * n_top + rk] = s; out_ix[(size_t)u * n_top + rk] = j; }
-    }
+    const unsigned u = blockIdx.x;
+    const size_t o = (size_t)u * nslices * n_top;
+    tb_merge_lists(ms, mj, part_score + o, part_ix + o, nslices, n_top, out_score + (size_t)u * n_top, out_ix + (size_t)u * n_top);
 }
 
 // exclude_seen needs to know whether the resident rows may be binary-searched: flag[0] = 1 when some row is not strictly ascending
