@@ -2,40 +2,58 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Eleven translation units per precision -- the host side (poismf_hip_host.hip), one per inner solver (the row kernels of
-PG, CG and TNCG are the bulk of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the
-rocPRIM-based COO conversion, the serving kernels, the likelihood (llk.hip), the batched top-N (topn_batch.hip), the
-batched ranks (rank_batch.hip) and the batched top-N over include lists (topn_include.hip; the three share tb_tile.hpp and tb_batch.hpp) -- are compiled to object files side by
-side and linked.  Every object and library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
-digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full
-build takes ~2 minutes on 8 cores.
+Fifteen translation units per precision -- the host side in five (session.hip the session object, planner.hip the planner,
+half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver;
+they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
+of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
+the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip) and
+the batched top-N over include lists (topn_include.hip; the three share tb_tile.hpp and tb_batch.hpp) -- are compiled to object files
+side by side and linked.  What an object depends on is derived from its file's #include "..." lines (_deps), never listed by hand.
+Every object and library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
+digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full build takes ~11.5 minutes on 8 cores
+(692 s and 717 s; 690 s before the host side was split into five units); after an edit of drivers.hip alone ~50 s (52 s; 57 s for the one host
+file before), most of it the three links and the ISA guard.
 """
 import fcntl
 import hashlib
 import os
+import re
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "poismf_hip.h")
-_ROW = ["poismf_hip.hip", "plan.hpp", "devmem.hpp", "solvers.hpp", "row_eval.hpp", "reg_eval.hpp", "lane_eval.hpp", "wave_ops.hpp"]
-_HOST = ["poismf_hip_host.hip", "plan.hpp", "devmem.hpp", "row_eval.hpp", "wave_ops.hpp", "tb_batch.hpp", "tb_tile.hpp"]
-# unit -> (source files, first is the one compiled; extra flags).  poismf_hip.hip is compiled four times: one
-# translation unit per inner solver (its row kernels are the bulk of the compile time); the host side is its own file.
+# unit -> (the file compiled, extra flags).  poismf_hip.hip is compiled four times: one translation unit per inner solver
+# (its row kernels are the bulk of the compile time); the host side is five files around session.hpp.
 UNITS = {
-    "poismf_hip_host": (_HOST, []),
-    "poismf_hip_tncg": (_ROW, ["-DPMF_TU=1"]),
-    "poismf_hip_cg": (_ROW, ["-DPMF_TU=2"]),
-    "poismf_hip_pg": (_ROW, ["-DPMF_TU=3"]),
-    "poismf_hip_eval": (_ROW, ["-DPMF_TU=4"]),   # evaluation-only kernels behind poismf_hip_debug_row_eval (testing aid)
-    "coo_convert": (["coo_convert.hip", "devmem.hpp"], []),
-    "serve": (["serve.hip", "devmem.hpp"], []),
-    "llk": (["llk.hip", "devmem.hpp", "wave_ops.hpp"], []),
-    "topn_batch": (["topn_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
-    "rank_batch": (["rank_batch.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
-    "topn_include": (["topn_include.hip", "tb_batch.hpp", "tb_tile.hpp", "devmem.hpp"], []),
+    "session": ("session.hip", []),
+    "planner": ("planner.hip", []),
+    "half_sweep": ("half_sweep.hip", []),
+    "drivers": ("drivers.hip", []),
+    "multi_device": ("multi_device.hip", []),
+    "poismf_hip_tncg": ("poismf_hip.hip", ["-DPMF_TU=1"]),
+    "poismf_hip_cg": ("poismf_hip.hip", ["-DPMF_TU=2"]),
+    "poismf_hip_pg": ("poismf_hip.hip", ["-DPMF_TU=3"]),
+    "poismf_hip_eval": ("poismf_hip.hip", ["-DPMF_TU=4"]),   # evaluation-only kernels behind poismf_hip_debug_row_eval (testing aid)
+    "coo_convert": ("coo_convert.hip", []),
+    "serve": ("serve.hip", []),
+    "llk": ("llk.hip", []),
+    "topn_batch": ("topn_batch.hip", []),
+    "rank_batch": ("rank_batch.hip", []),
+    "topn_include": ("topn_include.hip", []),
 }
+_INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"/]+)"', re.M)   # (the includes inside csrc/ are flat quoted names)
+
+
+def _deps(source):
+    """What an object compiled from csrc/`source` is built from: the file and, transitively, every csrc/ header it includes by
+    quoted name (the first is the one compiled).  Derived, so that no header can be forgotten and leave a stale object."""
+    seen = [source]
+    for name in seen:
+        with open(os.path.join(CSRC, name)) as fh:
+            seen += [inc for inc in dict.fromkeys(_INCLUDE.findall(fh.read())) if inc not in seen and os.path.exists(os.path.join(CSRC, inc))]
+    return seen
 
 
 # flavour -> flags: the reference builds its core twice for Python (ref: setup.py:225-243) and once for R with int indices
@@ -89,9 +107,7 @@ STAMP = os.path.join(HERE, ".build_stamp")   # hash of the sources + flags the i
 def _units():
     """The -DPMF_TIMING development build keeps its phase timers in one device-side array, so it stays one translation unit."""
     if "-DPMF_TIMING" in os.environ.get("POISMF_HIP_EXTRA_FLAGS", "").split():
-        return {"poismf_hip_host": UNITS["poismf_hip_host"], "poismf_hip_all": (_ROW, []), "coo_convert": UNITS["coo_convert"],
-                "serve": UNITS["serve"], "llk": UNITS["llk"], "topn_batch": UNITS["topn_batch"], "rank_batch": UNITS["rank_batch"],
-                "topn_include": UNITS["topn_include"]}
+        return {**{u: v for u, v in UNITS.items() if "-DPMF_TU=" not in " ".join(v[1])}, "poismf_hip_all": ("poismf_hip.hip", [])}
     return UNITS
 
 
@@ -102,7 +118,7 @@ def _flags():
 
 
 def _source_hash():
-    names = sorted({f for files, _ in _units().values() for f in files})
+    names = sorted({f for source, _ in _units().values() for f in _deps(source)})
     return _digest([_flags(), sorted((u, f) for u, (_, f) in _units().items())], [os.path.join(CSRC, f) for f in names] + [HEADER])
 
 
@@ -140,12 +156,12 @@ def _build_locked(force, verbose):
     compiles = []
     digests = {}
     for flavour, fl_flags in FLAVOURS.items():
-        for unit, (files, unit_flags) in _units().items():
-            deps = [os.path.join(CSRC, f) for f in files] + [HEADER]
+        for unit, (source, unit_flags) in _units().items():
+            deps = [os.path.join(CSRC, f) for f in _deps(source)] + [HEADER]
             obj = _obj_path(unit, flavour)
             if obj in digests:
                 continue   # the R flavour's row kernels are the double flavour's objects
-            cmd = [hipcc] + fl_flags + flags + unit_flags + ["-c", os.path.join(CSRC, files[0]), "-o", obj]
+            cmd = [hipcc] + fl_flags + flags + unit_flags + ["-c", os.path.join(CSRC, source), "-o", obj]
             digests[obj] = _digest(cmd, deps)
             if force or not _fresh(obj, digests[obj]):
                 if verbose:

@@ -33,11 +33,7 @@
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
 #include "wave_ops.hpp"
-
-// coo_convert.hip
-int poismf_hip_device_coo_to_cs(const unsigned* d_major, const unsigned* d_minor, const real_t* d_val, size_t n, size_t major_begin,
-                                size_t major_end, unsigned* out_minor, real_t* out_val, unsigned long long* out_indptr,
-                                size_t* nnz_out, hipStream_t stream);
+#include "cores.hpp"
 
 namespace {
 

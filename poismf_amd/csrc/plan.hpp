@@ -1,4 +1,4 @@
-// plan.hpp -- what the host side (poismf_hip_host.hip) and the row-kernel translation units (poismf_hip.hip, compiled once
+// plan.hpp -- what the host side (session.hpp and the units that include it) and the row-kernel translation units (poismf_hip.hip, compiled once
 // per inner solver) share: the kernel argument block, the description of one planned launch, and the constants / small
 // functions that decide which engine and which instance a row-length bin takes.
 #pragma once
@@ -279,7 +279,7 @@ int slots_per_lane(size_t k)
 
 }  // namespace
 
-// The kernel family of a launch.  The planner (poismf_hip_host.hip, plan_half) picks one per row bin; launch_one_here dispatches on it
+// The kernel family of a launch.  The planner (planner.hip, plan_half) picks one per row bin; launch_one_here dispatches on it
 // first, then on the solver and the instance.
 enum class Engine {
     Reg,        // half_sweep_reg_kernel: one wave per row, the tile in registers (reg_eval.hpp)
@@ -310,3 +310,5 @@ int pmf_launch_one_tu1(int method, const OneLaunch& o, const HalfArgs<real_t>& a
 int pmf_launch_one_tu2(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu3(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu4(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
+// -DPMF_TIMING development builds: read and reset the phase timers (they live in the row-kernel translation unit)
+int pmf_read_timing(unsigned long long* out);

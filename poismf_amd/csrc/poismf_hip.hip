@@ -1,7 +1,7 @@
 // poismf_hip.hip -- the row kernels of the MI355X implementation of poismf's alternating factor-update path and their
 // launchers.  Compiled once per inner solver and precision (-DPMF_TU=1 tncg / 2 cg / 3 pg / 4 the evaluation-only kernels of poismf_hip_debug_row_eval; without it all three, the
 // -DPMF_TIMING development build) into libpoismf_hip_d.so / libpoismf_hip_f.so (-DUSE_FLOAT); the host side
-// (sessions, run_poismf, planning) is poismf_hip_host.hip, the C-ABI is declared in include/poismf_hip.h.
+// (sessions, planning, issuing a half-sweep, run_poismf) is session.hip, planner.hip, half_sweep.hip, drivers.hip and multi_device.hip; the C-ABI is declared in include/poismf_hip.h.
 //
 // Device: one launch per (half-sweep, row bin); one wavefront per row, or 2 / 4 / 8 for longer rows
 // (reg_eval.hpp, row_eval.hpp, solvers.hpp).

@@ -20,6 +20,7 @@
 
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
+#include "cores.hpp"
 
 namespace {
 

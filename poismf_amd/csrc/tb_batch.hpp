@@ -1,5 +1,5 @@
 // tb_batch.hpp -- the host side the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip) have in common, and what the
-// session (poismf_hip_host.hip) hands to the two cores
+// session (session.hip) hands to the two cores
 #pragma once
 #include <cstddef>
 #include <cstring>

@@ -1,6 +1,6 @@
 """bench.py's multi-GPU planning on CPU: the per-rank row ranges tile the matrix, are identical on every rank (they are
 computed from the seeded triplets alone), balance the nonzeros, and the segments the sharded driver exchanges tile each
-rank's range exactly as the C session cuts them (poismf_hip_host.hip, finish_half)."""
+rank's range exactly as the C session cuts them (session.hip, finish_half)."""
 import importlib.util
 import os
 

@@ -1,4 +1,4 @@
-"""Several devices behind run_poismf() itself (poismf_hip_host.hip, run_poismf_multi): POISMF_HIP_DEVICES lists them, the rows of A
+"""Several devices behind run_poismf() itself (multi_device.hip, run_poismf_multi): POISMF_HIP_DEVICES lists them, the rows of A
 and of B are cut into one nnz-balanced range per entry, every entry gets a session with its shard and replicas of both factors,
 and after each half the updated rows travel device to device.  One GPU is what a test box has, so the list names it twice or
 three times: every line of the path runs (shards, host threads, peer copies, events, re-padding, the summed early-stop counter);
