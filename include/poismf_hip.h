@@ -285,6 +285,56 @@ POISMF_HIP_API size_t poismf_hip_topn_include_scratch_bytes(size_t n_users, size
 POISMF_HIP_API size_t poismf_hip_topn_include_slice(size_t len, size_t n_top);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1i. Batched top-N over candidate lists SHARED between users: a few lists (the items in stock in a region, a category page,
+ *     a campaign slate), each referred to by many users, in one fused pass.  Section 1h serves a list per user: the host reads
+ *     every user's copy of its list and every user gathers its own rows of B.  Here the host reads each list once, and on the
+ *     device 64 users that refer to one list share every row of B they gather (the f32-MFMA tile of section 1f).  Use 1h when
+ *     the lists really differ from user to user -- a batch in which every user has a list of its own is valid here but
+ *     degenerates to one user per tile, and the library does not re-route -- and this section when few lists serve many users.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), n_top, and
+ *
+ *   L_0..L_{G-1} a table of candidate lists: CSR-shaped host arrays list_indptr [G + 1], list_indices; indices are < dimB and
+ *                strictly ascending within a row.  Rows may be empty.  A list no user refers to is valid and costs nothing on
+ *                the device.
+ *   list_of [m]  the list of user u_i, values < G.
+ *   E(u)         an exclusion set exactly as in section 1f: exclude_seen on a session and / or the CSR-shaped host list
+ *                excl_indptr / excl_indices with one row per entry of `users` (excl_indptr = NULL: no list).
+ *   score(u, j)  section 1f's score,  s = +0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t: bit for bit what
+ *                predict_multiple / poismf_hip_session_predict return.
+ *   answer(u)    the first n_top of L_{list_of(u)} \ E(u) under section 1f's total order (score descending, then item index
+ *                ascending).  It is a function of (A[u], B, L_{list_of(u)}, E(u), n_top) alone: not of the other users, how
+ *                users are grouped into tiles, the order of the batch or of the list table, how a list is cut into slices or
+ *                how the batch is cut into chunks.  It therefore equals section 1h's answer with I(u) = L_{list_of(u)}, bit
+ *                for bit in items and scores.
+ *   short rows   are not an error: a row with fewer than n_top admissible items is padded as in section 1h with
+ *                POISMF_HIP_TOPN_NONE and -inf.  No per-user pre-check is made.
+ *   output       out_ix [m x n_top] (row-major) and, unless NULL, out_score [m x n_top]; host arrays, in the caller's order.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, when: a user index
+ * >= dimA; an item index >= dimB; a list or exclusion row not strictly ascending, or row pointers that decrease;
+ * list_indptr == NULL or list_of == NULL; n_lists == 0 with n_users > 0; an entry of list_of >= n_lists; n_top == 0 or
+ * n_top > POISMF_HIP_TOPN_BATCH_MAX_N_TOP; k outside 1..512 float / 1..256 double; exclude_seen for a user outside the
+ * session's rows of A; an exclusion row over section 1f's limit; a list table whose rows hold more than
+ * POISMF_HIP_TOPN_SHARED_MAX_CELLS indices in all (the 32-bit indices a quarter of the scratch budget holds: the table is
+ * uploaded once per call and stays beside every chunk's other parts).  n_users == 0 is not an error (returns 0).  Factors are
+ * assumed finite.
+ *
+ * Memory: ONE scratch allocation per call (session: the one the calls of sections 1f - 1h share) of at most
+ * POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB, for any number of users, lists and cells; the batch is cut into chunks of consecutive
+ * users.  poismf_hip_topn_shared_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate for a table
+ * of n_lists lists that hold n_cells indices in all.  Host work is proportional to n_cells + n_users (+ the exclusion lists).
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_SHARED_MAX_CELLS 16777216        /* most indices of a list table, all rows together: 2^24 */
+POISMF_HIP_API int poismf_hip_topn_shared(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *list_indptr, const sparse_ix *list_indices, size_t n_lists, const sparse_ix *list_of,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_shared_scratch_bytes(size_t n_users, size_t n_lists, size_t n_cells, size_t n_top,
+        size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -422,6 +472,12 @@ POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sp
 /* Section 1h from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
         const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1i from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *list_indptr, const sparse_ix *list_indices, size_t n_lists, const sparse_ix *list_of,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 

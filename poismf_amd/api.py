@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
     "poismf_hip_topn_include", "poismf_hip_session_topn_include", "poismf_hip_topn_include_scratch_bytes", "poismf_hip_topn_include_slice",
+    "poismf_hip_topn_shared", "poismf_hip_session_topn_shared", "poismf_hip_topn_shared_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -59,6 +60,7 @@ RANK_BATCH_MAX_ROW = 65536   # of include/poismf_hip.h section 1g (tests/test_ra
 RANK_BATCH_BUDGET_MB = 256
 TOPN_NONE = 2**64 - 1               # POISMF_HIP_TOPN_NONE and POISMF_HIP_TOPN_INCLUDE_MAX_ROW of include/poismf_hip.h section 1h
 TOPN_INCLUDE_MAX_ROW = 16777216     # (tests/test_topn_include_cpu.py compares them with the header)
+TOPN_SHARED_MAX_CELLS = 2**24       # POISMF_HIP_TOPN_SHARED_MAX_CELLS of section 1i (tests/test_topn_shared_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -155,6 +157,12 @@ def load_library(use_float):
     lib.poismf_hip_topn_include_scratch_bytes.restype = sz
     lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
     lib.poismf_hip_topn_include_slice.restype = sz
+    lib.poismf_hip_topn_shared.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_shared.restype = i
+    lib.poismf_hip_session_topn_shared.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_shared.restype = i
+    lib.poismf_hip_topn_shared_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, sz]
+    lib.poismf_hip_topn_shared_scratch_bytes.restype = sz
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -575,6 +583,53 @@ def _topn_include_args(users, n, include, exclude, dimA, dimB):
     return users, ip, ii, ep, ei
 
 
+def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
+    """The argument checks of the batched top-N over lists shared between users (include/poismf_hip.h section 1i) that need no
+    device, as the library itself makes them: `include` is the table of lists (any number of rows G >= 1), include_of names every
+    user's row of it (an integer array with one entry per user, or one int for all).  Returns (users, list_indptr, list_indices,
+    list_of, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if include is None:
+        raise ValueError("include_of needs include, the table of lists it refers to")
+    if isinstance(include, (tuple, list)) and len(include) == 2 and not hasattr(include, "tocsr"):
+        G = max(len(np.asarray(include[0]).reshape(-1)) - 1, 0)
+    elif hasattr(include, "shape") and len(include.shape) == 2:
+        G = int(include.shape[0])
+    else:
+        raise ValueError("include must be a SciPy sparse matrix or an (indptr, indices) pair")
+    if G < 1:
+        raise ValueError("include: the table of lists has no rows")
+    lp, li = _csr_list(include, G, dimB, "include", keep_zeros=True)
+    if len(li) > TOPN_SHARED_MAX_CELLS:
+        raise ValueError(f"include: the table of lists holds more than {TOPN_SHARED_MAX_CELLS} indices")
+    if isinstance(include_of, (bool, np.bool_)):
+        raise ValueError("include_of must be integers")
+    if isinstance(include_of, (int, np.integer)):
+        if include_of < 0:
+            raise ValueError("include_of: negative index")
+        lof = np.full(m, int(include_of), np.uint64)
+    else:
+        if np.ndim(include_of) != 1:
+            raise ValueError("include_of must be a 1-d array with one entry per user, or one int")
+        lof = _index_array(include_of, "include_of")
+    if len(lof) != m:
+        raise ValueError(f"include_of has {len(lof)} entries for {m} users")
+    if m and int(lof.max()) >= G:
+        raise ValueError(f"an entry of include_of is not a row of include ({G} lists)")
+    if exclude is None:
+        return users, lp, li, lof, None, None
+    ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, lp, li, lof, ep, ei
+
+
 def _opt_ptr(a):
     return _ptr(a) if a is not None and len(a) else None
 
@@ -592,7 +647,7 @@ def _outside_shard(users, shardA):
         raise ValueError("exclude_seen: a user lies outside this session's rows of A")
 
 
-def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=None):
+def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=None, include_of=None):
     """The n best items of every user in `users` (rows of the fitted A) under "score descending, item index ascending", in one
     fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
     `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
@@ -600,10 +655,16 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
     empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A.
     include: a candidate list per user, in the same two forms (a sparse matrix's stored columns): each user is ranked among its
     own list only and only those rows of B are read (section 1h).  n may then exceed what a user has left: the row is padded
-    with TOPN_NONE and -inf."""
+    with TOPN_NONE and -inf.
+    include_of: with it, `include` is a TABLE of lists shared between users (any number of rows G >= 1) and include_of names each
+    user's row of it: an integer array with one entry per user, or one int for all (section 1i).  The answers are those of
+    include= with every user's list written out, bit for bit; the table is read once, and users of one list share the rows of B
+    they read.  Few lists for many users belong here, a list per user belongs in include= alone."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
-    if include is not None:
+    if include_of is not None:
+        users, lp, li, lof, indptr, indices = _topn_shared_args(users, n, include, include_of, exclude, self.nusers, self.nitems)
+    elif include is not None:
         users, ip, ii, indptr, indices = _topn_include_args(users, n, include, exclude, self.nusers, self.nitems)
     else:
         users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
@@ -616,6 +677,11 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
     A = np.ascontiguousarray(self.A, dtype=dt)
     B = np.ascontiguousarray(self.B, dtype=dt)
     lib = load_library(self.use_float)
+    if include_of is not None:
+        _batch_rc(lib.poismf_hip_topn_shared(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(lp), _opt_ptr(li),
+                                             len(lp) - 1, _ptr(lof), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                             _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
     if include is not None:
         _batch_rc(lib.poismf_hip_topn_include(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii),
                                               _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
@@ -962,15 +1028,20 @@ class Session:
             raise MemoryError("poismf_hip_session_topn failed")
         return ix, sc
 
-    def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False, include=None):
+    def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False, include=None, include_of=None):
         """The top_n best items of every user in `users` from the resident factors, in one fused pass (include/poismf_hip.h section
         1f): "score descending, item index ascending", scores bit for bit those of predict().  exclude_seen leaves out the items of
         the user's row of the session's own CSR; exclude (a SciPy sparse matrix with one row per entry of `users`, or an
         (indptr, indices) pair with strictly ascending rows) leaves out more.  Returns (items uint64 [m x top_n], scores [m x top_n],
         empty unless output_score).  include (same two forms) gives every user a candidate list of its own: it is ranked among
         that list only, and only those rows of B are read (section 1h); top_n may then exceed what a user has left, and the row
-        is padded with TOPN_NONE and -inf."""
-        if include is not None:
+        is padded with TOPN_NONE and -inf.  include_of makes `include` a TABLE of lists shared between users (G >= 1 rows) and
+        names each user's row of it -- an integer array with one entry per user, or one int for all (section 1i): the same answers
+        bit for bit, the table read once and the rows of B shared by the users of a list.  Few lists for many users belong
+        there, a list per user in include= alone."""
+        if include_of is not None:
+            users, lp, li, lof, indptr, indices = _topn_shared_args(users, top_n, include, include_of, exclude, self.dimA, self.dimB)
+        elif include is not None:
             users, ip, ii, indptr, indices = _topn_include_args(users, top_n, include, exclude, self.dimA, self.dimB)
         else:
             users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
@@ -980,6 +1051,11 @@ class Session:
         ix = np.empty((m, n), np.uint64)
         sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
         if m == 0:
+            return ix, sc
+        if include_of is not None:
+            _batch_rc(self.lib.poismf_hip_session_topn_shared(self.h, _ptr(users), m, n, _ptr(lp), _opt_ptr(li), len(lp) - 1, _ptr(lof),
+                                                              int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
+                                                              _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
             return ix, sc
         if include is not None:
             _batch_rc(self.lib.poismf_hip_session_topn_include(self.h, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii), int(bool(exclude_seen)),

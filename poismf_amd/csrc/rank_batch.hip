@@ -192,7 +192,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile
         worst_j[r] = n > 0 ? Tj[(urow0 + r) * RB_GS + n - 1] : 0u;
     }
 
-    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, a.dimB, tile0, tile1, user_row, [&](T (&acc)[4][4], unsigned j_base) {
+    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, tile0, tile1, user_row, tb_all_items(a.dimB), [&](T (&acc)[4][4], unsigned j_base) {
         // ---- counting: the bins of rows 16 wave .. 16 wave + 15 are touched by this wave alone ----
 #pragma unroll
         for (int r = 0; r < 4; r++) {

@@ -597,6 +597,25 @@ int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* user
                                        exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Batched top-N over candidate lists shared between users from the resident (compact) factors (topn_shared.hip; include/poismf_hip.h
+// section 1i), ordered as the calls above and in the same scratch.
+int poismf_hip_session_topn_shared(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* list_indptr,
+                                   const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of, int exclude_seen,
+                                   const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_shared_check(users, n_users, n_top, s->dimA, s->dimB, s->k, list_indptr, list_indices, n_lists, list_of,
+                                                    excl_indptr, excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_shared_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, list_indptr, list_indices, n_lists,
+                                      list_of, exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix,
+                                      out_score);
+}
+
 // Batched exact ranks from the resident (compact) factors (rank_batch.hip; include/poismf_hip.h section 1g), ordered as the call above.
 // The scratch is the batched top-N's: either call grows it to what it needs and neither keeps anything in it between calls.
 int poismf_hip_session_rank_batch(poismf_hip_session* s, const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr,

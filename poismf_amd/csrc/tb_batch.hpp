@@ -51,6 +51,16 @@ int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real
                                 const sparse_ix* incl_indices, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
                                 const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
 
+// (topn_shared.hip; section 1i) the same pair for the top-N over lists shared between users: list_of[i] names user i's row of the table
+int poismf_hip_topn_shared_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                 const sparse_ix* list_indptr, const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of,
+                                 const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                               const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* list_indptr,
+                               const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of, PmfTopnSeen* seen,
+                               const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
+                               sparse_ix* out_ix, real_t* out_score);
+
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 namespace {

@@ -3,7 +3,7 @@
 // users' rows and the items' rows go through LDS in chunks of TB_KC columns, zero padded to a multiple of four columns.  tb_compute gives
 // each (user, item) the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  -- fp32 on v_mfma_f32_16x16x4_f32, fp64
 // on a VALU chain with the same register layout -- bit for bit what pair_dot_kernel (serve.hip) computes.  tb_walk is that walk with the
-// kernel's epilogue as a functor; tb_excluded is the pair's one test "is item j in E(u)?".
+// items' rows and the kernel's epilogue as functors (tb_all_items: every item in order; topn_shared.hip: the items of a list); tb_excluded is the pair's one test "is item j in E(u)?".
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -90,15 +90,15 @@ template <class T, bool MFMA> __device__ __forceinline__ void tb_compute(T (&acc
     }
 }
 
-// The walk of one workgroup over the item tiles tile0 .. tile1 - 1: acc[t][r] = the whole chain for user 16 wave + 4 (lane >> 4) + r and item
-// j_base + 16 t + (lane & 15), then epilogue(acc, j_base).  As / Bs: [TB_TU][TB_KS] each in LDS; user_row(row) is the tile row's row of A (< 0: none).
-template <class T, bool MFMA, class UserRow, class Epilogue>
-__device__ __forceinline__ void tb_walk(T* As, T* Bs, const T* A, const T* B, int k, unsigned dimB, unsigned tile0, unsigned tile1, UserRow user_row,
-                                        Epilogue epilogue)
+// The walk of one workgroup over the item tiles tile0 .. tile1 - 1: acc[t][r] = the whole chain for user 16 wave + 4 (lane >> 4) + r and the
+// item of tile row 16 t + (lane & 15), then epilogue(acc, j_base), j_base = TB_TJ x the tile.  As / Bs: [TB_TU][TB_KS] each in LDS;
+// user_row(row) is the tile row's row of A and item_row(j_base)(row) the tile row's row of B (< 0: none).
+template <class T, bool MFMA, class UserRow, class ItemRow, class Epilogue>
+__device__ __forceinline__ void tb_walk(T* As, T* Bs, const T* A, const T* B, int k, unsigned tile0, unsigned tile1, UserRow user_row,
+                                        ItemRow item_row, Epilogue epilogue)
 {
     static_assert(TB_TU == TB_TJ, "tb_fetch / tb_store serve both tiles");
     const int nchunks = (k + TB_KC - 1) / TB_KC;
-    auto item_row = [dimB](unsigned j_base) { return [dimB, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < dimB ? (long long)j : -1ll; }; };
 
     // k <= TB_KC: the users' tile is loaded once and the items' next tile travels in registers while this one is multiplied
     T b_next[TB_NL];
@@ -136,6 +136,12 @@ __device__ __forceinline__ void tb_walk(T* As, T* Bs, const T* A, const T* B, in
         }
         epilogue(acc, j_base);
     }
+}
+
+// The items in order: tile row `row` of the step at j_base is item j_base + row, none from dimB on.
+__device__ __forceinline__ auto tb_all_items(unsigned dimB)
+{
+    return [dimB](unsigned j_base) { return [dimB, j_base](int row) { const unsigned j = j_base + (unsigned)row; return j < dimB ? (long long)j : -1ll; }; };
 }
 
 // ---- "is item j in E(u)?" ----

@@ -95,7 +95,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
     bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
 
-    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, a.dimB, tile0, tile1, user_row, [&](T (&acc)[4][4], unsigned j_base) {
+    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, tile0, tile1, user_row, tb_all_items(a.dimB), [&](T (&acc)[4][4], unsigned j_base) {
         // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
 #pragma unroll
         for (int t = 0; t < 4; t++) {
