@@ -335,6 +335,58 @@ POISMF_HIP_API size_t poismf_hip_topn_shared_scratch_bytes(size_t n_users, size_
         size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1j. Batched exact ranks among per-user candidate lists (sampled evaluation): where each held-out item of many users stands
+ *     among a candidate list of the user's own -- sampled negatives plus the positives, the output of a retrieval stage, the
+ *     items in stock -- in one fused pass.  Section 1g ranks against the whole catalogue; here only the listed rows of B are
+ *     read, so the cost follows the lists' lengths, not dimB.  poismf_amd/metrics.py applies unchanged.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), per user
+ *
+ *   T(u)         a held-out list exactly as in section 1g: test_indptr [m + 1], test_indices, strictly ascending rows.
+ *   I(u)         an include list exactly as in section 1h: incl_indptr [m + 1], incl_indices, indices < dimB and strictly
+ *                ascending within a row; rows may be empty and hold at most POISMF_HIP_TOPN_INCLUDE_MAX_ROW indices.
+ *   E(u)         an exclusion set exactly as in section 1f: exclude_seen on a session and / or the CSR-shaped host list
+ *                excl_indptr / excl_indices (excl_indptr = NULL: no list).
+ *   C(u), N(u)   C(u) = I(u) \ E(u), N(u) = |C(u)|.  N(u) = 0 is valid (an empty list, or one wholly excluded).
+ *   rank(u, t)   for t in T(u) and in C(u): the number of j in C(u) that come before t under section 1f's total order with
+ *                section 1f's score (bit for bit what predict_multiple / poismf_hip_session_predict return).  The answer is
+ *                by definition section 1g's for the exclusion set E(u) united with {0..dimB-1} \ I(u), in out_rank and in
+ *                out_n_adm alike, as section 1h states for the top-N; the batched top-N of section 1h with the same lists
+ *                and n_top > rank lists t at index rank.  A rank is a function of (A[u], B, I(u), E(u), t) alone: not of
+ *                the other users or cells, the batch order, how a list is cut into slices or how the batch is cut into
+ *                chunks.  All counting is in integers; there are no float atomics.
+ *   excluded     a held-out cell whose item is not in C(u) -- in E(u), or not listed in I(u) -- gets
+ *                POISMF_HIP_RANK_EXCLUDED; it is not an error.  (A caller that passes sampled negatives alone unites each
+ *                user's held-out row into its list first; poismf_amd.api.eval_ranking(include=) does.)
+ *   output       out_rank: one unsigned int per entry of test_indices, in the caller's order; out_n_adm [m]: N(u).  Host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, in the cases of sections
+ * 1g and 1h together: a user index >= dimA; an item index >= dimB; a test, include or exclusion row not strictly ascending, or
+ * row pointers that decrease; test_indptr == NULL or incl_indptr == NULL; k outside 1..512 float / 1..256 double; exclude_seen
+ * for a user outside the session's rows of A; an exclusion row over section 1f's limit; a held-out row longer than
+ * POISMF_HIP_RANK_BATCH_MAX_ROW; an include row longer than POISMF_HIP_TOPN_INCLUDE_MAX_ROW.  n_users == 0 is not an error
+ * (returns 0).  Factors are assumed finite.
+ *
+ * Memory: ONE scratch allocation per call (session: the one the calls of sections 1f - 1i share) of at most
+ * POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB, for any number of users, held-out cells and candidates; the batch is cut into chunks of
+ * users whose lists fit.  poismf_hip_rank_include_scratch_bytes (testing aid, no HIP call) is the size both entry points
+ * allocate for a batch with n_test_cells held-out cells and n_incl_cells candidates in all.  A list is cut into slices of
+ * POISMF_HIP_RANK_INCLUDE_SLICE candidates, one wave each; a wave keeps up to POISMF_HIP_RANK_INCLUDE_GROUP of the user's
+ * held-out scores in LDS, and a user with more has them searched in device memory instead (slower per candidate, same answer).
+ * poismf_hip_rank_include's own copies of B and of A (all of A, or only the batch's rows when n_users < dimA) come on top.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_RANK_INCLUDE_SLICE 1024   /* candidates of a list that one wave scores */
+#define POISMF_HIP_RANK_INCLUDE_GROUP 128    /* held-out items of a user whose scores a wave keeps in LDS */
+POISMF_HIP_API int poismf_hip_rank_include(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
+POISMF_HIP_API size_t poismf_hip_rank_include_scratch_bytes(size_t n_users, size_t n_test_cells, size_t n_incl_cells,
+        size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -484,6 +536,13 @@ POISMF_HIP_API int poismf_hip_session_topn_shared(poismf_hip_session *s, const s
 /* Section 1g from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_rank_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
         const sparse_ix *test_indptr, const sparse_ix *test_indices, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
+
+/* Section 1j from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_rank_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         unsigned int *out_rank, unsigned int *out_n_adm);
 

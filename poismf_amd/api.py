@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_debug_plan_widths", "poismf_hip_debug_lane_full_width",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
+    "poismf_hip_rank_include", "poismf_hip_session_rank_include", "poismf_hip_rank_include_scratch_bytes",
     "poismf_hip_topn_include", "poismf_hip_session_topn_include", "poismf_hip_topn_include_scratch_bytes", "poismf_hip_topn_include_slice",
     "poismf_hip_topn_shared", "poismf_hip_session_topn_shared", "poismf_hip_topn_shared_scratch_bytes",
 )
@@ -58,6 +59,8 @@ TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
 RANK_BATCH_MAX_ROW = 65536   # of include/poismf_hip.h section 1g (tests/test_rank_batch_cpu.py compares them with the header)
 RANK_BATCH_BUDGET_MB = 256
+RANK_INCLUDE_SLICE = 1024    # POISMF_HIP_RANK_INCLUDE_SLICE and _GROUP of section 1j (tests/test_rank_include_cpu.py compares them with the header)
+RANK_INCLUDE_GROUP = 128
 TOPN_NONE = 2**64 - 1               # POISMF_HIP_TOPN_NONE and POISMF_HIP_TOPN_INCLUDE_MAX_ROW of include/poismf_hip.h section 1h
 TOPN_INCLUDE_MAX_ROW = 16777216     # (tests/test_topn_include_cpu.py compares them with the header)
 TOPN_SHARED_MAX_CELLS = 2**24       # POISMF_HIP_TOPN_SHARED_MAX_CELLS of section 1i (tests/test_topn_shared_cpu.py compares the two)
@@ -149,6 +152,12 @@ def load_library(use_float):
     lib.poismf_hip_session_rank_batch.restype = i
     lib.poismf_hip_rank_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_rank_batch_scratch_bytes.restype = sz
+    lib.poismf_hip_rank_include.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_rank_include.restype = i
+    lib.poismf_hip_session_rank_include.argtypes = [vp, vp, sz, vp, vp, vp, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_rank_include.restype = i
+    lib.poismf_hip_rank_include_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_rank_include_scratch_bytes.restype = sz
     lib.poismf_hip_topn_include.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_topn_include.restype = i
     lib.poismf_hip_session_topn_include.argtypes = [vp, vp, sz, sz, vp, vp, i, vp, vp, vp, vp]
@@ -696,9 +705,15 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
 PoisMF.topN_batch = _topN_batch
 
 
+def _rank_include_list(include, m, dimB):
+    """The include lists of the batched ranks (include/poismf_hip.h section 1j), checked as the library checks them: (incl_indptr,
+    incl_indices) as uint64 arrays"""
+    return _csr_list(include, m, dimB, "include", TOPN_INCLUDE_MAX_ROW, keep_zeros=True)
+
+
 def _rank_batch_args(users, test, exclude, dimA, dimB, k):
-    """The argument checks of the batched ranks (include/poismf_hip.h section 1g) that need no device, as the library itself makes
-    them; returns (users, test_indptr, test_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    """The argument checks of the batched ranks (include/poismf_hip.h sections 1g and 1j) that need no device, as the library itself
+    makes them; returns (users, test_indptr, test_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
     users = _index_array(users, "users")
     m = len(users)
     if m and int(users.max()) >= dimA:
@@ -714,23 +729,32 @@ def _rank_batch_args(users, test, exclude, dimA, dimB, k):
     return users, tp, ti, ep, ei
 
 
-def rank_batch(A, B, users, test, exclude=None):
+def rank_batch(A, B, users, test, exclude=None, include=None):
     """poismf_hip_rank_batch on host factors A [dimA x k], B [dimB x k] (float32 or float64, both alike): for every cell of `test`
     (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with strictly ascending rows) the
     0-based position of its item in the user's complete ranked list, exclusion set left out (include/poismf_hip.h section 1g).
     Returns (ranks uint32, one per cell in row order, RANK_EXCLUDED where the item is in the user's `exclude` row; n_adm uint32
-    [m], the admissible items of each user)."""
+    [m], the admissible items of each user).  include: a candidate list per user, in the same two forms (a sparse matrix's stored
+    columns), passed as given: every cell is ranked among its user's own list only, minus `exclude`, only those rows of B are
+    read, and a cell whose item is not listed gets RANK_EXCLUDED too (poismf_hip_rank_include, section 1j)."""
     A, B = np.asarray(A), np.asarray(B)
     if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
         raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
     use_float = A.dtype == np.float32
     users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, A.shape[0], B.shape[0], A.shape[1])
     m = len(users)
+    if include is not None:
+        ip, ii = _rank_include_list(include, m, B.shape[0])
     ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
     if m == 0:
         return ranks, n_adm
     A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
     lib = load_library(use_float)
+    if include is not None:
+        _batch_rc(lib.poismf_hip_rank_include(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
+                                              _ptr(ip), _opt_ptr(ii), _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks),
+                                              _ptr(n_adm)), "ranks")
+        return ranks, n_adm
     _batch_rc(lib.poismf_hip_rank_batch(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
                                         _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
     return ranks, n_adm
@@ -766,6 +790,36 @@ def _eval_ranking_args(X_test, exclude, users, k, dimA, dimB):
     return users, (np.asarray(test.indptr, np.uint64), np.asarray(test.indices, np.uint64)), exclude, k
 
 
+def _include_rows(include, users, dimA, dimB):
+    """eval_ranking's include=, given either for the whole matrix (a sparse matrix of the model's shape, whose rows for `users` are
+    taken) or for the batch (an (indptr, indices) pair with one row per user): the batch's (indptr, indices), checked"""
+    import scipy.sparse as sp
+    if sp.issparse(include):
+        if include.shape != (dimA, dimB):
+            raise ValueError(f"include has shape {include.shape}, the model {(dimA, dimB)}")
+        include = sp.csr_matrix(include)[users.astype(np.int64)]
+    return _rank_include_list(include, len(users), dimB)
+
+
+def _unite_rows(a, b):
+    """Row by row, the union of two CSR-shaped lists with strictly ascending rows and the same number of rows: (indptr, indices) as
+    uint64 arrays, rows strictly ascending.  No device is involved."""
+    ap, ai = np.asarray(a[0], np.int64), np.asarray(a[1], np.int64)
+    bp, bi = np.asarray(b[0], np.int64), np.asarray(b[1], np.int64)
+    if len(ap) != len(bp):
+        raise ValueError("the two lists have different numbers of rows")
+    m = len(ap) - 1
+    ai, bi = ai[ap[0]:ap[-1]], bi[bp[0]:bp[-1]]
+    if len(ai) and int(ai.max()) >= 2 ** 32 or len(bi) and int(bi.max()) >= 2 ** 32:
+        raise ValueError("an item index is out of range")
+    rows = np.concatenate((np.repeat(np.arange(m, dtype=np.int64), np.diff(ap)), np.repeat(np.arange(m, dtype=np.int64), np.diff(bp))))
+    key = np.unique((rows << 32) | np.concatenate((ai, bi)))      # one sort: (row, item) ascending, repeats merged
+    rows, items = key >> 32, key & (2 ** 32 - 1)
+    indptr = np.zeros(m + 1, np.uint64)
+    indptr[1:] = np.cumsum(np.bincount(rows, minlength=m))
+    return indptr, np.ascontiguousarray(items, dtype=np.uint64)
+
+
 def _ranking_result(tp, ranks, n_adm, k, per_user):
     from . import metrics
     each = metrics.metrics_from_ranks(tp, ranks, n_adm, k)
@@ -776,7 +830,7 @@ def _ranking_result(tp, ranks, n_adm, k, per_user):
     return out
 
 
-def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False):
+def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, include=None):
     """Held-out ranking metrics of the fitted model, from exact ranks computed in one fused pass on the GPU (include/poismf_hip.h
     section 1g; the definitions are those of poismf_amd/metrics.py).  X_test: a SciPy sparse matrix with the model's shape whose
     stored cells are the held-out positives (values play no part; explicit zeros dropped, duplicates merged).  users: the rows to
@@ -784,12 +838,19 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False):
     stored cells leave the ranking (the training matrix; its rows for `users` are taken here), or an (indptr, indices) pair with
     one strictly ascending row per entry of `users`; a held-out cell that is excluded takes no part in any metric.  Returns a dict
     of the means of hit, precision, recall, ap, ndcg, rr, auc at cut-off k over the users that counted, plus n_users; with per_user
-    also "per_user" (the same names, one value per user), "ranks", "n_adm" and "test_indptr"."""
+    also "per_user" (the same names, one value per user), "ranks", "n_adm" and "test_indptr".
+    include: sampled evaluation (section 1j) -- a candidate list per user, as a sparse matrix with the model's shape (its rows for
+    `users` are taken) or an (indptr, indices) pair with one strictly ascending row per entry of `users`.  Every user is ranked
+    among its own list only, and only those rows of B are read.  Each user's held-out row is united into its list first, so the
+    sampled negatives alone may be passed; lists that already hold the positives change nothing."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
     users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.nusers, self.nitems)
+    if include is not None:
+        include = _unite_rows(_include_rows(include, users, self.nusers, self.nitems), test)
     dt = np.float32 if self.use_float else np.float64
-    ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude)
+    ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude,
+                              include=include)
     return _ranking_result(test[0], ranks, n_adm, k, per_user)
 
 
@@ -1067,27 +1128,38 @@ class Session:
                                                          _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
-    def rank_batch(self, users, test, exclude_seen=False, exclude=None):
+    def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None):
         """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with
         strictly ascending rows) the 0-based position of its item in the user's complete ranked list from the resident factors
         (include/poismf_hip.h section 1g); exclude_seen / exclude as in topn_batch.  Returns (ranks uint32, one per cell in row
-        order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m], the admissible items of each user)."""
+        order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m], the admissible items of each user).  include (same two
+        forms, passed as given) gives every user a candidate list of its own: a cell is ranked among that list only, minus the
+        exclusions, only those rows of B are read, and a cell whose item is not listed gets RANK_EXCLUDED too (section 1j)."""
         users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, self.dimA, self.dimB, self.k)
         m = len(users)
+        if include is not None:
+            ip, ii = _rank_include_list(include, m, self.dimB)
         if exclude_seen:
             _outside_shard(users, self.shardA)
         ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
         if m == 0:
             return ranks, n_adm
+        if include is not None:
+            _batch_rc(self.lib.poismf_hip_session_rank_include(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), _ptr(ip), _opt_ptr(ii),
+                                                               int(bool(exclude_seen)), _ptr(ep) if ep is not None else None, _opt_ptr(ei),
+                                                               _ptr(ranks), _ptr(n_adm)), "ranks")
+            return ranks, n_adm
         _batch_rc(self.lib.poismf_hip_session_rank_batch(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), int(bool(exclude_seen)),
                                                          _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
         return ranks, n_adm
 
-    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False):
+    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None):
         """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
-        CSR (nothing is uploaded), exclude leaves out more."""
+        CSR (nothing is uploaded), exclude leaves out more; include as there (sampled evaluation, section 1j)."""
         users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.dimA, self.dimB)
-        ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude)
+        if include is not None:
+            include = _unite_rows(_include_rows(include, users, self.dimA, self.dimB), test)
+        ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include)
         return _ranking_result(test[0], ranks, n_adm, k, per_user)
 
     def _text(self, fn, which):

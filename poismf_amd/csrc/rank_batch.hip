@@ -4,6 +4,7 @@
 //
 // rank(u, t) = #{j in 0..dimB-1 before t} - #{e in E(u) before t}: a dense count over every item and a sparse correction.
 //
+//   (tb_rank.hpp, shared with rank_include.hip: rank_threshold_kernel, rank_order_kernel and rank_finish_kernel)
 //   rank_threshold_kernel  one thread per held-out cell: its score with the scalar chain (the "threshold"), and whether it is in E(u).
 //   rank_order_kernel      one thread per cell: its position among the user's cells (valid ones best first under the total order, cells
 //                          in E(u) behind them), by counting -- quadratic in a row's length, hence POISMF_HIP_RANK_BATCH_MAX_ROW.
@@ -37,6 +38,7 @@
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
 #include "tb_tile.hpp"
+#include "tb_rank.hpp"
 #include "tb_batch.hpp"
 
 namespace {
@@ -46,92 +48,6 @@ constexpr int RB_GS = RB_G + 1;                           // LDS row stride of t
 constexpr size_t RB_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many
 constexpr size_t RB_CHUNK_USERS_MAX = 262144;
 constexpr size_t RB_BUDGET = (size_t)POISMF_HIP_RANK_BATCH_BUDGET_MB << 20;
-constexpr size_t RB_ROW_MAX = POISMF_HIP_RANK_BATCH_MAX_ROW;
-constexpr unsigned RB_EXCLUDED = POISMF_HIP_RANK_EXCLUDED;
-
-struct RbArgs {
-    const real_t* A;                  // rows addressed by `arow`
-    const real_t* B;                  // [dimB x k]
-    int k;
-    unsigned dimB, n_users, n_cells;
-    const unsigned* arow;             // [n_users] the chunk's rows of A
-    const unsigned* tptr;             // [n_users + 1] the chunk's held-out rows, from 0
-    const unsigned* cell_row;         // [n_cells] chunk user of a cell
-    const unsigned* cell_item;        // [n_cells]
-    real_t* cell_score;               // [n_cells] thresholds in the caller's order
-    unsigned* cell_excl;              // [n_cells] 1: the item is in E(u)
-    real_t* s_score;                  // [n_cells] per user: valid thresholds best first, then the excluded cells
-    unsigned* s_item;
-    unsigned* s_origin;               // the cell an ordered entry came from
-    unsigned* nvalid;                 // [n_users] cells not in E(u)
-    unsigned* dense;                  // [n_cells] (ordered) items of 0..dimB-1 before the threshold
-    unsigned* corr;                   // [n_cells] (ordered) difference array: items of E(u) whose first beaten threshold this is
-    unsigned* rank;                   // [n_cells] (caller's order)
-    unsigned* n_adm;                  // [n_users]
-    const unsigned* grow;             // [ngroups] chunk user of a group
-    const unsigned* gstart;           // [ngroups] its first ordered entry
-    unsigned ngroups, nslices, tiles_per_slice;
-    TbExcl excl;                      // E(u) of the chunk's users
-};
-
-__device__ __forceinline__ float rb_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double rb_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// the k-ordered fused chain of pair_dot_kernel
-__device__ __forceinline__ real_t rb_dot(const real_t* A, const real_t* B, int k, unsigned u, unsigned j)
-{
-    const real_t* p = A + (size_t)u * (size_t)k;
-    const real_t* q = B + (size_t)j * (size_t)k;
-    real_t s = 0;
-    for (int c = 0; c < k; c++) s = rb_fma(p[c], q[c], s);
-    return s;
-}
-
-// the first of n thresholds ordered best first that (s, j) comes before; n when there is none
-__device__ __forceinline__ unsigned rb_first_beaten(const real_t* ts, const unsigned* tj, unsigned n, real_t s, unsigned j)
-{
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-        const unsigned mid = lo + (hi - lo) / 2;
-        if (tb_better(s, j, ts[mid], tj[mid])) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(256) void rank_threshold_kernel(RbArgs a)
-{
-    const unsigned c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= a.n_cells) return;
-    const unsigned i = a.cell_row[c], j = a.cell_item[c];
-    a.cell_score[c] = rb_dot(a.A, a.B, a.k, a.arow[i], j);
-    a.cell_excl[c] = tb_excluded(a.excl, i, a.arow[i], j) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void rank_order_kernel(RbArgs a)
-{
-    const unsigned c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= a.n_cells) return;
-    const unsigned i = a.cell_row[c];
-    const unsigned p0 = a.tptr[i], p1 = a.tptr[i + 1];
-    const real_t s = a.cell_score[c];
-    const unsigned j = a.cell_item[c];
-    const bool valid = a.cell_excl[c] == 0;
-    unsigned pos = 0, nv = 0;
-    for (unsigned q = p0; q < p1; q++) {
-        const bool vq = a.cell_excl[q] == 0;
-        nv += vq ? 1u : 0u;
-        bool first;   // cell q stands before cell c
-        if (vq && valid) first = tb_better(a.cell_score[q], a.cell_item[q], s, j);
-        else if (vq != valid) first = vq;
-        else first = q < c;
-        pos += first ? 1u : 0u;
-    }
-    a.s_score[p0 + pos] = s;
-    a.s_item[p0 + pos] = j;
-    a.s_origin[p0 + pos] = c;
-    if (c == p0) a.nvalid[i] = nv;
-}
 
 template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void rank_tile_kernel(RbArgs a)
 {
@@ -292,21 +208,6 @@ __global__ __launch_bounds__(256) void rank_excl_kernel(RbArgs a)
         }
     }
     if (lane == 0) a.n_adm[i] = a.dimB - n_excl;
-}
-
-__global__ __launch_bounds__(256) void rank_finish_kernel(RbArgs a)
-{
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.n_users) return;
-    const unsigned p0 = a.tptr[i], p1 = a.tptr[i + 1], nv = a.nvalid[i];
-    unsigned run = 0;
-    for (unsigned p = p0; p < p1; p++) {
-        if (p - p0 < nv) {
-            run += a.corr[p];
-            a.rank[a.s_origin[p]] = a.dense[p] - run;
-        } else
-            a.rank[a.s_origin[p]] = RB_EXCLUDED;
-    }
 }
 
 // The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
@@ -477,9 +378,11 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
         a.ngroups = (unsigned)ng;
         a.nslices = (unsigned)sl.nslices;
         a.tiles_per_slice = (unsigned)sl.tiles_per_slice;
+        a.iptr = nullptr;
+        a.incl = nullptr;
         if (nc > 0) {
             const unsigned cell_blocks = (unsigned)pmf_ceil_div(nc, 256);
-            hipLaunchKernelGGL(rank_threshold_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
+            hipLaunchKernelGGL(rank_threshold_kernel<false>, dim3(cell_blocks), dim3(256), 0, stream, a);
             TB_TRY(hipGetLastError());
             hipLaunchKernelGGL(rank_order_kernel, dim3(cell_blocks), dim3(256), 0, stream, a);
             TB_TRY(hipGetLastError());
@@ -489,7 +392,7 @@ int poismf_hip_rank_batch_run(hipStream_t stream, const real_t* dA, const real_t
         hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)pmf_ceil_div(nu, 4)), dim3(256), 0, stream, a);
         TB_TRY(hipGetLastError());
         if (nc > 0) {
-            hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)pmf_ceil_div(nu, 256)), dim3(256), 0, stream, a);
+            hipLaunchKernelGGL(rank_finish_kernel<false>, dim3((unsigned)pmf_ceil_div(nu, 256)), dim3(256), 0, stream, a);
             TB_TRY(hipGetLastError());
             TB_TRY(pmf_download(out_rank + c_base, base + L.rank, nc * sizeof(unsigned), stream));
         }

@@ -1,5 +1,5 @@
-// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip) and the batched ranks (rank_batch.hip) have in common, and what the
-// session (session.hip) hands to the two cores
+// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip) and the batched ranks
+// (rank_batch.hip, rank_include.hip) have in common, and what the session (session.hip) hands to their cores
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -60,6 +60,17 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
                                const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of, PmfTopnSeen* seen,
                                const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
                                sparse_ix* out_ix, real_t* out_score);
+
+// (rank_include.hip; section 1j) the same pair for the ranks among per-user include lists: the check makes no device call, the core
+// returns 0 or 1
+int poismf_hip_rank_include_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
+                                  const sparse_ix* test_indices, const sparse_ix* incl_indptr, const sparse_ix* incl_indices,
+                                  const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_rank_include_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices,
+                                const sparse_ix* incl_indptr, const sparse_ix* incl_indices, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                                const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, unsigned int* out_rank,
+                                unsigned int* out_n_adm);
 
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 

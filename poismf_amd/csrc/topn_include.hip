@@ -9,7 +9,7 @@
 // Work items are planned on the host, which has the row pointers: a user's list is cut into slices of poismf_hip_topn_include_slice()
 // candidates and ONE WAVE owns one (user, slice); four such waves share a workgroup and nothing else -- no workgroup barrier, every
 // LDS region belongs to one wave.  The wave walks its slice 64 candidates at a time, lane l owning candidate l of the pass:
-//   gather   the 64 rows of B go through LDS in chunks of 256 bytes of a row.  All lanes load aligned 16-byte pieces, four
+//   gather   (tb_gather.hpp, shared with rank_include.hip) the 64 rows of B go through LDS in chunks of 256 bytes of a row.  All lanes load aligned 16-byte pieces, four
 //            neighbouring lanes one row's 64 consecutive bytes; rows start on sizeof(real_t) only, so a row's first and last piece
 //            carry up to 12 bytes of its neighbours (allocations of B carry 16 bytes of slack), which the copy into LDS drops:
 //            element by element to the row's own slot, 68 dwords apart, where each lane then reads its row 16 bytes at a time
@@ -33,17 +33,12 @@
 #include "../../include/poismf_hip.h"
 #include "devmem.hpp"
 #include "tb_tile.hpp"
+#include "tb_gather.hpp"
 #include "tb_batch.hpp"
 
 namespace {
 
 constexpr int TI_WAVES = 4;                               // work items per workgroup
-constexpr int TI_R = sizeof(real_t);
-constexpr int TI_KC = 256 / TI_R;                         // columns of B per staged chunk: 256 bytes of a row
-constexpr int TI_VN = 16 / TI_R;                          // elements of a 16-byte piece
-constexpr int TI_SLOT = 256 + 16;                         // bytes between two rows of the LDS tile: 68 dwords = 4 x 17
-constexpr int TI_NP_MAX = (256 + 16 - TI_R + 15) / 16;    // 16-byte pieces that cover 256 bytes starting anywhere on sizeof(real_t)
-constexpr int TI_NI = 4 * ((TI_NP_MAX + 3) / 4);          // loads per lane and chunk: four lanes per row, sixteen rows per load
 constexpr unsigned TI_CAP = (unsigned)TB_N_TOP_MAX + 64;  // slots of a wave's candidate list: a pass can add 64
 constexpr size_t TI_SLICE_MIN = 1024;                     // candidates per work item, unless the merge's LDS asks for more
 constexpr size_t TI_MAX_ROW = POISMF_HIP_TOPN_INCLUDE_MAX_ROW;
@@ -51,7 +46,6 @@ constexpr size_t TI_PART_BYTES = (size_t)16 << 20;        // most a chunk's part
 constexpr unsigned TI_PART = 0x80000000u;                 // TiItem::dst: a row of the partial lists, not of the results
 static_assert(TI_CAP <= (unsigned)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
 static_assert(TI_MAX_ROW * sizeof(unsigned) == TB_BUDGET / 4, "the longest include row fills a quarter of the scratch");
-static_assert(TI_NP_MAX == 17 && TI_SLOT % 16 == 0 && (TI_SLOT / 16) % 2 == 1, "rows of the LDS tile: 16-byte aligned, 4 x odd dwords apart");
 
 struct TiItem { unsigned ui, p0, len, dst; };             // chunk user, first candidate in the chunk's index area, candidates, result row
 
@@ -70,12 +64,6 @@ struct TiArgs {
     real_t* out_score;                // [chunk users][n_top]
     unsigned* out_ix;
 };
-
-typedef unsigned ti_u32x4 __attribute__((ext_vector_type(4)));
-typedef real_t ti_vec __attribute__((ext_vector_type(TI_VN)));
-
-__device__ __forceinline__ float ti_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double ti_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 __host__ __device__ inline size_t ti_wave_lds(size_t k)
 {
@@ -109,64 +97,15 @@ template <bool STREAM> __global__ __launch_bounds__(64 * TI_WAVES) void topn_inc
     const unsigned* lst = a.incl + it.p0;
     const unsigned npass = (it.len + 63) / 64;
     const int nch = (k + TI_KC - 1) / TI_KC;
-    const unsigned frow = lane >> 2, fq = lane & 3;   // the gather: this lane loads piece fq + 4 g of rows frow + 16 r
-    const char* Bb = (const char*)a.B;
-
+    const TiGather g = { (const char*)a.B, Bs, k, lane >> 2, lane & 3 };   // (tb_gather.hpp) this lane loads piece fq + 4 g of rows frow + 16 r
     ti_u32x4 pre[TI_NI];
-    // the 16-byte pieces of columns c0 .. c0 + len - 1 of the rows jl (lane l: row l of the tile; TB_NONE: none) into `pre`
-    auto fetch = [&](unsigned jl, int c0, int len) {
-        const unsigned np = (unsigned)(len * TI_R + 16 - TI_R + 15) / 16;
-        size_t byte0[4];
-        bool has[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const unsigned jr = (unsigned)__shfl((int)jl, (int)(frow + 16 * r));
-            has[r] = jr != TB_NONE;
-            byte0[r] = ((size_t)jr * (size_t)k + (size_t)c0) * TI_R;
-        }
-#pragma unroll
-        for (int i = 0; i < TI_NI; i++) {
-            const int r = i & 3;
-            const unsigned q = fq + 4 * (unsigned)(i >> 2);
-            if (4 * (unsigned)(i >> 2) >= np) break;   // (uniform)
-            const unsigned mis = (unsigned)(byte0[r] & 15);
-            if (has[r] && 16 * q < mis + (unsigned)(len * TI_R))
-                pre[i] = *(const ti_u32x4*)(Bb + (byte0[r] & ~(size_t)15) + 16 * (size_t)q);
-        }
-    };
-    // `pre` into the tile: element by element, to column (its place in the row) of the row's slot; what belongs to a neighbouring row is dropped
-    auto store = [&](unsigned jl, int c0, int len) {
-        const unsigned np = (unsigned)(len * TI_R + 16 - TI_R + 15) / 16;
-        int shift[4];
-        bool has[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const unsigned jr = (unsigned)__shfl((int)jl, (int)(frow + 16 * r));
-            has[r] = jr != TB_NONE;
-            shift[r] = (int)((((size_t)jr * (size_t)k + (size_t)c0) * TI_R) & 15) / TI_R;
-        }
-#pragma unroll
-        for (int i = 0; i < TI_NI; i++) {
-            const int r = i & 3;
-            const unsigned q = fq + 4 * (unsigned)(i >> 2);
-            if (4 * (unsigned)(i >> 2) >= np) break;   // (uniform)
-            if (!has[r]) continue;
-            real_t* dst = (real_t*)(Bs + (frow + 16 * r) * TI_SLOT);
-            const ti_vec v = __builtin_bit_cast(ti_vec, pre[i]);
-#pragma unroll
-            for (int e = 0; e < TI_VN; e++) {
-                const int cc = (int)q * TI_VN + e - shift[r];
-                if (cc >= 0 && cc < len) dst[cc] = v[e];   // (a piece past the row's end was not loaded and has cc >= len)
-            }
-        }
-    };
 
     real_t thr = -std::numeric_limits<real_t>::infinity();
     unsigned thj = 0;
     unsigned j_cur = lane < it.len ? lst[lane] : TB_NONE;
     unsigned j_nxt = 64 + lane < it.len ? lst[64 + lane] : TB_NONE;
     const real_t* brow = (const real_t*)(Bs + lane * TI_SLOT);
-    if (!STREAM && npass) fetch(j_cur, 0, k < TI_KC ? k : TI_KC);
+    if (!STREAM && npass) g.fetch(pre, j_cur, 0, k < TI_KC ? k : TI_KC);
 
     for (unsigned pass = 0; pass < npass; pass++) {
         real_t s = 0;
@@ -180,12 +119,12 @@ template <bool STREAM> __global__ __launch_bounds__(64 * TI_WAVES) void topn_inc
                 const int c0 = ch * TI_KC;
                 const int len = k - c0 < TI_KC ? k - c0 : TI_KC;
                 tb_wave_sync();   // the wave is done with the tile of the step before
-                store(j_cur, c0, len);
+                g.store(pre, j_cur, c0, len);
                 tb_wave_sync();
                 {   // the step after this one: the next chunk of these rows, or the first chunk of the next pass's
                     const bool same = ch + 1 < nch;
                     const int n0 = same ? c0 + TI_KC : 0;
-                    if (same || pass + 1 < npass) fetch(same ? j_cur : j_nxt, n0, k - n0 < TI_KC ? k - n0 : TI_KC);
+                    if (same || pass + 1 < npass) g.fetch(pre, same ? j_cur : j_nxt, n0, k - n0 < TI_KC ? k - n0 : TI_KC);
                 }
                 if (j_cur != TB_NONE) {
                     int c = 0;
