@@ -387,6 +387,64 @@ POISMF_HIP_API size_t poismf_hip_rank_include_scratch_bytes(size_t n_users, size
         size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1k. Batched exact ranks among candidate lists SHARED between users (sampled evaluation against one pool): section 1j's ranks
+ *     when few lists serve many users -- 1000 negatives sampled once for everybody, a popularity-stratified pool, the items in
+ *     stock in a region.  Section 1j takes every user's copy of its list and every user gathers its own rows of B.  Here the
+ *     host reads each list once, and on the device 64 rows of held-out items that refer to one list share every row of B they
+ *     gather (the f32-MFMA tile of section 1f with section 1g's counting).  It is to section 1j what section 1i is to 1h.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed), and
+ *
+ *   T(u)         a held-out list exactly as in section 1g: test_indptr [m + 1], test_indices, strictly ascending rows.
+ *   L_0..L_{G-1} a table of candidate lists and list_of [m] exactly as in section 1i: list_indptr [G + 1], list_indices,
+ *                indices < dimB and strictly ascending within a row; list_of[i] < G.  Rows may be empty.  A list no user
+ *                refers to is valid and costs nothing on the device.  At most POISMF_HIP_TOPN_SHARED_MAX_CELLS indices in all.
+ *   E(u)         an exclusion set exactly as in section 1f: exclude_seen on a session and / or the CSR-shaped host list
+ *                excl_indptr / excl_indices (excl_indptr = NULL: no list).
+ *   unite_test   == 0: C(u) = L_{list_of(u)} \ E(u).  A held-out cell whose item is not in C(u) -- in E(u), or not listed --
+ *                gets POISMF_HIP_RANK_EXCLUDED.  By definition this is section 1j's answer with I(u) = L_{list_of(u)}, in
+ *                out_rank and in out_n_adm alike.
+ *                != 0: C(u) = (L_{list_of(u)} united with T(u)) \ E(u); only the cells in E(u) are marked.  By definition this is
+ *                section 1j's answer with I(u) the union of the list and the user's held-out row.  It is the mode a shared
+ *                pool of negatives needs: a shared list cannot have each user's positives written into it.
+ *   N(u)         |C(u)|.  N(u) = 0 is valid (an empty list, or one wholly excluded).
+ *   rank(u, t)   for t in T(u) and in C(u): the number of j in C(u) that come before t under section 1f's total order with
+ *                section 1f's score (bit for bit what predict_multiple / poismf_hip_session_predict return).  The batched
+ *                top-N of section 1i with the same table and n_top > rank lists a listed t at index rank when unite_test == 0.
+ *                A rank is a function of (A[u], B, L_{list_of(u)}, T(u) when united, E(u), t) alone: not of the other users,
+ *                how users or held-out items are grouped into tiles, the order of the batch or of the table, how a list is
+ *                cut into slices or how the batch is cut into chunks.  All counting is in integers; there are no float atomics.
+ *   output       out_rank: one unsigned int per entry of test_indices, in the caller's order; out_n_adm [m]: N(u).  Host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, in the cases of sections
+ * 1g and 1i together: a user index >= dimA; an item index >= dimB; a test, list or exclusion row not strictly ascending, or row
+ * pointers that decrease; test_indptr == NULL, list_indptr == NULL or list_of == NULL; n_lists == 0 with n_users > 0; an entry
+ * of list_of >= n_lists; k outside 1..512 float / 1..256 double; exclude_seen for a user outside the session's rows of A; an
+ * exclusion row over section 1f's limit; a held-out row longer than POISMF_HIP_RANK_BATCH_MAX_ROW; a list table whose rows hold
+ * more than POISMF_HIP_TOPN_SHARED_MAX_CELLS indices in all.  n_users == 0 is not an error (returns 0).  Factors are assumed
+ * finite.
+ *
+ * Memory: ONE scratch allocation per call (session: the one the calls of sections 1f - 1j share) of at most
+ * POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB, for any number of users, held-out cells, lists and list indices.  The table goes up once
+ * per call, narrowed to 32 bits, and a chunk's parts lie beside it; the batch is cut into chunks of consecutive users that
+ * carry at most POISMF_HIP_RANK_SHARED_CHUNK_CELLS held-out cells together (one row of the longest kind always fits).
+ * poismf_hip_rank_shared_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate; it never decreases
+ * when one of its arguments grows.  Host work is proportional to n_list_cells + n_users + n_test_cells (+ the exclusion lists),
+ * never to users x list length.  poismf_hip_rank_shared's own copies of B and of A (all of A, or only the batch's rows when
+ * n_users < dimA) come on top.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_RANK_SHARED_CHUNK_CELLS 524288   /* most held-out cells of one chunk of users: 2^19 */
+POISMF_HIP_API int poismf_hip_rank_shared(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices,
+        const sparse_ix *list_indptr, const sparse_ix *list_indices, size_t n_lists, const sparse_ix *list_of,
+        int unite_test,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
+POISMF_HIP_API size_t poismf_hip_rank_shared_scratch_bytes(size_t n_users, size_t n_test_cells, size_t n_lists,
+        size_t n_list_cells, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -543,6 +601,14 @@ POISMF_HIP_API int poismf_hip_session_rank_batch(poismf_hip_session *s, const sp
 POISMF_HIP_API int poismf_hip_session_rank_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
         const sparse_ix *test_indptr, const sparse_ix *test_indices,
         const sparse_ix *incl_indptr, const sparse_ix *incl_indices, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm);
+
+/* Section 1k from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_rank_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices,
+        const sparse_ix *list_indptr, const sparse_ix *list_indices, size_t n_lists, const sparse_ix *list_of,
+        int unite_test, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         unsigned int *out_rank, unsigned int *out_n_adm);
 

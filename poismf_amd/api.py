@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_rank_include", "poismf_hip_session_rank_include", "poismf_hip_rank_include_scratch_bytes",
     "poismf_hip_topn_include", "poismf_hip_session_topn_include", "poismf_hip_topn_include_scratch_bytes", "poismf_hip_topn_include_slice",
     "poismf_hip_topn_shared", "poismf_hip_session_topn_shared", "poismf_hip_topn_shared_scratch_bytes",
+    "poismf_hip_rank_shared", "poismf_hip_session_rank_shared", "poismf_hip_rank_shared_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -64,6 +65,7 @@ RANK_INCLUDE_GROUP = 128
 TOPN_NONE = 2**64 - 1               # POISMF_HIP_TOPN_NONE and POISMF_HIP_TOPN_INCLUDE_MAX_ROW of include/poismf_hip.h section 1h
 TOPN_INCLUDE_MAX_ROW = 16777216     # (tests/test_topn_include_cpu.py compares them with the header)
 TOPN_SHARED_MAX_CELLS = 2**24       # POISMF_HIP_TOPN_SHARED_MAX_CELLS of section 1i (tests/test_topn_shared_cpu.py compares the two)
+RANK_SHARED_CHUNK_CELLS = 2**19     # POISMF_HIP_RANK_SHARED_CHUNK_CELLS of section 1k (tests/test_rank_shared_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -172,6 +174,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_shared.restype = i
     lib.poismf_hip_topn_shared_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, sz]
     lib.poismf_hip_topn_shared_scratch_bytes.restype = sz
+    lib.poismf_hip_rank_shared.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, sz, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_rank_shared.restype = i
+    lib.poismf_hip_session_rank_shared.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz, vp, i, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_rank_shared.restype = i
+    lib.poismf_hip_rank_shared_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, sz]
+    lib.poismf_hip_rank_shared_scratch_bytes.restype = sz
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -592,20 +600,10 @@ def _topn_include_args(users, n, include, exclude, dimA, dimB):
     return users, ip, ii, ep, ei
 
 
-def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
-    """The argument checks of the batched top-N over lists shared between users (include/poismf_hip.h section 1i) that need no
-    device, as the library itself makes them: `include` is the table of lists (any number of rows G >= 1), include_of names every
-    user's row of it (an integer array with one entry per user, or one int for all).  Returns (users, list_indptr, list_indices,
-    list_of, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
+def _shared_table_args(include, include_of, m, dimB):
+    """A table of lists shared between users and every user's row of it (include/poismf_hip.h sections 1i and 1k), checked without a
+    device as the library itself checks them: `include` is the table (any number of rows G >= 1), include_of an integer array with
+    one entry per user, or one int for all.  Returns (list_indptr, list_indices, list_of) as uint64 arrays."""
     if include is None:
         raise ValueError("include_of needs include, the table of lists it refers to")
     if isinstance(include, (tuple, list)) and len(include) == 2 and not hasattr(include, "tocsr"):
@@ -633,6 +631,24 @@ def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
         raise ValueError(f"include_of has {len(lof)} entries for {m} users")
     if m and int(lof.max()) >= G:
         raise ValueError(f"an entry of include_of is not a row of include ({G} lists)")
+    return lp, li, lof
+
+
+def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
+    """The argument checks of the batched top-N over lists shared between users (include/poismf_hip.h section 1i) that need no
+    device, as the library itself makes them: `include` is the table of lists (any number of rows G >= 1), include_of names every
+    user's row of it (an integer array with one entry per user, or one int for all).  Returns (users, list_indptr, list_indices,
+    list_of, excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    lp, li, lof = _shared_table_args(include, include_of, m, dimB)
     if exclude is None:
         return users, lp, li, lof, None, None
     ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
@@ -729,27 +745,41 @@ def _rank_batch_args(users, test, exclude, dimA, dimB, k):
     return users, tp, ti, ep, ei
 
 
-def rank_batch(A, B, users, test, exclude=None, include=None):
+def rank_batch(A, B, users, test, exclude=None, include=None, include_of=None, unite_test=False):
     """poismf_hip_rank_batch on host factors A [dimA x k], B [dimB x k] (float32 or float64, both alike): for every cell of `test`
     (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with strictly ascending rows) the
     0-based position of its item in the user's complete ranked list, exclusion set left out (include/poismf_hip.h section 1g).
     Returns (ranks uint32, one per cell in row order, RANK_EXCLUDED where the item is in the user's `exclude` row; n_adm uint32
     [m], the admissible items of each user).  include: a candidate list per user, in the same two forms (a sparse matrix's stored
     columns), passed as given: every cell is ranked among its user's own list only, minus `exclude`, only those rows of B are
-    read, and a cell whose item is not listed gets RANK_EXCLUDED too (poismf_hip_rank_include, section 1j)."""
+    read, and a cell whose item is not listed gets RANK_EXCLUDED too (poismf_hip_rank_include, section 1j).
+    include_of: with it, `include` is a TABLE of lists shared between users (any number of rows G >= 1) and include_of names each
+    user's row of it: an integer array with one entry per batch entry, or one int for all (poismf_hip_rank_shared, section 1k).
+    The answers are those of include= with every user's list written out; the table is read once, and users of one list share
+    the rows of B they read.  unite_test (with include_of only): every user is ranked among its list united with its own
+    held-out row, so a shared pool of negatives may be passed as it is; only excluded cells get RANK_EXCLUDED."""
     A, B = np.asarray(A), np.asarray(B)
     if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
         raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
     use_float = A.dtype == np.float32
     users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, A.shape[0], B.shape[0], A.shape[1])
     m = len(users)
-    if include is not None:
+    if include_of is not None:
+        lp, li, lof = _shared_table_args(include, include_of, m, B.shape[0])
+    elif unite_test:
+        raise ValueError("unite_test needs include_of: a list per user has its held-out row united in by the caller")
+    elif include is not None:
         ip, ii = _rank_include_list(include, m, B.shape[0])
     ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
     if m == 0:
         return ranks, n_adm
     A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
     lib = load_library(use_float)
+    if include_of is not None:
+        _batch_rc(lib.poismf_hip_rank_shared(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
+                                             _ptr(lp), _opt_ptr(li), len(lp) - 1, _ptr(lof), int(bool(unite_test)),
+                                             _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
+        return ranks, n_adm
     if include is not None:
         _batch_rc(lib.poismf_hip_rank_include(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
                                               _ptr(ip), _opt_ptr(ii), _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks),
@@ -801,6 +831,21 @@ def _include_rows(include, users, dimA, dimB):
     return _rank_include_list(include, len(users), dimB)
 
 
+def _include_of_rows(include_of, users, dimA):
+    """eval_ranking's include_of=, given for the whole model (one int, or an integer array with one entry per user of the model,
+    indexed by user id): what rank_batch takes -- the int itself, or the entries of `users`"""
+    if isinstance(include_of, (bool, np.bool_)):
+        raise ValueError("include_of must be integers")
+    if isinstance(include_of, (int, np.integer)):
+        return include_of
+    if np.ndim(include_of) != 1:
+        raise ValueError("include_of must be a 1-d array with one entry per user of the model, or one int")
+    lof = _index_array(include_of, "include_of")
+    if len(lof) != dimA:
+        raise ValueError(f"include_of has {len(lof)} entries, the model {dimA} users")
+    return lof[users.astype(np.int64)]
+
+
 def _unite_rows(a, b):
     """Row by row, the union of two CSR-shaped lists with strictly ascending rows and the same number of rows: (indptr, indices) as
     uint64 arrays, rows strictly ascending.  No device is involved."""
@@ -830,7 +875,7 @@ def _ranking_result(tp, ranks, n_adm, k, per_user):
     return out
 
 
-def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, include=None):
+def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, include=None, include_of=None):
     """Held-out ranking metrics of the fitted model, from exact ranks computed in one fused pass on the GPU (include/poismf_hip.h
     section 1g; the definitions are those of poismf_amd/metrics.py).  X_test: a SciPy sparse matrix with the model's shape whose
     stored cells are the held-out positives (values play no part; explicit zeros dropped, duplicates merged).  users: the rows to
@@ -842,13 +887,22 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, 
     include: sampled evaluation (section 1j) -- a candidate list per user, as a sparse matrix with the model's shape (its rows for
     `users` are taken) or an (indptr, indices) pair with one strictly ascending row per entry of `users`.  Every user is ranked
     among its own list only, and only those rows of B are read.  Each user's held-out row is united into its list first, so the
-    sampled negatives alone may be passed; lists that already hold the positives change nothing."""
+    sampled negatives alone may be passed; lists that already hold the positives change nothing.
+    include_of: with it, `include` is a TABLE of pools shared between users (section 1k) -- a sparse matrix or an (indptr, indices)
+    pair with any number of rows and at most the model's number of columns -- and include_of names each user's row of it: one int
+    for all, or an integer array with one entry per user of the model (indexed by user id; the entries of `users` are taken here).
+    The held-out rows are united in on the device, so a pool of negatives sampled once for everybody is passed as it is and no
+    per-user list is built."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
     users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    if include_of is not None:
+        ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude,
+                                  include=include, include_of=_include_of_rows(include_of, users, self.nusers), unite_test=True)
+        return _ranking_result(test[0], ranks, n_adm, k, per_user)
     if include is not None:
         include = _unite_rows(_include_rows(include, users, self.nusers, self.nitems), test)
-    dt = np.float32 if self.use_float else np.float64
     ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude,
                               include=include)
     return _ranking_result(test[0], ranks, n_adm, k, per_user)
@@ -1128,21 +1182,35 @@ class Session:
                                                          _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
-    def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None):
+    def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):
         """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with
         strictly ascending rows) the 0-based position of its item in the user's complete ranked list from the resident factors
         (include/poismf_hip.h section 1g); exclude_seen / exclude as in topn_batch.  Returns (ranks uint32, one per cell in row
         order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m], the admissible items of each user).  include (same two
         forms, passed as given) gives every user a candidate list of its own: a cell is ranked among that list only, minus the
-        exclusions, only those rows of B are read, and a cell whose item is not listed gets RANK_EXCLUDED too (section 1j)."""
+        exclusions, only those rows of B are read, and a cell whose item is not listed gets RANK_EXCLUDED too (section 1j).
+        include_of makes `include` a TABLE of lists shared between users (G >= 1 rows) and names each user's row of it -- an integer
+        array with one entry per batch entry, or one int for all (section 1k): the same answers, the table read once and the rows
+        of B shared by the users of a list.  unite_test (with include_of only) ranks every user among its list united with its own
+        held-out row, which is what a shared pool of negatives needs."""
         users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, self.dimA, self.dimB, self.k)
         m = len(users)
-        if include is not None:
+        if include_of is not None:
+            lp, li, lof = _shared_table_args(include, include_of, m, self.dimB)
+        elif unite_test:
+            raise ValueError("unite_test needs include_of: a list per user has its held-out row united in by the caller")
+        elif include is not None:
             ip, ii = _rank_include_list(include, m, self.dimB)
         if exclude_seen:
             _outside_shard(users, self.shardA)
         ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
         if m == 0:
+            return ranks, n_adm
+        if include_of is not None:
+            _batch_rc(self.lib.poismf_hip_session_rank_shared(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), _ptr(lp), _opt_ptr(li),
+                                                              len(lp) - 1, _ptr(lof), int(bool(unite_test)), int(bool(exclude_seen)),
+                                                              _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)),
+                      "ranks")
             return ranks, n_adm
         if include is not None:
             _batch_rc(self.lib.poismf_hip_session_rank_include(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), _ptr(ip), _opt_ptr(ii),
@@ -1153,10 +1221,15 @@ class Session:
                                                          _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
         return ranks, n_adm
 
-    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None):
+    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None):
         """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
-        CSR (nothing is uploaded), exclude leaves out more; include as there (sampled evaluation, section 1j)."""
+        CSR (nothing is uploaded), exclude leaves out more; include as there (sampled evaluation, section 1j), include with
+        include_of as there too (pools shared between users, section 1k)."""
         users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.dimA, self.dimB)
+        if include_of is not None:
+            ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include,
+                                           include_of=_include_of_rows(include_of, users, self.dimA), unite_test=True)
+            return _ranking_result(test[0], ranks, n_adm, k, per_user)
         if include is not None:
             include = _unite_rows(_include_rows(include, users, self.dimA, self.dimB), test)
         ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include)

@@ -652,6 +652,26 @@ int poismf_hip_session_rank_include(poismf_hip_session* s, const sparse_ix* user
                                        out_n_adm);
 }
 
+// Batched exact ranks among candidate lists shared between users from the resident (compact) factors (rank_shared.hip;
+// include/poismf_hip.h section 1k), ordered as the calls above and in the same scratch.
+int poismf_hip_session_rank_shared(poismf_hip_session* s, const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr,
+                                   const sparse_ix* test_indices, const sparse_ix* list_indptr, const sparse_ix* list_indices, size_t n_lists,
+                                   const sparse_ix* list_of, int unite_test, int exclude_seen, const sparse_ix* excl_indptr,
+                                   const sparse_ix* excl_indices, unsigned int* out_rank, unsigned int* out_n_adm)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
+    if (const int rc = poismf_hip_rank_shared_check(users, n_users, s->dimA, s->dimB, s->k, test_indptr, test_indices, list_indptr, list_indices,
+                                                    n_lists, list_of, excl_indptr, excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_rank_shared_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, test_indptr, test_indices, list_indptr,
+                                      list_indices, n_lists, list_of, unite_test != 0, exclude_seen ? &seen : nullptr, excl_indptr, excl_indices,
+                                      &s->d_topn, &s->topn_cap, out_rank, out_n_adm);
+}
+
 #ifdef PMF_PROBE
 // development only: the head words of the team buffer (a -DPMF_PROBE build sums phase cycles of the last team launch in [8, 16))
 extern "C" __attribute__((visibility("default"))) int poismf_hip_debug_team_head(poismf_hip_session* s, unsigned long long* out)

@@ -1,5 +1,5 @@
 // tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip) and the batched ranks
-// (rank_batch.hip, rank_include.hip) have in common, and what the session (session.hip) hands to their cores
+// (rank_batch.hip, rank_include.hip, rank_shared.hip) have in common, and what the session (session.hip) hands to their cores
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -71,6 +71,16 @@ int poismf_hip_rank_include_run(hipStream_t stream, const real_t* dA, const real
                                 const sparse_ix* incl_indptr, const sparse_ix* incl_indices, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
                                 const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, unsigned int* out_rank,
                                 unsigned int* out_n_adm);
+
+// (rank_shared.hip; section 1k) the same pair for the ranks among lists shared between users: list_of[i] names user i's row of the table
+int poismf_hip_rank_shared_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
+                                 const sparse_ix* test_indices, const sparse_ix* list_indptr, const sparse_ix* list_indices, size_t n_lists,
+                                 const sparse_ix* list_of, const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_rank_shared_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                               const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices,
+                               const sparse_ix* list_indptr, const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of,
+                               bool unite_test, PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                               void** d_scratch, size_t* scratch_cap, unsigned int* out_rank, unsigned int* out_n_adm);
 
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
