@@ -31,6 +31,10 @@ constexpr bool tu_has(int kmethod) { return PMF_TU == -1 || PMF_TU == kmethod; }
 template <class EV, class = void> struct cold_constants : std::false_type {};
 template <class EV> struct cold_constants<EV, std::void_t<decltype(EV::COLD_CONSTANTS)>> : std::integral_constant<bool, EV::COLD_CONSTANTS> {};
 
+// An engine with idle_tile() (reg_eval.hpp) is told when a row has no tile to gather.
+template <class EV, class = void> struct has_idle_tile : std::false_type {};
+template <class EV> struct has_idle_tile<EV, std::void_t<decltype(&EV::idle_tile)>> : std::true_type {};
+
 // Everything after the row's tile has been requested: starting point, per-row constant term, inner solver, store.
 template <class EV, class T, int NC, int METHOD>
 __device__ __forceinline__ void solve_row(const HalfArgs<T>& a, EV& ev, const T (&bs)[NC], unsigned lrow, unsigned nnz)
@@ -197,6 +201,7 @@ __device__ __forceinline__ void sweep_rows(const HalfArgs<T>& a, EV& ev, unsigne
         while (t0 < a.nrows) {
             const unsigned long long p0 = ((unsigned long long)d0.p0_hi << 32) | d0.p0_lo;
             if (d0.nnz != 0) ev.gather(a.values + p0, d0.nnz);                  // indices are here: request the tile
+            else if constexpr (has_idle_tile<EV>::value) ev.idle_tile();
             const unsigned t2 = ticket();
             const RowDesc d2 = fetch(t2);
             if (t1 < a.nrows) ev.fetch_meta(a.indices + (((unsigned long long)d1.p0_hi << 32) | d1.p0_lo), d1.nnz);

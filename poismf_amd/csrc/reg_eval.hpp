@@ -118,6 +118,25 @@ __device__ __forceinline__ void fold16_banked(const float (&p)[16], float (&q)[8
         : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7]),
           "v"(p[8]), "v"(p[9]), "v"(p[10]), "v"(p[11]), "v"(p[12]), "v"(p[13]), "v"(p[14]), "v"(p[15]));
 }
+// The same level for TWELVE inputs (the last batch of S = 12, 28, 44: four pairs and four singles).  A single is one DPP add over
+// all four banks.  (Every other partial batch the kernels have -- 4 or 8 steps -- is singles only, which the generic fold_level
+// already turns into one DPP add each.)
+#define PMF_FOLD1(CTRL, Q, A) "v_add_f32_dpp " Q ", " A ", " A " " CTRL " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void fold12_banked(const float (&p)[16], float (&q)[8])
+{
+    asm("s_nop 1\n\t"
+        PMF_FOLD2("row_ror:8", "0x3", "0xc", "%0", "%8", "%16")
+        PMF_FOLD2("row_ror:8", "0x3", "0xc", "%1", "%9", "%17")
+        PMF_FOLD2("row_ror:8", "0x3", "0xc", "%2", "%10", "%18")
+        PMF_FOLD2("row_ror:8", "0x3", "0xc", "%3", "%11", "%19")
+        PMF_FOLD1("row_ror:8", "%4", "%12")
+        PMF_FOLD1("row_ror:8", "%5", "%13")
+        PMF_FOLD1("row_ror:8", "%6", "%14")
+        PMF_FOLD1("row_ror:8", "%7", "%15")
+        : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5]), "=&v"(q[6]), "=&v"(q[7])
+        : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7]),
+          "v"(p[8]), "v"(p[9]), "v"(p[10]), "v"(p[11]));
+}
 __device__ __forceinline__ void fold8_banked(const float (&q)[8], float (&r)[4])
 {
     asm("s_nop 1\n\t"
@@ -167,6 +186,9 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
     static constexpr int SN = Slot<T>::N;
     static constexpr int G = G_, NS = NS_;
     static constexpr bool PAIRED = PAIR_;
+    // The paired S = 40 instance is the one that pays for the lean PG call (PG_LEAN) and for the gather's per-lane multiplier with registers
+    // (227 -> 232 VGPRs; every other instance needs fewer than before): it keeps the masked point, the accumulate and the select per step.
+    static constexpr bool ROOMY = !(PAIR_ && S >= 40);
     static_assert(!PAIR_ || (SN == 4 && G_ == 16 && NS_ == 1 && NW_ == 1 && M_ == 1 && S % 2 == 0), "step pairs: fp32 one-wave tiles of whole pairs");
     typedef T V2 __attribute__((ext_vector_type(2)));
     static constexpr int JG = WAVE / G;           // nonzeros per step
@@ -203,6 +225,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
     int lane, g, jg, wid;
     int jlane;      // JG g + jg
     bool cls8, cls4, cls2, cls1;
+    int xor32_addr; // floats: the ds_bpermute address of lane ^ 32 (combine_groups), a function of the lane alone
     struct ElemOf {   // factor dimension held in element i of this lane (computed, not kept: registers are what sets the waves per SIMD)
         int g;
         __device__ __forceinline__ int operator[](int i) const { return (g + G * (i / SN)) * SN + i % SN; }
@@ -254,6 +277,9 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
         g = lane & (G - 1); elem.g = g; jg = lane / G; wid = NW > 1 ? (int)(threadIdx.x / WAVE) : 0;
         jlane = JG * g + jg;
         cls8 = (lane & 8) != 0; cls4 = (lane & 4) != 0; cls2 = (lane & 2) != 0; cls1 = (lane & 1) != 0;
+        // (opaque: left visible, the compiler rebuilds the address from the lane number wherever it is used -- in every pass)
+        xor32_addr = (lane ^ 32) << 2;
+        asm volatile("" : "+v"(xor32_addr));
 #pragma unroll
         for (int n = 0; n < NS; n++) {
             const int q = g + G * n;
@@ -590,11 +616,22 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
         }
         // byte offset of this lane's slot of factor row c: 24-bit multiply-add, 32-bit result (the host only takes
         // this engine when the factor has < 2^24 rows and < 4 GiB).  Lanes whose slot does not exist read the first
-        // 16 bytes of the zero row instead.
+        // 16 bytes of the zero row instead: their multiplier is 0 and their base the zero row's offset, two per-lane
+        // constants of the row instead of a select per step.
         const unsigned rowbytes = (unsigned)ldF * (unsigned)sizeof(T);
-        unsigned lane_off[NS];
+        // (ROOMY false: the select per step, and the zero row's first bytes through offset 0)
+        unsigned lane_mul[NS], lane_off[NS];
 #pragma unroll
-        for (int n = 0; n < NS; n++) lane_off[n] = slot_on[n] ? (unsigned)((g + G * n) * 16) : 0u;
+        for (int n = 0; n < NS; n++) {
+            const unsigned slot_off = (unsigned)((g + G * n) * 16);
+            if constexpr (ROOMY) {
+                lane_mul[n] = slot_on[n] ? rowbytes : 0u;
+                lane_off[n] = slot_on[n] ? slot_off : __umul24(zero_row, rowbytes);
+            } else {
+                lane_mul[n] = rowbytes;
+                lane_off[n] = slot_on[n] ? slot_off : 0u;
+            }
+        }
         SU raw[PAIRED ? S : 1];   // PAIRED: the loads land here, all in flight before the first is waited for
         static_for<0, S>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
@@ -602,7 +639,9 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
             const unsigned c = group_bcast<G, s % G>(idx[s / G]);
 #pragma unroll
             for (int n = 0; n < NS; n++) {
-                const unsigned off = __umul24(slot_on[n] ? c : zero_row, rowbytes) + lane_off[n];
+                unsigned row = c;
+                if constexpr (!ROOMY) row = slot_on[n] ? c : zero_row;
+                const unsigned off = __umul24(row, lane_mul[n]) + lane_off[n];
                 const SU v = *(const SU*)((const char*)F + (size_t)off);
                 if constexpr (PAIRED) raw[s] = v;
                 else {
@@ -625,10 +664,36 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
             }
         }
     }
+    // A row without nonzeros has no tile.  Saying so -- zeros -- keeps the paired tile from being carried from one row of the kernel's loop to the
+    // next: carried, its registers meet the gather's swapped pairs at the loop head, and how many of those copies the compiler can fold away
+    // changes with unrelated edits of the pass (16 registers more in every instance, S = 24 and 28 in scratch, once both exchanges of
+    // combine_groups had lost their address arithmetic).  The empty asm pins the moves to the empty row's own path: without it they are placed
+    // in front of the branch and every row pays S / 2 * 4 of them.
+    __device__ __forceinline__ void idle_tile()
+    {
+        if constexpr (PAIRED) {
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < S / 2; i++) {
+#pragma unroll
+                for (int e = 0; e < SN; e++) tp[i][e] = (V2){ (T)0, (T)0 };
+            }
+        }
+    }
     __device__ __forceinline__ void set_point(const T (&x)[NC])
     {
 #pragma unroll
         for (int i = 0; i < NC; i++) a[i] = act[i] ? x[i] : (T)0;
+    }
+
+    // PG (solvers.hpp, pg_row): the point is zero wherever `act` is false -- load_vec leaves it so, and every update keeps it so: the
+    // tile, the shift and with them the gradient are zero there (or, after a division by a zero prediction, NaN), and the update ends
+    // in x > 0 ? x : 0, which sends both to +0.  Nothing to mask, and `a` is the caller's x itself, not a second copy.
+    static constexpr bool PG_LEAN = ROOMY;
+    __device__ __forceinline__ void set_point_as_is(const T (&x)[NC])
+    {
+#pragma unroll
+        for (int i = 0; i < NC; i++) a[i] = x[i];
     }
 
     // this lane's share of F[ind_j] . a for step s
@@ -679,6 +744,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
         constexpr int N8 = N < 8 ? N : 8;
         constexpr bool F32 = std::is_same<T, float>::value;
         if constexpr (F32 && G == 16 && N == 16) fold16_banked(p, q);             // row_ror:8           lane ^ 8
+        else if constexpr (F32 && G == 16 && N == 12) fold12_banked(p, q);
         else if constexpr (G == 16) fold_level<0x128, 8, N>(cls8, p, q);
         else {
 #pragma unroll
@@ -694,7 +760,8 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
     }
 
     // add up the JG groups' partial sums (every group ends with the total) and accumulate
-    __device__ __forceinline__ void combine_groups(T (&part)[NC], T (&acc)[NC]) const
+    // FRESH: the caller's acc is all zeros (PG): the total itself is handed back, no 0 + total
+    template <bool FRESH = false> __device__ __forceinline__ void combine_groups(T (&part)[NC], T (&acc)[NC]) const
     {
         if constexpr (G == 8) {
 #pragma unroll
@@ -717,19 +784,23 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
 #pragma unroll
             for (int i = 0; i < NC; i++) part[i] = xor_sum<32>(part[i]);
         } else {
+            // lane ^ 16 stays inside a half-wave: ds_swizzle in bit-mask mode (and 0x1f, or 0, xor 0x10) needs no address register;
+            // lane ^ 32: the address is a launch constant (init).  Same lanes, same addends as __shfl_xor, which builds its
+            // address -- ten VALU instructions for the two -- wherever it is called.
 #pragma unroll
-            for (int i = 0; i < NC; i++) part[i] += __shfl_xor(part[i], 16);
+            for (int i = 0; i < NC; i++) part[i] += __builtin_bit_cast(T, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, part[i]), 0x401f));
 #pragma unroll
-            for (int i = 0; i < NC; i++) part[i] += __shfl_xor(part[i], 32);
+            for (int i = 0; i < NC; i++) part[i] += __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(xor32_addr, __builtin_bit_cast(int, part[i])));
         }
 #pragma unroll
-        for (int i = 0; i < NC; i++) acc[i] += part[i];
+        for (int i = 0; i < NC; i++) acc[i] = FRESH ? part[i] : acc[i] + part[i];
     }
 
     // Same contract as RowEval::eval (store is not supported here: pq_cap == 0)
     // FROM_CACHE: the predictions are those kept in pv (p = T.x, advanced by the accepted step): no dots, no butterfly --
     // the backward half of a pass only
-    template <bool WANT_F, bool WANT_G, bool FROM_CACHE = false> __device__ __forceinline__ double eval(T sgn, T (&acc)[NC], T* store = nullptr)
+    // FRESH: acc is all zeros on entry (PG's gradient): the sums are handed back as they are instead of being added to it
+    template <bool WANT_F, bool WANT_G, bool FROM_CACHE = false, bool FRESH = false> __device__ __forceinline__ double eval(T sgn, T (&acc)[NC], T* store = nullptr)
     {
         n_eval++;
         PMF_STAMP(*this, 0);
@@ -809,7 +880,7 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
             T tot[NC];
 #pragma unroll
             for (int i = 0; i < NC; i++) tot[i] = (T)0;
-            if constexpr (WANT_G) combine_groups(part, tot);
+            if constexpr (WANT_G) combine_groups<true>(part, tot);
             PMF_STAMP(*this, 6);
             double lsum = 0.0;
             if constexpr (WANT_F) lsum = wave_sum(lpart);
@@ -823,11 +894,11 @@ template <class T, int S, int G_ = 16, int NS_ = 1, int NW_ = 1, int M_ = 1, boo
             PMF_STAMP(*this, 8);
             if constexpr (WANT_G) {
 #pragma unroll
-                for (int i = 0; i < NC; i++) acc[i] += tot[i];
+                for (int i = 0; i < NC; i++) acc[i] = FRESH ? tot[i] : acc[i] + tot[i];
             }
             return lsum;
         } else {
-            if constexpr (WANT_G) combine_groups(part, acc);
+            if constexpr (WANT_G) combine_groups<FRESH>(part, acc);
             PMF_STAMP(*this, 6);
             if constexpr (WANT_F) return wave_sum(lpart);
             else return 0.0;

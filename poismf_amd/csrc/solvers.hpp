@@ -32,14 +32,24 @@ struct SolveStats { int niter = 0, nfeval = 0, rc = 0; };
 // ------------------------------------------------------------------------------------------------
 // Proximal gradient
 // ------------------------------------------------------------------------------------------------
+// An engine with `static constexpr bool PG_LEAN = true` (reg_eval.hpp) takes the point as it is -- x is zero outside the row's k elements
+// at load and after every update below, so there is nothing to mask -- and hands the gradient back instead of adding it to zeros.
+template <class EV, class = void> struct pg_lean : std::false_type {};
+template <class EV> struct pg_lean<EV, std::void_t<decltype(EV::PG_LEAN)>> : std::integral_constant<bool, EV::PG_LEAN> {};
+
 template <class EV, class T, int NC>
 __device__ __forceinline__ void pg_row(EV& ev, const RowParams<T>& P, T (&x)[NC], const T (&shift)[NC])
 {
     for (int u = 0; u < P.maxupd; u++) {
-        ev.set_point(x);
         T g[NC];
         PMF_EW g[i] = (T)0;
-        ev.template eval<false, true>((T)1, g);                   // calc_grad_pgd, ref: :126-133
+        if constexpr (pg_lean<EV>::value) {
+            ev.set_point_as_is(x);
+            ev.template eval<false, true, false, true>((T)1, g);  // calc_grad_pgd, ref: :126-133
+        } else {
+            ev.set_point(x);
+            ev.template eval<false, true>((T)1, g);
+        }
         PMF_EW {
             x[i] = fma_t(P.step, g[i], x[i]);              // a += step * grad
             x[i] = x[i] + shift[i];                                // a += (pre-scaled) Bsum
