@@ -445,6 +445,50 @@ POISMF_HIP_API size_t poismf_hip_rank_shared_scratch_bytes(size_t n_users, size_
         size_t n_list_cells, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1l. Deep batched top-N: section 1f's answer for n_top up to POISMF_HIP_TOPN_DEEP_MAX_N_TOP = 1024 -- candidate generation for a
+ *     re-ranker, the stage whose output sections 1h and 1i consume.  (The reference's topN has no cap on n_top but serves one user
+ *     per call, ref: src/topN.c:112-284.)
+ *
+ * Arguments, E(u), score(u, j), the total order, the output arrays and the return codes are section 1f's, except:
+ *
+ *   range        n_top is 1 .. POISMF_HIP_TOPN_DEEP_MAX_N_TOP.  Where n_top <= POISMF_HIP_TOPN_BATCH_MAX_N_TOP and every user keeps
+ *                n_top admissible items, items and score bits are those of poismf_hip_topn_batch.
+ *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under "score descending, then item index ascending": a function of
+ *                (A[u], B, E(u), n_top) alone -- not of the other users, their order, how the items are cut into slices or how the
+ *                batch is cut into chunks.
+ *   short rows   are not an error (section 1h's rule, not 1f's): when only c < n_top items are admissible, entries c .. n_top-1
+ *                of the row are POISMF_HIP_TOPN_NONE in out_ix and -inf in out_score.  n_top > dimB is therefore valid.  No
+ *                per-user pre-check is made and nothing of a resident row is downloaded to count a union.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for n_top == 0,
+ * n_top > POISMF_HIP_TOPN_DEEP_MAX_N_TOP and everything that is 2 in section 1f except "too few items left" (an exclusion row may
+ * hold up to min(dimB, POISMF_HIP_TOPN_BATCH_BUDGET_MB / 8 Mi) entries, as there).  n_users == 0 returns 0.
+ *
+ * Memory: a user's candidate list cannot live in LDS at this depth (section 1f keeps n_top + 48 entries for each of a
+ * workgroup's 64 users there).  It lives in the call's scratch: per (user, slice of the items) `cap` entries of (score, item),
+ * cap = the power of two at or above n_top + max(n_top / 2, 64) (2048 at n_top = 1024), sorted down to the best n_top by the
+ * list's own wave whenever fewer than 64 slots are free.  ONE allocation per call (session: the one sections 1f - 1k share; it grows
+ * and never shrinks under them) of at most POISMF_HIP_TOPN_DEEP_BUDGET_MB MiB for any n_users;
+ * poismf_hip_topn_deep_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate, and it never decreases
+ * when n_users grows.  The budget's arithmetic, for the largest case (float, n_top = 1024, cap = 2048, 8 B per entry):
+ *   - the lists are sized for items cut into slices until a chunk of users has 512 workgroups = two on each of the 256 CUs; 64
+ *     lists each: 64 x 512 x 2048 x 8 B = 512 MiB.  A chunk of u users adds at most one more list per user: u x 2048 x 8 B;
+ *   - exclusion indices of a chunk: 128 MiB at most (section 1f's area);  results: u x 1024 x 8 B;  users and row pointers: u x 8 B.
+ *   1024 MiB leave 384 MiB for the parts that grow with u: chunks of 16 320 users = 255 tiles of 64, two workgroups per CU before
+ *   the items are cut at all.  In double an entry is 12 B: 768 MiB of lists for 512 workgroups, chunks of 3 584 users.  The chunk
+ *   grows as n_top shrinks (262 144 users at most, section 1f's bound).  (Where a CU's LDS holds only one workgroup, as at this
+ *   depth, the planner stops cutting at 256 workgroups: more would add lists to fill and merge, and no parallelism.)
+ * poismf_hip_topn_deep's own copies of B and of A (all of A, or only the batch's rows) come on top.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_DEEP_MAX_N_TOP 1024    /* largest n_top of the deep entry points */
+#define POISMF_HIP_TOPN_DEEP_BUDGET_MB 1024    /* upper bound of their scratch allocation, MiB */
+POISMF_HIP_API int poismf_hip_topn_deep(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_deep_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -576,6 +620,11 @@ POISMF_HIP_API int poismf_hip_session_topn(poismf_hip_session *s, size_t user,
 /* Section 1f from the session-resident factors (and, with exclude_seen, the session's own CSR rows).  Ordered after the work already
  * enqueued on the session stream; reads the compact factors, as poismf_hip_session_llk does. */
 POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1l from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_deep(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_include", "poismf_hip_session_topn_include", "poismf_hip_topn_include_scratch_bytes", "poismf_hip_topn_include_slice",
     "poismf_hip_topn_shared", "poismf_hip_session_topn_shared", "poismf_hip_topn_shared_scratch_bytes",
     "poismf_hip_rank_shared", "poismf_hip_session_rank_shared", "poismf_hip_rank_shared_scratch_bytes",
+    "poismf_hip_topn_deep", "poismf_hip_session_topn_deep", "poismf_hip_topn_deep_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -66,6 +67,8 @@ TOPN_NONE = 2**64 - 1               # POISMF_HIP_TOPN_NONE and POISMF_HIP_TOPN_I
 TOPN_INCLUDE_MAX_ROW = 16777216     # (tests/test_topn_include_cpu.py compares them with the header)
 TOPN_SHARED_MAX_CELLS = 2**24       # POISMF_HIP_TOPN_SHARED_MAX_CELLS of section 1i (tests/test_topn_shared_cpu.py compares the two)
 RANK_SHARED_CHUNK_CELLS = 2**19     # POISMF_HIP_RANK_SHARED_CHUNK_CELLS of section 1k (tests/test_rank_shared_cpu.py compares the two)
+TOPN_DEEP_MAX_N_TOP = 1024          # POISMF_HIP_TOPN_DEEP_MAX_N_TOP and POISMF_HIP_TOPN_DEEP_BUDGET_MB of section 1l
+TOPN_DEEP_BUDGET_MB = 1024          # (tests/test_topn_deep_cpu.py compares them with the header)
 
 
 def load_library(use_float):
@@ -148,6 +151,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_batch.restype = i
     lib.poismf_hip_topn_batch_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_batch_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_deep.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp]
+    lib.poismf_hip_topn_deep.restype = i
+    lib.poismf_hip_session_topn_deep.argtypes = [vp, vp, sz, sz, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_deep.restype = i
+    lib.poismf_hip_topn_deep_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_topn_deep_scratch_bytes.restype = sz
     lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_rank_batch.restype = i
     lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
@@ -580,6 +589,27 @@ def _topn_batch_args(users, n, exclude, dimA, dimB):
     return users, indptr, indices
 
 
+def _topn_deep_args(users, n, exclude, dimA, dimB):
+    """The argument checks of the deep batched top-N (include/poismf_hip.h section 1l) that need no device, as the library itself
+    makes them: n up to TOPN_DEEP_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).  Returns (users,
+    excl_indptr or None, excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_DEEP_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the deep batched limit of {TOPN_DEEP_MAX_N_TOP}")
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if exclude is None:
+        return users, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, indptr, indices
+
+
 def _topn_include_args(users, n, include, exclude, dimA, dimB):
     """The argument checks of the batched top-N over include lists (include/poismf_hip.h section 1h) that need no device, as the
     library itself makes them: n may exceed what a user has left (short rows are padded).  Returns (users, incl_indptr,
@@ -719,6 +749,33 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
 
 
 PoisMF.topN_batch = _topN_batch
+
+
+def _topN_deep(self, users, n=1000, exclude=None, output_score=False):
+    """topN_batch for deep lists -- candidate generation for a re-ranker: the n <= TOPN_DEEP_MAX_N_TOP best items of every user in
+    `users` under "score descending, item index ascending", in one fused pass on the GPU (include/poismf_hip.h section 1l).
+    exclude as in topN_batch.  n may exceed what a user has left, or the number of items: the row is padded with TOPN_NONE and
+    -inf.  Up to n = TOPN_BATCH_MAX_N_TOP the answers are topN_batch's bit for bit, which keeps its lists on chip and is the faster
+    of the two there.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    users, indptr, indices = _topn_deep_args(users, n, exclude, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    m, n = len(users), int(n)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    lib = load_library(self.use_float)
+    _batch_rc(lib.poismf_hip_topn_deep(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
+                                       _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                       _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+    return ix, sc
+
+
+PoisMF.topN_deep = _topN_deep
 
 
 def _rank_include_list(include, m, dimB):
@@ -1180,6 +1237,25 @@ class Session:
         _batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
                                                          _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
                                                          _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
+
+    def topn_deep(self, users, top_n=1000, exclude_seen=False, exclude=None, output_score=False):
+        """topn_batch for deep lists: the top_n <= TOPN_DEEP_MAX_N_TOP best items of every user in `users` from the resident factors
+        in one fused pass (include/poismf_hip.h section 1l); order, scores, exclude_seen and exclude as in topn_batch.  top_n may
+        exceed what a user has left, or the number of items: the row is padded with TOPN_NONE and -inf.  Up to
+        TOPN_BATCH_MAX_N_TOP the answers are topn_batch's bit for bit.  Returns (items uint64 [m x top_n], scores [m x top_n], empty
+        unless output_score)."""
+        users, indptr, indices = _topn_deep_args(users, top_n, exclude, self.dimA, self.dimB)
+        m, n = len(users), int(top_n)
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
+        if m == 0:
+            return ix, sc
+        _batch_rc(self.lib.poismf_hip_session_topn_deep(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
+                                                        _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):

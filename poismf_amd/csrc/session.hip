@@ -13,6 +13,7 @@
 #include "session.hpp"
 #include "cores.hpp"
 #include "tb_batch.hpp"
+#include "tb_deep.hpp"
 
 // Streams are recycled across sessions: creating one costs 7.5 ms on this stack (scripts/probes/h2d_probe.hip) -- with two
 // per run_poismf call that was most of the call's set-up time on config C2.  Idle streams wait here, per device.
@@ -578,6 +579,21 @@ int poismf_hip_session_topn_batch(poismf_hip_session* s, const sparse_ix* users,
     HIP_TRY(hipSetDevice(s->device));
     return poismf_hip_topn_batch_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, exclude_seen ? &seen : nullptr,
                                      excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
+}
+
+// Deep batched top-N from the resident (compact) factors (topn_deep.hip; include/poismf_hip.h section 1l), ordered as the call above and
+// in the same scratch, which it may grow: a short row is padded, so nothing is counted beforehand.
+int poismf_hip_session_topn_deep(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, int exclude_seen,
+                                 const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_deep_check(users, n_users, n_top, s->dimA, s->dimB, s->k, excl_indptr, excl_indices)) return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_deep_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, exclude_seen ? &seen : nullptr,
+                                    excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
 // Batched top-N over per-user include lists from the resident (compact) factors (topn_include.hip; include/poismf_hip.h section 1h),

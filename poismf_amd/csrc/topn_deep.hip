@@ -1,0 +1,402 @@
+// topn_deep.hip -- deep batched top-N (include/poismf_hip.h, section 1l): section 1f's answer for n_top up to 1024, a short row padded.
+//
+//   score(u, j) = the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t   (tb_tile.hpp)
+//
+// The walk, the threshold test and the exclusion look-up are topn_batch.hip's: a workgroup of four waves owns 64 users and a slice of
+// the items, scores 64 x 64 at a time (fp32 on the f32 MFMA, fp64 on the VALU chain) and lets a score die in registers unless it beats
+// the user's threshold (the n_top-th best so far; registers, with its copy and the item in LDS).  What differs is where a survivor goes,
+// and that a pass's survivors are queued in LDS first, so that their exclusion look-ups run side by side over the lanes.
+// At this depth 64 lists do not fit LDS, so a list lives in the call's scratch, [user][slice][cap] with cap = td_cap(n_top) a power of
+// two; the append position still comes from an integer counter in LDS.  A list belongs to one wave.  Whenever fewer than 64 slots are
+// free (a step over 64 item columns can add 64 candidates to one user) the wave stages the list into its own LDS area, orders it with a
+// bitonic network (td_sort) and writes the best n_top back in order; the threshold becomes the last of them.  The appends are global
+// stores of some lanes read back by others, so a workgroup-scope fence stands between them (td_global_sync).  Arrival order in a list
+// varies from run to run; positions under a strict total order do not, so the output is deterministic.
+// topn_deep_merge_kernel gives an entry of a user's nslices sorted lists its final position: its position in its own list plus, for every
+// other list, the number of entries there that come before it (binary search).  Nothing of the merge lives in LDS but one counter.
+// With one slice the tile kernel writes the results itself.  No float atomics anywhere.
+//
+// The host side cuts the batch into chunks of users so that ONE scratch allocation of at most POISMF_HIP_TOPN_DEEP_BUDGET_MB holds a
+// chunk's user list, exclusion lists, candidate lists and results (TdLayout; poismf_hip_topn_deep_scratch_bytes reports its size).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <limits>
+#include <vector>
+
+#include "../../include/poismf_hip.h"
+#include "devmem.hpp"
+#include "tb_tile.hpp"
+#include "tb_batch.hpp"
+#include "tb_deep.hpp"
+
+namespace {
+
+constexpr int TD_ROOM = TB_TJ;                            // free slots a list must have before a step over 64 item columns
+constexpr size_t TD_LDS_LIMIT = 156 * 1024;
+constexpr size_t TD_TARGET_WGS = 512;                     // items are split over workgroups until a chunk has about this many, two per CU ...
+constexpr size_t TD_LDS_CU = 160 * 1024;                  // ... or one per CU where a CU's LDS holds only one: a second round of workgroups would
+                                                          // add lists to fill, prune and merge, and no parallelism
+constexpr size_t TD_IDX_MAX = TB_BUDGET / 2 / sizeof(unsigned);   // exclusion indices a chunk may carry: section 1f's
+constexpr int TD_MERGE_WG = 256;
+
+struct TdArgs {
+    const real_t* A;                  // rows addressed by `users`
+    const real_t* B;                  // [dimB x k]
+    const unsigned* users;            // the chunk's rows of A
+    unsigned n_users, dimB;
+    int k;
+    unsigned n_top, cap;              // list capacity in scratch
+    unsigned nslices, tiles_per_slice;
+    TbExcl excl;                      // E(u) of the chunk's users
+    real_t* list_score;               // [n_users][nslices][cap]
+    unsigned* list_ix;
+    real_t* fin_score;                // where a slice's sorted best n_top go: [n_users][nslices][fin_stride]
+    unsigned* fin_ix;
+    unsigned fin_stride;
+};
+
+template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_deep_tile_kernel(TdArgs a)
+{
+    extern __shared__ __align__(16) unsigned char td_smem[];
+    T* As = (T*)td_smem;                                  // [TB_TU][TB_KS]
+    T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
+    const size_t stage = a.cap > TD_STAGE_MIN ? a.cap : TD_STAGE_MIN;
+    T* Ss = Bs + TB_TJ * TB_KS;                           // [4 waves][stage] staged scores of the list being pruned
+    unsigned* Sj = (unsigned*)(Ss + 4 * stage);           // [4 waves][stage] ... and items
+    T* thr_s = (T*)(Sj + 4 * stage);                      // [TB_TU] threshold: score ...
+    unsigned* thr_j = (unsigned*)(thr_s + TB_TU);         // ... and item
+    unsigned* cnt = thr_j + TB_TU;                        // [TB_TU] entries in the list
+    unsigned* uid = cnt + TB_TU;                          // [TB_TU] row of A, TB_NONE beyond the chunk
+
+    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned u_base = blockIdx.x * TB_TU;
+    const T neg_inf = -std::numeric_limits<T>::infinity();
+    if (tid < TB_TU) {
+        const unsigned u = u_base + tid;
+        uid[tid] = u < a.n_users ? a.users[u] : TB_NONE;
+        cnt[tid] = 0;
+        thr_s[tid] = neg_inf;
+        thr_j[tid] = 0;
+    }
+    __syncthreads();
+
+    const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
+    const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
+    const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
+    const unsigned col = lane & 15, quad = lane >> 4;
+    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
+    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
+    auto list_of = [&](unsigned uu) { return ((size_t)(u_base + uu) * a.nslices + blockIdx.y) * a.cap; };
+
+    // Orders list uu (whole wave, uniform arguments).  In the walk: the best min(count, n_top) go back to the list in order, the count and,
+    // once the list is full, the threshold follow.  At the end (`last`): they go to fin_*, the rest of the row marked empty.
+    T* ss = Ss + (size_t)wave * stage;
+    unsigned* sj = Sj + (size_t)wave * stage;
+    auto prune = [&](unsigned uu, bool last) {
+        T* gs = a.list_score + list_of(uu);
+        unsigned* gj = a.list_ix + list_of(uu);
+        const unsigned c = cnt[uu] < a.cap ? cnt[uu] : a.cap;
+        unsigned p = TD_SORT_MIN;
+        while (p < c) p <<= 1;                            // (p <= cap: cap is a power of two >= TD_SORT_MIN)
+        td_global_sync();
+        for (unsigned i = lane; i < p; i += 64) {
+            ss[i] = i < c ? gs[i] : neg_inf;
+            sj[i] = i < c ? gj[i] : TB_NONE;
+        }
+        tb_wave_sync();
+        td_sort(ss, sj, p);
+        const unsigned keep = c < a.n_top ? c : a.n_top;
+        if (!last) {
+            for (unsigned i = lane; i < keep; i += 64) { gs[i] = ss[i]; gj[i] = sj[i]; }
+            if (lane == 0) {
+                cnt[uu] = keep;
+                if (c >= a.n_top) { thr_s[uu] = ss[a.n_top - 1]; thr_j[uu] = sj[a.n_top - 1]; }
+            }
+        } else {
+            const size_t o = ((size_t)(u_base + uu) * a.nslices + blockIdx.y) * a.fin_stride;
+            for (unsigned i = lane; i < a.n_top; i += 64) {
+                a.fin_score[o + i] = i < keep ? ss[i] : neg_inf;
+                a.fin_ix[o + i] = i < keep ? sj[i] : TB_NONE;
+            }
+        }
+        tb_wave_sync();
+        td_global_sync();
+    };
+
+    // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
+    T thr_reg[4];
+    bool u_valid[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
+    bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
+
+    tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, tile0, tile1, user_row, tb_all_items(a.dimB), [&](T (&acc)[4][4], unsigned j_base) {
+        // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone.  Room is
+        // made once per step, for all four passes (TD_ROOM), so the sort's code stands in the loop once ----
+        if (dirty) {
+            const unsigned c_mine = cnt[16 * wave + col];
+            unsigned long long full = __ballot(quad == 0 && c_mine + TD_ROOM > a.cap);
+            if (full) {
+                while (full) {
+                    const unsigned uu = 16 * wave + (unsigned)__builtin_ctzll(full);
+                    full &= full - 1;
+                    prune(uu, false);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; r++) thr_reg[r] = thr_s[urow0 + r];
+            }
+            dirty = false;
+        }
+        // A pass: the scores that beat their user's threshold are queued in the wave's staging area (free between prunes; ballots give
+        // the positions), then the queue is looked up in the exclusion lists and appended 64 entries at a time.  Deep lists keep a good
+        // part of a tile alive, and a look-up is a chain of dependent loads: one per queue entry, side by side over the lanes, costs a
+        // pass as many round trips as it has survivors / 64, not one per (user, item) slot of a lane.
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const unsigned j = j_base + 16 * t + col;
+            unsigned nq = 0;   // (uniform over the wave)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const unsigned uu = urow0 + r;
+                const T s = acc[t][r];
+                const bool alive = j < a.dimB && u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu]);
+                const unsigned long long m = __ballot(alive);
+                if (alive) {
+                    const unsigned q = nq + (unsigned)__popcll(m & ((1ull << lane) - 1));
+                    ss[q] = s;
+                    sj[q] = (uu << 6) | (16 * t + col);   // the wave's user row and the item's place in the tile
+                }
+                nq += (unsigned)__popcll(m);
+            }
+            if (nq) {
+                tb_wave_sync();
+                for (unsigned e = lane; e < nq; e += 64) {   // (nq <= 256 = TD_STAGE_MIN)
+                    const T s = ss[e];
+                    const unsigned uu = sj[e] >> 6, jj = j_base + (sj[e] & 63);
+                    if (!tb_excluded(a.excl, u_base + uu, uid[uu], jj)) {
+                        const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
+                        if (pos < a.cap) {   // (always: a step adds at most TD_ROOM to a list that had as many slots free)
+                            a.list_score[list_of(uu) + pos] = s;
+                            a.list_ix[list_of(uu) + pos] = jj;
+                        }
+                    }
+                }
+                dirty = true;
+                tb_wave_sync();
+            }
+        }
+    });
+
+    // ---- the slice's answer per user: the best min(count, n_top) in order, the rest marked empty ----
+    for (unsigned q = 0; q < 16; q++) {
+        const unsigned uu = 16 * wave + q;
+        if (uid[uu] == TB_NONE) continue;   // (uniform over the wave)
+        prune(uu, true);
+    }
+}
+
+// One workgroup per user: the best n_top of its nslices sorted lists of n_top entries, list sl at lists + sl cap.  An entry's final
+// position is its position in its own list plus the number of entries of every other list that come before it; empty entries
+// (-inf, TB_NONE) end every list and come before nothing.  Positions the real entries do not reach are marked empty.
+__global__ __launch_bounds__(TD_MERGE_WG) void topn_deep_merge_kernel(const real_t* list_score, const unsigned* list_ix, unsigned nslices,
+                                                                      unsigned cap, unsigned n_top, real_t* out_score, unsigned* out_ix)
+{
+    __shared__ unsigned n_real;
+    const unsigned tid = threadIdx.x;
+    const size_t o = (size_t)blockIdx.x * nslices * cap;
+    const real_t* ls = list_score + o;
+    const unsigned* lj = list_ix + o;
+    real_t* os = out_score + (size_t)blockIdx.x * n_top;
+    unsigned* oj = out_ix + (size_t)blockIdx.x * n_top;
+    if (tid == 0) n_real = 0;
+    __syncthreads();
+    for (unsigned sl = tid; sl < nslices; sl += TD_MERGE_WG) {
+        unsigned lo = 0, hi = n_top;   // the list's real entries: the first lo
+        while (lo < hi) {
+            const unsigned mid = (lo + hi) / 2;
+            if (lj[(size_t)sl * cap + mid] != TB_NONE) lo = mid + 1;
+            else hi = mid;
+        }
+        atomicAdd(&n_real, lo);        // (LDS, integer; nslices n_top < 2^32)
+    }
+    __syncthreads();
+    for (unsigned i = (n_real < n_top ? n_real : n_top) + tid; i < n_top; i += TD_MERGE_WG) {
+        os[i] = -std::numeric_limits<real_t>::infinity();
+        oj[i] = TB_NONE;
+    }
+    const unsigned m = nslices * n_top;
+    for (unsigned e = tid; e < m; e += TD_MERGE_WG) {
+        const unsigned own = e / n_top;
+        unsigned rk = e % n_top;
+        const real_t s = ls[(size_t)own * cap + rk];
+        const unsigned j = lj[(size_t)own * cap + rk];
+        if (j == TB_NONE) continue;
+        for (unsigned sl = 0; sl < nslices && rk < n_top; sl++) {
+            if (sl == own) continue;
+            const real_t* ps = ls + (size_t)sl * cap;
+            const unsigned* pj = lj + (size_t)sl * cap;
+            unsigned lo = 0, hi = n_top - rk;   // (n_top - rk better entries or more put this one past the end either way)
+            while (lo < hi) {
+                const unsigned mid = (lo + hi) / 2;
+                if (tb_better(ps[mid], pj[mid], s, j)) lo = mid + 1;
+                else hi = mid;
+            }
+            rk += lo;
+        }
+        if (rk < n_top) { os[rk] = s; oj[rk] = j; }
+    }
+}
+
+// The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
+struct TdLayout {
+    size_t chunk_users;      // users per chunk
+    size_t idx_cap;          // exclusion indices a chunk may carry
+    size_t cap;              // entries of one (user, slice) list
+    size_t list_rows;        // (user, slice) lists
+    size_t users, ex_indptr, ex_indices, list_score, list_ix, out_score, out_ix, total;
+    TdLayout(size_t n_users, size_t n_top, size_t dimB)
+    {
+        const size_t E = sizeof(real_t) + sizeof(unsigned);
+        n_users = std::max<size_t>(n_users, 1);
+        n_top = std::min(std::max<size_t>(n_top, 1), TD_N_TOP_MAX);
+        dimB = std::min<size_t>(std::max<size_t>(dimB, 1), 0x7fffffffull);
+        cap = td_cap(n_top);
+        // lists: users x slices <= TB_TU x TD_TARGET_WGS + users + TB_TU  (tb_slices: at most target / tiles + 1 slices), results: users
+        const size_t rest = TD_BUDGET - TD_IDX_MAX * sizeof(unsigned) - 256;   // (256: alignment of the seven parts)
+        const size_t fixed = 16 + (TB_TU * TD_TARGET_WGS + TB_TU) * cap * E;
+        const size_t per_user = 8 + (cap + n_top) * E;
+        size_t uc = std::min((rest - fixed) / per_user, TB_CHUNK_USERS_MAX);
+        uc -= uc % TB_TU;
+        uc = std::min(uc, n_users);
+        chunk_users = uc;
+        idx_cap = std::min(TD_IDX_MAX, uc * dimB);                             // (no overflow: 2^18 x 2^31)
+        const size_t item_tiles = pmf_ceil_div(dimB, TB_TJ);
+        list_rows = std::min(uc * std::min(item_tiles, TD_TARGET_WGS), TB_TU * TD_TARGET_WGS + TB_TU + uc);
+        TbTake take;
+        users = take(uc * sizeof(unsigned));
+        ex_indptr = take((uc + 1) * sizeof(unsigned));
+        ex_indices = take(idx_cap * sizeof(unsigned));
+        list_score = take(list_rows * cap * sizeof(real_t));
+        list_ix = take(list_rows * cap * sizeof(unsigned));
+        out_score = take(uc * n_top * sizeof(real_t));
+        out_ix = take(uc * n_top * sizeof(unsigned));
+        total = take.o;
+    }
+};
+static_assert((TB_TU * TD_TARGET_WGS + TB_TU) * 2048 * 12 + 16 + TD_IDX_MAX * 4 + 256 + TB_TU * (8 + 3072 * 12) <= TD_BUDGET,
+              "the budget holds the lists of TD_TARGET_WGS workgroups and a tile of users at the deepest n_top in double");
+
+size_t td_lds_bytes(size_t cap)
+{
+    return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + 4 * std::max(cap, TD_STAGE_MIN) * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12);
+}
+static_assert(2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + 4 * 2048 * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12) <= TD_LDS_LIMIT,
+              "the two tiles and four staging areas of the deepest list fit LDS");
+
+}  // namespace
+
+extern "C" size_t poismf_hip_topn_deep_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k)
+{
+    (void)k;   // (the factors' chunks live in LDS: no part of the scratch depends on k)
+    return TdLayout(n_users, n_top, dimB).total;
+}
+
+// The argument checks of both entry points: 0, or 2.  No device call.
+int poismf_hip_topn_deep_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                               const sparse_ix* excl_indptr, const sparse_ix* excl_indices)
+{
+    if (n_top == 0 || n_top > TD_N_TOP_MAX) return 2;
+    if (k < 1 || k > TB_K_MAX || dimB < 1 || dimB > 0x7fffffffull || dimA > 0x7fffffffull) return 2;
+    if (users == nullptr) return 2;
+    for (size_t i = 0; i < n_users; i++)
+        if ((size_t)users[i] >= dimA) return 2;
+    if (excl_indptr != nullptr && !tb_rows_ok(excl_indptr, excl_indices, n_users, dimB, TD_IDX_MAX)) return 2;
+    return 0;
+}
+
+// ---- core on device-resident factors (tb_deep.hpp) ----
+int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                             const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                             const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score)
+{
+    if (seen != nullptr && poismf_hip_topn_seen_sorted(*seen, stream)) return 1;
+    const TdLayout L(n_users, n_top, dimB);
+    TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
+    unsigned char* base = (unsigned char*)*d_scratch;
+
+    const size_t lds = td_lds_bytes(L.cap);
+    if (lds > TD_LDS_LIMIT) return 1;   // (cannot happen: the static_assert above covers the deepest list)
+    auto kern = topn_deep_tile_kernel<real_t, sizeof(real_t) == 4>;
+    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_LIMIT));
+
+    TdArgs a;
+    std::vector<unsigned> hu, hp, hx, hix;
+    for (size_t u0 = 0; u0 < n_users;) {
+        // the chunk: up to chunk_users users whose exclusion lists fit the index area together
+        size_t u1 = u0, nx = 0;
+        while (u1 < n_users && u1 - u0 < L.chunk_users) {
+            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
+            if (u1 > u0 && nx + len > L.idx_cap) break;
+            nx += len;
+            u1++;
+        }
+        const size_t nu = u1 - u0;
+        if (nx > L.idx_cap) return 1;   // (cannot happen: the check bounds a row by the area's smallest size)
+        hu.resize(nu);
+        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
+        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
+        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
+                             hx, stream));
+        const size_t tiles = pmf_ceil_div(nu, TB_TU);
+        const TbSlices sl = tb_slices(tiles, dimB, 2 * lds > TD_LDS_CU ? TD_TARGET_WGS / 2 : TD_TARGET_WGS);
+        const size_t nslices = sl.nslices;
+        if (nu * nslices > L.list_rows) return 1;   // (cannot happen: TdLayout sizes the lists for any slicing of a chunk)
+        a.A = dA;
+        a.B = dB;
+        a.users = (const unsigned*)(base + L.users);
+        a.n_users = (unsigned)nu;
+        a.dimB = (unsigned)dimB;
+        a.k = (int)k;
+        a.n_top = (unsigned)n_top;
+        a.cap = (unsigned)L.cap;
+        a.nslices = (unsigned)nslices;
+        a.tiles_per_slice = (unsigned)sl.tiles_per_slice;
+        a.list_score = (real_t*)(base + L.list_score);
+        a.list_ix = (unsigned*)(base + L.list_ix);
+        // (one slice: its sorted lists are the results; more: they stay at the head of the lists for the merge)
+        a.fin_score = nslices == 1 ? (real_t*)(base + L.out_score) : a.list_score;
+        a.fin_ix = nslices == 1 ? (unsigned*)(base + L.out_ix) : a.list_ix;
+        a.fin_stride = (unsigned)(nslices == 1 ? n_top : L.cap);
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nslices), dim3(TB_WG), lds, stream, a);
+        TB_TRY(hipGetLastError());
+        if (nslices > 1) {
+            hipLaunchKernelGGL(topn_deep_merge_kernel, dim3((unsigned)nu), dim3(TD_MERGE_WG), 0, stream, a.list_score, a.list_ix, (unsigned)nslices,
+                               (unsigned)L.cap, (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
+            TB_TRY(hipGetLastError());
+        }
+        hix.resize(nu * n_top);
+        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
+        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
+        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        u0 = u1;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int poismf_hip_topn_deep(const real_t* A, const real_t* B, int k, size_t dimA, size_t dimB, const sparse_ix* users, size_t n_users,
+                         size_t n_top, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (k < 1 || A == nullptr || B == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_deep_check(users, n_users, n_top, dimA, dimB, (size_t)k, excl_indptr, excl_indices)) return rc;
+    return tb_dropin(A, B, (size_t)k, dimA, dimB, users, n_users,
+                     [&](hipStream_t st, const real_t* dA, const real_t* dB, bool compact, void** d_scratch, size_t* scratch_cap) {
+                         return poismf_hip_topn_deep_run(st, dA, dB, dimB, (size_t)k, compact, users, n_users, n_top, nullptr, excl_indptr,
+                                                         excl_indices, d_scratch, scratch_cap, out_ix, out_score);
+                     });
+}
+
+}  // extern "C"
