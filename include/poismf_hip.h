@@ -731,10 +731,20 @@ POISMF_HIP_API size_t poismf_hip_debug_plan(const unsigned *row_nnz, size_t nrow
  * slots' 52) carries "[KU=<width>]" behind its name. */
 POISMF_HIP_API size_t poismf_hip_debug_plan_widths(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
                           size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
+
+/* The listing of poismf_hip_debug_plan_widths with the engine of the one-wave register launches marked as well: "[quad]" behind the name of a launch
+ * that holds each nonzero in four lanes instead of sixteen (PG on floats, k = 50, the line-padded factor copy; poismf_hip_debug_reg_quad_off). */
+POISMF_HIP_API size_t poismf_hip_debug_plan_engines(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
+                          size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
 /* Testing aid: full != 0 -- the lane launches this process plans from now on take the instances that carry every element of their slots, also
  * where one specialised on the used width exists (the two agree bit for bit; a -DPMF_LANE_KU50=0 build never selects the latter); 0 -- the
  * default again.  Returns the previous setting. */
 POISMF_HIP_API int poismf_hip_debug_lane_full_width(int full);
+
+/* Testing aid: off != 0 -- the one-wave register launches this process plans from now on take the sixteen-lane engine also where the quad engine
+ * exists (PG on floats, k = 50, the line-padded factor copy: four lanes per nonzero, marked "[quad]" by poismf_hip_debug_plan_engines; a
+ * -DPMF_REG_QUAD=0 build never selects it); 0 -- the default again.  Returns the previous setting. */
+POISMF_HIP_API int poismf_hip_debug_reg_quad_off(int off);
 
 /* Number of nonzeros held by this session for half `which` (shard only). */
 POISMF_HIP_API size_t poismf_hip_session_nnz(poismf_hip_session *s, int which);

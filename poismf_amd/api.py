@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
     "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
-    "poismf_hip_debug_plan_widths", "poismf_hip_debug_lane_full_width",
+    "poismf_hip_debug_plan_widths", "poismf_hip_debug_plan_engines", "poismf_hip_debug_lane_full_width", "poismf_hip_debug_reg_quad_off",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
     "poismf_hip_rank_include", "poismf_hip_session_rank_include", "poismf_hip_rank_include_scratch_bytes",
@@ -386,14 +386,15 @@ def debug_row_eval(B, Bsum, point, Xr_indptr, Xr_indices, Xr, l2_reg, w_mult=1.,
     return f, G
 
 
-def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256, widths=False):
+def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256, widths=False, engines=False):
     """Testing aid (include/poismf_hip.h, poismf_hip_debug_plan): the launches the planner gives a half whose rows have row_nnz nonzeros,
     cut into nseg segments, for one call over segment `seg` (< 0: all of them): [(kernel instance, rows), ...].  Needs no GPU.
-    widths: poismf_hip_debug_plan_widths -- a lane instance specialised on the used width of its factor rows is marked "[KU=<width>]"."""
+    widths: poismf_hip_debug_plan_widths -- a lane instance specialised on the used width of its factor rows is marked "[KU=<width>]";
+    engines: poismf_hip_debug_plan_engines -- that, and a one-wave register launch on the quad engine is marked "[quad]"."""
     lib = load_library(use_float)
     row_nnz = np.ascontiguousarray(row_nnz, dtype=np.uint32)
     real = C.c_float if use_float else C.c_double
-    fn = lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan
+    fn = lib.poismf_hip_debug_plan_engines if engines else lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan
     fn.restype = C.c_size_t
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, real, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
@@ -408,6 +409,14 @@ def lane_full_width(use_float, full):
     fn = load_library(use_float).poismf_hip_debug_lane_full_width
     fn.restype, fn.argtypes = C.c_int, [C.c_int]
     return bool(fn(int(bool(full))))
+
+
+def reg_quad_off(use_float, off):
+    """Testing aid (poismf_hip_debug_reg_quad_off): off -- the one-wave register launches this process plans from now on take the sixteen-lane
+    engine also where the quad engine exists; not off -- the default again.  Returns the previous setting."""
+    fn = load_library(use_float).poismf_hip_debug_reg_quad_off
+    fn.restype, fn.argtypes = C.c_int, [C.c_int]
+    return bool(fn(int(bool(off))))
 
 
 class PoisMF:

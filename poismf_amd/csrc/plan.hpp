@@ -265,6 +265,19 @@ inline int lane_used_width(size_t k, int s_load, int method, const LaneShape& ls
     return 0;
 }
 
+// The quad engine (quad_eval.hpp): whether the one-wave register launches of a plan hold each nonzero in four lanes instead of sixteen.  PG on
+// floats at k = 50 -- the BASELINE configs' k -- reading the factor from its line-padded copy (rows of 64 floats: every load of the layout
+// is aligned); without that copy (POISMF_HIP_NO_PAD), and for every other k, solver and precision, the sixteen-lane engine.  A function of k, the
+// solver and the row stride alone.  -DPMF_REG_QUAD=0 builds a library without it.
+#ifndef PMF_REG_QUAD
+#define PMF_REG_QUAD 1
+#endif
+constexpr int QUAD_K = 50, QUAD_LD = 64;
+inline int reg_quad(size_t k, int s_load, int method, size_t ldF)
+{
+    return PMF_REG_QUAD && REG_G == 16 && sizeof(real_t) == 4 && method == POISMF_PG && s_load == 13 && k == (size_t)QUAD_K && ldF == (size_t)QUAD_LD;
+}
+
 // Long-row path: rows above this many nonzeros get a whole workgroup of LONG_NW waves (row_eval.hpp, NW > 1).
 constexpr unsigned LONG_ROW_NNZ = 8192;
 constexpr int LONG_NW = 8;
@@ -302,6 +315,7 @@ struct OneLaunch {
     size_t lds;
     unsigned grid, grid_mult;
     int device, num_cu;
+    int quad;                     // Reg: != 0 -- half_sweep_quad_kernel<reg_S / 4>, four lanes per nonzero (quad_eval.hpp; reg_quad above)
 };
 
 

@@ -86,6 +86,9 @@ TileGeom plan_geom(size_t k, unsigned bin_max_nnz, bool single_pass, bool want_p
 // poismf_hip_debug_lane_full_width (testing aid): != 0 -- the lane launches planned from now on carry every element of their slots, also where an
 // instance specialised on the used width exists (plan.hpp, lane_used_width): the two must agree bit for bit (tests/test_gpu_lane_width.py)
 std::atomic<int> g_lane_full_width{0};
+// poismf_hip_debug_reg_quad_off (testing aid): != 0 -- the one-wave register launches planned from now on take the sixteen-lane engine also where
+// the quad engine exists (plan.hpp, reg_quad): one process can run both (tests/test_gpu_quad.py)
+std::atomic<int> g_reg_quad_off{0};
 
 }  // namespace
 
@@ -225,6 +228,8 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
             const int S = reg_steps_for(ride ? b.max_nnz : b.cls);
             place(b, Engine::Reg, g, 1, S, 0, LaneShape{},
                   [&](const PlannedLaunch& P) { return P.reg_S >= S && (P.reg_S == S || (ride && b.count < 4096u)); });
+            // (one decision per plan: every Reg launch of it gets the same answer, so joining bins never mixes the two engines)
+            launches.back().quad = g_reg_quad_off.load(std::memory_order_relaxed) == 0 ? reg_quad(c.k, g.s_load, pm, c.ldF) : 0;
             continue;
         }
         if (regw_ok && b.cls <= regw_nnz_max(pm)) {
@@ -299,11 +304,13 @@ std::string launch_name(int method, const PlannedLaunch& L)
 }
 
 // ... and as poismf_hip_session_plan lists it (widths: a lane launch specialised on the used width says so behind its name, "...>[KU=50]" --
-// poismf_hip_debug_plan_widths; the names themselves are what they were before such instances existed)
-std::string plan_item(int method, const PlannedLaunch& L, bool widths)
+// poismf_hip_debug_plan_widths; engines: a one-wave register launch on the quad engine says so too, "...>[quad]" -- poismf_hip_debug_plan_engines;
+// the names themselves are what they were before such instances existed)
+std::string plan_item(int method, const PlannedLaunch& L, bool widths, bool engines)
 {
     std::string name = launch_name(method, L);
     if (widths && L.engine == Engine::Lane && L.lane.ku > 0) name += "[KU=" + std::to_string(L.lane.ku) + "]";
+    if (engines && L.engine == Engine::Reg && L.quad != 0) name += "[quad]";
     return name + " rows=" + std::to_string(L.count) + ";";
 }
 
@@ -335,7 +342,7 @@ size_t copy_text(const std::string& t, char* buf, size_t cap)
 // finish_half_launch / finish_half_collect do it; then the plan of a half-sweep call over segment `seg` (< 0: over all of them), as
 // poismf_hip_session_plan words it.  No HIP call.
 static size_t debug_plan_impl(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
-                              real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap, bool widths)
+                              real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap, bool widths, bool engines = false)
 {
     std::string text;
     nseg = std::max(nseg, 1);
@@ -349,7 +356,7 @@ static size_t debug_plan_impl(const unsigned* row_nnz, size_t nrows, int nseg, i
         }
         const PlanCtx c = plan_ctx(k, dimF, method, maxupd, w_mult, limit_step != 0, false, num_cu);
         for (const auto& pass : plan_call(segs, seg, c))
-            for (const PlannedLaunch& L : pass) text += plan_item(method, L, widths);
+            for (const PlannedLaunch& L : pass) text += plan_item(method, L, widths, engines);
     }
     return copy_text(text, buf, cap);
 }
@@ -367,8 +374,17 @@ size_t poismf_hip_debug_plan_widths(const unsigned* row_nnz, size_t nrows, int n
 {
     return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, true);
 }
+// The listing of poismf_hip_debug_plan_widths, every one-wave register launch that takes the quad engine (plan.hpp, reg_quad) marked "[quad]" as well.
+size_t poismf_hip_debug_plan_engines(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                                     real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+{
+    return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, true, true);
+}
 // Testing aid: != 0 -- from now on this process plans its lane launches on the instances that carry every element of their slots (what a
 // -DPMF_LANE_KU50=0 build always does); 0 -- the default again.  Returns the previous setting.
 int poismf_hip_debug_lane_full_width(int full) { return g_lane_full_width.exchange(full != 0 ? 1 : 0); }
+// Testing aid: != 0 -- from now on this process plans its one-wave register launches on the sixteen-lane engine (what a -DPMF_REG_QUAD=0 build
+// always does); 0 -- the default again.  Returns the previous setting.
+int poismf_hip_debug_reg_quad_off(int off) { return g_reg_quad_off.exchange(off != 0 ? 1 : 0); }
 
 }  // extern "C"

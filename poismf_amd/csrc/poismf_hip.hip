@@ -15,6 +15,7 @@
 
 #include "plan.hpp"
 #include "reg_eval.hpp"
+#include "quad_eval.hpp"
 #include "lane_eval.hpp"
 #include "solvers.hpp"
 
@@ -432,6 +433,16 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(
 #endif
 }
 
+// The quad engine (quad_eval.hpp) for the same rows where the plan says so (plan.hpp, reg_quad: PG on floats, k = 50, the padded copy): Q = S / 4
+// steps of sixteen nonzeros, a tile of 14 Q registers.
+template <int Q>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(14 * Q, K_PG)))) void half_sweep_quad_kernel(const HalfArgs<float> a)
+{
+    using EV = QuadEval<Q>;
+    EV ev;
+    sweep_rows<EV, float, EV::NC, K_PG, 1>(a, ev, nullptr);
+}
+
 // The same engine with NW = 2, 4 or 8 wavefronts per row (reg_eval.hpp, NW_ > 1): rows of up to NW (64 / G) S nonzeros.
 // The fewest waves whose shares fit their registers are used: every evaluation ends in a barrier and a round trip
 // through LDS, which costs more the more waves take part (C2-shaped PG(10), ns per nonzero and half: 100-nonzero rows on
@@ -705,6 +716,35 @@ template <int METHOD, int S, int NS> int launch_reg(hipStream_t stream, const Ha
     return 0;
 }
 
+template <int Q> int launch_quad(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
+{
+    if constexpr (tu_has(K_PG) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16 && Q >= 1 && Q <= 10) {
+        auto kern = half_sweep_quad_kernel<Q>;
+        static std::atomic<int> occ_cache{0};  // waves per CU the register budget of this instance allows (as launch_reg)
+        int occ = occ_cache.load(std::memory_order_relaxed);
+        if (occ == 0) {
+            int n = 0;
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), WAVE, 0));
+            occ = std::max(1, n);
+            occ_cache.store(occ, std::memory_order_relaxed);
+        }
+        const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    } else return 1;   // (a plan never names the quad engine in a unit or a build without it)
+}
+int launch_quad_steps(hipStream_t stream, int S, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
+{
+    if (method != POISMF_PG || a.geom.k != QUAD_K || a.geom.ldF != QUAD_LD) return 1;
+    switch (S) {
+#define X(NZ) case (NZ) / REG_JG: return launch_quad<(NZ) / 16>(stream, a, grid_mult);
+        PMF_REG_SIZES(X)
+#undef X
+    }
+    return 1;
+}
+
 template <int S, int NS> int launch_reg_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
 {
     switch (method) {
@@ -925,6 +965,7 @@ int launch_one_here(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
             if (o.team == 4 && o.reg_S == 32) return launch_team<4, 32>(st, method, a);
             return 1;
         case Engine::Reg:
+            if (o.quad != 0) return launch_quad_steps(st, o.reg_S, method, a, o.grid_mult);
             if constexpr (REG_NS_MAX == 1) return launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult);
             else return o.s_load <= REG_G ? launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult) : launch_reg_steps<2>(st, o.reg_S, method, a, o.grid_mult);
         case Engine::RegW:

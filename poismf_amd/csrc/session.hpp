@@ -124,7 +124,7 @@ size_t padded_row_bytes(size_t k);
 PlanCtx plan_ctx(size_t k, size_t dimF, int method, size_t maxupd, real_t w_mult, bool limit_step, bool teams_off, int num_cu);
 TileGeom long_geom(TileGeom g);
 std::string launch_name(int method, const PlannedLaunch& L);
-std::string plan_item(int method, const PlannedLaunch& L, bool widths = false);
+std::string plan_item(int method, const PlannedLaunch& L, bool widths = false, bool engines = false);
 std::vector<std::vector<PlannedLaunch>> plan_call(const std::vector<Half::Segment>& segs, int seg, const PlanCtx& c);
 size_t copy_text(const std::string& t, char* buf, size_t cap);
 

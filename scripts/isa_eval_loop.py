@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""isa_eval_loop.py <tag> <poismf_hip.s> [S] : the evaluation loop (one pass over the tile) of every one-wave PG fp32 register kernel
+"""isa_eval_loop.py [--quad] <tag> <poismf_hip.s> [S] : the evaluation loop (one pass over the tile) of every one-wave PG fp32 register kernel
 half_sweep_reg_kernel<float, 3, S, 16, 1> in an assembly listing of the PG unit
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -DUSE_FLOAT -DPMF_TU=3 --cuda-device-only -S poismf_amd/csrc/poismf_hip.hip -o poismf_hip.s
@@ -7,7 +7,8 @@ half_sweep_reg_kernel<float, 3, S, 16, 1> in an assembly listing of the PG unit
 One line per S (the format of profiles/r07/isa_eval_loop.txt with two more columns and the per-row gather block): instr = all instructions
 of the loop body, VALU = v_* among them; add = unpacked v_add_f32 (DPP adds not counted, they are in "other VALU"); gather-block VALU = the
 v_* of the basic block that broadcasts the row's indices and issues its loads (address arithmetic, the swaps of the step pairs and whatever
-copies the compiler adds around them).  With S: the loop's VALU instructions of that instance by opcode.
+copies the compiler adds around them).  With S: the loop's VALU instructions of that instance by opcode.  --quad: the same for the quad
+engine's kernels half_sweep_quad_kernel<S / 4> (quad_eval.hpp), every S from 4 to 40, so that the two listings line up S by S.
 
 The pass loop is the kernel's inner loop (the blocks LLVM marks "Depth=2"); the script stops if those blocks hold no v_pk_fma_f32, or the
 gather block is not found, instead of printing zeros."""
@@ -19,12 +20,15 @@ STEPS = (12, 16, 20, 24, 28, 32, 36, 40)
 LABEL = re.compile(r"^(\.LBB\d+_\d+):")
 
 
-def kernels(path):
+QUAD_STEPS = tuple(range(4, 41, 4))
+
+
+def kernels(path, quad=False):
     """{S: lines of the kernel's body}"""
     lines = open(path).read().split("\n")
     out = {}
-    for S in STEPS:
-        name = f"_Z21half_sweep_reg_kernelIfLi3ELi{S}ELi16ELi1EEv8HalfArgsIT_E:"
+    for S in QUAD_STEPS if quad else STEPS:
+        name = f"_Z22half_sweep_quad_kernelILi{S // 4}EEv8HalfArgsIfE:" if quad else f"_Z21half_sweep_reg_kernelIfLi3ELi{S}ELi16ELi1EEv8HalfArgsIT_E:"
         begin = next(i for i, line in enumerate(lines) if line.startswith(name))
         end = next(i for i in range(begin, len(lines)) if lines[i].startswith(".Lfunc_end"))
         out[S] = lines[begin:end]
@@ -77,9 +81,11 @@ def gather_valu(body, S):
 
 
 def main():
-    tag, path = sys.argv[1], sys.argv[2]
-    detail = int(sys.argv[3]) if len(sys.argv) > 3 else None
-    for S, body in kernels(path).items():
+    args = [a for a in sys.argv[1:] if a != "--quad"]
+    quad = "--quad" in sys.argv[1:]
+    tag, path = args[0], args[1]
+    detail = int(args[2]) if len(args) > 2 else None
+    for S, body in kernels(path, quad).items():
         st, count = loop_stats(body, S)
         print(f"S={S:2d}  {tag} instr {st['instr']:4d}  VALU {st['valu']:4d}  v_pk_mul_f32 {st['pk_mul']:3d}  v_pk_fma_f32 {st['pk_fma']:3d}  "
               f"v_add_f32 {st['add']:3d}  v_mov_b32 {st['mov']:2d}  s_nop {st['nop']:3d}  v_cndmask {st['cnd']:3d}  other VALU {st['other']:3d}  "
