@@ -736,6 +736,11 @@ POISMF_HIP_API size_t poismf_hip_debug_plan_widths(const unsigned *row_nnz, size
  * that holds each nonzero in four lanes instead of sixteen (PG on floats, k = 50, the line-padded factor copy; poismf_hip_debug_reg_quad_off). */
 POISMF_HIP_API size_t poismf_hip_debug_plan_engines(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
                           size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
+/* Of the listing of poismf_hip_debug_plan_engines, only the launches for which the solver's row-kernel translation unit has no instance: what
+ * the dispatcher itself answers when it is asked to find each planned launch's kernel without launching it (no HIP call is made).  Empty unless
+ * the planner names an instance that was never compiled -- such a launch would fail at run time. */
+POISMF_HIP_API size_t poismf_hip_debug_plan_missing(const unsigned *row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method,
+                          size_t maxupd, real_t w_mult, int limit_step, int num_cu, char *buf, size_t cap);
 /* Testing aid: full != 0 -- the lane launches this process plans from now on take the instances that carry every element of their slots, also
  * where one specialised on the used width exists (the two agree bit for bit; a -DPMF_LANE_KU50=0 build never selects the latter); 0 -- the
  * default again.  Returns the previous setting. */

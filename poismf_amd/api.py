@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
     "poismf_hip_session_partials_ready", "eval_llk", "poismf_hip_session_llk", "poismf_hip_debug_plan",
-    "poismf_hip_debug_plan_widths", "poismf_hip_debug_plan_engines", "poismf_hip_debug_lane_full_width", "poismf_hip_debug_reg_quad_off",
+    "poismf_hip_debug_plan_widths", "poismf_hip_debug_plan_engines", "poismf_hip_debug_plan_missing", "poismf_hip_debug_lane_full_width", "poismf_hip_debug_reg_quad_off",
     "poismf_hip_topn_batch", "poismf_hip_session_topn_batch", "poismf_hip_topn_batch_scratch_bytes",
     "poismf_hip_rank_batch", "poismf_hip_session_rank_batch", "poismf_hip_rank_batch_scratch_bytes",
     "poismf_hip_rank_include", "poismf_hip_session_rank_include", "poismf_hip_rank_include_scratch_bytes",
@@ -386,18 +386,22 @@ def debug_row_eval(B, Bsum, point, Xr_indptr, Xr_indices, Xr, l2_reg, w_mult=1.,
     return f, G
 
 
-def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256, widths=False, engines=False):
+def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_mult=1., limit_step=True, num_cu=256, widths=False, engines=False,
+               missing=False):
     """Testing aid (include/poismf_hip.h, poismf_hip_debug_plan): the launches the planner gives a half whose rows have row_nnz nonzeros,
     cut into nseg segments, for one call over segment `seg` (< 0: all of them): [(kernel instance, rows), ...].  Needs no GPU.
     widths: poismf_hip_debug_plan_widths -- a lane instance specialised on the used width of its factor rows is marked "[KU=<width>]";
-    engines: poismf_hip_debug_plan_engines -- that, and a one-wave register launch on the quad engine is marked "[quad]"."""
+    engines: poismf_hip_debug_plan_engines -- that, and a one-wave register launch on the quad engine is marked "[quad]";
+    missing: poismf_hip_debug_plan_missing -- of that listing, only the launches the dispatcher has no kernel instance for (none, normally).
+    method: "pg", "cg", "tncg", or "eval" (the evaluation-only kernels of debug_row_eval, planned like CG)."""
     lib = load_library(use_float)
     row_nnz = np.ascontiguousarray(row_nnz, dtype=np.uint32)
     real = C.c_float if use_float else C.c_double
-    fn = lib.poismf_hip_debug_plan_engines if engines else lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan
+    fn = (lib.poismf_hip_debug_plan_missing if missing else lib.poismf_hip_debug_plan_engines if engines else
+          lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan)
     fn.restype = C.c_size_t
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, real, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
+    args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), 4 if method == "eval" else _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
     buf = C.create_string_buffer(int(fn(*args, None, 0)) + 1)
     fn(*args, buf, len(buf))
     return [(name.strip(), int(rows)) for name, rows in (item.rsplit(" rows=", 1) for item in buf.value.decode().split(";") if item.strip())]

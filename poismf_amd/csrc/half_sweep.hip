@@ -10,12 +10,6 @@
 
 #include "session.hpp"
 
-static int launch_one(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
-{
-    return method == POISMF_PG ? pmf_launch_one_tu3(method, o, a) : method == POISMF_CG ? pmf_launch_one_tu2(method, o, a) :
-           method == POISMF_EVAL ? pmf_launch_one_tu4(method, o, a) : pmf_launch_one_tu1(method, o, a);
-}
-
 #define PMF_EW _Pragma("unroll") for (int i = 0; i < NC; i++)
 
 // ---- compact factor -> line-padded copy (the pad columns stay zero from the allocation) --------------------------
@@ -461,7 +455,7 @@ int issue_half(poismf_hip_session* s, int which, int method, const std::vector<P
             lr.which = which; lr.name = name; lr.rows = L.count; lr.nnz = L.nnz;
             HIP_TRY(hipEventRecord(lr.t0, o.stream));
         }
-        const int rc = launch_one(method, o, a);
+        const int rc = pmf_launch_one(method, o, a);
         if (!rc && a.arrive != nullptr) {
             arrive_goal += std::min<unsigned>(grid, (unsigned)s->num_cu);   // (one eight-wave workgroup per CU)
             // (hold_back_gate_kernel: returns when that many workgroups are on the chip, or after 2 ms)
@@ -492,7 +486,7 @@ int half_epilogue(poismf_hip_session* s, const Half& h, int method, const HalfAr
                            s->d_team_backup + tslots[r.slot].backup_at, s->d_team_err + 2 + r.slot, base.eval_rows,
                            base.eval_rows != nullptr ? s->d_team_eval_backup + tslots[r.slot].eval_at : nullptr);
 #ifndef PMF_LANE_ONLY   // (development builds without the streamed kernels: no re-run)
-        if (launch_one(method, r.of, r.af)) return 1;
+        if (pmf_launch_one(method, r.of, r.af)) return 1;
 #endif
     }
     if (!reruns.empty()) {

@@ -86,7 +86,7 @@ struct RowDesc { unsigned p0_lo, p0_hi, nnz, lrow; };
 // is specialised on it (lane_eval.hpp, KU_; lane_used_width below), 0 = all elements of its slots
 struct LaneShape {
     int lv, la, ll, waves; int small; int lp = 0; int tx = 0; int ku = 0;
-    bool operator==(const LaneShape& o) const
+    constexpr bool operator==(const LaneShape& o) const
     {
         return lv == o.lv && la == o.la && ll == o.ll && waves == o.waves && small == o.small && lp == o.lp && tx == o.tx && ku == o.ku;
     }
@@ -135,18 +135,36 @@ int reg_steps_for(unsigned max_nnz)
 #define PMF_REG_MAX_TNCG 160
 #endif
 constexpr int REG_NNZ_MAX_CG = PMF_REG_MAX_CG, REG_NNZ_MAX_TNCG = PMF_REG_MAX_TNCG;
-unsigned reg_nnz_max(int method) { return method == POISMF_PG ? REG_NNZ_MAX : method == POISMF_CG ? REG_NNZ_MAX_CG : REG_NNZ_MAX_TNCG; }
+// ... and from a tile of two slots per lane (kernel-resource-usage: CG with 40 steps of two slots spills 360 bytes per lane even at one wave per
+// SIMD, 36 steps 60; TNC's ~21 k-vectors leave room for 112 nonzeros of tile)
+constexpr int REG2_NNZ_MAX_CG = 144, REG2_NNZ_MAX_TNCG = 112;
+constexpr int plan_method(int method) { return method == POISMF_EVAL ? POISMF_CG : method; }   // the evaluation-only kernels are planned like CG
+constexpr unsigned reg_nnz_max(int method, int ns = 1)
+{
+    const int m = plan_method(method);
+    const int one = m == POISMF_PG ? REG_NNZ_MAX : m == POISMF_CG ? REG_NNZ_MAX_CG : REG_NNZ_MAX_TNCG;
+    const int two = m == POISMF_PG ? REG_NNZ_MAX : m == POISMF_CG ? REG2_NNZ_MAX_CG : REG2_NNZ_MAX_TNCG;
+    return (unsigned)(ns == 2 && two < one ? two : one);
+}
+// whether half_sweep_reg_kernel<method, S steps, ns slots per lane> is compiled: what the planner may name and what the dispatcher launches
+constexpr bool reg_instance(int method, int S, int ns) { return ns >= 1 && ns <= REG_NS_MAX && (unsigned)(S * REG_JG) <= reg_nnz_max(method, ns); }
 
 constexpr int REG_NW_MAX = 8;   // the same engine with 2, 4 or 8 wavefronts per row
 // Several waves per row: the longest share of a row one wave keeps in registers, per solver (CG / TNCG carry more state)
 // (CG: 144 although the 32- and 36-step fp32 instances spill 200-300 bytes per lane at two waves per SIMD -- for rows of
 // 1025-1152 nonzeros the alternative is the streamed LDS path: C4's matrix, CG fp32, B half 25.0 -> 16.8 ms)
 constexpr int REGW_WAVE_NNZ_MAX_PG = 160, REGW_WAVE_NNZ_MAX_CG = 144, REGW_WAVE_NNZ_MAX_TNCG = 96;
-unsigned regw_wave_nnz_max(int method)
+constexpr unsigned regw_wave_nnz_max(int method)
 {
-    return (unsigned)(method == POISMF_PG ? REGW_WAVE_NNZ_MAX_PG : method == POISMF_CG ? REGW_WAVE_NNZ_MAX_CG : REGW_WAVE_NNZ_MAX_TNCG);
+    const int m = plan_method(method);
+    return (unsigned)(m == POISMF_PG ? REGW_WAVE_NNZ_MAX_PG : m == POISMF_CG ? REGW_WAVE_NNZ_MAX_CG : REGW_WAVE_NNZ_MAX_TNCG);
 }
-unsigned regw_nnz_max(int method) { return (unsigned)REG_NW_MAX * regw_wave_nnz_max(method); }
+constexpr unsigned regw_nnz_max(int method) { return (unsigned)REG_NW_MAX * regw_wave_nnz_max(method); }
+// whether half_sweep_regw_kernel<method, S steps, nw waves per row> is compiled (a wave's share is at least 32 nonzeros, regw_steps_for)
+constexpr bool regw_instance(int method, int S, int nw)
+{
+    return (nw == 2 || nw == 4 || nw == 8) && S * REG_JG >= 32 && (unsigned)(S * REG_JG) <= regw_wave_nnz_max(method);
+}
 // (Sixteen waves per row -- one 1024-thread workgroup, four waves per SIMD, shares of <= 64 nonzeros -- for rows of 513 .. 1024
 // nonzeros was measured and NOT adopted; its build switch is gone.  One such row occupies a CU either way and a SIMD
 // gets four instruction streams instead of two, but the per-pass fixed work of a wave (point update, group combine, reading 16
@@ -170,16 +188,16 @@ int regw_steps_for(unsigned max_nnz, int nw)
 // Two CUs where they hold the row; the 28-step instance (no scratch) where three are needed anyway.
 // Below TEAM_MIN_NNZ a row's tile (k = 50 fp64: 400 B per nonzero) is resident in one CU's LDS: the LDS engine keeps it.
 constexpr unsigned TEAM_MIN_NNZ = 385;
+// The shapes with an instance of half_sweep_team_kernel, (members, steps), in the order team_shape_for tries them; the dispatcher
+// (poismf_hip.hip, Engine::RegTeam) is the expansion of the same list.
+#define PMF_TEAM_SHAPES(X) X(2, 32) X(2, 36) X(3, 28) X(3, 32) X(4, 32)
 struct TeamShape { int members, steps; };
 inline TeamShape team_shape_for(unsigned max_nnz)
 {
-    const unsigned per_step = (unsigned)(REG_JG * TEAM_NW);
     if (max_nnz < TEAM_MIN_NNZ) return { 0, 0 };
-    if (max_nnz <= 2u * 32u * per_step) return { 2, 32 };
-    if (max_nnz <= 2u * 36u * per_step) return { 2, 36 };
-    if (max_nnz <= 3u * 28u * per_step) return { 3, 28 };
-    if (max_nnz <= 3u * 32u * per_step) return { 3, 32 };
-    if (max_nnz <= 4u * 32u * per_step) return { 4, 32 };
+#define X(M, S) if (max_nnz <= (unsigned)((M) * (S) * REG_JG * TEAM_NW)) return { M, S };
+    PMF_TEAM_SHAPES(X)
+#undef X
     return { 0, 0 };
 }
 
@@ -265,6 +283,46 @@ inline int lane_used_width(size_t k, int s_load, int method, const LaneShape& ls
     return 0;
 }
 
+// Every instance of half_sweep_lane_kernel that is compiled, one row each: the solvers it is built for, then KS (slots per factor row) and
+// LV, LA, LL, NW, SMALL, LP, TX, KU as LaneShape names them.  The dispatcher (poismf_hip.hip, launch_lane_shape) is the expansion of this table
+// and finds a planned shape in it with LaneShape::operator==; lane_shape_for and lane_used_width above name rows of it and nothing else, and every
+// row is named by some plan (tests/test_plan_instances.py).  A new instance is a row here and the branch of lane_shape_for that picks it.
+// (the rows with a used width are built only where PMF_LANE_KU50 is on)
+constexpr unsigned LANE_PG = 1u << K_PG, LANE_CG = 1u << K_CG | 1u << K_EVAL, LANE_CG_TNCG = LANE_CG | 1u << K_TNCG;   // (EVAL keeps the set CG has)
+#define PMF_LANE_INSTANCES_F64(X)                   \
+    X(LANE_CG_TNCG, 25, 1, 0, 0, 1, 1,  0,  0,  0) \
+    X(LANE_CG,      25, 1, 0, 0, 1, 1, 32,  0,  0) \
+    X(LANE_CG_TNCG, 25, 1, 0, 1, 1, 0,  0,  0,  0) \
+    X(LANE_CG_TNCG, 25, 1, 2, 1, 1, 0,  0,  0,  0) \
+    X(LANE_CG_TNCG, 25, 1, 2, 1, 2, 0,  0,  0,  0) \
+    X(LANE_CG_TNCG, 25, 1, 2, 1, 4, 0,  0,  0,  0) \
+    X(LANE_CG_TNCG, 25, 1, 2, 1, 4, 0, 16,  0,  0) \
+    X(LANE_CG_TNCG, 50, 1, 0, 0, 1, 0,  0, 48,  0) \
+    X(LANE_CG_TNCG, 50, 1, 0, 0, 1, 0,  0, 64,  0) \
+    X(LANE_CG_TNCG, 50, 1, 0, 0, 2, 0,  0,  0,  0) \
+    X(LANE_CG_TNCG, 50, 1, 0, 0, 4, 0, 32,  0,  0)
+#define PMF_LANE_INSTANCES_F32(X)                   \
+    X(LANE_PG,      13, 4, 0, 0, 4, 1,  0,  0,  0) \
+    X(LANE_PG,      13, 4, 0, 0, 4, 1, 16,  0,  0) \
+    X(LANE_PG,      13, 4, 0, 0, 4, 1,  0,  0, 50) \
+    X(LANE_PG,      13, 4, 0, 0, 4, 1, 16,  0, 50) \
+    X(LANE_CG_TNCG, 13, 1, 0, 0, 1, 1,  0,  0,  0) \
+    X(LANE_CG_TNCG, 13, 2, 0, 0, 1, 1,  0,  0,  0) \
+    X(LANE_CG_TNCG, 13, 2, 0, 0, 2, 1,  0,  0,  0) \
+    X(LANE_CG_TNCG, 13, 2, 0, 0, 4, 1,  0,  0,  0) \
+    X(LANE_CG_TNCG, 13, 2, 0, 0, 8, 1,  0,  0,  0) \
+    X(LANE_CG_TNCG, 13, 3, 0, 0, 8, 1,  0,  0,  0)
+#ifdef USE_FLOAT
+#define PMF_LANE_INSTANCES(X) PMF_LANE_INSTANCES_F32(X)
+#else
+#define PMF_LANE_INSTANCES(X) PMF_LANE_INSTANCES_F64(X)
+#endif
+// The lane-team instance (half_sweep_lane_team_kernel; lane_eval.hpp, TM_): doubles under TNCG, factor rows of LANE_TEAM_KS slots, each member
+// LANE_TEAM_SHAPE's share of up to LANE_TEAM_NNZ nonzeros of the row
+constexpr int LANE_TEAM_KS = 50;
+constexpr LaneShape LANE_TEAM_SHAPE = { 1, 0, 0, 4, 0, 32 };
+constexpr unsigned LANE_TEAM_NNZ = (unsigned)(LANE_TEAM_SHAPE.waves * (WAVE * LANE_TEAM_SHAPE.lv + LANE_TEAM_SHAPE.lp));
+
 // The quad engine (quad_eval.hpp): whether the one-wave register launches of a plan hold each nonzero in four lanes instead of sixteen.  PG on
 // floats at k = 50 -- the BASELINE configs' k -- reading the factor from its line-padded copy (rows of 64 floats: every load of the layout
 // is aligned); without that copy (POISMF_HIP_NO_PAD), and for every other k, solver and precision, the sixteen-lane engine.  A function of k, the
@@ -293,7 +351,8 @@ int slots_per_lane(size_t k)
 }  // namespace
 
 // The kernel family of a launch.  The planner (planner.hip, plan_half) picks one per row bin; launch_one_here dispatches on it
-// first, then on the solver and the instance.
+// first, then on the solver (with_method) and the instance.  Which instances exist is written down once, above, for both sides: PMF_REG_SIZES with
+// reg_instance / regw_instance, PMF_TEAM_SHAPES, PMF_LANE_INSTANCES, LANE_TEAM_SHAPE.
 enum class Engine {
     Reg,        // half_sweep_reg_kernel: one wave per row, the tile in registers (reg_eval.hpp)
     RegW,       // half_sweep_regw_kernel: 2 / 4 / 8 waves per row, each its share of the tile in registers
@@ -316,6 +375,7 @@ struct OneLaunch {
     unsigned grid, grid_mult;
     int device, num_cu;
     int quad;                     // Reg: != 0 -- half_sweep_quad_kernel<reg_S / 4>, four lanes per nonzero (quad_eval.hpp; reg_quad above)
+    int dry;                      // != 0: find the instance, return 0 where a launch would be made and make no HIP call (poismf_hip_debug_plan_missing)
 };
 
 
@@ -324,5 +384,10 @@ int pmf_launch_one_tu1(int method, const OneLaunch& o, const HalfArgs<real_t>& a
 int pmf_launch_one_tu2(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu3(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu4(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
+inline int pmf_launch_one(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return method == POISMF_PG ? pmf_launch_one_tu3(method, o, a) : method == POISMF_CG ? pmf_launch_one_tu2(method, o, a) :
+           method == POISMF_EVAL ? pmf_launch_one_tu4(method, o, a) : pmf_launch_one_tu1(method, o, a);
+}
 // -DPMF_TIMING development builds: read and reset the phase timers (they live in the row-kernel translation unit)
 int pmf_read_timing(unsigned long long* out);

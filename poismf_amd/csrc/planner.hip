@@ -142,7 +142,7 @@ size_t padded_row_bytes(size_t k)
 
 PlanCtx plan_ctx(size_t k, size_t dimF, int method, size_t maxupd, real_t w_mult, bool limit_step, bool teams_off, int num_cu)
 {
-    const int pm = method == POISMF_EVAL ? POISMF_CG : method;   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
+    const int pm = plan_method(method);   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
     const bool single_pass = method == POISMF_PG && maxupd <= 1 && w_mult == (real_t)1.;
     return { k, dimF, padded_row_bytes(k) / sizeof(real_t), pm, single_pass, limit_step, teams_off, num_cu };
 }
@@ -181,11 +181,9 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
     const int reg_ns = reg_slots_per_lane((c.k * sizeof(real_t) + 15) / 16);
     const bool reg_ok = !kn.no_reg && reg_ns > 0 &&
                         c.dimF < ((size_t)1 << 24) && (c.dimF + 1) * c.ldF * sizeof(real_t) + 16 < ((size_t)1 << 32);
-    // two slots per lane: single-wave rows only, and TNC's ~21 k-vectors leave room for 112 nonzeros of tile
+    // two slots per lane: single-wave rows only, and shorter ones for CG and TNCG (plan.hpp, REG2_NNZ_MAX_*)
     const bool regw_ok = reg_ok && (reg_ns == 1 || REG_G == 8);
-    // (kernel-resource-usage: CG with 40 steps of two slots spills 360 bytes per lane even at one wave per SIMD, 36 steps 60)
-    const unsigned reg_max = reg_ns == 2 && REG_G == 16 ? (pm == POISMF_TNCG ? 112u : pm == POISMF_CG ? 144u : reg_nnz_max(pm))
-                                                        : reg_nnz_max(pm);
+    const unsigned reg_max = reg_nnz_max(pm, reg_ns);
     // (a bin of a few thousand rows is not worth a launch of its own: it rides along with the next longer size.  TNC keeps the tile size its
     // length class names: in fp32 its results move in the last bits with the size of the instance -- 62 of 900 rows in tests/test_gpu_parity.py's
     // segment test -- and a row must not depend on which other rows share its shard; PG and CG, and fp64 TNC, are bit-identical across instances)
@@ -212,10 +210,10 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
             // 697 GB per sweep).  The team size is a function of the row's length class alone.  POISMF_HIP_NO_LANE_TEAMS=1: the eight-wave
             // streamed kernel (round 5a)
             int lane_team = 0;
-            if (ls.waves == 0 && sizeof(real_t) == 8 && g.s_load == 50 && pm == POISMF_TNCG && !kn.no_lane_teams && !no_team && !kn.static_rows &&
-                b.cls > 384 && b.cls <= LONG_ROW_NNZ) {
-                const int m = (int)((b.cls + 383u) / 384u);
-                if (m >= 2 && c.num_cu >= 2 * m) { ls = LaneShape{ 1, 0, 0, 4, 0, 32 }; lane_team = m; }
+            if (ls.waves == 0 && sizeof(real_t) == 8 && g.s_load == LANE_TEAM_KS && pm == POISMF_TNCG && !kn.no_lane_teams && !no_team && !kn.static_rows &&
+                b.cls > LANE_TEAM_NNZ && b.cls <= LONG_ROW_NNZ) {
+                const int m = (int)((b.cls + LANE_TEAM_NNZ - 1u) / LANE_TEAM_NNZ);
+                if (m >= 2 && c.num_cu >= 2 * m) { ls = LANE_TEAM_SHAPE; lane_team = m; }
             }
             if (ls.waves > 0) {
                 place(b, lane_team ? Engine::LaneTeam : Engine::Lane, g, ls.waves, 0, lane_team, ls,
@@ -284,12 +282,13 @@ std::string launch_name(int method, const PlannedLaunch& L)
     const char* m = method == POISMF_PG ? "pg" : method == POISMF_EVAL ? "eval" : method == POISMF_CG ? "cg" : "tncg";
     const char* t = sizeof(real_t) == 4 ? "float" : "double";
     const LaneShape& l = L.lane;
-    char txt[160] = "";
+    char txt[160] = "", lp[16] = "";
+    if (l.lp != 0) snprintf(lp, sizeof lp, "+%d", l.lp);
     switch (L.engine) {
         case Engine::LaneTeam: snprintf(txt, sizeof txt, "half_sweep_lane_team_kernel<%s,%s,KS=%d,V=%d,L=0+%d,NW=%d,M=%d>", t, m, L.geom.s_load, l.lv, l.lp, L.nw, L.team); break;
         case Engine::Lane:
             snprintf(txt, sizeof txt, "half_sweep_lane_kernel<%s,%s,KS=%d,V=%d,A=%d,L=%d%s,NW=%d%s%s>", t, m, L.geom.s_load, l.lv, l.la, l.ll,
-                     l.lp == 32 ? "+32" : l.lp ? "+16" : "", L.nw, l.small ? ",2/SIMD" : "", l.tx == 48 ? ",TX=48" : l.tx == 64 ? ",TX=64" : "");
+                     lp, L.nw, l.small ? ",2/SIMD" : "", l.tx == 48 ? ",TX=48" : l.tx == 64 ? ",TX=64" : "");
             break;
         case Engine::Giant: snprintf(txt, sizeof txt, "half_sweep_giant_kernel<%s,%s,NW=%d,M=%d,streamed cap=%d>", t, m, L.nw, L.team, L.geom.cap); break;
         case Engine::RegTeam: snprintf(txt, sizeof txt, "half_sweep_team_kernel<%s,%s,S=%d,NW=%d,M=%d>", t, m, L.reg_S, L.nw, L.team); break;
@@ -338,11 +337,22 @@ size_t copy_text(const std::string& t, char* buf, size_t cap)
     return t.size();
 }
 
+// Whether the solver's row-kernel translation unit has the instance launch L names: the dispatcher's own answer, from a dry run of the launch
+// (plan.hpp, OneLaunch::dry -- no HIP call).
+static bool has_instance(int method, const PlannedLaunch& L)
+{
+    OneLaunch o = L;
+    o.dry = 1;
+    HalfArgs<real_t> a{};
+    a.nrows = L.count; a.geom = L.geom;
+    return pmf_launch_one(method, o, a) == 0;
+}
+
 // Testing aid: the planner without a device.  Rows of row_nnz[0 .. nrows) nonzeros, cut into nseg segments, sorted and binned as
 // finish_half_launch / finish_half_collect do it; then the plan of a half-sweep call over segment `seg` (< 0: over all of them), as
 // poismf_hip_session_plan words it.  No HIP call.
 static size_t debug_plan_impl(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
-                              real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap, bool widths, bool engines = false)
+                              real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap, bool widths, bool engines = false, bool missing = false)
 {
     std::string text;
     nseg = std::max(nseg, 1);
@@ -356,7 +366,8 @@ static size_t debug_plan_impl(const unsigned* row_nnz, size_t nrows, int nseg, i
         }
         const PlanCtx c = plan_ctx(k, dimF, method, maxupd, w_mult, limit_step != 0, false, num_cu);
         for (const auto& pass : plan_call(segs, seg, c))
-            for (const PlannedLaunch& L : pass) text += plan_item(method, L, widths, engines);
+            for (const PlannedLaunch& L : pass)
+                if (!missing || !has_instance(method, L)) text += plan_item(method, L, widths, engines);
     }
     return copy_text(text, buf, cap);
 }
@@ -379,6 +390,13 @@ size_t poismf_hip_debug_plan_engines(const unsigned* row_nnz, size_t nrows, int 
                                      real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
 {
     return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, true, true);
+}
+// Of that listing, the launches for which the solver's translation unit has no kernel instance (poismf_hip.hip, launch_one_here): nothing, unless
+// the planner names something the dispatcher lacks.
+size_t poismf_hip_debug_plan_missing(const unsigned* row_nnz, size_t nrows, int nseg, int seg, size_t k, size_t dimF, int method, size_t maxupd,
+                                     real_t w_mult, int limit_step, int num_cu, char* buf, size_t cap)
+{
+    return debug_plan_impl(row_nnz, nrows, nseg, seg, k, dimF, method, maxupd, w_mult, limit_step, num_cu, buf, cap, true, true, true);
 }
 // Testing aid: != 0 -- from now on this process plans its lane launches on the instances that carry every element of their slots (what a
 // -DPMF_LANE_KU50=0 build always does); 0 -- the default again.  Returns the previous setting.

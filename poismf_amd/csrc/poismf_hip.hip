@@ -639,300 +639,79 @@ __global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(lane_t
 
 namespace {
 
-constexpr int MAX_DEVICES = 64;        // per-device caches of kernel attributes below
-// device and CU count of the launch being issued by this thread (set by launch_one_here from the session's values)
-thread_local int t_device = 0, t_num_cu = 256;
+using std::integral_constant;
+constexpr int MAX_DEVICES = 64;        // per-device cache of kernel attributes below
 
-template <int NC, int METHOD, int SL, int NW> int launch_bin(hipStream_t stream, const HalfArgs<real_t>& a, size_t lds, unsigned grid)
+// ---- the two ways a launch is made ------------------------------------------------------------------------------------------------------
+// A kernel without dynamic LDS: the grid is given, or (launch_occ) follows from the waves per CU the register budget of the instance allows --
+// a property of the code object, asked for once per instance.
+template <auto Kern, int THREADS> int launch_grid(const OneLaunch& o, const HalfArgs<real_t>& a, unsigned grid, size_t lds = 0)
 {
-    auto kern = half_sweep_kernel<real_t, NC, METHOD, SL, NW>;
-    // hipFuncAttributeMaxDynamicSharedMemorySize is per device: remember it per device id
-    static std::atomic<bool> attr_set[MAX_DEVICES];
-    const int dev = t_device >= 0 && t_device < MAX_DEVICES ? t_device : 0;
-    if (!attr_set[dev].load(std::memory_order_acquire) || dev != t_device) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_PER_CU));
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * NW), lds, stream, a);
+    if (o.dry) return 0;
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(THREADS), lds, o.stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-
-template <int NC, int METHOD, int SL> int launch_giant(hipStream_t stream, const HalfArgs<real_t>& a, size_t lds, unsigned grid)
+template <auto Kern, int THREADS> int launch_occ(const OneLaunch& o, const HalfArgs<real_t>& a)
 {
-    auto kern = half_sweep_giant_kernel<real_t, NC, METHOD, SL, LONG_NW>;
-    static std::atomic<bool> attr_set[MAX_DEVICES];
-    const int dev = t_device >= 0 && t_device < MAX_DEVICES ? t_device : 0;
-    if (!attr_set[dev].load(std::memory_order_acquire) || dev != t_device) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_PER_CU));
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * LONG_NW), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-// giant-row teams: TNCG only (the solver whose evaluations re-stream the row; CG has its cached line search and the register teams)
-template <int NC, int SL> int launch_giant_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, size_t lds, unsigned grid)
-{
-    if constexpr (tu_has(K_TNCG)) {
-        if (method == POISMF_TNCG) return launch_giant<NC, K_TNCG, SL>(stream, a, lds, grid);
-    }
-    return 1;
-}
-
-template <int NC, int SL, int NW = 1> int launch_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, size_t lds, unsigned grid)
-{
-    switch (method) {
-        case POISMF_PG:
-            if constexpr (tu_has(K_PG)) return launch_bin<NC, K_PG, SL, NW>(stream, a, lds, grid);
-            else return 1;
-        case POISMF_CG:
-            if constexpr (tu_has(K_CG)) return launch_bin<NC, K_CG, SL, NW>(stream, a, lds, grid);
-            else return 1;
-        case POISMF_EVAL:
-            if constexpr (tu_has(K_EVAL)) return launch_bin<NC, K_EVAL, SL, NW>(stream, a, lds, grid);
-            else return 1;
-        default:
-            if constexpr (tu_has(K_TNCG)) return launch_bin<NC, K_TNCG, SL, NW>(stream, a, lds, grid);
-            else return 1;
-    }
-}
-
-template <int METHOD, int S, int NS> int launch_reg(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    auto kern = half_sweep_reg_kernel<real_t, METHOD, S, REG_G, NS>;
-    static std::atomic<int> occ_cache{0};  // waves per CU the register budget of this instance allows (a property of the code object)
+    if (o.dry) return 0;
+    static std::atomic<int> occ_cache{0};
     int occ = occ_cache.load(std::memory_order_relaxed);
     if (occ == 0) {
         int n = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), WAVE, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(Kern), THREADS, 0));
         occ = std::max(1, n);
         occ_cache.store(occ, std::memory_order_relaxed);
     }
-    const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_grid<Kern, THREADS>(o, a, (unsigned)std::min<size_t>(a.nrows, (size_t)o.num_cu * (size_t)occ * o.grid_mult));
 }
-
-template <int Q> int launch_quad(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
+// A kernel of the LDS engine: o.grid workgroups with o.lds bytes of dynamic LDS each.  hipFuncAttributeMaxDynamicSharedMemorySize is per device:
+// remembered per device id (ids past the cache set it for every launch).
+template <auto Kern, int THREADS> int launch_lds(const OneLaunch& o, const HalfArgs<real_t>& a)
 {
-    if constexpr (tu_has(K_PG) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16 && Q >= 1 && Q <= 10) {
-        auto kern = half_sweep_quad_kernel<Q>;
-        static std::atomic<int> occ_cache{0};  // waves per CU the register budget of this instance allows (as launch_reg)
-        int occ = occ_cache.load(std::memory_order_relaxed);
-        if (occ == 0) {
-            int n = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), WAVE, 0));
-            occ = std::max(1, n);
-            occ_cache.store(occ, std::memory_order_relaxed);
-        }
-        const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    } else return 1;   // (a plan never names the quad engine in a unit or a build without it)
-}
-int launch_quad_steps(hipStream_t stream, int S, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    if (method != POISMF_PG || a.geom.k != QUAD_K || a.geom.ldF != QUAD_LD) return 1;
-    switch (S) {
-#define X(NZ) case (NZ) / REG_JG: return launch_quad<(NZ) / 16>(stream, a, grid_mult);
-        PMF_REG_SIZES(X)
-#undef X
+    if (o.dry) return 0;
+    static std::atomic<bool> attr_set[MAX_DEVICES];
+    const int dev = o.device >= 0 && o.device < MAX_DEVICES ? o.device : 0;
+    if (!attr_set[dev].load(std::memory_order_acquire) || dev != o.device) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_PER_CU));
+        attr_set[dev].store(true, std::memory_order_release);
     }
-    return 1;
+    return launch_grid<Kern, THREADS>(o, a, o.grid, o.lds);
 }
 
-template <int S, int NS> int launch_reg_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
+// ---- run-time values to compile-time ones ------------------------------------------------------------------------------------------------
+// f(the solver) where this translation unit has that solver's kernels; 1 where it does not
+template <class F> int with_method(int method, F f)
 {
     switch (method) {
         case POISMF_PG:
-            if constexpr (tu_has(K_PG)) return launch_reg<K_PG, S, NS>(stream, a, grid_mult);
+            if constexpr (tu_has(K_PG)) return f(integral_constant<int, K_PG>{});
             else return 1;
         case POISMF_CG:
-            if constexpr (tu_has(K_CG) && S * REG_JG <= REG_NNZ_MAX_CG && (NS == 1 || S * REG_JG <= 144)) return launch_reg<K_CG, S, NS>(stream, a, grid_mult);
-            else return 1;
-        case POISMF_EVAL:   // (the sizes CG has)
-            if constexpr (tu_has(K_EVAL) && S * REG_JG <= REG_NNZ_MAX_CG && (NS == 1 || S * REG_JG <= 144)) return launch_reg<K_EVAL, S, NS>(stream, a, grid_mult);
-            else return 1;
-        default:
-            if constexpr (tu_has(K_TNCG) && S * REG_JG <= REG_NNZ_MAX_TNCG && (NS == 1 || S * REG_JG <= 112)) return launch_reg<K_TNCG, S, NS>(stream, a, grid_mult);
-            else return 1;
-    }
-}
-
-template <int METHOD, int S, int NS, int NW> int launch_regw(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    auto kern = half_sweep_regw_kernel<real_t, METHOD, S, REG_G, NS, NW>;
-    static std::atomic<int> occ_cache{0};  // workgroups per CU
-    int occ = occ_cache.load(std::memory_order_relaxed);
-    if (occ == 0) {
-        int n = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), WAVE * NW, 0));
-        occ = std::max(1, n);
-        occ_cache.store(occ, std::memory_order_relaxed);
-    }
-    const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * NW), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// team launches: CG on doubles with two slots per lane (k = 50 fp64) is what asks for them
-template <int M, int S> int launch_team(hipStream_t stream, int method, const HalfArgs<real_t>& a)
-{
-    if constexpr ((tu_has(K_CG) || tu_has(K_EVAL)) && sizeof(real_t) == 8 && REG_G == 16) {
-        constexpr int KM = tu_has(K_CG) ? K_CG : K_EVAL;   // (the translation unit of the evaluation-only kernels has no CG)
-        if (method != (KM == K_CG ? POISMF_CG : POISMF_EVAL)) return 1;
-        auto kern = half_sweep_team_kernel<real_t, KM, S, REG_G, 2, TEAM_NW, M>;
-        // as many workgroups as CUs: each takes a CU's whole register file (one wave of 512 per SIMD)
-        const unsigned grid = (unsigned)std::min<size_t>((size_t)a.nrows * M, (size_t)t_num_cu / M * M);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * TEAM_NW), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    } else return 1;
-}
-
-// lane-per-nonzero launches
-template <int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL = false, int LP = 0, int TX = 0, int KU = 0> int launch_lane(hipStream_t stream, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    if constexpr (tu_has(METHOD)) {
-        using EV = LaneEval<real_t, KS, LV, LA, LL, NW, SMALL, LP, TX, false, KU>;
-        auto kern = half_sweep_lane_kernel<real_t, METHOD, KS, LV, LA, LL, NW, SMALL, LP, TX, KU>;
-        // workgroups per CU: one (SMALL: two) waves per SIMD, and the LDS each takes
-        const int occ = std::max(1, std::min((lane_two<SMALL>() ? 8 : 4) / NW, (int)(LDS_PER_CU / (size_t)EV::SMEM_BYTES)));
-        const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)t_num_cu * (size_t)occ * grid_mult);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * NW), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    } else return 1;
-}
-// lane teams: k = 100 fp64 TNCG rows of 385 .. 8192 nonzeros, M = a.team_members four-wave workgroups per row
-int launch_lane_team(hipStream_t stream, int method, int s_load, const LaneShape& l, const HalfArgs<real_t>& a, unsigned grid)
-{
-    if constexpr (tu_has(K_TNCG) && sizeof(real_t) == 8) {
-        if (method == POISMF_TNCG && s_load == 50 && l.lv == 1 && l.la == 0 && l.ll == 0 && l.waves == 4 && l.lp == 32) {
-            hipLaunchKernelGGL((half_sweep_lane_team_kernel<real_t, K_TNCG, 50, 1, 0, 0, 4, 32>), dim3(grid), dim3(WAVE * 4), 0, stream, a);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-    }
-    return 1;
-}
-template <int METHOD> int launch_lane_shape(hipStream_t stream, int s_load, const LaneShape& l, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    const int lp = l.lp, tx = l.tx;
-    const int key = (((l.lv * 10 + l.la) * 10 + l.ll) * 10 + l.waves) * 10 + l.small + (lp > 0 ? 100000 : 0);
-    if constexpr (sizeof(real_t) == 8) {
-        if constexpr (METHOD == K_PG) return 1;
-        else if (s_load == 25) {
-            switch (key) {
-                case 10011: return launch_lane<METHOD, 25, 1, 0, 0, 1, true>(stream, a, grid_mult);
-                case 10110: return launch_lane<METHOD, 25, 1, 0, 1, 1>(stream, a, grid_mult);
-                case 12110: return launch_lane<METHOD, 25, 1, 2, 1, 1>(stream, a, grid_mult);
-                case 12120: return launch_lane<METHOD, 25, 1, 2, 1, 2>(stream, a, grid_mult);
-                case 12140: return launch_lane<METHOD, 25, 1, 2, 1, 4>(stream, a, grid_mult);
-                case 112140: return launch_lane<METHOD, 25, 1, 2, 1, 4, false, 16>(stream, a, grid_mult);
-                case 110011:
-                    if constexpr (METHOD != K_TNCG) {
-                        if (lp == 32) return launch_lane<METHOD, 25, 1, 0, 0, 1, true, 32>(stream, a, grid_mult);
-                    }
-                    break;
-            }
-        } else if (s_load == 50) {
-            if (tx == 48 && key == 10010) return launch_lane<METHOD, 50, 1, 0, 0, 1, false, 0, 48>(stream, a, grid_mult);
-            if (tx == 64 && key == 10010) return launch_lane<METHOD, 50, 1, 0, 0, 1, false, 0, 64>(stream, a, grid_mult);
-            switch (key) {
-                case 10020: return launch_lane<METHOD, 50, 1, 0, 0, 2>(stream, a, grid_mult);
-                case 110040: if (lp == 32) return launch_lane<METHOD, 50, 1, 0, 0, 4, false, 32>(stream, a, grid_mult); break;
-            }
-        }
-    } else {
-        if (s_load == 13) {
-            if constexpr (METHOD == K_PG) {
-                // (l.ku: the planner names the used width, lane_used_width -- 50 at k = 50, else 0 = every element of the 13 slots)
-                if (l.ku == LANE_KU_50) {
-                    if constexpr (PMF_LANE_KU50 != 0) switch (key) {
-                        case 40041: return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 0, 0, LANE_KU_50>(stream, a, grid_mult);
-                        case 140041: if (lp == 16) return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 16, 0, LANE_KU_50>(stream, a, grid_mult); break;
-                    }
-                } else if (l.ku == 0) {
-                    switch (key) {
-                        case 40041: return launch_lane<METHOD, 13, 4, 0, 0, 4, true>(stream, a, grid_mult);
-                        case 140041: if (lp == 16) return launch_lane<METHOD, 13, 4, 0, 0, 4, true, 16>(stream, a, grid_mult); break;
-                    }
-                }
-            } else if (l.ku == 0) {
-                switch (key) {
-                    case 10011: return launch_lane<METHOD, 13, 1, 0, 0, 1, true>(stream, a, grid_mult);
-                    case 20011: return launch_lane<METHOD, 13, 2, 0, 0, 1, true>(stream, a, grid_mult);
-                    case 20021: return launch_lane<METHOD, 13, 2, 0, 0, 2, true>(stream, a, grid_mult);
-                    case 20041: return launch_lane<METHOD, 13, 2, 0, 0, 4, true>(stream, a, grid_mult);
-                    case 20081: return launch_lane<METHOD, 13, 2, 0, 0, 8, true>(stream, a, grid_mult);
-                    case 30081: return launch_lane<METHOD, 13, 3, 0, 0, 8, true>(stream, a, grid_mult);
-                }
-            }
-        }
-    }
-    return 1;
-}
-
-template <int S, int NS, int NW> int launch_regw_method(hipStream_t stream, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    if constexpr (S * REG_JG < 32) return 1;
-    else switch (method) {
-        case POISMF_PG:
-            if constexpr (tu_has(K_PG)) return launch_regw<K_PG, S, NS, NW>(stream, a, grid_mult);
-            else return 1;
-        case POISMF_CG:
-            if constexpr (tu_has(K_CG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG) return launch_regw<K_CG, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_CG)) return f(integral_constant<int, K_CG>{});
             else return 1;
         case POISMF_EVAL:
-            if constexpr (tu_has(K_EVAL) && S * REG_JG <= REGW_WAVE_NNZ_MAX_CG) return launch_regw<K_EVAL, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_EVAL)) return f(integral_constant<int, K_EVAL>{});
             else return 1;
         default:
-            if constexpr (tu_has(K_TNCG) && S * REG_JG <= REGW_WAVE_NNZ_MAX_TNCG) return launch_regw<K_TNCG, S, NS, NW>(stream, a, grid_mult);
+            if constexpr (tu_has(K_TNCG)) return f(integral_constant<int, K_TNCG>{});
             else return 1;
     }
 }
-
-template <int NS, int NW> int launch_regw_steps_nw(hipStream_t stream, int S, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
+// f(S) for the tile steps S of the register engines (plan.hpp, PMF_REG_SIZES)
+template <class F> int with_steps(int S, F f)
 {
     switch (S) {
-#define X(NZ) case (NZ) / REG_JG: return launch_regw_method<(NZ) / REG_JG, NS, NW>(stream, method, a, grid_mult);
+#define X(NZ) case (NZ) / REG_JG: return f(integral_constant<int, (NZ) / REG_JG>{});
         PMF_REG_SIZES(X)
 #undef X
     }
     return 1;
 }
-template <int NS> int launch_regw_steps(hipStream_t stream, int nw, int S, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    switch (nw) {
-        case 2: return launch_regw_steps_nw<NS, 2>(stream, S, method, a, grid_mult);
-        case 4: return launch_regw_steps_nw<NS, 4>(stream, S, method, a, grid_mult);
-        case 8: return launch_regw_steps_nw<NS, 8>(stream, S, method, a, grid_mult);
-    }
-    return 1;
-}
-
-template <int NS> int launch_reg_steps(hipStream_t stream, int S, int method, const HalfArgs<real_t>& a, unsigned grid_mult)
-{
-    switch (S) {
-#define X(NZ) case (NZ) / REG_JG: return launch_reg_method<(NZ) / REG_JG, NS>(stream, method, a, grid_mult);
-        PMF_REG_SIZES(X)
-#undef X
-    }
-    return 1;
-}
-
-
 // The BASELINE configs' slot counts have instances of their own (the LDS engine prefetches the next chunk only in those); every other k takes
 // the generic ones, by slots per lane (tests/test_gpu_regtile.py).  f(NC, SL) launches the instance.
 template <class F> int with_slots(const OneLaunch& o, F f)
 {
-    using std::integral_constant;
     if (o.s_load == SPECIAL_SL_A) return f(integral_constant<int, SLOT_ELEMS>{}, integral_constant<int, SPECIAL_SL_A>{});
     if (o.s_load == SPECIAL_SL_B) return f(integral_constant<int, SLOT_ELEMS>{}, integral_constant<int, SPECIAL_SL_B>{});
     switch (o.spl) {
@@ -942,42 +721,140 @@ template <class F> int with_slots(const OneLaunch& o, F f)
     return 1;
 }
 
-int launch_one_here(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+// ---- the engines -------------------------------------------------------------------------------------------------------------------------
+// LDS engine, one wave per row or LONG_NW
+template <int NW> int launch_bin(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
 {
-    t_device = o.device; t_num_cu = o.num_cu;
-    const hipStream_t st = o.stream;
-    switch (o.engine) {
-        case Engine::LaneTeam: return launch_lane_team(st, method, o.s_load, o.lane, a, o.grid);
-        case Engine::Lane:
-            switch (method) {
-                case POISMF_PG: return launch_lane_shape<K_PG>(st, o.s_load, o.lane, a, o.grid_mult);
-                case POISMF_CG: return launch_lane_shape<K_CG>(st, o.s_load, o.lane, a, o.grid_mult);
-                case POISMF_TNCG: return launch_lane_shape<K_TNCG>(st, o.s_load, o.lane, a, o.grid_mult);
-                case POISMF_EVAL: return launch_lane_shape<K_EVAL>(st, o.s_load, o.lane, a, o.grid_mult);
+    return with_slots(o, [&](auto nc, auto sl) {
+        return with_method(method, [&](auto m) {
+            return launch_lds<half_sweep_kernel<real_t, decltype(nc)::value, decltype(m)::value, decltype(sl)::value, NW>, WAVE * NW>(o, a);
+        });
+    });
+}
+// giant-row teams: TNCG only (the solver whose evaluations re-stream the row; CG has its cached line search and the register teams)
+int launch_giant(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return with_slots(o, [&](auto nc, auto sl) {
+        if constexpr (tu_has(K_TNCG)) {
+            if (method == POISMF_TNCG)
+                return launch_lds<half_sweep_giant_kernel<real_t, decltype(nc)::value, K_TNCG, decltype(sl)::value, LONG_NW>, WAVE * LONG_NW>(o, a);
+        }
+        return 1;
+    });
+}
+
+// register engine, one wave per row: one or (REG_NS_MAX == 2) two slots per lane, by the factor row's slots
+int launch_reg(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return with_method(method, [&](auto m) {
+        return with_steps(o.reg_S, [&](auto s) {
+            constexpr int M = decltype(m)::value, S = decltype(s)::value;
+            const int ns = REG_NS_MAX == 1 || o.s_load <= REG_G ? 1 : 2;
+            if constexpr (reg_instance(M, S, 1)) {
+                if (ns == 1) return launch_occ<half_sweep_reg_kernel<real_t, M, S, REG_G, 1>, WAVE>(o, a);
+            }
+            if constexpr (reg_instance(M, S, 2)) {
+                if (ns == 2) return launch_occ<half_sweep_reg_kernel<real_t, M, S, REG_G, 2>, WAVE>(o, a);
             }
             return 1;
+        });
+    });
+}
+// ... four lanes per nonzero (quad_eval.hpp): PG on floats at k = 50 from the line-padded copy; a plan never names the quad engine in a unit or a
+// build without it
+int launch_quad(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    if (method != POISMF_PG || a.geom.k != QUAD_K || a.geom.ldF != QUAD_LD) return 1;
+    return with_steps(o.reg_S, [&](auto s) {
+        if constexpr (tu_has(K_PG) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16)
+            return launch_occ<half_sweep_quad_kernel<decltype(s)::value * REG_JG / 16>, WAVE>(o, a);
+        else return 1;
+    });
+}
+// ... 2, 4 or 8 waves per row
+template <int NW> int launch_regw(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return with_method(method, [&](auto m) {
+        return with_steps(o.reg_S, [&](auto s) {
+            constexpr int M = decltype(m)::value, S = decltype(s)::value;
+            if constexpr (regw_instance(M, S, NW)) {
+                if (REG_G == 16 || o.s_load <= REG_G) return launch_occ<half_sweep_regw_kernel<real_t, M, S, REG_G, 1, NW>, WAVE * NW>(o, a);
+                if constexpr (REG_G != 16) return launch_occ<half_sweep_regw_kernel<real_t, M, S, REG_G, 2, NW>, WAVE * NW>(o, a);
+            }
+            return 1;
+        });
+    });
+}
+// ... teams: CG on doubles with two slots per lane (k = 50 fp64) is what asks for them
+template <int M, int S> int launch_team(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    if constexpr ((tu_has(K_CG) || tu_has(K_EVAL)) && sizeof(real_t) == 8 && REG_G == 16) {
+        constexpr int KM = tu_has(K_CG) ? K_CG : K_EVAL;   // (the translation unit of the evaluation-only kernels has no CG)
+        if (method != (KM == K_CG ? POISMF_CG : POISMF_EVAL)) return 1;
+        // as many workgroups as CUs: each takes a CU's whole register file (one wave of 512 per SIMD)
+        const unsigned grid = (unsigned)std::min<size_t>((size_t)a.nrows * M, (size_t)o.num_cu / M * M);
+        return launch_grid<half_sweep_team_kernel<real_t, KM, S, REG_G, 2, TEAM_NW, M>, WAVE * TEAM_NW>(o, a, grid);
+    } else return 1;
+}
+
+// lane-per-nonzero engine: the instance of plan.hpp's table (PMF_LANE_INSTANCES) that the plan names
+template <int METHOD, int KS, int LV, int LA, int LL, int NW, bool SMALL, int LP, int TX, int KU> int launch_lane(const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    using EV = LaneEval<real_t, KS, LV, LA, LL, NW, SMALL, LP, TX, false, KU>;
+    // workgroups per CU: one (SMALL: two) waves per SIMD, and the LDS each takes
+    const int occ = std::max(1, std::min((lane_two<SMALL>() ? 8 : 4) / NW, (int)(LDS_PER_CU / (size_t)EV::SMEM_BYTES)));
+    const unsigned grid = (unsigned)std::min<size_t>(a.nrows, (size_t)o.num_cu * (size_t)occ * o.grid_mult);
+    return launch_grid<half_sweep_lane_kernel<real_t, METHOD, KS, LV, LA, LL, NW, SMALL, LP, TX, KU>, WAVE * NW>(o, a, grid);
+}
+int launch_lane_shape(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return with_method(method, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+#define X(FOR, KS, LV, LA, LL, NW, SMALL, LP, TX, KU)                                                  \
+        if constexpr ((((FOR) >> M) & 1u) != 0 && ((KU) == 0 || PMF_LANE_KU50 != 0)) {                 \
+            if (o.s_load == (KS) && o.lane == LaneShape{ LV, LA, LL, NW, SMALL, LP, TX, KU })          \
+                return launch_lane<M, KS, LV, LA, LL, NW, (SMALL) != 0, LP, TX, KU>(o, a);             \
+        }
+        PMF_LANE_INSTANCES(X)
+#undef X
+        return 1;
+    });
+}
+// lane teams: k = 100 fp64 TNCG rows of 385 .. 8192 nonzeros, M = a.team_members four-wave workgroups per row
+int launch_lane_team(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    return with_method(method, [&](auto m) {
+        if constexpr (decltype(m)::value == K_TNCG && sizeof(real_t) == 8) {
+            if (o.s_load == LANE_TEAM_KS && o.lane == LANE_TEAM_SHAPE)
+                return launch_grid<half_sweep_lane_team_kernel<real_t, K_TNCG, LANE_TEAM_KS, LANE_TEAM_SHAPE.lv, LANE_TEAM_SHAPE.la, LANE_TEAM_SHAPE.ll, LANE_TEAM_SHAPE.waves,
+                                                               LANE_TEAM_SHAPE.lp>, WAVE * LANE_TEAM_SHAPE.waves>(o, a, o.grid);
+        }
+        return 1;
+    });
+}
+
+int launch_one_here(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
+{
+    switch (o.engine) {
+        case Engine::LaneTeam: return launch_lane_team(method, o, a);
+        case Engine::Lane: return launch_lane_shape(method, o, a);
 #ifndef PMF_LANE_ONLY   // (development: compile the lane-per-nonzero kernels alone, seconds instead of minutes)
         case Engine::RegTeam:
-            if (o.team == 2 && o.reg_S == 32) return launch_team<2, 32>(st, method, a);
-            if (o.team == 2 && o.reg_S == 36) return launch_team<2, 36>(st, method, a);
-            if (o.team == 3 && o.reg_S == 28) return launch_team<3, 28>(st, method, a);
-            if (o.team == 3 && o.reg_S == 32) return launch_team<3, 32>(st, method, a);
-            if (o.team == 4 && o.reg_S == 32) return launch_team<4, 32>(st, method, a);
+#define X(M, S) if (o.team == (M) && o.reg_S == (S)) return launch_team<M, S>(method, o, a);
+            PMF_TEAM_SHAPES(X)
+#undef X
             return 1;
-        case Engine::Reg:
-            if (o.quad != 0) return launch_quad_steps(st, o.reg_S, method, a, o.grid_mult);
-            if constexpr (REG_NS_MAX == 1) return launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult);
-            else return o.s_load <= REG_G ? launch_reg_steps<1>(st, o.reg_S, method, a, o.grid_mult) : launch_reg_steps<2>(st, o.reg_S, method, a, o.grid_mult);
+        case Engine::Reg: return o.quad != 0 ? launch_quad(method, o, a) : launch_reg(method, o, a);
         case Engine::RegW:
-            if constexpr (REG_G == 16) return launch_regw_steps<1>(st, o.nw, o.reg_S, method, a, o.grid_mult);
-            else return o.s_load <= REG_G ? launch_regw_steps<1>(st, o.nw, o.reg_S, method, a, o.grid_mult)
-                                          : launch_regw_steps<2>(st, o.nw, o.reg_S, method, a, o.grid_mult);
-        case Engine::Giant:
-            return with_slots(o, [&](auto nc, auto sl) { return launch_giant_method<decltype(nc)::value, decltype(sl)::value>(st, method, a, o.lds, o.grid); });
-        case Engine::LdsLong:
-            return with_slots(o, [&](auto nc, auto sl) { return launch_method<decltype(nc)::value, decltype(sl)::value, LONG_NW>(st, method, a, o.lds, o.grid); });
-        case Engine::Lds:
-            return with_slots(o, [&](auto nc, auto sl) { return launch_method<decltype(nc)::value, decltype(sl)::value>(st, method, a, o.lds, o.grid); });
+            switch (o.nw) {
+                case 2: return launch_regw<2>(method, o, a);
+                case 4: return launch_regw<4>(method, o, a);
+                case 8: return launch_regw<8>(method, o, a);
+            }
+            return 1;
+        case Engine::Giant: return launch_giant(method, o, a);
+        case Engine::LdsLong: return launch_bin<LONG_NW>(method, o, a);
+        case Engine::Lds: return launch_bin<1>(method, o, a);
 #else
         default: return 1;
 #endif
