@@ -661,6 +661,64 @@ POISMF_HIP_API int poismf_hip_session_rank_shared(poismf_hip_session *s, const s
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         unsigned int *out_rank, unsigned int *out_n_adm);
 
+/* ---------------------------------------------------------------------------------------------
+ * 1m. New rows against a resident B: the factors of users the model has never seen (the reference's predict_factors, ref:
+ *     poismf/__init__.py:619-692), and their top-N (its topN_new) and exact ranks, without B travelling per request.  (Placed
+ *     here, after the session's types, which three of the four entries take.)
+ *
+ * The n_new rows are a host CSR (Xr, Xr_indptr [n_new + 1], Xr_indices; item indices < dimB), as factors_multiple takes them.
+ * They become a GUEST of the session: their CSR and an n_new x k factor of their own are kept on the device next to the
+ * session's B, which the guest borrows (with its line-padded gather copy, refreshed for the session if it was stale).  The
+ * guest is kept by the session and reused by the next call; nothing of it outlives the session.  A call allocates, uploads
+ * and copies nothing in proportion to dimB x k, writes nothing to the session's A, B or matrix, and is ordered after the work
+ * already enqueued on the session stream.
+ *
+ *   factors      bit for bit those of factors_multiple (section 1b) with the same B, Bsum, Amean, rows and solver arguments: the
+ *                same half-sweep of the same row kernels under the same plan.  Of *p: l2_reg, w_mult, step_size, method,
+ *                limit_step and maxupd mean what they mean there; reuse_prev is its reuse_mean; l1_reg and early_stop are
+ *                ignored (Bsum [k] already carries l1).  Rows start at Amean [k], broadcast on the device (TNCG without
+ *                reuse_prev: at 1e-3, set by the kernel).  An empty row's factors are zero; a call whose rows are all empty
+ *                gives zeros without a launch (quirk Q7).
+ *   top-N        section 1f's answer(u) for A = the new factors: the same total order, and score bits those of predict_multiple
+ *                on these factors.  E(u) is the union of (a) with exclude_own the items of new row u itself, read from the
+ *                guest's CSR on the device, nothing staged a second time -- a row that is not strictly ascending is treated as
+ *                exclude_seen treats such a resident row: the rows are then scanned, not binary-searched, and an item named
+ *                twice counts once -- and (b) the optional list excl_indptr [n_new + 1] / excl_indices of section 1f.
+ *   ranks        section 1g's rank(u, t) and N(u) for the same factors and the same E(u).
+ *   out_A        [n_new x k], host: the new factors.  Required by poismf_hip_session_factors_new; NULL elsewhere means the
+ *                factors never leave the device.
+ *
+ * Return 0; 1 on a device error / out of memory; 2, with no output touched and before any device work, when: the session, p,
+ * Bsum, Amean, Xr_indptr or a required output is NULL; row pointers decrease; an item index >= dimB; Xr or Xr_indices NULL
+ * with a nonzero stored; and whatever is 2 in section 1f (top-N) or 1g (ranks) for users 0 .. n_new-1 -- "too few items
+ * left" counts the union of the row's own items (with exclude_own) and its exclusion row.  n_new == 0 returns 0.
+ *
+ * poismf_hip_topn_new is the host-pointer drop-in: B [dimB x k] goes up once, to the device of POISMF_HIP_DEVICE, into a
+ * temporary session; the same core runs and everything is freed before it returns.  Its solver arguments are
+ * factors_multiple's, in that order.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_factors_new(poismf_hip_session *s, const real_t *Xr, const sparse_ix *Xr_indptr,
+        const sparse_ix *Xr_indices, size_t n_new, const real_t *Bsum, const real_t *Amean,
+        const poismf_hip_params *p, size_t niter, real_t *out_A);
+POISMF_HIP_API int poismf_hip_session_topn_new(poismf_hip_session *s, const real_t *Xr, const sparse_ix *Xr_indptr,
+        const sparse_ix *Xr_indices, size_t n_new, const real_t *Bsum, const real_t *Amean,
+        const poismf_hip_params *p, size_t niter, size_t n_top, int exclude_own,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_A);
+POISMF_HIP_API int poismf_hip_session_rank_new(poismf_hip_session *s, const real_t *Xr, const sparse_ix *Xr_indptr,
+        const sparse_ix *Xr_indices, size_t n_new, const real_t *Bsum, const real_t *Amean,
+        const poismf_hip_params *p, size_t niter,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, int exclude_own,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        unsigned int *out_rank, unsigned int *out_n_adm, real_t *out_A);
+POISMF_HIP_API int poismf_hip_topn_new(const real_t *B, const real_t *Bsum, const real_t *Amean,
+        const real_t *Xr, const sparse_ix *Xr_indptr, const sparse_ix *Xr_indices,
+        int k, size_t dimB, size_t n_new,
+        real_t l2_reg, real_t w_mult, real_t step_size, size_t niter, size_t maxupd,
+        int method, bool limit_step, bool reuse_mean,
+        size_t n_top, int exclude_own, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_A);
+
 /* The log-likelihood of section 1e for the session's resident CSR shard (rows [rowA_begin,rowA_end) of A) under its resident
  * factors; with include_missing, M covers the shard's rows of A times all of B.  No factor or matrix is copied: one double
  * comes back in *out.  Ordered after the work already enqueued on the session stream; reads the compact factors, so writes

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_shared", "poismf_hip_session_topn_shared", "poismf_hip_topn_shared_scratch_bytes",
     "poismf_hip_rank_shared", "poismf_hip_session_rank_shared", "poismf_hip_rank_shared_scratch_bytes",
     "poismf_hip_topn_deep", "poismf_hip_session_topn_deep", "poismf_hip_topn_deep_scratch_bytes",
+    "poismf_hip_session_factors_new", "poismf_hip_session_topn_new", "poismf_hip_session_rank_new", "poismf_hip_topn_new",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -189,6 +190,15 @@ def load_library(use_float):
     lib.poismf_hip_session_rank_shared.restype = i
     lib.poismf_hip_rank_shared_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, sz]
     lib.poismf_hip_rank_shared_scratch_bytes.restype = sz
+    new_rows = [vp, vp, vp, vp, sz, vp, vp, C.POINTER(lib.params_t), sz]   # session, Xr, indptr, indices, n_new, Bsum, Amean, p, niter
+    lib.poismf_hip_session_factors_new.argtypes = new_rows + [vp]
+    lib.poismf_hip_session_factors_new.restype = i
+    lib.poismf_hip_session_topn_new.argtypes = new_rows + [sz, i, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_new.restype = i
+    lib.poismf_hip_session_rank_new.argtypes = new_rows + [vp, vp, i, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_rank_new.restype = i
+    lib.poismf_hip_topn_new.argtypes = [vp] * 6 + [i, sz, sz, r, r, r, sz, sz, i, C.c_bool, C.c_bool, sz, i, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_new.restype = i
     lib.poismf_hip_session_plan.argtypes = [vp, i, C.c_char_p, sz]
     lib.poismf_hip_session_plan.restype = sz
     lib.poismf_hip_session_launch_profile.argtypes = [vp, i, C.c_char_p, sz]
@@ -602,6 +612,36 @@ def _topn_batch_args(users, n, exclude, dimA, dimB):
     return users, indptr, indices
 
 
+def _new_rows_args(X_new, dimB, use_float):
+    """The rows of users the model has never seen, as the fold-in calls take them (include/poismf_hip.h section 1m), checked without
+    a device as the library itself checks them: a SciPy sparse matrix with one row per new user and the model's number of columns,
+    coerced as transform() coerces it (CSR, duplicates summed, indices sorted).  Returns (data real_t, indptr, indices) with uint64
+    index arrays."""
+    import scipy.sparse as sp
+    if not sp.issparse(X_new):
+        raise ValueError("the new rows must be a SciPy sparse matrix with one row per new user")
+    if X_new.shape[1] != dimB:
+        raise ValueError(f"the new rows have {X_new.shape[1]} columns, the model {dimB} items")
+    csr = sp.csr_matrix(X_new)
+    if len(csr.indptr) != csr.shape[0] + 1 or np.any(np.diff(csr.indptr) < 0) or int(csr.indptr[-1]) > len(csr.indices):
+        raise ValueError("the new rows: row pointers must not decrease and must stay inside the index list")
+    if len(csr.indices) and (int(csr.indices.min()) < 0 or int(csr.indices.max()) >= dimB):
+        raise ValueError("an item index of the new rows is out of range")
+    csr.sum_duplicates(); csr.sort_indices()
+    dt = np.float32 if use_float else np.float64
+    return (np.ascontiguousarray(csr.data, dtype=dt), np.ascontiguousarray(csr.indptr, dtype=np.uint64),
+            np.ascontiguousarray(csr.indices, dtype=np.uint64))
+
+
+def _new_stats(Bsum, Amean, k, use_float):
+    """Bsum (with l1 already added) and Amean of the fold-in calls as C-contiguous real_t k-vectors"""
+    dt = np.float32 if use_float else np.float64
+    Bsum, Amean = np.ascontiguousarray(Bsum, dtype=dt).reshape(-1), np.ascontiguousarray(Amean, dtype=dt).reshape(-1)
+    if len(Bsum) != k or len(Amean) != k:
+        raise ValueError(f"Bsum and Amean must have k = {k} entries")
+    return Bsum, Amean
+
+
 def _topn_deep_args(users, n, exclude, dimA, dimB):
     """The argument checks of the deep batched top-N (include/poismf_hip.h section 1l) that need no device, as the library itself
     makes them: n up to TOPN_DEEP_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).  Returns (users,
@@ -720,7 +760,7 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
     fused pass on the GPU (include/poismf_hip.h section 1f).  exclude: None, a SciPy sparse matrix with one row per entry of
     `users` (its nonzero columns are left out: passing the training matrix's rows excludes what a user has seen -- the model
     does not keep X) or an (indptr, indices) pair with strictly ascending rows.  Returns (items uint64 [m x n], scores [m x n],
-    empty unless output_score).  For new users: transform() first, then poismf_hip_topn_batch with the new factors as A.
+    empty unless output_score).  For new users: topN_new (a resident model: Session.topn_new).
     include: a candidate list per user, in the same two forms (a sparse matrix's stored columns): each user is ranked among its
     own list only and only those rows of B are read (section 1h).  n may then exceed what a user has left: the row is padded
     with TOPN_NONE and -inf.
@@ -789,6 +829,36 @@ def _topN_deep(self, users, n=1000, exclude=None, output_score=False):
 
 
 PoisMF.topN_deep = _topN_deep
+
+
+def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False):
+    """The n best items of users the model has never seen (ref: poismf/__init__.py, topN_new), one row of X per new user: their
+    factors are obtained as transform(X) obtains them -- the model's own method and hyper-parameters -- and ranked against B under
+    "score descending, item index ascending" without leaving the device, B going up once (poismf_hip_topn_new, include/poismf_hip.h
+    section 1m).  exclude_own leaves out the items of the user's own row of X; exclude (a SciPy sparse matrix with one row per row
+    of X, or an (indptr, indices) pair with strictly ascending rows) leaves out more.  Returns (items uint64 [m x n], scores
+    [m x n], empty unless output_score): those of topN_batch on transform(X)'s factors, bit for bit."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    data, indptr, indices = _new_rows_args(X, self.nitems, self.use_float)
+    m, n = len(indptr) - 1, int(n)
+    _, ep, ei = _topn_batch_args(np.arange(m, dtype=np.uint64), n, exclude, max(m, 1), self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    Bsum, Amean = _new_stats(self.Bsum, self.Amean, self.k, self.use_float)
+    _batch_rc(load_library(self.use_float).poismf_hip_topn_new(
+        _ptr(B), _ptr(Bsum), _ptr(Amean), _opt_ptr(data), _ptr(indptr), _opt_ptr(indices), self.k, self.nitems, m, self.l2_reg_,
+        self.weight_mult, self.initial_step, int(self.niter_), int(self.maxupd_), _METHOD[self.method], bool(self.limit_step),
+        bool(self.reuse_prev), n, int(bool(exclude_own)), _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ix),
+        _ptr(sc) if output_score else None, None), "top-N of new rows")
+    return ix, sc
+
+
+PoisMF.topN_new = _topN_new
 
 
 def _rank_include_list(include, m, dimB):
@@ -1323,6 +1393,92 @@ class Session:
             include = _unite_rows(_include_rows(include, users, self.dimA, self.dimB), test)
         ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include)
         return _ranking_result(test[0], ranks, n_adm, k, per_user)
+
+    def _new_rows(self, X_new, params, niter, Bsum, Amean):
+        """what every fold-in call starts with (include/poismf_hip.h section 1m): the leading arguments of the C entry point, the
+        number of new rows, and the arrays those arguments point into"""
+        data, indptr, indices = _new_rows_args(X_new, self.dimB, self.use_float)
+        if Bsum is None or Amean is None:
+            if self.shardA != (0, self.dimA) or self.shardB != (0, self.dimB):
+                raise ValueError("this session updates only a shard of the factors: pass Bsum and Amean of the whole model")
+            A, B = self.get_factors()
+            Bsum = B.sum(axis=0) + params.l1_reg if Bsum is None else Bsum      # as PoisMF.fit leaves them
+            Amean = A.mean(axis=0) if Amean is None else Amean
+        Bsum, Amean = _new_stats(Bsum, Amean, self.k, self.use_float)
+        keep = (data, indptr, indices, Bsum, Amean)
+        return [self.h, _opt_ptr(data), _ptr(indptr), _opt_ptr(indices), len(indptr) - 1, _ptr(Bsum), _ptr(Amean), C.byref(params),
+                int(niter)], len(indptr) - 1, keep
+
+    def transform(self, X_new, params, niter, Bsum=None, Amean=None):
+        """Factors A_new [n_new x k] of users the model has never seen, against the resident B (section 1m): bit for bit those of
+        factors_multiple / PoisMF.transform with the same B, Bsum, Amean and solver arguments, without B travelling.  X_new: a SciPy
+        CSR / COO matrix with dimB columns, one row per new user (duplicates summed, indices sorted).  params as make_params gives
+        them (method, l2_reg, w_mult, step_size, limit_step, maxupd; reuse_prev starts every row at Amean also for tncg; l1_reg
+        and early_stop play no part in the solve).  Bsum (column sums of B plus l1) and Amean (column means of A) default to what
+        PoisMF.fit would leave for the resident factors -- B.sum(axis=0) + params.l1_reg and A.mean(axis=0) -- AT THE COST OF
+        DOWNLOADING BOTH FACTORS: serving code computes them once and passes them in."""
+        args, m, keep = self._new_rows(X_new, params, niter, Bsum, Amean)
+        A_new = np.empty((m, self.k), np.float32 if self.use_float else np.float64)
+        if m:
+            _batch_rc(self.lib.poismf_hip_session_factors_new(*args, _ptr(A_new)), "factors of new rows")
+        return A_new
+
+    def topn_new(self, X_new, params, niter, top_n=10, exclude_own=True, exclude=None, output_score=False, return_factors=False,
+                 Bsum=None, Amean=None):
+        """The top_n best items of every new user of X_new: transform()'s factors ranked against the resident B as topn_batch ranks
+        resident users, in one call, the factors staying on the device unless return_factors (section 1m).  exclude_own leaves
+        out the items of the user's own row of X_new (read from the copy the solve uses); exclude (a SciPy sparse matrix with one
+        row per new user, or an (indptr, indices) pair with strictly ascending rows) leaves out more.  Bsum / Amean as in
+        transform().  Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score), and with return_factors
+        a third entry, A_new."""
+        args, m, keep = self._new_rows(X_new, params, niter, Bsum, Amean)
+        n = int(top_n)
+        _, ep, ei = _topn_batch_args(np.arange(m, dtype=np.uint64), n, exclude, max(m, 1), self.dimB)
+        dt = np.float32 if self.use_float else np.float64
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), dt)
+        A_new = np.empty((m, self.k), dt) if return_factors else None
+        if m:
+            _batch_rc(self.lib.poismf_hip_session_topn_new(*args, n, int(bool(exclude_own)), _ptr(ep) if ep is not None else None,
+                                                           _opt_ptr(ei), _ptr(ix), _ptr(sc) if output_score else None,
+                                                           _ptr(A_new) if return_factors else None), "top-N of new rows")
+        return (ix, sc, A_new) if return_factors else (ix, sc)
+
+    def rank_new(self, X_new, test, params, niter, exclude_own=True, exclude=None, return_factors=False, Bsum=None, Amean=None):
+        """For every cell of `test` (a SciPy sparse matrix with one row per new user, or an (indptr, indices) pair with strictly
+        ascending rows) the 0-based position of its item in the new user's complete ranked list, as rank_batch gives it for a
+        resident user, from transform()'s factors (section 1m); exclude_own / exclude / Bsum / Amean as in topn_new.  Returns (ranks
+        uint32, one per cell in row order, RANK_EXCLUDED where the item is excluded; n_adm uint32 [m]), and with return_factors a
+        third entry, A_new."""
+        args, m, keep = self._new_rows(X_new, params, niter, Bsum, Amean)
+        _, tp, ti, ep, ei = _rank_batch_args(np.arange(m, dtype=np.uint64), test, exclude, max(m, 1), self.dimB, self.k)
+        ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
+        A_new = np.empty((m, self.k), np.float32 if self.use_float else np.float64) if return_factors else None
+        if m:
+            _batch_rc(self.lib.poismf_hip_session_rank_new(*args, _ptr(tp), _opt_ptr(ti), int(bool(exclude_own)),
+                                                           _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm),
+                                                           _ptr(A_new) if return_factors else None), "ranks of new rows")
+        return (ranks, n_adm, A_new) if return_factors else (ranks, n_adm)
+
+    def eval_ranking_new(self, X_observed, X_test, params, niter, k=10, per_user=False, exclude_own=True, exclude=None, Bsum=None,
+                         Amean=None):
+        """Held-out ranking metrics under strong generalisation: users held out of training are folded in on X_observed (one row per
+        user, dimB columns) and ranked on X_test (same shape; its stored cells are the held-out positives, values play no part,
+        explicit zeros dropped).  The ranks are rank_new's, the metrics those of poismf_amd/metrics.py, the result eval_ranking's:
+        the means of hit, precision, recall, ap, ndcg, rr, auc at cut-off k over the users that counted, plus n_users; with
+        per_user also "per_user", "ranks", "n_adm" and "test_indptr"."""
+        import scipy.sparse as sp
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if not sp.issparse(X_test) or X_test.shape != X_observed.shape:
+            raise ValueError("X_test must be a SciPy sparse matrix of X_observed's shape")
+        test = sp.csr_matrix(X_test)
+        test.sum_duplicates(); test.eliminate_zeros(); test.sort_indices()
+        tp = np.asarray(test.indptr, np.uint64)
+        ranks, n_adm = self.rank_new(X_observed, (tp, np.asarray(test.indices, np.uint64)), params, niter, exclude_own=exclude_own,
+                                     exclude=exclude, Bsum=Bsum, Amean=Amean)
+        return _ranking_result(tp, ranks, n_adm, k, per_user)
 
     def _text(self, fn, which):
         """a text report of the library, whole: ask for the length first (a fixed buffer cut long plans mid-item)"""

@@ -181,9 +181,39 @@ poismf_hip_params params_of(real_t l2_reg, real_t l1_reg, real_t w_mult, real_t 
     return p;
 }
 
+}  // namespace
+
 // -------------------------------------------------------------------------------------------------
 // factors_multiple: latent factors of new rows with B fixed          ref: src/pred.c:66-199
 // -------------------------------------------------------------------------------------------------
+// The solve, on a session whose A half holds the new rows, whose dA holds their start and whose dB holds B: factors_multiple below sets such
+// a session up and throws it away, the entry points of fold_in.hip run it on the guest of a resident session.  The same launches either way.
+int fold_in_solve(poismf_hip_session* s, const real_t* Bsum, real_t l2_reg, real_t w_mult, real_t step_size, size_t niter, size_t maxupd,
+                  int method, bool limit_step, bool reuse_mean)
+{
+    const size_t ks = s->k;
+    std::vector<real_t> bs(ks);
+    int rc = 0;
+    poismf_hip_params p = params_of(l2_reg, 0, w_mult, step_size, method, limit_step, maxupd, false, reuse_mean);
+    const bool weighted = w_mult != (real_t)1.;
+    if (method == POISMF_PG) {                                    // ref: :152-169
+        const real_t step0 = step_size;
+        for (size_t it = 0; it < niter && !rc; it++) {
+            for (size_t c = 0; c < ks; c++) bs[c] = weighted ? Bsum[c] : Bsum[c] * (-step_size);
+            const real_t cnst_div = 1. / (1. + 2. * l2_reg * step_size);
+            // w != 1: Bsum_w was scaled by -step at set-up (ref: :121-122) and again by -step here (ref: :162)
+            rc = half_sweep_impl(s, 1, &p, step_size, cnst_div, nullptr, bs.data(), -step0, weighted ? -step_size : (real_t)1);
+            step_size *= 0.5;
+        }
+    } else {
+        for (size_t c = 0; c < ks; c++) bs[c] = Bsum[c];
+        if (method == POISMF_CG) p.maxupd = maxupd * niter;      // ref: :175-178
+        rc = half_sweep_impl(s, 1, &p, step_size, (real_t)1, nullptr, bs.data(), -step_size);
+    }
+    return rc;
+}
+
+namespace {
 int factors_multiple_impl(real_t* A, real_t* B, real_t* Bsum, real_t* Amean, real_t* Xr, sparse_ix* Xr_indptr,
                                  sparse_ix* Xr_indices, int k, size_t dimA, real_t l2_reg, real_t w_mult, real_t step_size,
                                  size_t niter, size_t maxupd, int method, bool limit_step, bool reuse_mean, unsigned* decisions)
@@ -204,7 +234,6 @@ int factors_multiple_impl(real_t* A, real_t* B, real_t* Bsum, real_t* Amean, rea
     const int device = pmf_env_device();
     poismf_hip_session* s = nullptr;
     int rc = 0;
-    std::vector<real_t> bs(ks);
     if (poismf_hip_session_create(&s, device, nullptr, Xr, Xr_indptr, Xr_indices, nullptr, nullptr, nullptr, dimA, dimB, ks, 0,
                                   dimA, 0, 0) ||
         hipMemcpy(s->dA, A, dimA * ks * sizeof(real_t), hipMemcpyHostToDevice) != hipSuccess ||
@@ -212,22 +241,7 @@ int factors_multiple_impl(real_t* A, real_t* B, real_t* Bsum, real_t* Amean, rea
         rc = 1;
     } else {
         if (decisions != nullptr) poismf_hip_session_profile(s, 1);
-        poismf_hip_params p = params_of(l2_reg, 0, w_mult, step_size, method, limit_step, maxupd, false, reuse_mean);
-        const bool weighted = w_mult != (real_t)1.;
-        if (method == POISMF_PG) {                                    // ref: :152-169
-            const real_t step0 = step_size;
-            for (size_t it = 0; it < niter && !rc; it++) {
-                for (size_t c = 0; c < ks; c++) bs[c] = weighted ? Bsum[c] : Bsum[c] * (-step_size);
-                const real_t cnst_div = 1. / (1. + 2. * l2_reg * step_size);
-                // w != 1: Bsum_w was scaled by -step at set-up (ref: :121-122) and again by -step here (ref: :162)
-                rc = half_sweep_impl(s, 1, &p, step_size, cnst_div, nullptr, bs.data(), -step0, weighted ? -step_size : (real_t)1);
-                step_size *= 0.5;
-            }
-        } else {
-            for (size_t c = 0; c < ks; c++) bs[c] = Bsum[c];
-            if (method == POISMF_CG) p.maxupd = maxupd * niter;      // ref: :175-178
-            rc = half_sweep_impl(s, 1, &p, step_size, (real_t)1, nullptr, bs.data(), -step_size);
-        }
+        rc = fold_in_solve(s, Bsum, l2_reg, w_mult, step_size, niter, maxupd, method, limit_step, reuse_mean);
         if (!rc && (hipStreamSynchronize(s->stream) != hipSuccess ||
                     hipMemcpy(A, s->dA, dimA * ks * sizeof(real_t), hipMemcpyDeviceToHost) != hipSuccess))
             rc = 1;

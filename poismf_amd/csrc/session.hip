@@ -38,8 +38,6 @@ static void release_stream(int device, hipStream_t st)
     (void)hipStreamDestroy(st);
 }
 
-namespace {
-
 void free_half(Half& h, hipStream_t stream)
 {
     pmf_free(h.d_indptr, stream);
@@ -51,6 +49,8 @@ void free_half(Half& h, hipStream_t stream)
     pmf_free(h.d_dec_rows, stream);
     h = Half();
 }
+
+namespace {
 
 // ---- device-side set-up of one half ---------------------------------------------------------------------------------
 
@@ -369,6 +369,12 @@ void poismf_hip_session_destroy(poismf_hip_session* s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device);
+    if (s->guest != nullptr) { poismf_hip_session_destroy(s->guest); s->guest = nullptr; }   // (before anything the guest borrows goes)
+    if (s->borrows_B) {   // a guest (fold_in.hip): B, its padded copy, the streams and the events are its host's
+        s->dB = s->dBp = nullptr;
+        s->aux_stream = nullptr; s->owns_stream = false;
+        s->ev_fork = s->ev_join = nullptr;
+    }
     (void)hipStreamSynchronize(s->stream);
     if (s->aux_stream) (void)hipStreamSynchronize(s->aux_stream);
     for (auto& p : s->prof) { (void)hipEventDestroy(p.t0); (void)hipEventDestroy(p.t1); }

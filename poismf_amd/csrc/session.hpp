@@ -90,6 +90,12 @@ struct poismf_hip_session {
     size_t topn_cap = 0;              // ... in bytes
     std::vector<unsigned long long> topn_indptr;   // exclude_seen: host copy of the CSR shard's row pointers (fetched by the first such call)
     int csr_rows_sorted = -1;         // exclude_seen: -1 not checked yet, 0 some resident CSR row is not strictly ascending, 1 all are
+    // New rows against the resident B (fold_in.hip; include/poismf_hip.h section 1m).  The rows are the A half of a GUEST: a session of its
+    // own rows, factor (dA, dAp), column-sum vector, queue heads, team words and `seen` bookkeeping, which BORROWS this session's dB, dBp, ld,
+    // streams and events.  Kept here from the first such call to the session's end and refilled by every later one.
+    poismf_hip_session* guest = nullptr;
+    bool borrows_B = false;           // set on a guest: poismf_hip_session_destroy leaves what it borrows alone
+    size_t guest_rows = 0;            // on a guest: the rows its dA / dAp have room for
 };
 
 // what a half's set-up has launched and not yet collected (session.hip: finish_half_launch, finish_half_collect)
@@ -133,6 +139,7 @@ poismf_hip_session* session_alloc(int device, void* stream, size_t dimA, size_t 
 int build_half(Half& h, hipStream_t stream, const real_t* val, const sparse_ix* indptr, const sparse_ix* indices,
                size_t dimM, size_t dimF, size_t r0, size_t r1, int device = 0, HalfPending* pend = nullptr);
 int finish_half_collect(Half& h, hipStream_t stream, HalfPending& pend);
+void free_half(Half& h, hipStream_t stream);
 
 // half_sweep.hip
 int nc_for_k(size_t k);
@@ -144,6 +151,9 @@ int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p
 // drivers.hip: the interrupt flag of the running call, and its device-visible twin (nullptr until a call has allocated it)
 bool interrupt_requested();
 const unsigned* device_stop_word();
+// drivers.hip: factors_multiple's solve (ref: src/pred.c:149-180) on a session whose A half holds the new rows and whose dA holds their start
+int fold_in_solve(poismf_hip_session* s, const real_t* Bsum, real_t l2_reg, real_t w_mult, real_t step_size, size_t niter, size_t maxupd,
+                  int method, bool limit_step, bool reuse_mean);
 
 // multi_device.hip
 int run_poismf_multi(const std::vector<int>& devices, real_t* A, real_t* Xr, sparse_ix* Xr_indptr, sparse_ix* Xr_indices, real_t* B, real_t* Xc,
