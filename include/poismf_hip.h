@@ -489,6 +489,55 @@ POISMF_HIP_API int poismf_hip_topn_deep(const real_t *A, const real_t *B, int k,
 POISMF_HIP_API size_t poismf_hip_topn_deep_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1n. Batched top-N with per-group quotas: section 1f's ranked list with "at most q items of one brand / seller / category on a
+ *     page" applied on the device, in the same fused pass (no counterpart in the reference).
+ *
+ * Inputs are section 1f's -- users u_0 .. u_{m-1} (any order, repeats allowed), n_top, E(u), score(u, j) and the total order
+ * "score descending, then item index ascending" -- and two host arrays of sparse_ix:
+ *
+ *   group_of     [dimB]: the group g(j) in 0 .. n_groups-1 of every item.  A group with no items is fine.
+ *   quota        [n_groups]: q(g) >= 0.  q(g) = 0: no item of the group is ever returned.  q(g) >= n_top: the group is
+ *                unconstrained (quotas above n_top are clipped to n_top on the host when they are narrowed to 32 bits).
+ *
+ * With Adm(u) = {0..dimB-1} \ E(u):
+ *
+ *   r(u, j)      #{ i in Adm(u) : g(i) = g(j), i before j in the total order }   -- the in-group rank among ADMISSIBLE items
+ *   Q(u)         { j in Adm(u) : r(u, j) < q(g(j)) }
+ *   answer(u)    the first n_top of Q(u) under the total order.  This is exactly the result of walking u's complete ranked list
+ *                and taking an item iff fewer than q(g) items of its group were taken, until n_top are taken.  It is a function
+ *                of (A[u], B, E(u), group_of, quota, n_top) alone: not of the other users, the order of the batch, how the items
+ *                are cut into slices or how the users are cut into chunks.
+ *   scores       bit for bit predict_multiple's, as in section 1f.  No float atomics.
+ *   short rows   follow section 1h / 1l's rule, not 1f's: if |Q(u)| = c < n_top, entries c .. n_top-1 of the row are
+ *                POISMF_HIP_TOPN_NONE in out_ix and -inf in out_score.  No per-user pre-check is made and nothing of a resident
+ *                row is downloaded to count a union.
+ *   range        n_top is 1 .. POISMF_HIP_TOPN_BATCH_MAX_N_TOP.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for: everything that is 2 in
+ * section 1f except "too few items left"; group_of == NULL or quota == NULL with n_users > 0; n_groups == 0 (or above 2^31 - 1: a
+ * group id is narrowed to 32 bits); an entry of group_of that is >= n_groups, or negative in the R flavour; a negative quota in the
+ * R flavour; dimB > POISMF_HIP_TOPN_QUOTA_MAX_ITEMS.  n_users == 0 returns 0.
+ *
+ * Slow path: where the quotas of the groups that have admissible items sum to less than n_top, the selection threshold never
+ * rises, every admissible item becomes a candidate and the call is slow.  Its answer is correct and padded.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1l share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB for
+ * any n_users.  The two maps go up once per call, per item and narrowed to 32 bits (the group, and its quota): 2 x 4 B x dimB,
+ * together at most 128 MiB at the item limit.  They lie in front of the chunk's parts; the chunk of users is sized from what the
+ * budget leaves beside maps of that largest size and an exclusion area of min(dimB x chunk, 2^24) indices, so every valid exclusion
+ * row fits.  poismf_hip_topn_quota_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate; it never
+ * decreases when n_users grows.  poismf_hip_topn_quota's own copies of B and of A (all of A, or only the batch's rows) come on top.
+ * The session flavour, poismf_hip_session_topn_quota, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_QUOTA_MAX_ITEMS 16777216   /* largest dimB of the quota entry points (2^24) */
+POISMF_HIP_API int poismf_hip_topn_quota(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *group_of, size_t n_groups, const sparse_ix *quota,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_quota_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t n_groups, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -625,6 +674,12 @@ POISMF_HIP_API int poismf_hip_session_topn_batch(poismf_hip_session *s, const sp
 
 /* Section 1l from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_deep(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1n from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_quota(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *group_of, size_t n_groups, const sparse_ix *quota,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 

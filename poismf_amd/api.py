@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_rank_shared", "poismf_hip_session_rank_shared", "poismf_hip_rank_shared_scratch_bytes",
     "poismf_hip_topn_deep", "poismf_hip_session_topn_deep", "poismf_hip_topn_deep_scratch_bytes",
     "poismf_hip_session_factors_new", "poismf_hip_session_topn_new", "poismf_hip_session_rank_new", "poismf_hip_topn_new",
+    "poismf_hip_topn_quota", "poismf_hip_session_topn_quota", "poismf_hip_topn_quota_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -70,6 +71,7 @@ TOPN_SHARED_MAX_CELLS = 2**24       # POISMF_HIP_TOPN_SHARED_MAX_CELLS of sectio
 RANK_SHARED_CHUNK_CELLS = 2**19     # POISMF_HIP_RANK_SHARED_CHUNK_CELLS of section 1k (tests/test_rank_shared_cpu.py compares the two)
 TOPN_DEEP_MAX_N_TOP = 1024          # POISMF_HIP_TOPN_DEEP_MAX_N_TOP and POISMF_HIP_TOPN_DEEP_BUDGET_MB of section 1l
 TOPN_DEEP_BUDGET_MB = 1024          # (tests/test_topn_deep_cpu.py compares them with the header)
+TOPN_QUOTA_MAX_ITEMS = 2**24        # POISMF_HIP_TOPN_QUOTA_MAX_ITEMS of section 1n (tests/test_topn_quota_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -158,6 +160,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_deep.restype = i
     lib.poismf_hip_topn_deep_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_deep_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_quota.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_quota.restype = i
+    lib.poismf_hip_session_topn_quota.argtypes = [vp, vp, sz, sz, vp, sz, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_quota.restype = i
+    lib.poismf_hip_topn_quota_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_topn_quota_scratch_bytes.restype = sz
     lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_rank_batch.restype = i
     lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
@@ -663,6 +671,51 @@ def _topn_deep_args(users, n, exclude, dimA, dimB):
     return users, indptr, indices
 
 
+def _topn_quota_args(users, n, group_of, quota, exclude, dimA, dimB):
+    """The argument checks of the batched top-N with per-group quotas (include/poismf_hip.h section 1n) that need no device, as the
+    library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).
+    group_of: an integer array with one group id per item.  quota: one int for every group, or an array with one entry per group
+    (its length is then the number of groups and must cover every id).  Returns (users, group_of, quota, excl_indptr or None,
+    excl_indices or None) as uint64 arrays."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if dimB > TOPN_QUOTA_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the quota call's limit of {TOPN_QUOTA_MAX_ITEMS}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if group_of is None:
+        raise ValueError("group_of is required: one group id per item")
+    group_of = _index_array(group_of, "group_of")
+    if len(group_of) != dimB:
+        raise ValueError(f"group_of has {len(group_of)} entries for {dimB} items")
+    need = int(group_of.max()) + 1
+    if quota is None:
+        raise ValueError("quota is required: one int for every group, or one entry per group")
+    if np.ndim(quota) == 0:
+        if isinstance(quota, (bool, np.bool_)) or not isinstance(quota, (int, np.integer)):
+            raise ValueError("quota must be integers")
+        if int(quota) < 0:
+            raise ValueError("quota: negative entry")
+        quota = np.full(need, min(int(quota), 2**63), np.uint64)
+    else:
+        quota = _index_array(quota, "quota")
+        if len(quota) < need:
+            raise ValueError(f"quota has {len(quota)} entries, group_of names group {need - 1}")
+    if len(quota) > 2**31 - 1:
+        raise ValueError("there are more groups than the quota call supports (2^31 - 1)")
+    if exclude is None:
+        return users, group_of, quota, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, group_of, quota, indptr, indices
+
+
 def _topn_include_args(users, n, include, exclude, dimA, dimB):
     """The argument checks of the batched top-N over include lists (include/poismf_hip.h section 1h) that need no device, as the
     library itself makes them: n may exceed what a user has left (short rows are padded).  Returns (users, incl_indptr,
@@ -829,6 +882,34 @@ def _topN_deep(self, users, n=1000, exclude=None, output_score=False):
 
 
 PoisMF.topN_deep = _topN_deep
+
+
+def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_score=False):
+    """topN_batch with "at most quota[g] items of group g on a page": the user's complete ranked list ("score descending, item index
+    ascending", minus `exclude` as in topN_batch) is walked and an item is taken iff fewer than quota[g] items of its group
+    group_of[item] were taken before it, until n <= TOPN_BATCH_MAX_N_TOP are taken -- in one fused pass on the GPU
+    (include/poismf_hip.h section 1n).  group_of: one group id per item.  quota: one int for every group, or an array with one
+    entry per group; 0 bars a group, n or more leaves it unconstrained.  A user for whom the quotas admit fewer than n items gets a
+    row padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    users, group_of, quota, indptr, indices = _topn_quota_args(users, n, group_of, quota, exclude, self.nusers, self.nitems)
+    dt = np.float32 if self.use_float else np.float64
+    m, n = len(users), int(n)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    lib = load_library(self.use_float)
+    _batch_rc(lib.poismf_hip_topn_quota(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(group_of), len(quota),
+                                        _ptr(quota), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+    return ix, sc
+
+
+PoisMF.topN_quota = _topN_quota
 
 
 def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False):
@@ -1339,6 +1420,26 @@ class Session:
         _batch_rc(self.lib.poismf_hip_session_topn_deep(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
                                                         _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
                                                         _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
+
+    def topn_quota(self, users, top_n=10, group_of=None, quota=1, exclude_seen=False, exclude=None, output_score=False):
+        """topn_batch with "at most quota[g] items of group g on a page", from the resident factors in one fused pass
+        (include/poismf_hip.h section 1n): the user's complete ranked list (order, scores, exclude_seen and exclude as in topn_batch) is
+        walked and an item is taken iff fewer than quota[g] items of its group group_of[item] were taken before it, until
+        top_n <= TOPN_BATCH_MAX_N_TOP are taken.  group_of: one group id per item.  quota: one int for every group, or an array with
+        one entry per group; 0 bars a group, top_n or more leaves it unconstrained.  A row the quotas leave short is padded with
+        TOPN_NONE and -inf.  Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score)."""
+        users, group_of, quota, indptr, indices = _topn_quota_args(users, top_n, group_of, quota, exclude, self.dimA, self.dimB)
+        m, n = len(users), int(top_n)
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
+        if m == 0:
+            return ix, sc
+        _batch_rc(self.lib.poismf_hip_session_topn_quota(self.h, _ptr(users), m, n, _ptr(group_of), len(quota), _ptr(quota),
+                                                         int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
+                                                         _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):

@@ -602,6 +602,23 @@ int poismf_hip_session_topn_deep(poismf_hip_session* s, const sparse_ix* users, 
                                     excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Batched top-N with per-group quotas from the resident (compact) factors (topn_quota.hip; include/poismf_hip.h section 1n), ordered as
+// the calls above and in the same scratch: a short row is padded, so nothing is counted beforehand.
+int poismf_hip_session_topn_quota(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* group_of,
+                                  size_t n_groups, const sparse_ix* quota, int exclude_seen, const sparse_ix* excl_indptr,
+                                  const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_quota_check(users, n_users, n_top, s->dimA, s->dimB, s->k, group_of, n_groups, quota, excl_indptr, excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_quota_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, group_of, n_groups, quota,
+                                     exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
+}
+
 // Batched top-N over per-user include lists from the resident (compact) factors (topn_include.hip; include/poismf_hip.h section 1h),
 // ordered as the call above and in the same scratch.
 int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* incl_indptr,

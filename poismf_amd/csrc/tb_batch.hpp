@@ -82,6 +82,16 @@ int poismf_hip_rank_shared_run(hipStream_t stream, const real_t* dA, const real_
                                bool unite_test, PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
                                void** d_scratch, size_t* scratch_cap, unsigned int* out_rank, unsigned int* out_n_adm);
 
+// (topn_quota.hip; section 1n) the same pair for the top-N with per-group quotas: group_of [dimB] and quota [n_groups] are host arrays;
+// the check makes no device call, the core returns 0 or 1
+int poismf_hip_topn_quota_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                const sparse_ix* group_of, size_t n_groups, const sparse_ix* quota, const sparse_ix* excl_indptr,
+                                const sparse_ix* excl_indices);
+int poismf_hip_topn_quota_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                              const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* group_of, size_t n_groups,
+                              const sparse_ix* quota, PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                              void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
+
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 namespace {
