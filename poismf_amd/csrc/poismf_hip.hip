@@ -434,9 +434,9 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(
 }
 
 // The quad engine (quad_eval.hpp) for the same rows where the plan says so (plan.hpp, reg_quad: PG on floats, k = 50, the padded copy): Q = S / 4
-// steps of sixteen nonzeros, a tile of 14 Q registers.
+// steps of sixteen nonzeros, a tile of 12 Q + 2 ceil(Q / 4) registers.
 template <int Q>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(14 * Q, K_PG)))) void half_sweep_quad_kernel(const HalfArgs<float> a)
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(QuadEval<Q>::TILE_REGS, K_PG)))) void half_sweep_quad_kernel(const HalfArgs<float> a)
 {
     using EV = QuadEval<Q>;
     EV ev;
