@@ -1,5 +1,6 @@
-// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip) and the batched ranks
-// (rank_batch.hip, rank_include.hip, rank_shared.hip) have in common, and what the session (session.hip) hands to their cores
+// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip) and
+// the batched ranks (rank_batch.hip, rank_include.hip, rank_shared.hip) have in common -- the top-N cores' chunk loop opens with
+// tb_stage_chunk and closes with tb_fetch_results -- and what the session (session.hip) hands to their cores
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -155,6 +156,52 @@ inline hipError_t tb_stage_excl(TbExcl& x, const PmfTopnSeen* seen, const sparse
     for (size_t p = 0; p < nx; p++) hx[p] = (unsigned)excl_indices[p_base + p];
     const hipError_t e = pmf_upload(d_indptr, hp.data(), (nu + 1) * sizeof(unsigned), stream);
     return e != hipSuccess ? e : pmf_upload(d_indices, hx.data(), nx * sizeof(unsigned), stream);
+}
+
+// ---- the chunk loop of the five top-N cores (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip) ----
+// the three parts every scratch layout of theirs has: the chunk's rows of A and its exclusion lists
+struct TbChunkDev { unsigned *users, *ex_indptr, *ex_indices; };
+template <class Layout> TbChunkDev tb_chunk_dev(unsigned char* base, const Layout& L)
+{
+    return { (unsigned*)(base + L.users), (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices) };
+}
+
+// Cuts the chunk that starts at user u0 -- up to chunk_users users whose exclusion lists fit idx_cap indices together -- and stages it:
+// the users' rows of A (users[i], or i itself when compact_A) go to dev.users, their exclusion test to x (tb_stage_excl).  u1: the chunk's
+// end, nx: its exclusion indices; hu, hp, hx: staging the caller keeps between chunks.  0, or 1 (a device error; a single row longer
+// than idx_cap, which the checks rule out).
+inline int tb_stage_chunk(size_t& u1, size_t& nx, TbExcl& x, size_t u0, size_t n_users, size_t chunk_users, size_t idx_cap,
+                          const sparse_ix* excl_indptr, const sparse_ix* excl_indices, const sparse_ix* users, bool compact_A,
+                          const PmfTopnSeen* seen, const TbChunkDev& dev, std::vector<unsigned>& hu, std::vector<unsigned>& hp,
+                          std::vector<unsigned>& hx, hipStream_t stream)
+{
+    u1 = u0;
+    nx = 0;
+    while (u1 < n_users && u1 - u0 < chunk_users) {
+        const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
+        if (u1 > u0 && nx + len > idx_cap) break;
+        nx += len;
+        u1++;
+    }
+    if (nx > idx_cap) return 1;
+    const size_t nu = u1 - u0;
+    hu.resize(nu);
+    for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
+    TB_TRY(pmf_upload(dev.users, hu.data(), nu * sizeof(unsigned), stream));
+    TB_TRY(tb_stage_excl(x, seen, excl_indptr, excl_indices, u0, nu, nx, dev.ex_indptr, dev.ex_indices, hp, hx, stream));
+    return 0;
+}
+
+// A chunk's results, nu rows of n_top from user u0 on: the items widened to out_ix (an empty entry becomes POISMF_HIP_TOPN_NONE) and,
+// when asked for, the scores to out_score.  hix: staging the caller keeps between chunks.  0, or 1 on a device error.
+inline int tb_fetch_results(size_t u0, size_t nu, size_t n_top, const unsigned* d_out_ix, const real_t* d_out_score, std::vector<unsigned>& hix,
+                            sparse_ix* out_ix, real_t* out_score, hipStream_t stream)
+{
+    hix.resize(nu * n_top);
+    TB_TRY(pmf_download(hix.data(), d_out_ix, nu * n_top * sizeof(unsigned), stream));
+    for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
+    if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, d_out_score, nu * n_top * sizeof(real_t), stream));
+    return 0;
 }
 
 // The drop-in entry points: B and either all of A or (when that is less) the batch's rows go to the device of POISMF_HIP_DEVICE,

@@ -87,6 +87,16 @@ __device__ __forceinline__ void tb_prune_quota(real_t* ls, unsigned* li, unsigne
     tb_wave_sync();
 }
 
+// tb_select.hpp's prune with quotas: the wave's stage and the map travel with it, so the selection knows nothing about groups
+struct TbPruneQuota {
+    unsigned* gs;            // this wave's stage, TQ_STAGE words
+    const uint2* item_map;
+    __device__ __forceinline__ void operator()(real_t* ls, unsigned* li, unsigned c, unsigned n_top, unsigned* cnt_u, real_t* thr_s_u, unsigned* thr_j_u) const
+    {
+        tb_prune_quota(ls, li, gs, c, n_top, item_map, cnt_u, thr_s_u, thr_j_u);
+    }
+};
+
 // One wave (a workgroup of 64): the answer from nslices sorted partial lists of n_top entries each (part_*: the first of them; a short
 // list ends in empty entries), by the same two counts over their union, to out_*[0 .. n_top); the ranks no live entry reaches are marked
 // empty.  ms / mj / mg / mq: TB_MERGE_MAX entries of LDS each; n_live: one word of LDS.  Within a sorted list the entries that come

@@ -14,10 +14,8 @@
 // ascending) -- whether v_mfma_f64_16x16x4_f64 rounds as that chain does has not been measured, so it is not used.
 // Scores die in registers unless they beat the user's threshold (the n_top-th best so far, kept in LDS with its item index);
 // a survivor is then looked up in the exclusion lists (binary search; linear scan of a resident row not known to be sorted) and
-// appended to the user's candidate list in LDS through an LDS counter.  A list is pruned by its wave alone, by rank counting under
-// the total order, whenever fewer than 16 slots are left (a pass over 16 item columns can add 16 candidates to one user).
-// Arrival order in the list varies from run to run; ranks under a strict total order do not, so the output is deterministic.
-// Per (user, slice) the sorted best n_top go to scratch; topn_merge_kernel ranks the slices' lists of a user the same way.
+// appended to the user's candidate list in LDS: the selection of tb_select.hpp (TbSelect), which topn_quota.hip and topn_shared.hip
+// drive too.  Per (user, slice) the sorted best n_top go to scratch; topn_merge_kernel ranks the slices' lists of a user the same way.
 // No float atomics anywhere.
 //
 // The host side cuts the batch into chunks of users so that ONE scratch allocation of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB holds a
@@ -36,14 +34,13 @@
 #include "devmem.hpp"
 #include "tb_tile.hpp"
 #include "tb_batch.hpp"
+#include "tb_select.hpp"
 
 namespace {
 
-constexpr int TB_ROOM = 16;                               // free slots a list must have before a pass over 16 item columns
-constexpr size_t TB_LDS_LIMIT = 156 * 1024;
 constexpr size_t TB_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many
-static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
 static_assert(TB_N_TOP_MAX >= 128, "the header promises at least 128");
+static_assert(tb_lds_bytes(TB_N_TOP_MAX + TB_ROOM, 0) <= TB_LDS_LIMIT, "the two tiles and 64 lists of the deepest n_top with TB_ROOM free slots fit LDS");
 
 struct TbArgs {
     const real_t* A;                  // rows addressed by `users`
@@ -63,90 +60,26 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     extern __shared__ __align__(16) unsigned char tb_smem[];
     T* As = (T*)tb_smem;                                  // [TB_TU][TB_KS]
     T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
-    T* Ls = Bs + TB_TJ * TB_KS;                           // [TB_TU][cap] candidate scores
-    unsigned* Li = (unsigned*)(Ls + (size_t)TB_TU * a.cap);   // [TB_TU][cap] candidate items
-    T* thr_s = (T*)(Li + (size_t)TB_TU * a.cap);          // [TB_TU] threshold: score ...
-    unsigned* thr_j = (unsigned*)(thr_s + TB_TU);         // ... and item
-    unsigned* cnt = thr_j + TB_TU;                        // [TB_TU] entries in the list
-    unsigned* uid = cnt + TB_TU;                          // [TB_TU] row of A, TB_NONE beyond the chunk
-
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned u_base = blockIdx.x * TB_TU;
-    if (tid < TB_TU) {
-        const unsigned u = u_base + tid;
-        uid[tid] = u < a.n_users ? a.users[u] : TB_NONE;
-        cnt[tid] = 0;
-        thr_s[tid] = -std::numeric_limits<T>::infinity();
-        thr_j[tid] = 0;
-    }
-    __syncthreads();
+    TbSelect<T, TbPrunePlain> sel;
+    sel.init((unsigned char*)(Bs + TB_TJ * TB_KS), a.cap, a.n_top, TbPrunePlain(),
+             [&](unsigned row) { return u_base + row < a.n_users ? a.users[u_base + row] : TB_NONE; });
 
     const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
     const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
     const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
-    const unsigned col = lane & 15, quad = lane >> 4;
-    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
-    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
-
-    // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
-    T thr_reg[4];
-    bool u_valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
-    bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
+    const unsigned col = threadIdx.x & 15;
+    auto user_row = [&](int row) { return sel.user_row(row); };
+    auto pos_of = [u_base](unsigned uu) { return u_base + uu; };   // a tile row's position in the chunk
 
     tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, tile0, tile1, user_row, tb_all_items(a.dimB), [&](T (&acc)[4][4], unsigned j_base) {
-        // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            if (dirty) {
-                const unsigned c_mine = cnt[16 * wave + col];
-                unsigned long long full = __ballot(quad == 0 && c_mine + TB_ROOM > a.cap);
-                if (full) {
-                    while (full) {
-                        const unsigned uu = 16 * wave + (unsigned)__builtin_ctzll(full);
-                        full &= full - 1;
-                        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) thr_reg[r] = thr_s[urow0 + r];
-                }
-                dirty = false;
-            }
             const unsigned j = j_base + 16 * t + col;
-            bool appended = false;
-            if (j < a.dimB) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const unsigned uu = urow0 + r;
-                    const T s = acc[t][r];
-                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu]) && !tb_excluded(a.excl, u_base + uu, uid[uu], j)) {
-                        const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
-                        Ls[(size_t)uu * a.cap + pos] = s;
-                        Li[(size_t)uu * a.cap + pos] = j;
-                        appended = true;
-                    }
-                }
-            }
-            if (__ballot(appended)) {
-                dirty = true;
-                tb_wave_sync();
-            }
+            sel.pass(acc[t], j, j < a.dimB, a.excl, pos_of);
         }
     });
-
-    // ---- the slice's answer per user: the best min(count, n_top) in order, the rest marked empty ----
-    for (unsigned q = 0; q < 16; q++) {
-        const unsigned uu = 16 * wave + q;
-        if (uid[uu] == TB_NONE) continue;   // (uniform over the wave)
-        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
-        const unsigned c = cnt[uu];
-        const size_t o = ((size_t)(u_base + uu) * a.nslices + blockIdx.y) * a.n_top;
-        for (unsigned i = lane; i < a.n_top; i += 64) {
-            a.part_score[o + i] = i < c ? Ls[(size_t)uu * a.cap + i] : -std::numeric_limits<T>::infinity();
-            a.part_ix[o + i] = i < c ? Li[(size_t)uu * a.cap + i] : TB_NONE;
-        }
-    }
+    sel.finish(a.part_score, a.part_ix, a.nslices, blockIdx.y, pos_of);
 }
 
 // One wave per user: the best n_top of its nslices sorted partial lists, [user][nslices][n_top].
@@ -204,8 +137,6 @@ struct TbLayout {
         total = take.o;
     }
 };
-
-size_t tb_lds_bytes(size_t cap) { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * cap * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12); }
 
 }  // namespace
 
@@ -295,9 +226,8 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
     TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
     unsigned char* base = (unsigned char*)*d_scratch;
 
-    size_t cap = n_top + TB_ROOM + std::min<size_t>(n_top, 32);
-    while (tb_lds_bytes(cap) > TB_LDS_LIMIT && cap > n_top + TB_ROOM) cap -= 16;
-    const size_t lds = tb_lds_bytes(cap);
+    const size_t cap = tb_select_cap(n_top, 0);
+    const size_t lds = tb_lds_bytes(cap, 0);
     auto kern = topn_tile_kernel<real_t, sizeof(real_t) == 4>;
     TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TB_LDS_LIMIT));
 
@@ -305,19 +235,11 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
     std::vector<unsigned> hu, hp, hx, hix;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose exclusion lists fit the index area together
-        size_t u1 = u0, nx = 0;
-        while (u1 < n_users && u1 - u0 < L.chunk_users) {
-            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
-            if (u1 > u0 && nx + len > L.idx_cap) break;
-            nx += len;
-            u1++;
-        }
+        size_t u1, nx;
+        if (tb_stage_chunk(u1, nx, a.excl, u0, n_users, L.chunk_users, L.idx_cap, excl_indptr, excl_indices, users, compact_A, seen, tb_chunk_dev(base, L),
+                           hu, hp, hx, stream))
+            return 1;
         const size_t nu = u1 - u0;
-        hu.resize(nu);
-        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
-        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
-        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
-                             hx, stream));
         const size_t tiles = pmf_ceil_div(nu, TB_TU);
         const TbSlices sl = tb_slices(tiles, dimB, TB_TARGET_WGS, std::max<size_t>(1, TB_MERGE_MAX / n_top));   // (the merge kernel's LDS bounds them)
         const size_t nslices = sl.nslices;
@@ -342,10 +264,7 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
                                (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }
-        hix.resize(nu * n_top);
-        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
-        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = (sparse_ix)hix[i];
-        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
         u0 = u1;
     }
     return 0;

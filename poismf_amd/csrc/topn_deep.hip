@@ -2,7 +2,8 @@
 //
 //   score(u, j) = the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t   (tb_tile.hpp)
 //
-// The walk, the threshold test and the exclusion look-up are topn_batch.hip's: a workgroup of four waves owns 64 users and a slice of
+// The walk and the exclusion look-up are tb_tile.hpp's.  The selection is this file's own (tb_select.hpp's serves the kernels whose lists
+// fit LDS), with the same threshold test.  A workgroup of four waves owns 64 users and a slice of
 // the items, scores 64 x 64 at a time (fp32 on the f32 MFMA, fp64 on the VALU chain) and lets a score die in registers unless it beats
 // the user's threshold (the n_top-th best so far; registers, with its copy and the item in LDS).  What differs is where a survivor goes,
 // and that a pass's survivors are queued in LDS first, so that their exclusion look-ups run side by side over the lanes.
@@ -334,20 +335,12 @@ int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t*
     std::vector<unsigned> hu, hp, hx, hix;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose exclusion lists fit the index area together
-        size_t u1 = u0, nx = 0;
-        while (u1 < n_users && u1 - u0 < L.chunk_users) {
-            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
-            if (u1 > u0 && nx + len > L.idx_cap) break;
-            nx += len;
-            u1++;
-        }
+        // (the check bounds a row by the area's smallest size: every row fits)
+        size_t u1, nx;
+        if (tb_stage_chunk(u1, nx, a.excl, u0, n_users, L.chunk_users, L.idx_cap, excl_indptr, excl_indices, users, compact_A, seen, tb_chunk_dev(base, L),
+                           hu, hp, hx, stream))
+            return 1;
         const size_t nu = u1 - u0;
-        if (nx > L.idx_cap) return 1;   // (cannot happen: the check bounds a row by the area's smallest size)
-        hu.resize(nu);
-        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
-        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
-        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
-                             hx, stream));
         const size_t tiles = pmf_ceil_div(nu, TB_TU);
         const TbSlices sl = tb_slices(tiles, dimB, 2 * lds > TD_LDS_CU ? TD_TARGET_WGS / 2 : TD_TARGET_WGS);
         const size_t nslices = sl.nslices;
@@ -375,10 +368,7 @@ int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t*
                                (unsigned)L.cap, (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }
-        hix.resize(nu * n_top);
-        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
-        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
-        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
         u0 = u1;
     }
     return 0;

@@ -293,18 +293,21 @@ int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real
     auto row_len = [](const sparse_ix* indptr, size_t i) { return indptr ? (size_t)indptr[i + 1] - (size_t)indptr[i] : 0; };
     auto slices_of = [&](size_t len) { return std::max<size_t>(pmf_ceil_div(len, ti_slice(len, n_top)), 1); };
     for (size_t u0 = 0; u0 < n_users;) {
-        // the chunk: up to chunk_users users whose include lists, exclusion lists and partial lists fit their areas together
-        size_t u1 = u0, nx = 0, ni = 0, prow = 0;
-        while (u1 < n_users && u1 - u0 < L.chunk_users) {
-            const size_t len_e = row_len(excl_indptr, u1), len_i = row_len(incl_indptr, u1);
+        // the chunk: up to chunk_users users whose include lists, exclusion lists and partial lists fit their areas together.  `fit`: how
+        // many the include lists and the partial lists let in; the exclusion lists may cut the chunk shorter
+        size_t fit = 0;
+        for (size_t ni = 0, prow = 0; u0 + fit < n_users && fit < L.chunk_users; fit++) {
+            const size_t len_i = row_len(incl_indptr, u0 + fit);
             const size_t ns = slices_of(len_i), pr = ns > 1 ? ns : 0;
-            if (u1 > u0 && (nx + len_e > L.excl_cap || ni + len_i > L.incl_cap || prow + pr > L.part_rows)) break;
-            nx += len_e;
+            if (fit > 0 && (ni + len_i > L.incl_cap || prow + pr > L.part_rows)) break;
             ni += len_i;
             prow += pr;
-            u1++;
         }
-        const size_t nu = u1 - u0;
+        size_t u1, nx;
+        if (tb_stage_chunk(u1, nx, a.excl, u0, n_users, fit, L.excl_cap, excl_indptr, excl_indices, users, compact_A, seen, tb_chunk_dev(base, L), hu, hp, hx,
+                           stream))
+            return 1;
+        const size_t nu = u1 - u0, ni = (size_t)incl_indptr[u1] - (size_t)incl_indptr[u0];
         // the plan: one work item per (user, slice)
         items.clear();
         hm.clear();
@@ -323,13 +326,8 @@ int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real
             next_part += ns;
         }
         if (items.size() > L.item_cap || next_part > L.part_rows || ni > L.incl_cap) return 1;   // (cannot happen: TiLayout sizes the areas for any chunk)
-        hu.resize(nu);
-        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
         hi.resize(ni);
         for (size_t p = 0; p < ni; p++) hi[p] = (unsigned)incl_indices[i_base + p];
-        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
-        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
-                             hx, stream));
         TB_TRY(pmf_upload(base + L.incl, hi.data(), ni * sizeof(unsigned), stream));
         TB_TRY(pmf_upload(base + L.items, items.data(), items.size() * sizeof(TiItem), stream));
         TB_TRY(pmf_upload(base + L.mitems, hm.data(), hm.size() * sizeof(unsigned), stream));
@@ -352,10 +350,7 @@ int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real
                                (const unsigned*)(base + L.mitems), (unsigned)n_top, a.out_score, a.out_ix);
             TB_TRY(hipGetLastError());
         }
-        hix.resize(nu * n_top);
-        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
-        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
-        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
         u0 = u1;
     }
     return 0;

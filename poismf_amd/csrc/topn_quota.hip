@@ -3,9 +3,10 @@
 //
 //   score(u, j) = the k-ordered fused chain  s = 0; for c in 0..k-1: s = fma(A[u,c], B[j,c], s)  in real_t   (tb_tile.hpp)
 //
-// The walk, the threshold test, the exclusion look-up and the append are topn_batch.hip's (topn_quota_tile_kernel drives tb_walk with
-// tb_all_items and tb_excluded unchanged: a workgroup of four waves, 64 users, one slice of the items, candidate lists of
-// n_top + TB_ROOM + slack entries in LDS).  What differs is the prune (tb_quota.hpp: tb_prune_quota): an entry with q(g) entries of its
+// The walk is tb_tile.hpp's and the selection -- the threshold test, the exclusion look-up, the append -- tb_select.hpp's, as in
+// topn_batch.hip (topn_quota_tile_kernel drives tb_walk with tb_all_items and TbSelect: a workgroup of four waves, 64 users, one slice of
+// the items, candidate lists of n_top + TB_ROOM + slack entries in LDS).  What differs is the prune, handed to the selection as its
+// policy (tb_quota.hpp: TbPruneQuota, tb_prune_quota): an entry with q(g) entries of its
 // own group before it dies, the rest are ranked among themselves, and the threshold is the n_top-th LIVE entry -- it exists only once
 // n_top live entries do.  DESIGN.md section 4.19 has the argument why dropping below that threshold, and cutting the items into slices,
 // stays exact.  The groups of a list's entries are staged per wave (TQ_STAGE words), not per user: 64 more arrays of `cap` words do not
@@ -28,17 +29,19 @@
 #include "devmem.hpp"
 #include "tb_tile.hpp"
 #include "tb_batch.hpp"
+#include "tb_select.hpp"
 #include "tb_quota.hpp"
 
 namespace {
 
-constexpr int TQ_ROOM = 16;                               // free slots a list must have before a pass over 16 item columns (topn_batch.hip's TB_ROOM)
-constexpr size_t TQ_LDS_LIMIT = 156 * 1024;
+constexpr size_t TQ_STAGE_BYTES = 4 * (size_t)TQ_STAGE * sizeof(unsigned);   // a group stage per wave, behind the selection in LDS
 constexpr size_t TQ_TARGET_WGS = 768;                     // items are split over workgroups until a chunk has about this many (topn_batch.hip's target)
 constexpr size_t TQ_MAX_ITEMS = POISMF_HIP_TOPN_QUOTA_MAX_ITEMS;
 constexpr size_t TQ_MAPS_MAX = 2 * TQ_MAX_ITEMS * sizeof(unsigned);   // the two maps at the item limit: 128 MiB
 constexpr size_t TQ_IDX_MAX = TQ_MAX_ITEMS;               // exclusion indices a chunk may carry: any valid row fits (a row is shorter than dimB)
-static_assert(TB_N_TOP_MAX + TQ_ROOM + 32 <= (size_t)TQ_STAGE, "a prune keeps a whole list in TB_PRUNE_Q registers per lane and its groups in the stage");
+static_assert(TB_N_TOP_MAX + TB_ROOM + 32 <= (size_t)TQ_STAGE, "a prune keeps a whole list in TB_PRUNE_Q registers per lane and its groups in the stage");
+static_assert(tb_lds_bytes(TB_N_TOP_MAX + TB_ROOM, TQ_STAGE_BYTES) <= TB_LDS_LIMIT,
+              "the two tiles, 64 lists of the deepest n_top with TB_ROOM free slots and four group stages fit LDS");
 static_assert(TQ_MAPS_MAX + TQ_IDX_MAX * sizeof(unsigned) + (32u << 20) <= TB_BUDGET, "the budget holds the maps, a chunk's exclusion lists and 32 MiB of lists");
 
 struct TqArgs {
@@ -47,7 +50,7 @@ struct TqArgs {
     const unsigned* users;            // the chunk's rows of A
     unsigned n_users, dimB;
     int k;
-    unsigned n_top, cap;              // list capacity in LDS (n_top + TQ_ROOM + slack)
+    unsigned n_top, cap;              // list capacity in LDS (n_top + TB_ROOM + slack)
     unsigned nslices, tiles_per_slice;
     TbExcl excl;                      // E(u) of the chunk's users
     const uint2* item_map;            // [dimB] (g(j), min(q(g(j)), n_top))
@@ -60,98 +63,28 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_quot
     extern __shared__ __align__(16) unsigned char tq_smem[];
     T* As = (T*)tq_smem;                                  // [TB_TU][TB_KS]
     T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
-    T* Ls = Bs + TB_TJ * TB_KS;                           // [TB_TU][cap] candidate scores
-    unsigned* Li = (unsigned*)(Ls + (size_t)TB_TU * a.cap);   // [TB_TU][cap] candidate items
-    T* thr_s = (T*)(Li + (size_t)TB_TU * a.cap);          // [TB_TU] threshold: score ...
-    unsigned* thr_j = (unsigned*)(thr_s + TB_TU);         // ... and item
-    unsigned* cnt = thr_j + TB_TU;                        // [TB_TU] entries in the list
-    unsigned* uid = cnt + TB_TU;                          // [TB_TU] row of A, TB_NONE beyond the chunk
-    unsigned* Gs = uid + TB_TU;                           // [4 waves][TQ_STAGE] groups of the list being pruned
-
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned char* sel_lds = (unsigned char*)(Bs + TB_TJ * TB_KS);
+    unsigned* Gs = (unsigned*)(sel_lds + tb_select_bytes(a.cap));   // [4 waves][TQ_STAGE] groups of the list being pruned
     const unsigned u_base = blockIdx.x * TB_TU;
-    if (tid < TB_TU) {
-        const unsigned u = u_base + tid;
-        uid[tid] = u < a.n_users ? a.users[u] : TB_NONE;
-        cnt[tid] = 0;
-        thr_s[tid] = -std::numeric_limits<T>::infinity();
-        thr_j[tid] = 0;
-    }
-    __syncthreads();
+    TbSelect<T, TbPruneQuota> sel;
+    sel.init(sel_lds, a.cap, a.n_top, TbPruneQuota{ Gs + (size_t)(threadIdx.x >> 6) * TQ_STAGE, a.item_map },
+             [&](unsigned row) { return u_base + row < a.n_users ? a.users[u_base + row] : TB_NONE; });
 
     const unsigned ntiles = (a.dimB + TB_TJ - 1) / TB_TJ;
     const unsigned tile0 = blockIdx.y * a.tiles_per_slice;
     const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
-    const unsigned col = lane & 15, quad = lane >> 4;
-    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
-    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
-    unsigned* gs = Gs + (size_t)wave * TQ_STAGE;
-    auto prune = [&](unsigned uu) {
-        tb_prune_quota(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, gs, cnt[uu] < a.cap ? cnt[uu] : a.cap, a.n_top, a.item_map, cnt + uu,
-                       thr_s + uu, thr_j + uu);
-    };
-
-    // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
-    T thr_reg[4];
-    bool u_valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
-    bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
+    const unsigned col = threadIdx.x & 15;
+    auto user_row = [&](int row) { return sel.user_row(row); };
+    auto pos_of = [u_base](unsigned uu) { return u_base + uu; };   // a tile row's position in the chunk
 
     tb_walk<T, MFMA>(As, Bs, a.A, a.B, a.k, tile0, tile1, user_row, tb_all_items(a.dimB), [&](T (&acc)[4][4], unsigned j_base) {
-        // ---- selection: four passes of 16 item columns; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            if (dirty) {
-                const unsigned c_mine = cnt[16 * wave + col];
-                unsigned long long full = __ballot(quad == 0 && c_mine + TQ_ROOM > a.cap);
-                if (full) {
-                    while (full) {
-                        const unsigned uu = 16 * wave + (unsigned)__builtin_ctzll(full);
-                        full &= full - 1;
-                        prune(uu);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) thr_reg[r] = thr_s[urow0 + r];
-                }
-                dirty = false;
-            }
             const unsigned j = j_base + 16 * t + col;
-            bool appended = false;
-            if (j < a.dimB) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const unsigned uu = urow0 + r;
-                    const T s = acc[t][r];
-                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu]) && !tb_excluded(a.excl, u_base + uu, uid[uu], j)) {
-                        const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
-                        if (pos < a.cap) {   // (always: a pass adds at most TQ_ROOM to a list that had as many slots free)
-                            Ls[(size_t)uu * a.cap + pos] = s;
-                            Li[(size_t)uu * a.cap + pos] = j;
-                        }
-                        appended = true;
-                    }
-                }
-            }
-            if (__ballot(appended)) {
-                dirty = true;
-                tb_wave_sync();
-            }
+            sel.pass(acc[t], j, j < a.dimB, a.excl, pos_of);
         }
     });
-
-    // ---- the slice's answer per user: the best min(live, n_top) in order, the rest marked empty ----
-    for (unsigned q = 0; q < 16; q++) {
-        const unsigned uu = 16 * wave + q;
-        if (uid[uu] == TB_NONE) continue;   // (uniform over the wave)
-        prune(uu);
-        const unsigned c = cnt[uu];
-        const size_t o = ((size_t)(u_base + uu) * a.nslices + blockIdx.y) * a.n_top;
-        for (unsigned i = lane; i < a.n_top; i += 64) {
-            a.part_score[o + i] = i < c ? Ls[(size_t)uu * a.cap + i] : -std::numeric_limits<T>::infinity();
-            a.part_ix[o + i] = i < c ? Li[(size_t)uu * a.cap + i] : TB_NONE;
-        }
-    }
+    sel.finish(a.part_score, a.part_ix, a.nslices, blockIdx.y, pos_of);   // (the best min(live, n_top))
 }
 
 // One wave per user: the answer from its nslices sorted partial lists, [user][nslices][n_top].
@@ -209,15 +142,6 @@ struct TqLayout {
     }
 };
 
-size_t tq_lds_bytes(size_t cap)
-{
-    return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * cap * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12) +
-           4 * (size_t)TQ_STAGE * sizeof(unsigned);
-}
-static_assert(2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * (TB_N_TOP_MAX + TQ_ROOM) * (sizeof(real_t) + 4) +
-                      (size_t)TB_TU * (sizeof(real_t) + 12) + 4 * (size_t)TQ_STAGE * sizeof(unsigned) <= TQ_LDS_LIMIT,
-              "the two tiles, 64 lists of the deepest n_top with TQ_ROOM free slots and four group stages fit LDS");
-
 }  // namespace
 
 extern "C" size_t poismf_hip_topn_quota_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t n_groups, size_t k)
@@ -259,12 +183,11 @@ int poismf_hip_topn_quota_run(hipStream_t stream, const real_t* dA, const real_t
     TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
     unsigned char* base = (unsigned char*)*d_scratch;
 
-    size_t cap = n_top + TQ_ROOM + std::min<size_t>(n_top, 32);
-    while (tq_lds_bytes(cap) > TQ_LDS_LIMIT && cap > n_top + TQ_ROOM) cap -= 16;
-    const size_t lds = tq_lds_bytes(cap);
-    if (lds > TQ_LDS_LIMIT || cap > (size_t)TQ_STAGE) return 1;   // (cannot happen: the static_asserts above cover the deepest n_top)
+    const size_t cap = tb_select_cap(n_top, TQ_STAGE_BYTES);
+    const size_t lds = tb_lds_bytes(cap, TQ_STAGE_BYTES);
+    if (lds > TB_LDS_LIMIT || cap > (size_t)TQ_STAGE) return 1;   // (cannot happen: the static_asserts above cover the deepest n_top)
     auto kern = topn_quota_tile_kernel<real_t, sizeof(real_t) == 4>;
-    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TQ_LDS_LIMIT));
+    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TB_LDS_LIMIT));
 
     std::vector<unsigned> hu, hp, hx, hix;
     // the maps, per item, narrowed and interleaved: the group, and its quota clipped to n_top (n_top items of a group ahead: past the answer anyway)
@@ -278,20 +201,12 @@ int poismf_hip_topn_quota_run(hipStream_t stream, const real_t* dA, const real_t
     TqArgs a;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose exclusion lists fit the index area together
-        size_t u1 = u0, nx = 0;
-        while (u1 < n_users && u1 - u0 < L.chunk_users) {
-            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
-            if (u1 > u0 && nx + len > L.idx_cap) break;
-            nx += len;
-            u1++;
-        }
+        // (a row is no longer than dimB, and the area holds min(TQ_IDX_MAX, chunk x dimB): every row fits)
+        size_t u1, nx;
+        if (tb_stage_chunk(u1, nx, a.excl, u0, n_users, L.chunk_users, L.idx_cap, excl_indptr, excl_indices, users, compact_A, seen, tb_chunk_dev(base, L),
+                           hu, hp, hx, stream))
+            return 1;
         const size_t nu = u1 - u0;
-        if (nx > L.idx_cap) return 1;   // (cannot happen: a row is no longer than dimB, and the area holds min(TQ_IDX_MAX, chunk x dimB))
-        hu.resize(nu);
-        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
-        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
-        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
-                             hx, stream));
         const size_t tiles = pmf_ceil_div(nu, TB_TU);
         const TbSlices sl = tb_slices(tiles, dimB, TQ_TARGET_WGS, std::max<size_t>(1, TB_MERGE_MAX / n_top));   // (the merge kernel's LDS bounds them)
         const size_t nslices = sl.nslices;
@@ -318,10 +233,7 @@ int poismf_hip_topn_quota_run(hipStream_t stream, const real_t* dA, const real_t
                                (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }
-        hix.resize(nu * n_top);
-        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
-        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
-        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
         u0 = u1;
     }
     return 0;

@@ -12,8 +12,8 @@
 // the step at list position p is row lst[p + r] of B, "no row" (zeros) past the list's end -- through tb_walk / tb_compute
 // (tb_tile.hpp), so a row of B read once serves 64 users (fp32: v_mfma_f32_16x16x4_f32; fp64: the VALU chain).  A candidate past the
 // end of the list is left out by its POSITION, never by its score: an all-zero row of A scores 0 against a phantom zero row too.  The
-// selection is topn_tile_kernel's: a threshold per user held in registers between prunes, tb_excluded, an LDS integer counter,
-// tb_prune by rank counting.  No float atomics.  Every tile row carries its user's position in the chunk (the caller's order), which is
+// selection is tb_select.hpp's (TbSelect, as in topn_batch.hip): a threshold per user held in registers between prunes, tb_excluded, an
+// LDS integer counter, tb_prune by rank counting.  No float atomics.  Every tile row carries its user's position in the chunk (the caller's order), which is
 // the row of the result, the row of the partial lists and the index tb_excluded wants: results come down already in order.
 // A chunk with few user tiles cuts the lists into slices (one slice length per launch, taken from the longest list of the chunk; a
 // (tile, slice) that starts past its list's end leaves at once); topn_shared_merge_kernel ranks a user's partial lists
@@ -34,15 +34,15 @@
 #include "devmem.hpp"
 #include "tb_tile.hpp"
 #include "tb_batch.hpp"
+#include "tb_select.hpp"
 
 namespace {
 
-constexpr int TS_ROOM = 16;                               // free slots a list must have before a pass over 16 candidates
-constexpr size_t TS_LDS_LIMIT = 156 * 1024;
+constexpr size_t TS_UPOS_BYTES = TB_TU * sizeof(unsigned);   // the tile rows' positions in the chunk, behind the selection in LDS
 constexpr size_t TS_TARGET_WGS = 768;                     // lists are split over workgroups until a chunk has about this many
 constexpr size_t TS_MAX_CELLS = POISMF_HIP_TOPN_SHARED_MAX_CELLS;
 constexpr size_t TS_PART_BYTES = (size_t)32 << 20;        // most a chunk's partial lists take
-static_assert(TB_N_TOP_MAX + TS_ROOM + 32 <= (size_t)TB_PRUNE_Q * 64, "a prune keeps a whole list in TB_PRUNE_Q registers per lane");
+static_assert(tb_lds_bytes(TB_N_TOP_MAX + TB_ROOM, TS_UPOS_BYTES) <= TB_LDS_LIMIT, "the two tiles, 64 lists of the deepest n_top with TB_ROOM free slots and the positions fit LDS");
 static_assert(TS_MAX_CELLS * sizeof(unsigned) == TB_BUDGET / 4, "the list table fills a quarter of the scratch at most");
 
 struct TsTile { unsigned l0, len, first, count; };        // the list (start in the table's index area, length), first sorted user, users <= TB_TU
@@ -55,7 +55,7 @@ struct TsArgs {
     const TsTile* tiles;
     const unsigned* lists;            // the table's indices, one row after the other
     int k;
-    unsigned n_top, cap;              // list capacity in LDS (n_top + TS_ROOM + slack)
+    unsigned n_top, cap;              // list capacity in LDS (n_top + TB_ROOM + slack)
     unsigned nslices, tiles_per_slice;
     TbExcl excl;                      // E(u) of the chunk's users, by chunk position
     real_t* part_score;               // [chunk position][nslices][n_top]
@@ -67,13 +67,8 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_shar
     extern __shared__ __align__(16) unsigned char ts_smem[];
     T* As = (T*)ts_smem;                                  // [TB_TU][TB_KS]
     T* Bs = As + TB_TU * TB_KS;                           // [TB_TJ][TB_KS]
-    T* Ls = Bs + TB_TJ * TB_KS;                           // [TB_TU][cap] candidate scores
-    unsigned* Li = (unsigned*)(Ls + (size_t)TB_TU * a.cap);   // [TB_TU][cap] candidate items
-    T* thr_s = (T*)(Li + (size_t)TB_TU * a.cap);          // [TB_TU] threshold: score ...
-    unsigned* thr_j = (unsigned*)(thr_s + TB_TU);         // ... and item
-    unsigned* cnt = thr_j + TB_TU;                        // [TB_TU] entries in the list
-    unsigned* uid = cnt + TB_TU;                          // [TB_TU] row of A, TB_NONE for a tile row without a user
-    unsigned* upos = uid + TB_TU;                         // [TB_TU] the user's position in the chunk
+    unsigned char* sel_lds = (unsigned char*)(Bs + TB_TJ * TB_KS);
+    unsigned* upos = (unsigned*)(sel_lds + tb_select_bytes(a.cap));   // [TB_TU] the user's position in the chunk
 
     const TsTile tile = a.tiles[blockIdx.x];
     const unsigned len = tile.len;
@@ -83,31 +78,17 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_shar
     const unsigned tile1 = tile0 + a.tiles_per_slice < ntiles ? tile0 + a.tiles_per_slice : ntiles;
     const unsigned* lst = a.lists + tile.l0;
 
-    const unsigned tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < TB_TU) {
-        const unsigned p = tid < tile.count ? a.perm[tile.first + tid] : 0u;
-        uid[tid] = tid < tile.count ? a.users[p] : TB_NONE;
-        upos[tid] = p;
-        cnt[tid] = 0;
-        thr_s[tid] = -std::numeric_limits<T>::infinity();
-        thr_j[tid] = 0;
-    }
-    __syncthreads();
+    if (threadIdx.x < TB_TU) upos[threadIdx.x] = threadIdx.x < tile.count ? a.perm[tile.first + threadIdx.x] : 0u;
+    TbSelect<T, TbPrunePlain> sel;
+    sel.init(sel_lds, a.cap, a.n_top, TbPrunePlain(), [&](unsigned row) { return row < tile.count ? a.users[upos[row]] : TB_NONE; });   // (row: the thread's own)
 
-    const unsigned col = lane & 15, quad = lane >> 4;
-    const unsigned urow0 = 16 * wave + 4 * quad;          // this lane's four users are urow0 .. urow0 + 3
-    auto user_row = [&](int row) { const unsigned r = uid[row]; return r == TB_NONE ? -1ll : (long long)r; };
+    const unsigned col = threadIdx.x & 15;
+    auto user_row = [&](int row) { return sel.user_row(row); };
     // tile row `row` of the step at list position p: the list's entry there, none past its end
     auto item_rows = [lst, len](unsigned p) {
         return [lst, len, p](int row) { const unsigned q = p + (unsigned)row; return q < len ? (long long)lst[q] : -1ll; };
     };
-
-    // the thresholds of this lane's four users stay in registers between prunes (only this wave's prunes move them)
-    T thr_reg[4];
-    bool u_valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { thr_reg[r] = thr_s[urow0 + r]; u_valid[r] = uid[urow0 + r] != TB_NONE; }
-    bool dirty = true;   // (uniform over the wave) candidates were appended since the lists' room was last checked
+    auto pos_of = [upos](unsigned uu) { return upos[uu]; };   // a tile row's position in the chunk
 
     // this lane's four candidates of a step, fetched one step ahead like the rows they name
     unsigned j_next[4];
@@ -125,57 +106,11 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_shar
 #pragma unroll
         for (int t = 0; t < 4; t++) j_cur[t] = j_next[t];
         if (p_base + TB_TJ < tile1 * TB_TJ) fetch_items(p_base + TB_TJ);
-        // ---- selection: four passes of 16 candidates; the lists of users 16 wave .. 16 wave + 15 belong to this wave alone ----
 #pragma unroll
-        for (int t = 0; t < 4; t++) {
-            if (dirty) {
-                const unsigned c_mine = cnt[16 * wave + col];
-                unsigned long long full = __ballot(quad == 0 && c_mine + TS_ROOM > a.cap);
-                if (full) {
-                    while (full) {
-                        const unsigned uu = 16 * wave + (unsigned)__builtin_ctzll(full);
-                        full &= full - 1;
-                        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) thr_reg[r] = thr_s[urow0 + r];
-                }
-                dirty = false;
-            }
-            const unsigned j = j_cur[t];
-            bool appended = false;
-            if (p_base + 16 * t + col < len) {   // (by position: a phantom row past the list's end scores 0 like any zero row)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const unsigned uu = urow0 + r;
-                    const T s = acc[t][r];
-                    if (u_valid[r] && s >= thr_reg[r] && (s > thr_reg[r] || j < thr_j[uu]) && !tb_excluded(a.excl, upos[uu], uid[uu], j)) {
-                        const unsigned pos = atomicAdd(&cnt[uu], 1u);   // (LDS, integer)
-                        Ls[(size_t)uu * a.cap + pos] = s;
-                        Li[(size_t)uu * a.cap + pos] = j;
-                        appended = true;
-                    }
-                }
-            }
-            if (__ballot(appended)) {
-                dirty = true;
-                tb_wave_sync();
-            }
-        }
+        for (int t = 0; t < 4; t++)   // (in range by position: a phantom row past the list's end scores 0 like any zero row)
+            sel.pass(acc[t], j_cur[t], p_base + 16 * t + col < len, a.excl, pos_of);
     });
-
-    // ---- the slice's answer per user: the best min(count, n_top) in order, the rest marked empty ----
-    for (unsigned q = 0; q < 16; q++) {
-        const unsigned uu = 16 * wave + q;
-        if (uid[uu] == TB_NONE) continue;   // (uniform over the wave)
-        tb_prune(Ls + (size_t)uu * a.cap, Li + (size_t)uu * a.cap, cnt[uu], a.n_top, cnt + uu, thr_s + uu, thr_j + uu);
-        const unsigned c = cnt[uu];
-        const size_t o = ((size_t)upos[uu] * a.nslices + blockIdx.y) * a.n_top;
-        for (unsigned i = lane; i < a.n_top; i += 64) {
-            a.part_score[o + i] = i < c ? Ls[(size_t)uu * a.cap + i] : -std::numeric_limits<T>::infinity();
-            a.part_ix[o + i] = i < c ? Li[(size_t)uu * a.cap + i] : TB_NONE;
-        }
-    }
+    sel.finish(a.part_score, a.part_ix, a.nslices, blockIdx.y, pos_of);
 }
 
 // One wave per chunk position: the best n_top of the user's ns[u] <= nslices sorted partial lists, [position][nslices][n_top].
@@ -239,8 +174,6 @@ struct TsLayout {
     }
 };
 
-size_t ts_lds_bytes(size_t cap) { return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + (size_t)TB_TU * cap * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 16); }
-
 }  // namespace
 
 extern "C" size_t poismf_hip_topn_shared_scratch_bytes(size_t n_users, size_t n_lists, size_t n_cells, size_t n_top, size_t dimB, size_t k)
@@ -280,11 +213,10 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
     TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
     unsigned char* base = (unsigned char*)*d_scratch;
 
-    size_t cap = n_top + TS_ROOM + std::min<size_t>(n_top, 32);
-    while (ts_lds_bytes(cap) > TS_LDS_LIMIT && cap > n_top + TS_ROOM) cap -= 16;
-    const size_t lds = ts_lds_bytes(cap);
+    const size_t cap = tb_select_cap(n_top, TS_UPOS_BYTES);
+    const size_t lds = tb_lds_bytes(cap, TS_UPOS_BYTES);
     auto kern = topn_shared_kernel<real_t, sizeof(real_t) == 4>;
-    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TS_LDS_LIMIT));
+    TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TB_LDS_LIMIT));
 
     TsArgs a;
     std::vector<unsigned> hl, hu, hperm, hns, hp, hx, hix, touched, count;
@@ -300,16 +232,11 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
 
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users consecutive users whose exclusion lists fit the index area together
-        size_t u1 = u0, nx = 0;
-        while (u1 < n_users && u1 - u0 < L.chunk_users) {
-            const size_t len = excl_indptr ? (size_t)excl_indptr[u1 + 1] - (size_t)excl_indptr[u1] : 0;
-            if (u1 > u0 && nx + len > L.idx_cap) break;
-            nx += len;
-            u1++;
-        }
+        size_t u1, nx;
+        if (tb_stage_chunk(u1, nx, a.excl, u0, n_users, L.chunk_users, L.idx_cap, excl_indptr, excl_indices, users, compact_A, seen, tb_chunk_dev(base, L),
+                           hu, hp, hx, stream))
+            return 1;
         const size_t nu = u1 - u0;
-        hu.resize(nu);
-        for (size_t i = 0; i < nu; i++) hu[i] = compact_A ? (unsigned)(u0 + i) : (unsigned)users[u0 + i];
 
         // the users in order of their list (a stable counting sort over the lists the chunk refers to), cut into tiles of one list each
         touched.clear();
@@ -337,7 +264,6 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
         const TbSlices sl = tb_slices(tiles.size(), std::max<size_t>(max_len, 1), TS_TARGET_WGS, slice_cap);
         const size_t nslices = sl.nslices;
         if (tiles.size() > L.chunk_users || (nslices > 1 && nu * nslices > L.part_rows)) return 1;   // (cannot happen: TsLayout sizes the areas for any chunk)
-        TB_TRY(pmf_upload(base + L.users, hu.data(), nu * sizeof(unsigned), stream));
         TB_TRY(pmf_upload(base + L.perm, hperm.data(), nu * sizeof(unsigned), stream));
         TB_TRY(pmf_upload(base + L.tiles, tiles.data(), tiles.size() * sizeof(TsTile), stream));
         if (nslices > 1) {
@@ -346,8 +272,6 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
                 hns[i] = (unsigned)std::max<size_t>(1, pmf_ceil_div(pmf_ceil_div(list_len((size_t)list_of[u0 + i]), (size_t)TB_TJ), sl.tiles_per_slice));
             TB_TRY(pmf_upload(base + L.ns, hns.data(), nu * sizeof(unsigned), stream));
         }
-        TB_TRY(tb_stage_excl(a.excl, seen, excl_indptr, excl_indices, u0, nu, nx, (unsigned*)(base + L.ex_indptr), (unsigned*)(base + L.ex_indices), hp,
-                             hx, stream));
         a.A = dA;
         a.B = dB;
         a.users = (const unsigned*)(base + L.users);
@@ -370,10 +294,7 @@ int poismf_hip_topn_shared_run(hipStream_t stream, const real_t* dA, const real_
                                (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }
-        hix.resize(nu * n_top);
-        TB_TRY(pmf_download(hix.data(), base + L.out_ix, nu * n_top * sizeof(unsigned), stream));
-        for (size_t i = 0; i < nu * n_top; i++) out_ix[u0 * n_top + i] = hix[i] == TB_NONE ? POISMF_HIP_TOPN_NONE : (sparse_ix)hix[i];
-        if (out_score != nullptr) TB_TRY(pmf_download(out_score + u0 * n_top, base + L.out_score, nu * n_top * sizeof(real_t), stream));
+        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
         u0 = u1;
     }
     return 0;

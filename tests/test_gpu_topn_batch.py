@@ -1,6 +1,6 @@
 """Batched top-N (include/poismf_hip.h section 1f) on the GPU: bits against the existing predict path, independence of the
-batch a user is in, ties, float64 truth, the host-pointer entry and PoisMF.topN_batch, one call over 10^5 users, and the argument
-checks on a machine that has a device.
+batch a user is in, ties, float64 truth, the host-pointer entry and PoisMF.topN_batch, one call over 10^5 users, the argument
+checks on a machine that has a device, and lists that are exactly full through the three kernels that share the selection.
 
 The expectation of the exact tests is built from Session.predict -- the pair_dot_kernel path, which the batched code does not
 share: the user's whole score row, minus E(u), ordered by (score descending, item ascending) with np.lexsort.  No sampled user
@@ -340,3 +340,43 @@ def test_fitted_model_end_to_end():
     none = np.empty(0, np.uint64)
     for u in users:
         H.check_topn(m.A[u], m.B, ix[u], sc[u], none, csr.indices[csr.indptr[u]:csr.indptr[u + 1]].astype(np.uint64), 10, 1e-5)
+
+
+def test_lists_exactly_full_across_the_three_tile_kernels(prec):
+    """9. The guarded append at a list that is exactly full (tb_select.hpp), through the three kernels that share the selection:
+    three users over 300 items, k = 5, scores that rise strictly with the item index, fall strictly, and are all equal (every pass
+    appends 16 candidates or none, and the tie rule decides everything).  n_top = 1 gives lists of 1 + 16 + 1 slots -- a prune every
+    pass -- and 128 is the deepest.  Three users alone cut the items into several slices; the same three listed 16384 times each make
+    768 tiles of users, which is one slice.  Every score is a small integer, so the chains are exact in both precisions and the
+    expectation (tests.helpers.check_topn with no tolerance, and the lexsort of the float64 product for the order among ties) has no
+    rounding in it.  topn_batch, topn_quota with every quota equal to n_top and the shared table of one list of all items agree bit
+    for bit."""
+    dimB, k = 300, 5
+    dt = H.dtype_of(prec)
+    rng = np.random.default_rng(4)
+    j = np.arange(dimB)
+    r = rng.integers(0, 8, dimB)
+    B = np.stack([j + 1, dimB - j, np.ones(dimB), r, 8 - r], axis=1).astype(dt)
+    A = np.array([[2, 0, 3, 1, 1], [0, 1, 0, 2, 2], [0, 0, 5, 3, 3]], dt)   # 2 j + 13, 316 - j, 29
+    true = B.astype(np.float64) @ A.astype(np.float64).T
+    assert np.all(np.diff(true[:, 0]) > 0) and np.all(np.diff(true[:, 1]) < 0) and np.all(true[:, 2] == 29)
+    s = _session(sp.coo_matrix((np.ones(3), ([0, 1, 2], [0, 1, 2])), shape=(3, dimB)), k, prec, A, B)
+    try:
+        everything = (np.array([0, dimB], np.uint64), j.astype(np.uint64))
+        none = np.empty(0, np.uint64)
+        for users in (np.arange(3, dtype=np.uint64), np.tile(np.arange(3, dtype=np.uint64), 16384)):
+            for n in (1, 128):
+                plain = s.topn_batch(users, n, output_score=True)
+                quota = s.topn_quota(users, n, group_of=j % 4, quota=n, output_score=True)
+                shared = s.topn_batch(users, n, include=everything, include_of=0, output_score=True)
+                for what, got in (("quota", quota), ("shared", shared)):
+                    assert got[0].tobytes() == plain[0].tobytes() and got[1].tobytes() == plain[1].tobytes(), (what, len(users), n)
+                ix, sc = plain
+                assert ix.shape == (len(users), n) and sc.shape == (len(users), n) and sc.dtype == dt
+                for u in range(3):
+                    eix, esc = _expect(true[:, u], none, n)
+                    assert np.array_equal(ix[u::3], np.broadcast_to(eix, ix[u::3].shape)), (len(users), n, u, ix[u], eix)
+                    assert np.array_equal(sc[u::3], np.broadcast_to(esc.astype(dt), sc[u::3].shape)), (len(users), n, u)
+                    H.check_topn(A[u], B, ix[u], sc[u], none, none, n, 0.0)
+    finally:
+        s.close()
