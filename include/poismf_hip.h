@@ -538,6 +538,53 @@ POISMF_HIP_API int poismf_hip_topn_quota(const real_t *A, const real_t *B, int k
 POISMF_HIP_API size_t poismf_hip_topn_quota_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t n_groups, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1o. Batched top-N with per-item score weights: section 1f's ranked list of "score times a value of the item" -- expected revenue
+ *     (rate x price), a popularity discount, a freshness decay, a boost or a penalty -- with the multiplication made on the device,
+ *     in the same fused pass, before anything is pruned (no counterpart in the reference).
+ *
+ * Inputs are section 1f's -- users u_0 .. u_{m-1} (any order, repeats allowed), n_top, E(u), score(u, j) -- and one host array:
+ *
+ *   item_weight  [dimB] of real_t: finite and >= 0.  A weight of 0 does NOT bar an item: the item scores 0 (-0 is taken as 0) and
+ *                ties with its like by index; barring an item is what the exclusion lists are for.
+ *
+ *   wscore(u, j) score(u, j) * item_weight[j]: ONE multiplication rounded to real_t, made after the k-ordered fused chain and never
+ *                contracted into it.
+ *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under "wscore descending, then item index ascending".  It is a function of
+ *                (A[u], B, item_weight, E(u), n_top) alone: not of the other users, the order of the batch, how the items are cut
+ *                into slices or how the users are cut into chunks.
+ *   scores       out_score is wscore: bit for bit predict_multiple's score multiplied by item_weight[j] in real_t.  With every
+ *                weight 1 the rows are section 1f's, bit for bit.  No float atomics.  Where a product is denormal the result is
+ *                unspecified (the score or the order of such items may differ from the host's product).
+ *   short rows   follow section 1h / 1l / 1n's rule, not 1f's: if fewer than n_top items are admissible, the rest of the row is
+ *                POISMF_HIP_TOPN_NONE in out_ix and -inf in out_score.  No per-user pre-check is made and nothing of a resident row
+ *                is downloaded to count a union.
+ *   range        n_top is 1 .. POISMF_HIP_TOPN_BATCH_MAX_N_TOP.
+ *
+ * A caller of poismf_hip_topn_weighted who wants the items most similar to some items passes B as A too (users then index rows of
+ * B and dimA = dimB); the session call has query_B for that.  With item_weight[j] = 1 / |B_j| the order is the order by cosine
+ * similarity, and exclusion row i = { the query item } leaves the item itself out.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for: everything that is 2 in
+ * section 1f except "too few items left"; item_weight == NULL with n_users > 0; a weight that is NaN, infinite or negative;
+ * dimB > POISMF_HIP_TOPN_WEIGHTED_MAX_ITEMS.  n_users == 0 returns 0.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1n share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB for
+ * any n_users.  The weights go up once per call, sizeof(real_t) x dimB, at most 128 MiB in double at the item limit.  They lie in
+ * front of the chunk's parts; the chunk of users is sized from what the budget leaves beside weights of that largest size and an
+ * exclusion area of min(dimB x chunk, 2^24) indices, so every valid exclusion row fits.  poismf_hip_topn_weighted_scratch_bytes
+ * (testing aid, no HIP call) is the size both entry points allocate; it does not depend on k.  poismf_hip_topn_weighted's own copies
+ * of B and of A (all of A, or only the batch's rows) come on top.  The session flavour, poismf_hip_session_topn_weighted, is declared
+ * in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_WEIGHTED_MAX_ITEMS 16777216   /* largest dimB of the weighted entry points (2^24) */
+POISMF_HIP_API int poismf_hip_topn_weighted(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const real_t *item_weight,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_weighted_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -681,6 +728,14 @@ POISMF_HIP_API int poismf_hip_session_topn_deep(poismf_hip_session *s, const spa
 POISMF_HIP_API int poismf_hip_session_topn_quota(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
         const sparse_ix *group_of, size_t n_groups, const sparse_ix *quota,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1o from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above.
+ * query_B != 0: `users` index rows of the resident B (checked against dimB) -- those rows are the queries and B is also the corpus,
+ * the item-to-item call.  exclude_seen together with query_B returns 2. */
+POISMF_HIP_API int poismf_hip_session_topn_weighted(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        const real_t *item_weight, int query_B, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 
 /* Section 1h from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_deep", "poismf_hip_session_topn_deep", "poismf_hip_topn_deep_scratch_bytes",
     "poismf_hip_session_factors_new", "poismf_hip_session_topn_new", "poismf_hip_session_rank_new", "poismf_hip_topn_new",
     "poismf_hip_topn_quota", "poismf_hip_session_topn_quota", "poismf_hip_topn_quota_scratch_bytes",
+    "poismf_hip_topn_weighted", "poismf_hip_session_topn_weighted", "poismf_hip_topn_weighted_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -72,6 +73,7 @@ RANK_SHARED_CHUNK_CELLS = 2**19     # POISMF_HIP_RANK_SHARED_CHUNK_CELLS of sect
 TOPN_DEEP_MAX_N_TOP = 1024          # POISMF_HIP_TOPN_DEEP_MAX_N_TOP and POISMF_HIP_TOPN_DEEP_BUDGET_MB of section 1l
 TOPN_DEEP_BUDGET_MB = 1024          # (tests/test_topn_deep_cpu.py compares them with the header)
 TOPN_QUOTA_MAX_ITEMS = 2**24        # POISMF_HIP_TOPN_QUOTA_MAX_ITEMS of section 1n (tests/test_topn_quota_cpu.py compares the two)
+TOPN_WEIGHTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_WEIGHTED_MAX_ITEMS of section 1o (tests/test_topn_weighted_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -166,6 +168,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_quota.restype = i
     lib.poismf_hip_topn_quota_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
     lib.poismf_hip_topn_quota_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_weighted.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_weighted.restype = i
+    lib.poismf_hip_session_topn_weighted.argtypes = [vp, vp, sz, sz, vp, i, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_weighted.restype = i
+    lib.poismf_hip_topn_weighted_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_topn_weighted_scratch_bytes.restype = sz
     lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_rank_batch.restype = i
     lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
@@ -716,6 +724,87 @@ def _topn_quota_args(users, n, group_of, quota, exclude, dimA, dimB):
     return users, group_of, quota, indptr, indices
 
 
+def _topn_weighted_args(users, n, item_weight, exclude, dimA, dimB, dtype=np.float64):
+    """The argument checks of the batched top-N with per-item score weights (include/poismf_hip.h section 1o) that need no device, as
+    the library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).
+    item_weight: a 1-d array with one weight per item, or one number for all; converted to `dtype`, the model's real_t, and finite
+    and non-negative AFTER that conversion (a double above float32's range is refused for a float32 model).  Returns (users,
+    item_weight, excl_indptr or None, excl_indices or None): uint64 arrays around the weights in `dtype`."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if dimB > TOPN_WEIGHTED_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the weighted call's limit of {TOPN_WEIGHTED_MAX_ITEMS}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if item_weight is None:
+        raise ValueError("item_weight is required: one weight per item, or one number for all")
+    w = np.asarray(item_weight)
+    if w.dtype.kind not in "fiu":
+        raise ValueError("item_weight must be real numbers")
+    if w.ndim == 0:
+        w = np.full(dimB, w)
+    elif w.ndim != 1:
+        raise ValueError("item_weight must be a 1-d array with one weight per item, or one number")
+    if len(w) != dimB:
+        raise ValueError(f"item_weight has {len(w)} entries for {dimB} items")
+    with np.errstate(over="ignore"):
+        w = np.ascontiguousarray(w, dtype=dtype)
+    if np.isnan(w).any():
+        raise ValueError("item_weight: NaN entry")
+    if np.isinf(w).any():
+        raise ValueError("item_weight: an entry is infinite in the model's precision")
+    if (w < 0).any():
+        raise ValueError("item_weight: negative entry (a weight of 0 keeps an item at score 0; exclude= bars one)")
+    if exclude is None:
+        return users, w, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, w, indptr, indices
+
+
+def _inv_norms(n2, dimB, dtype):
+    """similar_items: inv[j] = real_t(1) / sqrt(n2[j]) in real_t, 0 where n2[j] == 0; n2[j] is the fused chain of B[j] with itself"""
+    n2 = np.ascontiguousarray(n2, dtype=dtype).reshape(-1)
+    if len(n2) != dimB:
+        raise ValueError(f"item_norm has {len(n2)} entries for {dimB} items")
+    if not np.isfinite(n2).all() or (n2 < 0).any():
+        raise ValueError("item_norm must be finite and non-negative: the squared norms of the rows of B")
+    inv = np.zeros(dimB, dtype)
+    np.divide(dtype(1), np.sqrt(n2), out=inv, where=n2 != 0)
+    return inv
+
+
+def _similar_args(items, n, exclude_self, dimB):
+    """similar_items: the query items as uint64 and the exclusion lists that leave each query itself out (or None); n, the items and
+    the number of items are checked here, before any norm is computed"""
+    items = _index_array(items, "items")
+    if int(n) <= 0:
+        raise ValueError("n must be positive")
+    if int(n) > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {int(n)} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if dimB > TOPN_WEIGHTED_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the weighted call's limit of {TOPN_WEIGHTED_MAX_ITEMS}")
+    if len(items) and int(items.max()) >= dimB:
+        raise ValueError("an item index is out of range")
+    if not exclude_self:
+        return items, None
+    return items, (np.arange(len(items) + 1, dtype=np.uint64), items.copy())
+
+
+def _similar_scores(sc, inv, items):
+    """similar_items: wscore * inv[query] in real_t, a second rounded multiplication; padded entries stay -inf"""
+    if sc.size:
+        q = inv[items.astype(np.int64)][:, None]
+        np.multiply(sc, q, out=sc, where=np.isfinite(sc))
+    return sc
+
+
 def _topn_include_args(users, n, include, exclude, dimA, dimB):
     """The argument checks of the batched top-N over include lists (include/poismf_hip.h section 1h) that need no device, as the
     library itself makes them: n may exceed what a user has left (short rows are padded).  Returns (users, incl_indptr,
@@ -910,6 +999,67 @@ def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_
 
 
 PoisMF.topN_quota = _topN_quota
+
+
+def _weighted_host_call(use_float, Q, B, k, users, n, w, indptr, indices, output_score):
+    """poismf_hip_topn_weighted on host arrays: the rows `users` of Q ranked against all of B"""
+    m = len(users)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), np.float32 if use_float else np.float64)
+    if m == 0:
+        return ix, sc
+    lib = load_library(use_float)
+    _batch_rc(lib.poismf_hip_topn_weighted(_ptr(Q), _ptr(B), k, Q.shape[0], B.shape[0], _ptr(users), m, n, _ptr(w),
+                                           _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                           _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+    return ix, sc
+
+
+def _topN_weighted(self, users, n=10, item_weight=None, exclude=None, output_score=False):
+    """topN_batch under score x item_weight[item] -- expected revenue (rate x price), a popularity discount, a freshness decay, a
+    boost or a penalty: the n <= TOPN_BATCH_MAX_N_TOP best items of every user in `users` under "weighted score descending, item
+    index ascending", minus `exclude` as in topN_batch, the multiplication made on the GPU in the same fused pass before anything
+    is pruned (include/poismf_hip.h section 1o).  item_weight: one finite weight >= 0 per item, or one number for all.  A weight
+    of 0 does not bar an item -- it scores 0 and ties with its like by index; exclude= bars one.  The scores returned are the
+    weighted ones: predict's, times the weight, rounded once.  n may exceed what a user has left: the row is padded with TOPN_NONE
+    and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    dt = np.float32 if self.use_float else np.float64
+    users, w, indptr, indices = _topn_weighted_args(users, n, item_weight, exclude, self.nusers, self.nitems, dt)
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    return _weighted_host_call(self.use_float, A, B, self.k, users, int(n), w, indptr, indices, output_score)
+
+
+PoisMF.topN_weighted = _topN_weighted
+
+
+def _similar_items(self, items, n=10, output_score=False, exclude_self=True, item_norm=None):
+    """The n best items by cosine similarity of their rows of B to each item of `items`, under "similarity descending, item index
+    ascending" -- the weighted call with rows of B as the queries (section 1o):
+        n2[j]  = predict_multiple(B, B, j, j), the fused chain of B[j] with itself (item_norm= takes it precomputed)
+        inv[j] = 1 / sqrt(n2[j]) in the model's precision, 0 where n2[j] == 0
+        rows   = the weighted top-N of B[i] against B with item_weight = inv, minus the query itself when exclude_self
+        score  = weighted score x inv[i], a second rounded multiplication
+    A zero row of B has similarity 0 to everything, as a query and as a candidate; such rows come in index order.  Returns (items
+    uint64 [m x n], similarities [m x n], empty unless output_score); a row is padded with TOPN_NONE and -inf past the last item."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    dt = np.float32 if self.use_float else np.float64
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    items, excl = _similar_args(items, n, exclude_self, self.nitems)
+    if item_norm is None:
+        every = np.arange(self.nitems, dtype=np.uint64)
+        item_norm = np.empty(self.nitems, dt)
+        _predict_multiple(item_norm, B, B, every, every)
+    inv = _inv_norms(item_norm, self.nitems, dt)
+    items, w, indptr, indices = _topn_weighted_args(items, n, inv, excl, self.nitems, self.nitems, dt)
+    ix, sc = _weighted_host_call(self.use_float, B, B, self.k, items, int(n), w, indptr, indices, output_score)
+    return ix, _similar_scores(sc, inv, items)
+
+
+PoisMF.similar_items = _similar_items
 
 
 def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False):
@@ -1441,6 +1591,49 @@ class Session:
                                                          int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
                                                          _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
+
+    def topn_weighted(self, users, top_n=10, item_weight=None, exclude_seen=False, exclude=None, output_score=False, query_items=False):
+        """topn_batch under score x item_weight[item], from the resident factors in one fused pass (include/poismf_hip.h section 1o):
+        the top_n <= TOPN_BATCH_MAX_N_TOP best items of every user under "weighted score descending, item index ascending";
+        exclude_seen and exclude as in topn_batch.  item_weight: one finite weight >= 0 per item, or one number for all.  A weight of
+        0 does not bar an item -- it scores 0 and ties with its like by index; exclude= bars one.  The scores returned are the
+        weighted ones.  A short row is padded with TOPN_NONE and -inf.  query_items: `users` are rows of the resident B instead --
+        the queries of an item-to-item call (similar_items); exclude_seen has no meaning then.  Returns (items uint64 [m x top_n],
+        scores [m x top_n], empty unless output_score)."""
+        dt = np.float32 if self.use_float else np.float64
+        if query_items and exclude_seen:
+            raise ValueError("exclude_seen has no meaning with query_items: the session holds no seen rows for items")
+        users, w, indptr, indices = _topn_weighted_args(users, top_n, item_weight, exclude, self.dimB if query_items else self.dimA, self.dimB, dt)
+        m, n = len(users), int(top_n)
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), dt)
+        if m == 0:
+            return ix, sc
+        _batch_rc(self.lib.poismf_hip_session_topn_weighted(self.h, _ptr(users), m, n, _ptr(w), int(bool(query_items)), int(bool(exclude_seen)),
+                                                            _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                                            _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
+
+    def item_norms(self):
+        """n2[j] = the fused chain of row j of the resident B with itself, predict_multiple's bits: what similar_items takes as
+        item_norm=.  The factors come to the host for it, so a serving loop computes it once per model."""
+        B = self.get_factors()[1]
+        every = np.arange(self.dimB, dtype=np.uint64)
+        n2 = np.empty(self.dimB, B.dtype)
+        _predict_multiple(n2, B, B, every, every)
+        return n2
+
+    def similar_items(self, items, top_n=10, output_score=False, exclude_self=True, item_norm=None):
+        """The top_n best items by cosine similarity of their rows of the resident B to each item of `items`: PoisMF.similar_items from
+        the session, through topn_weighted(query_items=True).  item_norm: item_norms(), computed once per model; without it every
+        call computes it again, which brings the factors to the host."""
+        dt = np.float32 if self.use_float else np.float64
+        items, excl = _similar_args(items, top_n, exclude_self, self.dimB)
+        inv = _inv_norms(self.item_norms() if item_norm is None else item_norm, self.dimB, dt)
+        ix, sc = self.topn_weighted(items, top_n, item_weight=inv, exclude=excl, output_score=output_score, query_items=True)
+        return ix, _similar_scores(sc, inv, items)
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):
         """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with

@@ -619,6 +619,26 @@ int poismf_hip_session_topn_quota(poismf_hip_session* s, const sparse_ix* users,
                                      exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Batched top-N with per-item score weights from the resident (compact) factors (topn_weighted.hip; include/poismf_hip.h section 1o),
+// ordered as the calls above and in the same scratch.  query_B: `users` are rows of the resident B -- the queries of an item-to-item
+// call -- so B is both factor arguments of the core; the CSR shard has no rows for them, hence no exclude_seen.
+int poismf_hip_session_topn_weighted(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const real_t* item_weight,
+                                     int query_B, int exclude_seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                     sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (query_B && exclude_seen) return 2;
+    if (const int rc = poismf_hip_topn_weighted_check(users, n_users, n_top, query_B ? s->dimB : s->dimA, s->dimB, s->k, item_weight, excl_indptr,
+                                                      excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_weighted_run(s->stream, query_B ? s->dB : s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, item_weight,
+                                        exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
+}
+
 // Batched top-N over per-user include lists from the resident (compact) factors (topn_include.hip; include/poismf_hip.h section 1h),
 // ordered as the call above and in the same scratch.
 int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* incl_indptr,

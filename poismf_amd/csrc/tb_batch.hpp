@@ -1,4 +1,4 @@
-// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip) and
+// tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip, topn_weighted.hip) and
 // the batched ranks (rank_batch.hip, rank_include.hip, rank_shared.hip) have in common -- the top-N cores' chunk loop opens with
 // tb_stage_chunk and closes with tb_fetch_results -- and what the session (session.hip) hands to their cores
 #pragma once
@@ -93,6 +93,16 @@ int poismf_hip_topn_quota_run(hipStream_t stream, const real_t* dA, const real_t
                               const sparse_ix* quota, PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
                               void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
 
+// (topn_weighted.hip; section 1o) the same pair for the top-N with per-item score weights: item_weight [dimB] is a host array; the
+// check makes no device call, the core returns 0 or 1.  The core reads dA and dB only: the session passes its B for both when the
+// queries are rows of B
+int poismf_hip_topn_weighted_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                   const real_t* item_weight, const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_topn_weighted_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                 const sparse_ix* users, size_t n_users, size_t n_top, const real_t* item_weight, PmfTopnSeen* seen,
+                                 const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
+                                 sparse_ix* out_ix, real_t* out_score);
+
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 
 namespace {
@@ -158,7 +168,7 @@ inline hipError_t tb_stage_excl(TbExcl& x, const PmfTopnSeen* seen, const sparse
     return e != hipSuccess ? e : pmf_upload(d_indices, hx.data(), nx * sizeof(unsigned), stream);
 }
 
-// ---- the chunk loop of the five top-N cores (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip) ----
+// ---- the chunk loop of the six top-N cores (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip, topn_weighted.hip) ----
 // the three parts every scratch layout of theirs has: the chunk's rows of A and its exclusion lists
 struct TbChunkDev { unsigned *users, *ex_indptr, *ex_indices; };
 template <class Layout> TbChunkDev tb_chunk_dev(unsigned char* base, const Layout& L)

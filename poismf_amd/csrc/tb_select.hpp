@@ -1,6 +1,6 @@
 // tb_select.hpp -- the selection behind the score tile of tb_tile.hpp, shared by the batched top-N kernels that keep their candidate
-// lists in LDS (topn_batch.hip: topn_tile_kernel; topn_quota.hip: topn_quota_tile_kernel; topn_shared.hip: topn_shared_kernel), and how
-// the host sizes it.  Per workgroup: 64 candidate lists of `cap` entries (scores, items), per user a threshold (the n_top-th best so
+// lists in LDS (topn_batch.hip: topn_tile_kernel; topn_quota.hip: topn_quota_tile_kernel; topn_shared.hip: topn_shared_kernel;
+// topn_weighted.hip: topn_weighted_tile_kernel), how the host sizes it, and the plain merge of the slices' lists (topn_merge_kernel).  Per workgroup: 64 candidate lists of `cap` entries (scores, items), per user a threshold (the n_top-th best so
 // far, score and item), a counter and the user's row of A.  A score dies in registers unless it beats its user's threshold under the
 // total order; a survivor is looked up in E(u) (tb_excluded) and appended through the LDS counter; a list is pruned by its wave alone,
 // by rank counting, whenever fewer than TB_ROOM slots are left (a pass over 16 item columns can add 16 candidates to one user).  Arrival
@@ -166,5 +166,20 @@ template <class T, class Prune> struct TbSelect {
         }
     }
 };
+
+// One wave per user: the best n_top of its nslices sorted partial lists, [user][nslices][n_top] (topn_batch.hip, topn_weighted.hip).
+// PAD: a user may have fewer than n_top real entries in all, and the ranks none of them reaches are marked empty (-inf, TB_NONE);
+// without it they are left as they were (section 1f's checks see to it that there are none).
+template <bool PAD>
+__global__ __launch_bounds__(64) void topn_merge_kernel(const real_t* part_score, const unsigned* part_ix, unsigned n_users, unsigned nslices,
+                                                        unsigned n_top, real_t* out_score, unsigned* out_ix)
+{
+    __shared__ real_t ms[TB_MERGE_MAX];
+    __shared__ unsigned mj[TB_MERGE_MAX];
+    const unsigned u = blockIdx.x;
+    const size_t o = (size_t)u * nslices * n_top;
+    tb_merge_lists(ms, mj, part_score + o, part_ix + o, nslices, n_top, out_score + (size_t)u * n_top, out_ix + (size_t)u * n_top);
+    if constexpr (PAD) tb_merge_pad(mj, nslices, n_top, out_score + (size_t)u * n_top, out_ix + (size_t)u * n_top);
+}
 
 }  // namespace

@@ -252,4 +252,18 @@ __device__ __forceinline__ void tb_merge_lists(real_t* ms, unsigned* mj, const r
     }
 }
 
+// After tb_merge_lists, for a user that may have fewer than n_top real entries in all (a short row): the ranks none of them reached are
+// marked empty (-inf, TB_NONE).  mj: the items tb_merge_lists left in LDS.
+__device__ __forceinline__ void tb_merge_pad(const unsigned* mj, unsigned nslices, unsigned n_top, real_t* out_score, unsigned* out_ix)
+{
+    const unsigned lane = threadIdx.x;
+    const unsigned m = nslices * n_top;
+    unsigned real = 0;
+    for (unsigned e0 = 0; e0 < m; e0 += 64) real += (unsigned)__popcll(__ballot(e0 + lane < m && mj[e0 + lane] != TB_NONE));
+    for (unsigned i = real + lane; i < n_top; i += 64) {
+        out_score[i] = (real_t)-__builtin_huge_val();   // -inf
+        out_ix[i] = TB_NONE;
+    }
+}
+
 }  // namespace

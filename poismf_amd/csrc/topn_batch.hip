@@ -82,16 +82,7 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_tile
     sel.finish(a.part_score, a.part_ix, a.nslices, blockIdx.y, pos_of);
 }
 
-// One wave per user: the best n_top of its nslices sorted partial lists, [user][nslices][n_top].
-__global__ __launch_bounds__(64) void topn_merge_kernel(const real_t* part_score, const unsigned* part_ix, unsigned n_users, unsigned nslices,
-                                                        unsigned n_top, real_t* out_score, unsigned* out_ix)
-{
-    __shared__ real_t ms[TB_MERGE_MAX];
-    __shared__ unsigned mj[TB_MERGE_MAX];
-    const unsigned u = blockIdx.x;
-    const size_t o = (size_t)u * nslices * n_top;
-    tb_merge_lists(ms, mj, part_score + o, part_ix + o, nslices, n_top, out_score + (size_t)u * n_top, out_ix + (size_t)u * n_top);
-}
+// (topn_merge_kernel, one wave per user over its nslices sorted partial lists, lives in tb_select.hpp: topn_weighted.hip launches it too)
 
 // exclude_seen needs to know whether the resident rows may be binary-searched: flag[0] = 1 when some row is not strictly ascending
 __global__ __launch_bounds__(256) void topn_rows_sorted_kernel(const unsigned long long* indptr, const unsigned* indices, size_t nrows, unsigned* flag)
@@ -260,7 +251,7 @@ int poismf_hip_topn_batch_run(hipStream_t stream, const real_t* dA, const real_t
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)nslices), dim3(TB_WG), lds, stream, a);
         TB_TRY(hipGetLastError());
         if (nslices > 1) {
-            hipLaunchKernelGGL(topn_merge_kernel, dim3((unsigned)nu), dim3(64), 0, stream, a.part_score, a.part_ix, (unsigned)nu, (unsigned)nslices,
+            hipLaunchKernelGGL(topn_merge_kernel<false>, dim3((unsigned)nu), dim3(64), 0, stream, a.part_score, a.part_ix, (unsigned)nu, (unsigned)nslices,
                                (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }

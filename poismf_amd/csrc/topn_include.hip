@@ -180,18 +180,11 @@ __global__ __launch_bounds__(64) void topn_merge_ragged_kernel(const real_t* par
 {
     __shared__ real_t ms[TB_MERGE_MAX];
     __shared__ unsigned mj[TB_MERGE_MAX];
-    const unsigned lane = threadIdx.x;
     const unsigned row = mi[3 * blockIdx.x], p0 = mi[3 * blockIdx.x + 1], ns = mi[3 * blockIdx.x + 2];
     real_t* o_score = out_score + (size_t)row * n_top;
     unsigned* o_ix = out_ix + (size_t)row * n_top;
     tb_merge_lists(ms, mj, part_score + (size_t)p0 * n_top, part_ix + (size_t)p0 * n_top, ns, n_top, o_score, o_ix);
-    // a short row: ranks that no real entry reached
-    unsigned real = 0;
-    for (unsigned e0 = 0; e0 < ns * n_top; e0 += 64) real += (unsigned)__popcll(__ballot(e0 + lane < ns * n_top && mj[e0 + lane] != TB_NONE));
-    for (unsigned i = real + lane; i < n_top; i += 64) {
-        o_score[i] = -std::numeric_limits<real_t>::infinity();
-        o_ix[i] = TB_NONE;
-    }
+    tb_merge_pad(mj, ns, n_top, o_score, o_ix);   // a short row: ranks that no real entry reached
 }
 
 size_t ti_slice(size_t len, size_t n_top)

@@ -119,19 +119,12 @@ __global__ __launch_bounds__(64) void topn_shared_merge_kernel(const real_t* par
 {
     __shared__ real_t ms[TB_MERGE_MAX];
     __shared__ unsigned mj[TB_MERGE_MAX];
-    const unsigned lane = threadIdx.x;
     const unsigned u = blockIdx.x, n = ns[u];
     const size_t o = (size_t)u * nslices * n_top;
     real_t* o_score = out_score + (size_t)u * n_top;
     unsigned* o_ix = out_ix + (size_t)u * n_top;
     tb_merge_lists(ms, mj, part_score + o, part_ix + o, n, n_top, o_score, o_ix);
-    // a short row: ranks that no real entry reached
-    unsigned real = 0;
-    for (unsigned e0 = 0; e0 < n * n_top; e0 += 64) real += (unsigned)__popcll(__ballot(e0 + lane < n * n_top && mj[e0 + lane] != TB_NONE));
-    for (unsigned i = real + lane; i < n_top; i += 64) {
-        o_score[i] = -std::numeric_limits<real_t>::infinity();
-        o_ix[i] = TB_NONE;
-    }
+    tb_merge_pad(mj, n, n_top, o_score, o_ix);   // a short row: ranks that no real entry reached
 }
 
 // The one scratch allocation of a call: the list table and what a chunk of users needs, in bytes from the start.

@@ -1,13 +1,14 @@
 #!/bin/bash
 # usage: scripts/topn_resource_usage.sh [root of the tree to compile, default: this one] [out directory, default: <root>/profiles]
-# The compiler's resource report (-Rpass-analysis=kernel-resource-usage) of the three batched top-N units whose tile kernels share
+# The compiler's resource report (-Rpass-analysis=kernel-resource-usage) of the four batched top-N units whose tile kernels share
 # tb_select.hpp, one device-only compile per unit and precision with the product build's flags:
 #   <out>/topn/kernel_resource_usage.txt  <out>/topn_quota/kernel_resource_usage.txt  <out>/topn_shared/kernel_resource_usage.txt
+#   <out>/topn_weighted/kernel_resource_usage.txt
 set -e
 ROOT=$(cd "${1:-$(dirname "$0")/..}" && pwd)
 OUT=${2:-$ROOT/profiles}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-function -Wno-unused-const-variable -Wno-pass-failed"
-for unit in topn:topn_batch topn_quota:topn_quota topn_shared:topn_shared; do
+for unit in topn:topn_batch topn_quota:topn_quota topn_shared:topn_shared topn_weighted:topn_weighted; do
   dir=${unit%%:*}; src=${unit##*:}
   mkdir -p "$OUT/$dir"
   {
