@@ -585,6 +585,70 @@ POISMF_HIP_API int poismf_hip_topn_weighted(const real_t *A, const real_t *B, in
 POISMF_HIP_API size_t poismf_hip_topn_weighted_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1p. Diversified batched top-N: greedy maximal marginal relevance (MMR) over a pool of every user's best items, picked on the
+ *     device from the factors themselves -- no group label per item is needed, as section 1n needs one (no counterpart in the
+ *     reference).
+ *
+ * Inputs are section 1l's -- users u_0 .. u_{m-1} (any order, repeats allowed), E(u), score(u, j) and the total order "score
+ * descending, then item index ascending" -- and:
+ *
+ *   n_top          1 .. POISMF_HIP_TOPN_BATCH_MAX_N_TOP (128): the picks per user.
+ *   pool           n_top .. POISMF_HIP_TOPN_DEEP_MAX_N_TOP (1024): the candidates the picks are made among.
+ *   lambda         a double in [0, 1]: 1 is pure relevance, 0 pure diversity.
+ *   item_inv_norm  [dimB], a host array of real_t, finite and >= 0: 1 / sqrt(chain(B_j, B_j)), and 0 for a zero row of B.
+ *
+ * All arithmetic is in real_t; every operation below is rounded once and never contracted into a fused multiply-add.
+ *
+ *   P(u)         the first `pool` entries of section 1l's answer for (u, pool), at positions 0 .. c(u)-1, c(u) <= pool.  rel_i is the
+ *                score of position i, with predict_multiple's bits; j_i is its item.
+ *   r_i          rel_i / rel_0 (IEEE division) when rel_0 > 0, otherwise rel_i.
+ *   lam, oml     (real_t)lambda and (real_t)(1 - lambda), the difference taken in double; both rounded on the host.
+ *   chain(x, y)  the fused chain s = +0; for c in 0..k-1: s = fma(x_c, y_c, s): predict_multiple(B, B, j_i, j_q)'s, symmetric in
+ *                its arguments.
+ *   cos(i, q)    ((chain(B[j_i], B[j_q]) * inv[j_i]) * inv[j_q]), two rounded multiplications in this order.  Not clipped.
+ *   m_i          0 for every position before any pick; after picking position q, m_i = (cos(i, q) > m_i ? cos(i, q) : m_i) for
+ *                every unpicked i.
+ *   v_i          (lam * r_i) - (oml * m_i): two rounded products, one rounded difference.
+ *   picks        at each step the unpicked position with the largest v_i; ties (v equal, -0 = +0) go to the lowest position.  The
+ *                first pick is therefore always position 0.  Picking stops after n_top picks or when the pool is used up.
+ *
+ * Outputs, [n_users x n_top] in pick order: out_ix the picked items; out_score (may be NULL) the picked item's RELEVANCE rel, with
+ * predict_multiple's bits; out_value (may be NULL) v at the moment of the pick.  Short rows follow section 1l's rule: entries a row
+ * does not reach are POISMF_HIP_TOPN_NONE, -inf and -inf.  The answer is a function of (A[u], B, E(u), item_inv_norm, n_top, pool,
+ * lambda) alone: not of the other users, the order of the batch, how the items are cut into slices or how the users are cut into
+ * chunks.  No float atomics.  Where a product or a quotient is denormal the result is unspecified, as in section 1o.  Consequences:
+ *   - lambda = 1 gives the first n_top entries of section 1l's answer (and section 1f's, where every user keeps n_top items), items
+ *     and scores bit for bit: v_i = r_i, which does not increase with i;
+ *   - pool = n_top gives the SET of the plain top-N, in MMR order.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for everything that is 2 in
+ * section 1l (with `pool` as its n_top), and for: n_top == 0 or n_top > POISMF_HIP_TOPN_BATCH_MAX_N_TOP; pool < n_top or
+ * pool > POISMF_HIP_TOPN_DEEP_MAX_N_TOP; lambda NaN or outside [0, 1]; item_inv_norm == NULL with n_users > 0; an entry of
+ * item_inv_norm that is NaN, infinite or negative; dimB > POISMF_HIP_TOPN_DIVERSE_MAX_ITEMS.  n_users == 0 returns 0.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1o share) of at most POISMF_HIP_TOPN_DIVERSE_BUDGET_MB MiB
+ * for any n_users; poismf_hip_topn_diverse_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate, it does
+ * not depend on k and never decreases when n_users grows.  The budget's arithmetic:
+ *   - the inverse norms go up once per call and lie in front of the chunk's parts: sizeof(real_t) x dimB, at most 8 B x 2^24 =
+ *     128 MiB in double at the item limit;
+ *   - behind them lies section 1l's layout for n_top = pool, inside section 1l's budget of 1024 MiB, with the chunk of users cut so
+ *     that the picked rows fit the same budget: n_top x (4 B + 2 x sizeof(real_t)) per user, at most 128 x 20 B = 2.5 KiB against
+ *     the 36 KiB a user's lists and results take at pool = 1024 in double (chunks of 3 328 users there instead of 3 584).
+ *   1024 + 128 = 1152 MiB.
+ * The MMR stage keeps no pool in LDS: it reads the pool's rows of B again for every pick, (n_top - 1) x c(u) x k x sizeof(real_t)
+ * bytes per user out of the caches.  poismf_hip_topn_diverse's own copies of B and of A (all of A, or only the
+ * batch's rows) come on top.  The session flavour, poismf_hip_session_topn_diverse, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_DIVERSE_MAX_ITEMS 16777216   /* largest dimB of the diversified entry points (2^24) */
+#define POISMF_HIP_TOPN_DIVERSE_BUDGET_MB 1152       /* upper bound of their scratch allocation, MiB: section 1l's and the norms */
+POISMF_HIP_API int poismf_hip_topn_diverse(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top, size_t pool, double lambda,
+        const real_t *item_inv_norm,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_value);
+POISMF_HIP_API size_t poismf_hip_topn_diverse_scratch_bytes(size_t n_users, size_t n_top, size_t pool, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -737,6 +801,12 @@ POISMF_HIP_API int poismf_hip_session_topn_weighted(poismf_hip_session *s, const
         const real_t *item_weight, int query_B, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1p from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_diverse(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        size_t pool, double lambda, const real_t *item_inv_norm, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_value);
 
 /* Section 1h from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_factors_new", "poismf_hip_session_topn_new", "poismf_hip_session_rank_new", "poismf_hip_topn_new",
     "poismf_hip_topn_quota", "poismf_hip_session_topn_quota", "poismf_hip_topn_quota_scratch_bytes",
     "poismf_hip_topn_weighted", "poismf_hip_session_topn_weighted", "poismf_hip_topn_weighted_scratch_bytes",
+    "poismf_hip_topn_diverse", "poismf_hip_session_topn_diverse", "poismf_hip_topn_diverse_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -74,6 +75,8 @@ TOPN_DEEP_MAX_N_TOP = 1024          # POISMF_HIP_TOPN_DEEP_MAX_N_TOP and POISMF_
 TOPN_DEEP_BUDGET_MB = 1024          # (tests/test_topn_deep_cpu.py compares them with the header)
 TOPN_QUOTA_MAX_ITEMS = 2**24        # POISMF_HIP_TOPN_QUOTA_MAX_ITEMS of section 1n (tests/test_topn_quota_cpu.py compares the two)
 TOPN_WEIGHTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_WEIGHTED_MAX_ITEMS of section 1o (tests/test_topn_weighted_cpu.py compares the two)
+TOPN_DIVERSE_MAX_ITEMS = 2**24      # POISMF_HIP_TOPN_DIVERSE_MAX_ITEMS and POISMF_HIP_TOPN_DIVERSE_BUDGET_MB of section 1p
+TOPN_DIVERSE_BUDGET_MB = 1152       # (tests/test_topn_diverse_cpu.py compares them with the header)
 
 
 def load_library(use_float):
@@ -174,6 +177,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_weighted.restype = i
     lib.poismf_hip_topn_weighted_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_weighted_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_diverse.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, sz, C.c_double, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_diverse.restype = i
+    lib.poismf_hip_session_topn_diverse.argtypes = [vp, vp, sz, sz, sz, C.c_double, vp, i, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_diverse.restype = i
+    lib.poismf_hip_topn_diverse_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_topn_diverse_scratch_bytes.restype = sz
     lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_rank_batch.restype = i
     lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
@@ -780,6 +789,58 @@ def _inv_norms(n2, dimB, dtype):
     return inv
 
 
+def _topn_diverse_args(users, n, pool, lam, inv_norm, exclude, dimA, dimB, dtype=np.float64):
+    """The argument checks of the diversified batched top-N (include/poismf_hip.h section 1p) that need no device, as the library
+    itself makes them: n in 1 .. TOPN_BATCH_MAX_N_TOP, pool in n .. TOPN_DEEP_MAX_N_TOP (either may exceed what a user has left: short
+    rows are padded), lam in [0, 1], and inv_norm -- _inv_norms' array, one entry per item -- finite and non-negative in `dtype`, the
+    model's real_t.  Returns (users, inv_norm, excl_indptr or None, excl_indices or None): uint64 arrays around the norms in `dtype`."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n, pool = int(n), int(pool)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if pool < n:
+        raise ValueError(f"pool = {pool} is below n = {n}: the picks are made among the pool")
+    if pool > TOPN_DEEP_MAX_N_TOP:
+        raise ValueError(f"pool = {pool} is above the deep batched limit of {TOPN_DEEP_MAX_N_TOP}")
+    if isinstance(lam, (bool, np.bool_)) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError("lam must be a real number in [0, 1]")
+    if not 0.0 <= float(lam) <= 1.0:   # (NaN fails both)
+        raise ValueError(f"lam = {lam} is outside [0, 1]")
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if dimB > TOPN_DIVERSE_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the diversified call's limit of {TOPN_DIVERSE_MAX_ITEMS}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if inv_norm is None:
+        raise ValueError("the items' inverse norms are required: one per item")
+    inv = np.asarray(inv_norm)
+    if inv.dtype.kind not in "fiu" or inv.ndim != 1:
+        raise ValueError("the items' inverse norms must be a 1-d array of real numbers")
+    if len(inv) != dimB:
+        raise ValueError(f"there are {len(inv)} inverse norms for {dimB} items")
+    with np.errstate(over="ignore"):
+        inv = np.ascontiguousarray(inv, dtype=dtype)
+    if np.isnan(inv).any():
+        raise ValueError("inverse norm: NaN entry")
+    if np.isinf(inv).any():
+        raise ValueError("inverse norm: an entry is infinite in the model's precision")
+    if (inv < 0).any():
+        raise ValueError("inverse norm: negative entry")
+    if exclude is None:
+        return users, inv, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, inv, indptr, indices
+
+
+def _diverse_outputs(m, n, dt, output_score, output_value):
+    """the three output arrays of the diversified calls: items, relevances and values, the latter two empty unless asked for"""
+    return (np.empty((m, n), np.uint64), np.empty((m, n) if output_score else (0, n), dt), np.empty((m, n) if output_value else (0, n), dt))
+
+
 def _similar_args(items, n, exclude_self, dimB):
     """similar_items: the query items as uint64 and the exclusion lists that leave each query itself out (or None); n, the items and
     the number of items are checked here, before any norm is computed"""
@@ -1060,6 +1121,42 @@ def _similar_items(self, items, n=10, output_score=False, exclude_self=True, ite
 
 
 PoisMF.similar_items = _similar_items
+
+
+def _topN_diverse(self, users, n=10, pool=100, lam=0.7, exclude=None, output_score=False, output_value=False, item_norm=None):
+    """topN_batch diversified from the factors themselves -- no group label per item, as topN_quota needs one: greedy maximal marginal
+    relevance on the GPU (include/poismf_hip.h section 1p).  Of every user's best `pool` <= TOPN_DEEP_MAX_N_TOP items (topN_deep's
+    list, minus `exclude` as in topN_batch) n <= TOPN_BATCH_MAX_N_TOP are picked one by one, each the unpicked one with the largest
+        lam x (score / the user's best score)  -  (1 - lam) x (largest cosine of its row of B to the row of an item already picked)
+    ties to the better-ranked item; the cosine is similar_items'.  lam = 1 gives topN_deep's first n, lam = 0 ignores the scores
+    beyond the pool.  item_norm= takes the squared norms precomputed (Session.item_norms()), as similar_items does.  A row the pool
+    leaves short is padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n] in pick order, their scores [m x n] -- predict's,
+    empty unless output_score --, the value each was picked at [m x n], empty unless output_value)."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    dt = np.float32 if self.use_float else np.float64
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    # (everything else is judged before the norms are computed: zeros stand in for them)
+    inv = np.zeros(self.nitems, dt) if item_norm is None else _inv_norms(item_norm, self.nitems, dt)
+    users, inv, indptr, indices = _topn_diverse_args(users, n, pool, lam, inv, exclude, self.nusers, self.nitems, dt)
+    m, n = len(users), int(n)
+    ix, sc, val = _diverse_outputs(m, n, dt, output_score, output_value)
+    if m == 0:
+        return ix, sc, val
+    if item_norm is None:
+        every = np.arange(self.nitems, dtype=np.uint64)
+        item_norm = np.empty(self.nitems, dt)
+        _predict_multiple(item_norm, B, B, every, every)
+        inv = _inv_norms(item_norm, self.nitems, dt)
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    lib = load_library(self.use_float)
+    _batch_rc(lib.poismf_hip_topn_diverse(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, int(pool), float(lam),
+                                          _ptr(inv), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                          _ptr(ix), _ptr(sc) if output_score else None, _ptr(val) if output_value else None), "top-N")
+    return ix, sc, val
+
+
+PoisMF.topN_diverse = _topN_diverse
 
 
 def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False):
@@ -1634,6 +1731,32 @@ class Session:
         inv = _inv_norms(self.item_norms() if item_norm is None else item_norm, self.dimB, dt)
         ix, sc = self.topn_weighted(items, top_n, item_weight=inv, exclude=excl, output_score=output_score, query_items=True)
         return ix, _similar_scores(sc, inv, items)
+
+    def topn_diverse(self, users, top_n=10, pool=100, lam=0.7, exclude_seen=False, exclude=None, output_score=False, output_value=False,
+                     item_norm=None):
+        """topn_batch diversified from the factors themselves, from the resident factors: PoisMF.topN_diverse from the session
+        (include/poismf_hip.h section 1p) -- of every user's best `pool` items (topn_deep's list; exclude_seen and exclude as in
+        topn_batch) top_n are picked one by one by greedy maximal marginal relevance with weight lam on the relevance.  item_norm:
+        item_norms(), computed once per model; without it every call computes it again, which brings the factors to the host.
+        Returns (items uint64 [m x top_n] in pick order, their scores, empty unless output_score, the values they were picked at,
+        empty unless output_value); a short row is padded with TOPN_NONE and -inf."""
+        dt = np.float32 if self.use_float else np.float64
+        # (everything else is judged before the norms are computed: zeros stand in for them)
+        inv = np.zeros(self.dimB, dt) if item_norm is None else _inv_norms(item_norm, self.dimB, dt)
+        users, inv, indptr, indices = _topn_diverse_args(users, top_n, pool, lam, inv, exclude, self.dimA, self.dimB, dt)
+        m, n = len(users), int(top_n)
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
+        ix, sc, val = _diverse_outputs(m, n, dt, output_score, output_value)
+        if m == 0:
+            return ix, sc, val
+        if item_norm is None:
+            inv = _inv_norms(self.item_norms(), self.dimB, dt)
+        _batch_rc(self.lib.poismf_hip_session_topn_diverse(self.h, _ptr(users), m, n, int(pool), float(lam), _ptr(inv), int(bool(exclude_seen)),
+                                                           _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
+                                                           _ptr(ix), _ptr(sc) if output_score else None,
+                                                           _ptr(val) if output_value else None), "top-N")
+        return ix, sc, val
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):
         """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with

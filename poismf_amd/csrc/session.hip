@@ -639,6 +639,25 @@ int poismf_hip_session_topn_weighted(poismf_hip_session* s, const sparse_ix* use
                                         exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Diversified batched top-N from the resident (compact) factors (topn_diverse.hip; include/poismf_hip.h section 1p), ordered as the
+// calls above and in the same scratch, which it may grow: the deep pool, then greedy MMR picks on the device.
+int poismf_hip_session_topn_diverse(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, size_t pool, double lambda,
+                                    const real_t* item_inv_norm, int exclude_seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                    sparse_ix* out_ix, real_t* out_score, real_t* out_value)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_diverse_check(users, n_users, n_top, pool, lambda, s->dimA, s->dimB, s->k, item_inv_norm, excl_indptr,
+                                                     excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_diverse_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, pool, lambda, item_inv_norm,
+                                       exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score,
+                                       out_value);
+}
+
 // Batched top-N over per-user include lists from the resident (compact) factors (topn_include.hip; include/poismf_hip.h section 1h),
 // ordered as the call above and in the same scratch.
 int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* incl_indptr,

@@ -18,7 +18,9 @@
 // With one slice the tile kernel writes the results itself.  No float atomics anywhere.
 //
 // The host side cuts the batch into chunks of users so that ONE scratch allocation of at most POISMF_HIP_TOPN_DEEP_BUDGET_MB holds a
-// chunk's user list, exclusion lists, candidate lists and results (TdLayout; poismf_hip_topn_deep_scratch_bytes reports its size).
+// chunk's user list, exclusion lists, candidate lists and results (TdLayout, tb_deep.hpp; poismf_hip_topn_deep_scratch_bytes reports its
+// size).  The chunk loop, poismf_hip_topn_deep_chunks, hands a chunk's merged rows to a callable while they are still on the device: the
+// deep entry points fetch them, the diversified top-N (topn_diverse.hip) picks from them there.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,10 +37,9 @@ namespace {
 
 constexpr int TD_ROOM = TB_TJ;                            // free slots a list must have before a step over 64 item columns
 constexpr size_t TD_LDS_LIMIT = 156 * 1024;
-constexpr size_t TD_TARGET_WGS = 512;                     // items are split over workgroups until a chunk has about this many, two per CU ...
-constexpr size_t TD_LDS_CU = 160 * 1024;                  // ... or one per CU where a CU's LDS holds only one: a second round of workgroups would
-                                                          // add lists to fill, prune and merge, and no parallelism
-constexpr size_t TD_IDX_MAX = TB_BUDGET / 2 / sizeof(unsigned);   // exclusion indices a chunk may carry: section 1f's
+constexpr size_t TD_LDS_CU = 160 * 1024;                  // TD_TARGET_WGS (tb_deep.hpp) workgroups, two per CU, or one per CU where a CU's LDS holds
+                                                          // only one: a second round of workgroups would add lists to fill, prune and merge,
+                                                          // and no parallelism
 constexpr int TD_MERGE_WG = 256;
 
 struct TdArgs {
@@ -249,45 +250,6 @@ __global__ __launch_bounds__(TD_MERGE_WG) void topn_deep_merge_kernel(const real
     }
 }
 
-// The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
-struct TdLayout {
-    size_t chunk_users;      // users per chunk
-    size_t idx_cap;          // exclusion indices a chunk may carry
-    size_t cap;              // entries of one (user, slice) list
-    size_t list_rows;        // (user, slice) lists
-    size_t users, ex_indptr, ex_indices, list_score, list_ix, out_score, out_ix, total;
-    TdLayout(size_t n_users, size_t n_top, size_t dimB)
-    {
-        const size_t E = sizeof(real_t) + sizeof(unsigned);
-        n_users = std::max<size_t>(n_users, 1);
-        n_top = std::min(std::max<size_t>(n_top, 1), TD_N_TOP_MAX);
-        dimB = std::min<size_t>(std::max<size_t>(dimB, 1), 0x7fffffffull);
-        cap = td_cap(n_top);
-        // lists: users x slices <= TB_TU x TD_TARGET_WGS + users + TB_TU  (tb_slices: at most target / tiles + 1 slices), results: users
-        const size_t rest = TD_BUDGET - TD_IDX_MAX * sizeof(unsigned) - 256;   // (256: alignment of the seven parts)
-        const size_t fixed = 16 + (TB_TU * TD_TARGET_WGS + TB_TU) * cap * E;
-        const size_t per_user = 8 + (cap + n_top) * E;
-        size_t uc = std::min((rest - fixed) / per_user, TB_CHUNK_USERS_MAX);
-        uc -= uc % TB_TU;
-        uc = std::min(uc, n_users);
-        chunk_users = uc;
-        idx_cap = std::min(TD_IDX_MAX, uc * dimB);                             // (no overflow: 2^18 x 2^31)
-        const size_t item_tiles = pmf_ceil_div(dimB, TB_TJ);
-        list_rows = std::min(uc * std::min(item_tiles, TD_TARGET_WGS), TB_TU * TD_TARGET_WGS + TB_TU + uc);
-        TbTake take;
-        users = take(uc * sizeof(unsigned));
-        ex_indptr = take((uc + 1) * sizeof(unsigned));
-        ex_indices = take(idx_cap * sizeof(unsigned));
-        list_score = take(list_rows * cap * sizeof(real_t));
-        list_ix = take(list_rows * cap * sizeof(unsigned));
-        out_score = take(uc * n_top * sizeof(real_t));
-        out_ix = take(uc * n_top * sizeof(unsigned));
-        total = take.o;
-    }
-};
-static_assert((TB_TU * TD_TARGET_WGS + TB_TU) * 2048 * 12 + 16 + TD_IDX_MAX * 4 + 256 + TB_TU * (8 + 3072 * 12) <= TD_BUDGET,
-              "the budget holds the lists of TD_TARGET_WGS workgroups and a tile of users at the deepest n_top in double");
-
 size_t td_lds_bytes(size_t cap)
 {
     return 2 * (size_t)TB_TU * TB_KS * sizeof(real_t) + 4 * std::max(cap, TD_STAGE_MIN) * (sizeof(real_t) + 4) + (size_t)TB_TU * (sizeof(real_t) + 12);
@@ -316,23 +278,20 @@ int poismf_hip_topn_deep_check(const sparse_ix* users, size_t n_users, size_t n_
     return 0;
 }
 
-// ---- core on device-resident factors (tb_deep.hpp) ----
-int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
-                             const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
-                             const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score)
+// ---- the chunk loop (tb_deep.hpp): a chunk's merged rows stay on the device for `consume` ----
+int poismf_hip_topn_deep_chunks(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                                const sparse_ix* excl_indices, unsigned char* base, size_t extra_per_user, size_t extra_fixed,
+                                const TdConsume& consume)
 {
-    if (seen != nullptr && poismf_hip_topn_seen_sorted(*seen, stream)) return 1;
-    const TdLayout L(n_users, n_top, dimB);
-    TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
-    unsigned char* base = (unsigned char*)*d_scratch;
-
+    const TdLayout L(n_users, n_top, dimB, extra_per_user, extra_fixed);
     const size_t lds = td_lds_bytes(L.cap);
     if (lds > TD_LDS_LIMIT) return 1;   // (cannot happen: the static_assert above covers the deepest list)
     auto kern = topn_deep_tile_kernel<real_t, sizeof(real_t) == 4>;
     TB_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TD_LDS_LIMIT));
 
     TdArgs a;
-    std::vector<unsigned> hu, hp, hx, hix;
+    std::vector<unsigned> hu, hp, hx;
     for (size_t u0 = 0; u0 < n_users;) {
         // the chunk: up to chunk_users users whose exclusion lists fit the index area together
         // (the check bounds a row by the area's smallest size: every row fits)
@@ -368,10 +327,25 @@ int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t*
                                (unsigned)L.cap, (unsigned)n_top, (real_t*)(base + L.out_score), (unsigned*)(base + L.out_ix));
             TB_TRY(hipGetLastError());
         }
-        if (tb_fetch_results(u0, nu, n_top, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score), hix, out_ix, out_score, stream)) return 1;
+        if (const int rc = consume(u0, nu, (const unsigned*)(base + L.out_ix), (const real_t*)(base + L.out_score))) return rc;
         u0 = u1;
     }
     return 0;
+}
+
+// ---- core on device-resident factors (tb_deep.hpp) ----
+int poismf_hip_topn_deep_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                             const sparse_ix* users, size_t n_users, size_t n_top, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                             const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score)
+{
+    if (seen != nullptr && poismf_hip_topn_seen_sorted(*seen, stream)) return 1;
+    const TdLayout L(n_users, n_top, dimB);
+    TB_TRY(grow_buffer(*d_scratch, *scratch_cap, L.total, 1, stream));
+    std::vector<unsigned> hix;
+    return poismf_hip_topn_deep_chunks(stream, dA, dB, dimB, k, compact_A, users, n_users, n_top, seen, excl_indptr, excl_indices,
+                                       (unsigned char*)*d_scratch, 0, 0, [&](size_t u0, size_t nu, const unsigned* d_ix, const real_t* d_score) {
+                                           return tb_fetch_results(u0, nu, n_top, d_ix, d_score, hix, out_ix, out_score, stream);
+                                       });
 }
 
 extern "C" {
