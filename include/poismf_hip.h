@@ -649,6 +649,69 @@ POISMF_HIP_API int poismf_hip_topn_diverse(const real_t *A, const real_t *B, int
 POISMF_HIP_API size_t poismf_hip_topn_diverse_scratch_bytes(size_t n_users, size_t n_top, size_t pool, size_t dimB, size_t k);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1q. List-wise evaluation: where held-out items sit in given top-N lists, how similar the listed items are to each other and how
+ *     often each item is shown -- for lists from any source, in the form sections 1f - 1p return them (no counterpart in the
+ *     reference).  No user index and no A enter the call: the lists are the input.
+ *
+ *   B              [dimB x k] row-major.
+ *   lists          [n_users x n_list] item indices, 1 <= n_list <= POISMF_HIP_TOPN_BATCH_MAX_N_TOP (128).  Row u holds c(u) <= n_list
+ *                  real entries followed only by POISMF_HIP_TOPN_NONE; the real entries are distinct and below dimB.  Rows may repeat.
+ *   item_inv_norm  optional (NULL: none).  [dimB], a host array of real_t, finite and >= 0: section 1p's.
+ *   test_indptr    optional (NULL: none).  [n_users + 1] row pointers into test_indices, from any non-negative start; every row strictly
+ *   test_indices   ascending, below dimB and at most POISMF_HIP_RANK_BATCH_MAX_ROW long.  `cells` below is their number,
+ *                  test_indptr[n_users] - test_indptr[0], and cell p - test_indptr[0] stands for test_indices[p].
+ *
+ * Outputs, all integers, so that no result depends on the order of any sum:
+ *
+ *   out_pos    [cells] unsigned int, written only with a held-out CSR (then it must not be NULL): the 0-based position of the cell's
+ *              item in its row of `lists`, or POISMF_HIP_LIST_ABSENT when the row does not list it.
+ *   out_cos    [n_users] long long, written only with item_inv_norm (then it must not be NULL).  For the positions p < q < c(u) of a
+ *              row, with items jp and jq:
+ *                cs = ((chain(B[jq], B[jp]) * inv[jq]) * inv[jp])    section 1p's chain (s = +0; s = fma(x_c, y_c, s), c ascending,
+ *                                                                    predict_multiple's bits) and its two multiplications, each
+ *                                                                    rounded once in real_t and never contracted: the later position
+ *                                                                    is the candidate and the earlier the picked one, exactly as
+ *                                                                    section 1p multiplies;
+ *                t  = (double)cs, 0 when cs is NaN, clamped to [-2, 2];
+ *                Q  = llrint(t * 2^POISMF_HIP_LIST_COS_SHIFT), round half to even (the product is exact);
+ *              out_cos[u] is the sum of Q over the row's c (c - 1) / 2 pairs: at most 8128 x 2^41 in magnitude.
+ *   out_len    [n_users] unsigned int: c(u).
+ *   exposure   [dimB] unsigned int: how many rows list item j (a repeated row counts each time).  Zeroed by the call.
+ *
+ * Every output of a row is a function of that row, B and item_inv_norm alone -- not of the other rows, their order or how the rows are
+ * cut into chunks -- and exposure is the sum over the rows.  The only atomics are unsigned integer adds on `exposure`.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for: B, lists, out_len or
+ * exposure NULL; n_list == 0 or n_list > POISMF_HIP_TOPN_BATCH_MAX_N_TOP; k outside 1..512 float / 1..256 double;
+ * dimB > POISMF_HIP_LIST_EVAL_MAX_ITEMS; a row of `lists` with a real entry behind a POISMF_HIP_TOPN_NONE, a repeated real entry or
+ * an entry >= dimB; an entry of item_inv_norm that is NaN, infinite or negative; out_cos NULL with item_inv_norm; out_pos NULL or
+ * test_indices NULL with cells; a held-out CSR whose row pointers decrease or start below 0, a held-out row that is not strictly
+ * ascending, holds an index >= dimB or is longer than POISMF_HIP_RANK_BATCH_MAX_ROW; a budget_bytes below what one user needs (see
+ * below).  n_users == 0 returns 0 and touches nothing.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1p share) of at most POISMF_HIP_LIST_EVAL_BUDGET_MB MiB
+ * whatever n_users and cells.  It holds, once per call, the inverse norms (sizeof(real_t) x dimB) and the exposure counts (4 B x dimB) --
+ * 12 B x 2^24 = 192 MiB in double at the item limit -- and behind them a chunk of users: 4 n_list + 16 B per user (its row, its first
+ * cell, its sum and its length) and 8 B per cell (item and position).  budget_bytes = 0 means the default,
+ * POISMF_HIP_LIST_EVAL_BUDGET_MB MiB, and so does any larger value; a smaller one cuts the users into more chunks, and one too small for
+ * the norms, the counts, one user and min(cells, POISMF_HIP_RANK_BATCH_MAX_ROW) cells returns 2.
+ * poismf_hip_list_eval_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate -- 0 where they would return 2
+ * for the budget; it never exceeds the budget, and with the other arguments fixed it grows with n_users until a chunk is full and
+ * stays there, so the n_users from which it no longer grows is the most users one chunk takes (a chunk also ends where the next
+ * user's cells would not fit).  poismf_hip_list_eval's own copy of B comes on top.  The session flavour, poismf_hip_session_list_eval, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_LIST_ABSENT 0xFFFFFFFEu           /* out_pos of a held-out item its row does not list */
+#define POISMF_HIP_LIST_COS_SHIFT 40                 /* out_cos counts cosines in units of 2^-40 */
+#define POISMF_HIP_LIST_EVAL_MAX_ITEMS 16777216      /* largest dimB of the list evaluation (2^24) */
+#define POISMF_HIP_LIST_EVAL_BUDGET_MB 256           /* upper bound of its scratch allocation, MiB */
+POISMF_HIP_API int poismf_hip_list_eval(const real_t *B, int k, size_t dimB,
+        const sparse_ix *lists, size_t n_users, size_t n_list,
+        const real_t *item_inv_norm,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, size_t budget_bytes,
+        unsigned int *out_pos, long long *out_cos, unsigned int *out_len, unsigned int *exposure);
+POISMF_HIP_API size_t poismf_hip_list_eval_scratch_bytes(size_t n_users, size_t n_list, size_t n_cells, size_t dimB, size_t budget_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -807,6 +870,12 @@ POISMF_HIP_API int poismf_hip_session_topn_diverse(poismf_hip_session *s, const 
         size_t pool, double lambda, const real_t *item_inv_norm, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score, real_t *out_value);
+
+/* Section 1q against the session-resident B, ordered as the call above and in the same scratch: no factor is uploaded. */
+POISMF_HIP_API int poismf_hip_session_list_eval(poismf_hip_session *s, const sparse_ix *lists, size_t n_users, size_t n_list,
+        const real_t *item_inv_norm,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, size_t budget_bytes,
+        unsigned int *out_pos, long long *out_cos, unsigned int *out_len, unsigned int *exposure);
 
 /* Section 1h from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_quota", "poismf_hip_session_topn_quota", "poismf_hip_topn_quota_scratch_bytes",
     "poismf_hip_topn_weighted", "poismf_hip_session_topn_weighted", "poismf_hip_topn_weighted_scratch_bytes",
     "poismf_hip_topn_diverse", "poismf_hip_session_topn_diverse", "poismf_hip_topn_diverse_scratch_bytes",
+    "poismf_hip_list_eval", "poismf_hip_session_list_eval", "poismf_hip_list_eval_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -77,6 +78,10 @@ TOPN_QUOTA_MAX_ITEMS = 2**24        # POISMF_HIP_TOPN_QUOTA_MAX_ITEMS of section
 TOPN_WEIGHTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_WEIGHTED_MAX_ITEMS of section 1o (tests/test_topn_weighted_cpu.py compares the two)
 TOPN_DIVERSE_MAX_ITEMS = 2**24      # POISMF_HIP_TOPN_DIVERSE_MAX_ITEMS and POISMF_HIP_TOPN_DIVERSE_BUDGET_MB of section 1p
 TOPN_DIVERSE_BUDGET_MB = 1152       # (tests/test_topn_diverse_cpu.py compares them with the header)
+LIST_ABSENT = 0xFFFFFFFE            # POISMF_HIP_LIST_ABSENT, POISMF_HIP_LIST_COS_SHIFT, POISMF_HIP_LIST_EVAL_BUDGET_MB and
+LIST_COS_SHIFT = 40                 # POISMF_HIP_LIST_EVAL_MAX_ITEMS of section 1q (tests/test_list_eval_cpu.py compares them with
+LIST_EVAL_BUDGET_MB = 256           # the header)
+LIST_EVAL_MAX_ITEMS = 2**24
 
 
 def load_library(use_float):
@@ -183,6 +188,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_diverse.restype = i
     lib.poismf_hip_topn_diverse_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
     lib.poismf_hip_topn_diverse_scratch_bytes.restype = sz
+    lib.poismf_hip_list_eval.argtypes = [vp, i, sz, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.poismf_hip_list_eval.restype = i
+    lib.poismf_hip_session_list_eval.argtypes = [vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.poismf_hip_session_list_eval.restype = i
+    lib.poismf_hip_list_eval_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_list_eval_scratch_bytes.restype = sz
     lib.poismf_hip_rank_batch.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_rank_batch.restype = i
     lib.poismf_hip_session_rank_batch.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp, vp]
@@ -1379,6 +1390,242 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, 
 PoisMF.eval_ranking = _eval_ranking
 
 
+def _list_rows(items, dimB):
+    """The lists of the list-wise evaluation (include/poismf_hip.h section 1q), checked as the library checks them: a 2-d integer
+    array [m x n], 1 <= n <= TOPN_BATCH_MAX_N_TOP, whose rows hold distinct items below dimB followed only by TOPN_NONE -- what every
+    topN_* call returns.  Returns it as a C-contiguous uint64 array."""
+    a = np.asarray(items)
+    if a.ndim != 2:
+        raise ValueError("the lists must be a 2-d array with one row per user")
+    if a.dtype.kind not in "iu":
+        raise ValueError("the lists must hold integers")
+    m, n = a.shape
+    if n < 1:
+        raise ValueError("the lists have no column")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"lists of {n} items are above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if a.dtype.kind == "i" and a.size and int(a.min()) < 0:
+        raise ValueError("the lists: negative index (an empty entry is TOPN_NONE)")
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    real = a != TOPN_NONE
+    if np.any(real[:, 1:] & ~real[:, :-1]):
+        raise ValueError("the lists: an item follows an empty entry of its row")
+    if np.any(a[real] >= dimB):
+        raise ValueError("an item index of the lists is out of range")
+    if n > 1:
+        srt = np.sort(a, axis=1)
+        if np.any((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] != TOPN_NONE)):
+            raise ValueError("the lists: a row names an item twice")
+    return a
+
+
+def _list_eval_scratch(m, n, cells, dimB, budget_bytes, real_size):
+    """poismf_hip_list_eval_scratch_bytes, the same arithmetic on the host (include/poismf_hip.h section 1q): the one scratch
+    allocation of a call in bytes, 0 when budget_bytes is below what the norms, the counts, one user and its cells need.  Returns
+    (bytes, users per chunk, cells per chunk)."""
+    up = lambda v: (v + 31) // 32 * 32
+    m, n = max(int(m), 1), min(max(int(n), 1), TOPN_BATCH_MAX_N_TOP)
+    dimB = min(max(int(dimB), 1), LIST_EVAL_MAX_ITEMS)
+    full = LIST_EVAL_BUDGET_MB << 20
+    budget = full if budget_bytes == 0 or budget_bytes > full else int(budget_bytes)
+    fixed = up(dimB * real_size) + up(dimB * 4) + 256 + 4
+    per_user = 4 * n + 16
+    row_cells = min(int(cells), RANK_BATCH_MAX_ROW)
+    if budget < fixed + per_user + row_cells * 8:
+        return 0, 0, 0
+    room = budget - fixed
+    cell_cap = min(int(cells), max(row_cells, room // 2 // 8))
+    chunk = min(m, (room - cell_cap * 8) // per_user, 262144)
+    total = 0
+    for part in (dimB * real_size, dimB * 4, chunk * n * 4, (chunk + 1) * 4, cell_cap * 4, cell_cap * 4, chunk * 8, chunk * 4):
+        total = up(total + part)
+    return total, chunk, cell_cap
+
+
+def _list_eval_args(items, test, item_norm, budget_mb, dimB, k, dtype):
+    """The argument checks of the list-wise evaluation (section 1q) that need no device, as the library itself makes them.  Returns
+    (lists uint64 [m x n], test_indptr or None, test_indices or None, inverse norms in `dtype` or None, budget in bytes, 0 for the
+    default)."""
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if dimB > LIST_EVAL_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the list evaluation's limit of {LIST_EVAL_MAX_ITEMS}")
+    if not 1 <= int(k) <= (512 if dtype == np.float32 else 256):
+        raise ValueError("the number of factors is outside what the batched entry points support")
+    lists = _list_rows(items, dimB)
+    m, n = lists.shape
+    tp = ti = None
+    if test is not None:
+        tp, ti = _csr_list(test, m, dimB, "test", RANK_BATCH_MAX_ROW)
+    inv = None
+    if item_norm is not None:
+        if np.asarray(item_norm).dtype.kind not in "fiu":
+            raise ValueError("item_norm must be real numbers")
+        with np.errstate(over="ignore"):
+            inv = _inv_norms(item_norm, dimB, dtype)
+        if not np.isfinite(inv).all():
+            raise ValueError("item_norm: an inverse norm is infinite in the model's precision")
+    budget = 0
+    if budget_mb is not None:
+        if isinstance(budget_mb, (bool, np.bool_)) or not isinstance(budget_mb, (int, float, np.integer, np.floating)):
+            raise ValueError("budget_mb must be a positive number")
+        if not float(budget_mb) > 0 or not np.isfinite(float(budget_mb)):
+            raise ValueError("budget_mb must be a positive number")
+        budget = max(int(float(budget_mb) * 2**20), 1)
+    if _list_eval_scratch(m, n, len(ti) if ti is not None else 0, dimB, budget, np.dtype(dtype).itemsize)[0] == 0:
+        raise ValueError(f"budget_mb = {budget_mb} is below what the norms, the counts and one user need")
+    return lists, tp, ti, inv, budget
+
+
+def _list_eval_outputs(lists, ti, inv, dimB):
+    m = lists.shape[0]
+    return (np.empty(len(ti), np.uint32) if ti is not None else None, np.empty(m, np.int64) if inv is not None else None,
+            np.zeros(m, np.uint32), np.zeros(dimB, np.uint32))
+
+
+def list_eval(B, items, test=None, item_norm=None, budget_mb=None):
+    """poismf_hip_list_eval on host factors B [dimB x k] (float32 or float64): list-wise evaluation of the lists `items` [m x n] --
+    what any topN_* call returned, from any source (include/poismf_hip.h section 1q).  test: the held-out items, a SciPy sparse
+    matrix with one row per row of `items` or an (indptr, indices) pair with strictly ascending rows.  item_norm: the squared norms
+    of the rows of B as similar_items takes them (Session.item_norms()); without it no cosine is computed.  budget_mb: the bound of
+    the call's scratch, LIST_EVAL_BUDGET_MB by default; a smaller one cuts the rows into more chunks and changes no answer.
+    Returns (pos uint32, one per cell of `test` in row order: the item's 0-based position in its row, LIST_ABSENT when the row does
+    not list it -- None without test; cos_sum int64 [m]: the sum over the row's pairs of items of their cosine, similar_items',
+    in units of 2^-LIST_COS_SHIFT -- None without item_norm; length uint32 [m]: the row's items; exposure uint32 [dimB]: the rows
+    that list each item)."""
+    B = np.asarray(B)
+    if B.ndim != 2 or B.dtype not in (np.float32, np.float64):
+        raise ValueError("B must be a float32 or float64 matrix")
+    dt = B.dtype.type
+    lists, tp, ti, inv, budget = _list_eval_args(items, test, item_norm, budget_mb, B.shape[0], B.shape[1], dt)
+    pos, cos, length, expo = _list_eval_outputs(lists, ti, inv, B.shape[0])
+    if lists.shape[0] == 0:
+        return pos, cos, length, expo
+    B = np.ascontiguousarray(B)
+    lib = load_library(dt == np.float32)
+    _batch_rc(lib.poismf_hip_list_eval(_ptr(B), B.shape[1], B.shape[0], _ptr(lists), lists.shape[0], lists.shape[1],
+                                       _ptr(inv) if inv is not None else None, _ptr(tp) if tp is not None else None, _opt_ptr(ti), budget,
+                                       _opt_ptr(pos), _ptr(cos) if cos is not None else None, _ptr(length), _ptr(expo)), "list evaluation")
+    return pos, cos, length, expo
+
+
+def _eval_lists_args(items, users, X_test, k, exclude, item_pop, dimA, dimB):
+    """eval_lists' inputs cut down to the batch: (lists uint64 [m x k], the (indptr, indices) of the held-out rows with every
+    excluded cell removed, or None; item_pop as float64, or None)"""
+    import scipy.sparse as sp
+    lists = _list_rows(items, dimB)
+    m, width = lists.shape
+    if k is not None:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise ValueError("k must be an integer")
+        if not 1 <= int(k) <= width:
+            raise ValueError(f"k = {k} is outside 1 .. {width}, the lists' width")
+        lists = np.ascontiguousarray(lists[:, :int(k)])
+    if users is None:
+        if (X_test is not None or exclude is not None) and m != dimA:
+            raise ValueError(f"without users= the lists must have one row per user of the model: {m} rows for {dimA} users")
+        users = np.arange(m, dtype=np.uint64)
+    else:
+        users = _index_array(users, "users")
+        if len(users) != m:
+            raise ValueError(f"there are {m} lists for {len(users)} users")
+        if m and int(users.max()) >= dimA:
+            raise ValueError("a user index is out of range")
+    rows = users.astype(np.int64)
+    if item_pop is not None:
+        item_pop = np.asarray(item_pop)
+        if item_pop.ndim != 1 or item_pop.dtype.kind not in "fiu" or len(item_pop) != dimB:
+            raise ValueError(f"item_pop must be a 1-d array of real numbers with one entry per item ({dimB})")
+        item_pop = item_pop.astype(np.float64)
+        if not np.isfinite(item_pop).all() or (item_pop < 0).any():
+            raise ValueError("item_pop must be finite and non-negative")
+    test = None
+    if X_test is not None:
+        if not sp.issparse(X_test):
+            raise ValueError("X_test must be a SciPy sparse matrix")
+        if X_test.shape != (dimA, dimB):
+            raise ValueError(f"X_test has shape {X_test.shape}, the model {(dimA, dimB)}")
+        csr = sp.csr_matrix(X_test)
+        csr.sum_duplicates()
+        csr.eliminate_zeros()
+        t = csr[rows]
+        t.sort_indices()
+        tp, ti = np.asarray(t.indptr, np.int64), np.asarray(t.indices, np.int64)
+        if exclude is not None:
+            if sp.issparse(exclude):
+                if exclude.shape != (dimA, dimB):
+                    raise ValueError(f"exclude has shape {exclude.shape}, the model {(dimA, dimB)}")
+                exclude = sp.csr_matrix(exclude)[rows]
+            ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+            trow = np.repeat(np.arange(m, dtype=np.int64), np.diff(tp))
+            erow = np.repeat(np.arange(m, dtype=np.int64), np.diff(ep.astype(np.int64)))
+            keep = ~np.isin((trow << 32) | ti, (erow << 32) | ei.astype(np.int64))
+            tp = np.concatenate(([0], np.cumsum(np.bincount(trow[keep], minlength=m)))).astype(np.int64)
+            ti = ti[keep]
+        test = (tp.astype(np.uint64), ti.astype(np.uint64))
+    elif exclude is not None:
+        raise ValueError("exclude removes held-out cells: it needs X_test")
+    return lists, test, item_pop
+
+
+def _lists_result(lists, test, pos, cos, length, expo, item_pop, per_user):
+    from . import metrics
+    k = lists.shape[1]
+    each = {}
+    out = {}
+    if test is not None:
+        each.update(metrics.metrics_from_positions(test[0], pos, k))
+        out.update(metrics.mean_metrics(each, metrics.LIST_METRICS))
+    else:
+        out["n_users"] = 0
+    each["ild"] = metrics.ild(cos, length)
+    if item_pop is not None:
+        each["novelty"] = metrics.novelty(lists, item_pop)
+    for name in ("ild", "novelty"):
+        if name in each:
+            out[name] = metrics.nan_mean(each[name])
+    out["coverage"], out["gini"] = metrics.coverage(expo), metrics.gini(expo)
+    out["n_lists"] = int(lists.shape[0])
+    if per_user:
+        out["per_user"] = each
+        out["positions"], out["test_indptr"] = pos, (test[0] if test is not None else None)
+        out["cos_sum"], out["length"], out["exposure"] = cos, length, expo
+    return out
+
+
+_EVAL_LISTS_DOC = """List-wise evaluation of the lists `items` [m x n] -- what any topN_* call returned, or pages from anywhere else -- in one
+    pass on the GPU (include/poismf_hip.h section 1q; the definitions are those of poismf_amd/metrics.py).  users: the user of each
+    row, by default rows 0 .. m-1 of the model; repeats allowed.  k: evaluate items[:, :k], by default the lists' width.  X_test: a
+    SciPy sparse matrix with the model's shape whose stored cells are the held-out positives, as in eval_ranking; its rows for
+    `users` are taken.  exclude: as in eval_ranking -- a held-out cell that is excluded is removed here, on the host, and takes no
+    part.  item_norm: the squared norms of the rows of B as similar_items takes them (Session.item_norms(), computed once per
+    model), computed when absent -- on a session that brings the factors to the host on every call.  item_pop: one
+    non-negative number per item, how often it was seen in training, for `novelty`.  Returns a dict: the means of hit, precision,
+    recall, ap, ndcg, rr at k (only with X_test; a held-out item the list lacks still counts in the denominators), ild (1 - the
+    mean pairwise cosine of a list's items), coverage and gini of the exposure counts, novelty (only with item_pop), n_users (the
+    users with a valid held-out cell) and n_lists; with per_user also "per_user" (one value per row), "positions", "test_indptr",
+    "cos_sum", "length" and "exposure"."""
+
+
+def _eval_lists(self, items, users=None, X_test=None, k=None, exclude=None, item_norm=None, item_pop=None, per_user=False):
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    dt = np.float32 if self.use_float else np.float64
+    lists, test, item_pop = _eval_lists_args(items, users, X_test, k, exclude, item_pop, self.nusers, self.nitems)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    if item_norm is None:
+        _list_eval_args(lists, test, None, None, self.nitems, self.k, dt)   # (everything else is judged before the norms are computed)
+        every = np.arange(self.nitems, dtype=np.uint64)
+        item_norm = np.empty(self.nitems, dt)
+        _predict_multiple(item_norm, B, B, every, every)
+    pos, cos, length, expo = list_eval(B, lists, test, item_norm)
+    return _lists_result(lists, test, pos, cos, length, expo, item_pop, per_user)
+
+
+_eval_lists.__doc__ = _EVAL_LISTS_DOC
+PoisMF.eval_lists = _eval_lists
+
+
 
 class _DevArray:
     """Minimal __cuda_array_interface__ carrier so torch can alias session-owned device memory."""
@@ -1810,6 +2057,31 @@ class Session:
             include = _unite_rows(_include_rows(include, users, self.dimA, self.dimB), test)
         ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include)
         return _ranking_result(test[0], ranks, n_adm, k, per_user)
+
+    def list_eval(self, items, test=None, item_norm=None, budget_mb=None):
+        """api.list_eval against the resident B (include/poismf_hip.h section 1q): no factor is uploaded.  Returns (pos, cos_sum,
+        length, exposure) as there."""
+        dt = np.float32 if self.use_float else np.float64
+        lists, tp, ti, inv, budget = _list_eval_args(items, test, item_norm, budget_mb, self.dimB, self.k, dt)
+        pos, cos, length, expo = _list_eval_outputs(lists, ti, inv, self.dimB)
+        if lists.shape[0] == 0:
+            return pos, cos, length, expo
+        _batch_rc(self.lib.poismf_hip_session_list_eval(self.h, _ptr(lists), lists.shape[0], lists.shape[1],
+                                                        _ptr(inv) if inv is not None else None, _ptr(tp) if tp is not None else None,
+                                                        _opt_ptr(ti), budget, _opt_ptr(pos), _ptr(cos) if cos is not None else None,
+                                                        _ptr(length), _ptr(expo)), "list evaluation")
+        return pos, cos, length, expo
+
+    def eval_lists(self, items, users=None, X_test=None, k=None, exclude=None, item_norm=None, item_pop=None, per_user=False):
+        lists, test, item_pop = _eval_lists_args(items, users, X_test, k, exclude, item_pop, self.dimA, self.dimB)
+        if item_norm is None:
+            dt = np.float32 if self.use_float else np.float64
+            _list_eval_args(lists, test, None, None, self.dimB, self.k, dt)   # (everything else is judged before the norms are computed)
+            item_norm = self.item_norms()
+        pos, cos, length, expo = self.list_eval(lists, test, item_norm)
+        return _lists_result(lists, test, pos, cos, length, expo, item_pop, per_user)
+
+    eval_lists.__doc__ = _EVAL_LISTS_DOC
 
     def _new_rows(self, X_new, params, niter, Bsum, Amean):
         """what every fold-in call starts with (include/poismf_hip.h section 1m): the leading arguments of the C entry point, the

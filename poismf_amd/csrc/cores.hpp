@@ -18,6 +18,15 @@ size_t poismf_hip_llk_scratch(size_t nrows, size_t dimB, size_t k, size_t nnz);
 int poismf_hip_llk_enqueue(const real_t* A, const real_t* B, size_t nrows, size_t dimB, size_t k, const unsigned long long* indptr,
                            const unsigned* col, const real_t* val, size_t nnz, int full_llk, int include_missing, double* scratch,
                            hipStream_t stream);
+// list_eval.hip (section 1q): the argument checks of both entry points (0, or 2; no device call) and the core on a device-resident B
+// (arguments already checked; *d_scratch / *scratch_cap: the caller's scratch, grown when it is smaller than the call needs; 0 or 1)
+int poismf_hip_list_eval_check(const sparse_ix* lists, size_t n_users, size_t n_list, size_t dimB, size_t k, const real_t* item_inv_norm,
+                               const sparse_ix* test_indptr, const sparse_ix* test_indices, size_t budget_bytes, const unsigned int* out_pos,
+                               const long long* out_cos, const unsigned int* out_len, const unsigned int* exposure);
+int poismf_hip_list_eval_run(hipStream_t stream, const real_t* dB, size_t dimB, size_t k, const sparse_ix* lists, size_t n_users, size_t n_list,
+                             const real_t* item_inv_norm, const sparse_ix* test_indptr, const sparse_ix* test_indices, size_t budget_bytes,
+                             void** d_scratch, size_t* scratch_cap, unsigned int* out_pos, long long* out_cos, unsigned int* out_len,
+                             unsigned int* exposure);
 // coo_convert.hip (rocPRIM-based helpers)
 int poismf_hip_device_sort_rows(const unsigned long long* d_indptr, size_t nloc, unsigned base, unsigned* d_perm, unsigned* d_len_sorted,
                                 hipStream_t stream);

@@ -658,6 +658,22 @@ int poismf_hip_session_topn_diverse(poismf_hip_session* s, const sparse_ix* user
                                        out_value);
 }
 
+// List-wise evaluation against the resident B (list_eval.hip; include/poismf_hip.h section 1q), ordered as the calls above and in the
+// same scratch: the lists are the input, so neither A nor the CSR shard is read.
+int poismf_hip_session_list_eval(poismf_hip_session* s, const sparse_ix* lists, size_t n_users, size_t n_list, const real_t* item_inv_norm,
+                                 const sparse_ix* test_indptr, const sparse_ix* test_indices, size_t budget_bytes, unsigned int* out_pos,
+                                 long long* out_cos, unsigned int* out_len, unsigned int* exposure)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr) return 2;
+    if (const int rc = poismf_hip_list_eval_check(lists, n_users, n_list, s->dimB, s->k, item_inv_norm, test_indptr, test_indices, budget_bytes,
+                                                  out_pos, out_cos, out_len, exposure))
+        return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_list_eval_run(s->stream, s->dB, s->dimB, s->k, lists, n_users, n_list, item_inv_norm, test_indptr, test_indices,
+                                    budget_bytes, &s->d_topn, &s->topn_cap, out_pos, out_cos, out_len, exposure);
+}
+
 // Batched top-N over per-user include lists from the resident (compact) factors (topn_include.hip; include/poismf_hip.h section 1h),
 // ordered as the call above and in the same scratch.
 int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* incl_indptr,
