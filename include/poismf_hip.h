@@ -112,7 +112,8 @@ POISMF_HIP_API int poismf_hip_coo_to_csr_csc(
  *           topN,             ref: src/poismf.h:240-247 (prototype), src/topN.c:112-284.
  * Same names, argument order and return codes (topN: 0 ok, 1 out of memory / no device, 2 invalid combination of
  * include / exclude / n_top as at ref src/topN.c:126-130).  Among equal scores topN returns ascending indices (the
- * reference leaves that order to qsort).  Host pointers in and out; the factors are copied to the device per call.
+ * reference leaves that order to qsort).  An item whose score is -inf (finite factors whose chain overflows) still comes
+ * before every excluded item.  Host pointers in and out; the factors are copied to the device per call.
  * ------------------------------------------------------------------------------------------- */
 POISMF_HIP_API void predict_multiple(
     real_t *out, real_t *A, real_t *B, sparse_ix *ixA, sparse_ix *ixB, size_t n, int k, int nthreads);
@@ -159,6 +160,12 @@ POISMF_HIP_API long double eval_llk(
  *                predict_multiple / poismf_hip_session_predict return.  It is NOT the summation order of topN /
  *                poismf_hip_session_topn (sixteen strided partial chains and a butterfly): the last bit of a batched score
  *                may differ from theirs.  Factors are assumed finite; the result for a user with a NaN score is unspecified.
+ *                Everything else a finite chain can give is a score like any other, here and in sections 1g - 1n: negative
+ *                scores, exact zeros in any number, subnormal operands, products and sums (nothing is flushed: the bits are
+ *                predict_multiple's, measured on the MI355X for the f32-MFMA tile and the scalar chains alike), and the +inf or
+ *                -inf of a chain that overflows.  An infinite score takes its place in the total order: +inf items first,
+ *                -inf items last, each by ascending index, and a real item at -inf comes before every empty entry of a padded
+ *                row.  (Sections 1o and 1p multiply a score and keep their own clause on denormal products.)
  *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under the total order "score descending, then item index ascending".
  *                It is a function of (A[u], B, E(u), n_top) alone: not of the other users in the batch, their order, or how
  *                the library tiles users and items.

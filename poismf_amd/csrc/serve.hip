@@ -53,10 +53,14 @@ __global__ void score_kernel(const real_t* a, const real_t* B, const unsigned* c
         if (sub == 0) { scores[i] = s; ids[i] = j; }
     }
 }
+// An excluded item's key is a NaN with the sign bit set: the descending radix order puts it behind every number, -inf included, so
+// an item whose score is really -inf (finite factors whose chain overflows) still comes before every excluded one.  n_top never
+// reaches the excluded items (poismf_hip_serve_topn_check), so the key is never returned.
 __global__ void mask_kernel(const unsigned* excl, size_t n_excl, real_t* scores)
 {
+    const real_t last = __builtin_copysign(std::numeric_limits<real_t>::quiet_NaN(), (real_t)-1);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_excl; i += (size_t)gridDim.x * blockDim.x)
-        scores[excl[i]] = -std::numeric_limits<real_t>::infinity();
+        scores[excl[i]] = last;
 }
 
 struct DevBuf {

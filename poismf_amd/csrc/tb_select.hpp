@@ -80,8 +80,8 @@ template <class T, class Prune> struct TbSelect {
         if (tid < TB_TU) {
             uid[tid] = row_of(tid);
             cnt[tid] = 0;
-            thr_s[tid] = -std::numeric_limits<T>::infinity();
-            thr_j[tid] = 0;
+            thr_s[tid] = -std::numeric_limits<T>::infinity();   // the empty entry: every real (s, j), a score of -inf included, beats it
+            thr_j[tid] = TB_NONE;
         }
         __syncthreads();
 #pragma unroll

@@ -78,8 +78,8 @@ template <class T, bool MFMA> __global__ __launch_bounds__(TB_WG) void topn_deep
         const unsigned u = u_base + tid;
         uid[tid] = u < a.n_users ? a.users[u] : TB_NONE;
         cnt[tid] = 0;
-        thr_s[tid] = neg_inf;
-        thr_j[tid] = 0;
+        thr_s[tid] = neg_inf;                             // the empty entry: every real (s, j), a score of -inf included, beats it
+        thr_j[tid] = TB_NONE;
     }
     __syncthreads();
 

@@ -91,7 +91,8 @@ template <bool STREAM> __global__ __launch_bounds__(64 * TI_WAVES) void topn_inc
     const unsigned arow = a.users[it.ui];
     const real_t* Au = a.A + (size_t)arow * (size_t)k;
     for (int c = (int)lane; c < ka; c += 64) As[c] = c < k ? Au[c] : (real_t)0;
-    if (lane == 0) { *thr_s = -std::numeric_limits<real_t>::infinity(); *thr_j = 0; *cnt = 0; }
+    // the threshold starts as the empty entry (-inf, TB_NONE): every real (s, j), a score of -inf included, beats it
+    if (lane == 0) { *thr_s = -std::numeric_limits<real_t>::infinity(); *thr_j = TB_NONE; *cnt = 0; }
     tb_wave_sync();
 
     const unsigned* lst = a.incl + it.p0;
@@ -101,7 +102,7 @@ template <bool STREAM> __global__ __launch_bounds__(64 * TI_WAVES) void topn_inc
     ti_u32x4 pre[TI_NI];
 
     real_t thr = -std::numeric_limits<real_t>::infinity();
-    unsigned thj = 0;
+    unsigned thj = TB_NONE;
     unsigned j_cur = lane < it.len ? lst[lane] : TB_NONE;
     unsigned j_nxt = 64 + lane < it.len ? lst[64 + lane] : TB_NONE;
     const real_t* brow = (const real_t*)(Bs + lane * TI_SLOT);
