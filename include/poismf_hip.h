@@ -719,6 +719,66 @@ POISMF_HIP_API int poismf_hip_list_eval(const real_t *B, int k, size_t dimB,
 POISMF_HIP_API size_t poismf_hip_list_eval_scratch_bytes(size_t n_users, size_t n_list, size_t n_cells, size_t dimB, size_t budget_bytes);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1r. Batched top-N with per-(user, item) score factors: section 1f's ranked list where single cells of the score matrix are
+ *     multiplied by a factor of their own -- an impression discount, a repeat-consumption discount on the user's seen items, a
+ *     per-user boost -- on the device, exactly, in one call (no counterpart in the reference).
+ *
+ * Inputs are section 1f's -- users u_0 .. u_{m-1} (any order, repeats allowed), n_top, E(u), score(u, j) -- and a CSR-shaped host
+ * list with one row per user of the batch:
+ *
+ *   adj_indptr   [n_users + 1] row pointers into adj_indices / adj_factor, from any non-negative start, never decreasing.  An
+ *                all-empty list is passed as row pointers of zeros.
+ *   adj_indices  items, below dimB and strictly ascending within a row; a row holds at most POISMF_HIP_TOPN_ADJUSTED_MAX_ROW cells.
+ *   adj_factor   real_t, parallel to adj_indices: finite and >= 0.  A factor of 0 does NOT bar a cell: the cell scores 0 (-0 is
+ *                taken as 0) and ties with its like by index; barring a cell is what the exclusion lists are for.
+ *
+ *   ascore(u, j) score(u, j) * f(u, j) where (u, j) is listed -- ONE multiplication rounded to real_t, made after the k-ordered fused
+ *                chain and never contracted into it -- and score(u, j) untouched otherwise.
+ *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under "ascore descending, then item index ascending".  It is a function of
+ *                (A[u], B, the user's adjust row, E(u), n_top) alone: not of the other users, the order of the batch, how the items
+ *                or a long adjust row are cut into slices or how the users are cut into chunks.  A cell that is listed and in E(u)
+ *                is excluded.
+ *   scores       out_score is ascore: bit for bit predict_multiple's score, multiplied by the factor in real_t where the cell is
+ *                listed.  With no cell listed, or every factor 1, the rows are section 1f's, bit for bit.  No float atomics.  Where
+ *                a product is denormal or NaN (a factor of 0 on an infinite score) the result is unspecified, as in section 1o.
+ *   short rows   follow section 1h's rule: if fewer than n_top items are admissible, the rest of the row is POISMF_HIP_TOPN_NONE in
+ *                out_ix and -inf in out_score.
+ *   range        n_top is 1 .. POISMF_HIP_TOPN_BATCH_MAX_N_TOP; dimB <= POISMF_HIP_TOPN_ADJUSTED_MAX_ITEMS.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for: everything that is 2 in
+ * section 1o apart from its weight clauses; adj_indptr == NULL with n_users > 0; row pointers that decrease, start below 0 or leave
+ * the list (adj_indices or adj_factor NULL with cells); an index >= dimB; a row that is not strictly ascending or is longer than
+ * POISMF_HIP_TOPN_ADJUSTED_MAX_ROW; a factor that is NaN, infinite or negative.  n_users == 0 returns 0.
+ *
+ * Two stages and a merge: the dense pass of section 1f over all items with the user's listed cells treated
+ * as excluded, a gather of the listed rows of B only (section 1h's) whose scores are multiplied by their factors, and one merge per
+ * user of the sorted partial lists of both.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1q share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB for
+ * any n_users and any number of listed cells: an exclusion area of at most 2^24 indices (64 MiB; a user's exclusion row united with
+ * its adjust row is no longer than dimB, so every valid row fits), an adjust area of at most POISMF_HIP_TOPN_ADJUSTED_MAX_ROW cells
+ * (index and factor: 48 MiB in double), and in the rest the chunk's users, work items, partial lists and results; the chunk of
+ * users is cut where one of the areas is full.  A user's partial lists are its own: the item slices of the dense stage and, behind
+ * them, one per work item of its adjust row; a long row costs the other users of its chunk nothing.  An adjust row of len cells is
+ * cut into poismf_hip_topn_adjusted_slices(len, n_top, 0) work items (testing aid, no HIP call).  That count is not monotone in len
+ * (the cells per work item are rounded up to 64), and the row may lose cells to the exclusion list after the chunk was cut, so the
+ * cut charges the row poismf_hip_topn_adjusted_slices(len, n_top, 1) lists: a bound that never decreases with len and is no less
+ * than the work items of any row of at most len cells.  poismf_hip_topn_adjusted_scratch_bytes (testing aid, no HIP call; n_cells is
+ * adj_indptr[n_users] - adj_indptr[0]) is the size both entry points allocate; it does not depend on k.  poismf_hip_topn_adjusted's
+ * own copies of B and of A (all of A, or only the batch's rows) come on top.  The session flavour,
+ * poismf_hip_session_topn_adjusted, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_ADJUSTED_MAX_ITEMS 16777216   /* largest dimB of the adjusted entry points (2^24) */
+#define POISMF_HIP_TOPN_ADJUSTED_MAX_ROW 4194304      /* longest adjust row: 2^22 cells */
+POISMF_HIP_API int poismf_hip_topn_adjusted(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *adj_indptr, const sparse_ix *adj_indices, const real_t *adj_factor,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+POISMF_HIP_API size_t poismf_hip_topn_adjusted_scratch_bytes(size_t n_users, size_t n_cells, size_t n_top, size_t dimB, size_t k);
+POISMF_HIP_API size_t poismf_hip_topn_adjusted_slices(size_t len, size_t n_top, int bound);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -870,6 +930,12 @@ POISMF_HIP_API int poismf_hip_session_topn_quota(poismf_hip_session *s, const sp
 POISMF_HIP_API int poismf_hip_session_topn_weighted(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
         const real_t *item_weight, int query_B, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1r from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_adjusted(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        const sparse_ix *adj_indptr, const sparse_ix *adj_indices, const real_t *adj_factor,
+        int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
 
 /* Section 1p from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */

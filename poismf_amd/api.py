@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_weighted", "poismf_hip_session_topn_weighted", "poismf_hip_topn_weighted_scratch_bytes",
     "poismf_hip_topn_diverse", "poismf_hip_session_topn_diverse", "poismf_hip_topn_diverse_scratch_bytes",
     "poismf_hip_list_eval", "poismf_hip_session_list_eval", "poismf_hip_list_eval_scratch_bytes",
+    "poismf_hip_topn_adjusted", "poismf_hip_session_topn_adjusted", "poismf_hip_topn_adjusted_scratch_bytes", "poismf_hip_topn_adjusted_slices",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -82,6 +83,8 @@ LIST_ABSENT = 0xFFFFFFFE            # POISMF_HIP_LIST_ABSENT, POISMF_HIP_LIST_CO
 LIST_COS_SHIFT = 40                 # POISMF_HIP_LIST_EVAL_MAX_ITEMS of section 1q (tests/test_list_eval_cpu.py compares them with
 LIST_EVAL_BUDGET_MB = 256           # the header)
 LIST_EVAL_MAX_ITEMS = 2**24
+TOPN_ADJUSTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_ADJUSTED_MAX_ITEMS and POISMF_HIP_TOPN_ADJUSTED_MAX_ROW of section 1r
+TOPN_ADJUSTED_MAX_ROW = 2**22       # (tests/test_topn_adjusted_cpu.py compares them with the header)
 
 
 def load_library(use_float):
@@ -182,6 +185,14 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_weighted.restype = i
     lib.poismf_hip_topn_weighted_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_weighted_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_adjusted.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_adjusted.restype = i
+    lib.poismf_hip_session_topn_adjusted.argtypes = [vp, vp, sz, sz, vp, vp, vp, i, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_adjusted.restype = i
+    lib.poismf_hip_topn_adjusted_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
+    lib.poismf_hip_topn_adjusted_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_adjusted_slices.argtypes = [sz, sz, i]
+    lib.poismf_hip_topn_adjusted_slices.restype = sz
     lib.poismf_hip_topn_diverse.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, sz, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_topn_diverse.restype = i
     lib.poismf_hip_session_topn_diverse.argtypes = [vp, vp, sz, sz, sz, C.c_double, vp, i, vp, vp, vp, vp, vp]
@@ -744,6 +755,68 @@ def _topn_quota_args(users, n, group_of, quota, exclude, dimA, dimB):
     return users, group_of, quota, indptr, indices
 
 
+def _topn_adjusted_args(users, n, adjust, exclude, dimA, dimB, dtype=np.float64):
+    """The argument checks of the batched top-N with per-(user, item) score factors (include/poismf_hip.h section 1r) that need no
+    device, as the library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are
+    padded).  adjust: None (no cell listed), a SciPy sparse matrix with one row per user of the batch whose stored values are the
+    factors -- stored zeros are KEPT: a factor of 0 is a factor -- or an (indptr, indices, factors) triple; a row's indices strictly
+    ascending (a sparse matrix is sorted first) and at most TOPN_ADJUSTED_MAX_ROW of them.  The factors are converted to `dtype`,
+    the model's real_t, and must be finite and non-negative AFTER that conversion (a double above float32's range is refused for a
+    float32 model).  Returns (users, adj_indptr, adj_indices, adj_factor, excl_indptr or None, excl_indices or None): uint64 arrays
+    and the factors in `dtype`."""
+    users = _index_array(users, "users")
+    m = len(users)
+    n = int(n)
+    if n <= 0:
+        raise ValueError("n must be positive")
+    if n > TOPN_BATCH_MAX_N_TOP:
+        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
+    if dimB < 1:
+        raise ValueError("there are no items")
+    if dimB > TOPN_ADJUSTED_MAX_ITEMS:
+        raise ValueError(f"{dimB} items are above the adjusted call's limit of {TOPN_ADJUSTED_MAX_ITEMS}")
+    if m and int(users.max()) >= dimA:
+        raise ValueError("a user index is out of range")
+    if adjust is None:
+        pair, f = (np.zeros(m + 1, np.uint64), np.zeros(0, np.uint64)), np.zeros(0, dtype)
+    elif isinstance(adjust, (tuple, list)) and not hasattr(adjust, "tocsr"):
+        if len(adjust) != 3:
+            raise ValueError("adjust must be a SciPy sparse matrix or an (indptr, indices, factors) triple")
+        pair, f = (adjust[0], adjust[1]), np.asarray(adjust[2])
+    else:
+        import scipy.sparse as sp
+        if not sp.issparse(adjust):
+            raise ValueError("adjust must be a SciPy sparse matrix or an (indptr, indices, factors) triple")
+        csr = sp.csr_matrix(adjust)
+        if csr.shape[0] != m:
+            raise ValueError(f"adjust has {csr.shape[0]} rows for {m} users")
+        if csr.shape[1] > dimB:
+            raise ValueError("adjust has more columns than there are items")
+        if not csr.has_sorted_indices:
+            csr = csr.copy()
+            csr.sort_indices()          # (stored zeros stay; a cell stored twice fails the ascending check below)
+        pair, f = (csr.indptr, csr.indices), csr.data
+    if f.ndim != 1 or (f.size and f.dtype.kind not in "fiu"):
+        raise ValueError("adjust: the factors must be a 1-d array of real numbers")
+    a_indptr, a_indices = _csr_list(pair, m, dimB, "adjust", row_max=TOPN_ADJUSTED_MAX_ROW)   # (from 0; the factors follow below)
+    lo = int(np.asarray(pair[0]).reshape(-1)[0])
+    hi = lo + int(a_indptr[-1])
+    if len(f) < hi:
+        raise ValueError("adjust: there are fewer factors than item indices")
+    with np.errstate(over="ignore"):
+        f = np.ascontiguousarray(f[lo:hi], dtype=dtype)
+    if np.isnan(f).any():
+        raise ValueError("adjust: NaN factor")
+    if np.isinf(f).any():
+        raise ValueError("adjust: a factor is infinite in the model's precision")
+    if (f < 0).any():
+        raise ValueError("adjust: negative factor (a factor of 0 keeps a cell at score 0; exclude= bars one)")
+    if exclude is None:
+        return users, a_indptr, a_indices, f, None, None
+    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
+    return users, a_indptr, a_indices, f, indptr, indices
+
+
 def _topn_weighted_args(users, n, item_weight, exclude, dimA, dimB, dtype=np.float64):
     """The argument checks of the batched top-N with per-item score weights (include/poismf_hip.h section 1o) that need no device, as
     the library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).
@@ -1105,6 +1178,36 @@ def _topN_weighted(self, users, n=10, item_weight=None, exclude=None, output_sco
 
 
 PoisMF.topN_weighted = _topN_weighted
+
+
+def _topN_adjusted(self, users, n=10, adjust=None, exclude=None, output_score=False):
+    """topN_batch where single cells of the score matrix carry a factor of their own -- an impression discount, a discount on the
+    user's seen items instead of barring them, a per-user boost: the n <= TOPN_BATCH_MAX_N_TOP best items of every user in `users`
+    under "adjusted score descending, item index ascending", minus `exclude` as in topN_batch, exact and in one call on the GPU
+    (include/poismf_hip.h section 1r).  adjust: a SciPy sparse matrix with one row per user of the batch whose stored values are
+    finite factors >= 0 (stored zeros are kept), or an (indptr, indices, factors) triple; None lists no cell.  A listed cell scores
+    predict's score times its factor, rounded once; every other cell predict's score.  A factor of 0 does not bar a cell -- it
+    scores 0 and ties with its like by index; a cell both listed and excluded is excluded.  n may exceed what a user has left: the
+    row is padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    dt = np.float32 if self.use_float else np.float64
+    users, a_indptr, a_indices, f, indptr, indices = _topn_adjusted_args(users, n, adjust, exclude, self.nusers, self.nitems, dt)
+    m, n = len(users), int(n)
+    ix = np.empty((m, n), np.uint64)
+    sc = np.empty((m, n) if output_score else (0, n), dt)
+    if m == 0:
+        return ix, sc
+    A = np.ascontiguousarray(self.A, dtype=dt)
+    B = np.ascontiguousarray(self.B, dtype=dt)
+    lib = load_library(self.use_float)
+    _batch_rc(lib.poismf_hip_topn_adjusted(_ptr(A), _ptr(B), self.k, A.shape[0], B.shape[0], _ptr(users), m, n, _ptr(a_indptr),
+                                           _opt_ptr(a_indices), _opt_ptr(f), _ptr(indptr) if indptr is not None else None,
+                                           _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+    return ix, sc
+
+
+PoisMF.topN_adjusted = _topN_adjusted
 
 
 def _similar_items(self, items, n=10, output_score=False, exclude_self=True, item_norm=None):
@@ -1958,6 +2061,28 @@ class Session:
         _batch_rc(self.lib.poismf_hip_session_topn_weighted(self.h, _ptr(users), m, n, _ptr(w), int(bool(query_items)), int(bool(exclude_seen)),
                                                             _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
                                                             _ptr(ix), _ptr(sc) if output_score else None), "top-N")
+        return ix, sc
+
+    def topn_adjusted(self, users, top_n=10, adjust=None, exclude_seen=False, exclude=None, output_score=False):
+        """topn_batch where single cells of the score matrix carry a factor of their own, from the resident factors, exact and in
+        one call (include/poismf_hip.h section 1r): the top_n <= TOPN_BATCH_MAX_N_TOP best items of every user under "adjusted score
+        descending, item index ascending"; exclude_seen and exclude as in topn_batch.  adjust: a SciPy sparse matrix with one row
+        per user of the batch whose stored values are finite factors >= 0 (stored zeros are kept), or an (indptr, indices, factors)
+        triple; None lists no cell.  A factor of 0 does not bar a cell -- it scores 0 and ties with its like by index; a cell both
+        listed and excluded is excluded.  The scores returned are the adjusted ones.  A short row is padded with TOPN_NONE and -inf.
+        Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score)."""
+        dt = np.float32 if self.use_float else np.float64
+        users, a_indptr, a_indices, f, indptr, indices = _topn_adjusted_args(users, top_n, adjust, exclude, self.dimA, self.dimB, dt)
+        m, n = len(users), int(top_n)
+        if exclude_seen:
+            _outside_shard(users, self.shardA)
+        ix = np.empty((m, n), np.uint64)
+        sc = np.empty((m, n) if output_score else (0, n), dt)
+        if m == 0:
+            return ix, sc
+        _batch_rc(self.lib.poismf_hip_session_topn_adjusted(self.h, _ptr(users), m, n, _ptr(a_indptr), _opt_ptr(a_indices), _opt_ptr(f),
+                                                            int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
+                                                            _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
         return ix, sc
 
     def item_norms(self):

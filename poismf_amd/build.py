@@ -2,14 +2,14 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Twenty-four translation units per precision -- the host side in five (session.hip the session object, planner.hip the planner,
+Twenty-five translation units per precision -- the host side in five (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver;
 they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
 the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip), the
 batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip) and the batched ranks among
 include lists (rank_include.hip) and among lists shared between users (rank_shared.hip), the deep batched top-N (topn_deep.hip, with
-tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the ten share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units and topn_diverse tb_gather.hpp) and the
+tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and with per-(user, item) score factors (topn_adjust.hip: a dense pass on tb_select.hpp, a sparse one on tb_gather.hpp and a merge) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the eleven share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted / topn_adjust the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units, topn_diverse and topn_adjust tb_gather.hpp) and the
 new rows against a resident B (fold_in.hip: the guest of a session, on session.hpp and tb_batch.hpp) and the list-wise evaluation
 (list_eval.hip, on tb_gather.hpp and tb_batch.hpp) -- are compiled to object files
 side by side and linked.  What an object depends on is derived from its file's #include "..." lines (_deps), never listed by hand.
@@ -53,6 +53,7 @@ UNITS = {
     "topn_quota": ("topn_quota.hip", []),
     "topn_weighted": ("topn_weighted.hip", []),
     "topn_diverse": ("topn_diverse.hip", []),
+    "topn_adjust": ("topn_adjust.hip", []),
     "fold_in": ("fold_in.hip", []),
     "list_eval": ("list_eval.hip", []),
 }

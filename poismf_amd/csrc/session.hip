@@ -639,6 +639,24 @@ int poismf_hip_session_topn_weighted(poismf_hip_session* s, const sparse_ix* use
                                         exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Batched top-N with per-(user, item) score factors from the resident (compact) factors (topn_adjust.hip; include/poismf_hip.h section
+// 1r), ordered as the calls above and in the same scratch.
+int poismf_hip_session_topn_adjusted(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* adj_indptr,
+                                     const sparse_ix* adj_indices, const real_t* adj_factor, int exclude_seen, const sparse_ix* excl_indptr,
+                                     const sparse_ix* excl_indices, sparse_ix* out_ix, real_t* out_score)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_adjusted_check(users, n_users, n_top, s->dimA, s->dimB, s->k, adj_indptr, adj_indices, adj_factor, excl_indptr,
+                                                      excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_adjusted_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, adj_indptr, adj_indices, adj_factor,
+                                        exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
+}
+
 // Diversified batched top-N from the resident (compact) factors (topn_diverse.hip; include/poismf_hip.h section 1p), ordered as the
 // calls above and in the same scratch, which it may grow: the deep pool, then greedy MMR picks on the device.
 int poismf_hip_session_topn_diverse(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, size_t pool, double lambda,

@@ -1,5 +1,5 @@
 // tb_batch.hpp -- the host side the batched top-N (topn_batch.hip, topn_include.hip, topn_shared.hip, topn_deep.hip, topn_quota.hip, topn_weighted.hip,
-// topn_diverse.hip) and
+// topn_diverse.hip, topn_adjust.hip) and
 // the batched ranks (rank_batch.hip, rank_include.hip, rank_shared.hip) have in common -- the top-N cores' chunk loop opens with
 // tb_stage_chunk and closes with tb_fetch_results -- and what the session (session.hip) hands to their cores
 #pragma once
@@ -103,6 +103,16 @@ int poismf_hip_topn_weighted_run(hipStream_t stream, const real_t* dA, const rea
                                  const sparse_ix* users, size_t n_users, size_t n_top, const real_t* item_weight, PmfTopnSeen* seen,
                                  const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
                                  sparse_ix* out_ix, real_t* out_score);
+
+// (topn_adjust.hip; section 1r) the same pair for the top-N with per-(user, item) score factors: the adjust list is a host CSR with
+// one row per user of the batch and real_t factors; the check makes no device call, the core returns 0 or 1
+int poismf_hip_topn_adjusted_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
+                                   const sparse_ix* adj_indptr, const sparse_ix* adj_indices, const real_t* adj_factor,
+                                   const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_topn_adjusted_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                 const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* adj_indptr,
+                                 const sparse_ix* adj_indices, const real_t* adj_factor, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
+                                 const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
 
 // (topn_diverse.hip; section 1p) the same pair for the diversified top-N: greedy MMR over the best `pool` items; item_inv_norm [dimB] is
 // a host array; the check makes no device call, the core returns 0 or 1.  out_score and out_value may be NULL

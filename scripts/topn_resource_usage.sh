@@ -6,11 +6,13 @@
 #   <out>/topn_weighted/kernel_resource_usage.txt
 # and of the diversified top-N and the deep unit whose chunk loop it calls:
 #   <out>/topn_diverse/kernel_resource_usage.txt  <out>/topn_diverse/topn_deep_kernel_resource_usage.txt
+# and of the top-N with per-(user, item) score factors (its dense tile kernel, its sparse kernel and its merge):
+#   <out>/topn_adjusted/kernel_resource_usage.txt
 set -e
 ROOT=$(cd "${1:-$(dirname "$0")/..}" && pwd)
 OUT=${2:-$ROOT/profiles}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-function -Wno-unused-const-variable -Wno-pass-failed"
-for unit in topn:topn_batch topn_quota:topn_quota topn_shared:topn_shared topn_weighted:topn_weighted topn_diverse:topn_diverse topn_diverse:topn_deep; do
+for unit in topn:topn_batch topn_quota:topn_quota topn_shared:topn_shared topn_weighted:topn_weighted topn_diverse:topn_diverse topn_diverse:topn_deep topn_adjusted:topn_adjust; do
   dir=${unit%%:*}; src=${unit##*:}
   file=kernel_resource_usage.txt
   [ "$src" = topn_deep ] && file=topn_deep_kernel_resource_usage.txt
