@@ -874,6 +874,52 @@ POISMF_HIP_API int poismf_hip_session_segment_rows(poismf_hip_session *s, int wh
 POISMF_HIP_API int poismf_hip_half_sweep_segment(poismf_hip_session *s, int which, const poismf_hip_params *p,
                           real_t step_size, real_t cnst_div, int seg, size_t *n_unchanged);
 
+/* ---------------------------------------------------------------------------------------------
+ * 2b. Session updates: a user the model knows interacts again.  New counts are merged into the resident CSR and CSC
+ *     on the device and the rows they touch are refit, without rebuilding the session.  No counterpart in the reference.
+ *
+ * poismf_hip_session_add_coo: X += D.  D is HOST COO of the session's shape with n < 2^32 triplets.  Duplicates inside D
+ * are summed first (section 1c's conversion: the bits of tocsr()); a cell the session already stores then gets ONE rounded
+ * addition, a new cell is inserted at its place in the ascending row.  Both orientations are updated, so both halves of
+ * the next sweep see the same matrix.  *n_new_cells (may be NULL) receives the number of cells that were not stored
+ * before.  n == 0 is a no-op that returns 0.  No resident array comes to the host and nothing is sorted again: per
+ * orientation one lane per cell of D finds its place in the resident row (binary search), an exclusive scan over D's
+ * cells gives the new row pointers, one pass over the resident entries moves each to its new place (ranges between two
+ * touched rows shift by a constant), and one lane per cell of D writes the new cell or adds to the moved entry.
+ * Returns 0; 1 out of memory / no device; 3 an index lies outside the matrix; 4 a value is not finite or not > 0 (checked
+ * on the host: deletions and decrements are out of scope); 5 the session is not eligible: either shard is not the whole
+ * matrix (or the session has no CSC), or some resident row of either orientation is not strictly ascending
+ * (poismf_hip_session_create_coo sessions always qualify, a poismf_hip_session_create session built from unsorted host
+ * arrays does not).  3, 4 and 5 are found before anything is written: the session is exactly as it was.
+ * Memory: one orientation is merged after the other -- the CSR first -- and each one's new arrays are built beside its
+ * resident ones, which are freed when the new ones are complete.  Peak extra device memory is therefore ONE half's arrays,
+ * (nnz + new cells) x (4 + sizeof(real_t)) + 8 (dim + 1) bytes, plus O(n + dim) bytes of scratch for D -- not two halves'.
+ * A failure (rc 1) while the CSR is merged leaves the session as it was; the price of the bound is that a failure while
+ * the CSC is merged, after the CSR has been swapped, cannot be undone: the two orientations then disagree and the session
+ * is only good for poismf_hip_session_destroy.
+ * Afterwards: poismf_hip_session_nnz is updated, each half is sorted and binned again with the segments it had, "all values
+ * positive" is re-derived, and exclude_seen of the batched calls sees the new cells.  The factors, the profiling counters,
+ * the guest of the new-rows calls (section 1m) and every scratch area are untouched.
+ *
+ * poismf_hip_session_get_matrix: half `which`'s matrix to the host (1: the CSR shard, 0: the CSC shard): indptr [rows of the
+ * shard + 1] local to the shard (from 0), indices widened to sparse_ix and values, each poismf_hip_session_nnz(s, which)
+ * long; a NULL output is skipped.  The only way to see the CSR of a poismf_hip_session_create_coo session.  0 or 1.
+ *
+ * poismf_hip_half_sweep_rows: poismf_hip_half_sweep over the listed rows of half `which` only.  Every listed row is solved
+ * exactly as poismf_hip_half_sweep would solve it from the session's current factors -- the same bits, column sums of the
+ * WHOLE fixed factor and PG pre-scaling included (a row's arithmetic depends on its length class only) -- and every
+ * unlisted row of the moving factor keeps its bits, in the compact and in the line-padded copy.  `rows` are global row
+ * numbers, distinct and inside the shard, in any order: otherwise 3 is returned before any launch (two workgroups updating
+ * one row in place would race).  n_rows == 0 returns 0 and launches nothing.  n_unchanged (TNCG early stop) counts the
+ * listed rows only.  poismf_hip_session_plan then names this call's launches.  Synchronises the stream.  Returns 0, 1 or 3.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_add_coo(poismf_hip_session *s, const sparse_ix *row, const sparse_ix *col,
+                          const real_t *val, size_t n, size_t *n_new_cells);
+POISMF_HIP_API int poismf_hip_session_get_matrix(poismf_hip_session *s, int which,
+                          sparse_ix *indptr, sparse_ix *indices, real_t *values);
+POISMF_HIP_API int poismf_hip_half_sweep_rows(poismf_hip_session *s, int which, const sparse_ix *rows, size_t n_rows,
+                          const poismf_hip_params *p, real_t step_size, real_t cnst_div, size_t *n_unchanged);
+
 /* run_poismf's outer loop (ref: src/poismf.c:506-608: B half, PG step halving, A half, TNCG early stop, SIGINT
  * handling and return codes 0 / 1 / 2 exactly as in section 1) on a session that already holds X and the starting
  * factors; `p->step_size` is the initial step.  PoisMF.fit uses it with poismf_hip_session_create_coo so that the

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_nnz", "poismf_hip_selftest_log", "poismf_hip_session_eval_stats",
     "poismf_hip_session_create_coo", "poismf_hip_session_stream", "poismf_hip_session_factors_dirty", "poismf_hip_session_run",
     "poismf_hip_session_set_segments", "poismf_hip_session_segment_rows", "poismf_hip_half_sweep_segment", "poismf_hip_session_plan",
+    "poismf_hip_session_add_coo", "poismf_hip_session_get_matrix", "poismf_hip_half_sweep_rows",
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
@@ -153,6 +154,12 @@ def load_library(use_float):
     lib.poismf_hip_session_segment_rows.restype = i
     lib.poismf_hip_half_sweep_segment.argtypes = [vp, i, C.POINTER(lib.params_t), r, r, i, C.POINTER(sz)]
     lib.poismf_hip_half_sweep_segment.restype = i
+    lib.poismf_hip_session_add_coo.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz)]
+    lib.poismf_hip_session_add_coo.restype = i
+    lib.poismf_hip_session_get_matrix.argtypes = [vp, i, vp, vp, vp]
+    lib.poismf_hip_session_get_matrix.restype = i
+    lib.poismf_hip_half_sweep_rows.argtypes = [vp, i, vp, sz, C.POINTER(lib.params_t), r, r, C.POINTER(sz)]
+    lib.poismf_hip_half_sweep_rows.restype = i
     lib.poismf_hip_session_predict.argtypes = [vp, vp, vp, sz, vp]
     lib.poismf_hip_session_predict.restype = i
     lib.eval_llk.argtypes = [vp] * 5 + [sz, i, C.c_bool, C.c_bool, sz, sz, i]
@@ -1934,6 +1941,94 @@ class Session:
 
     def nnz(self, which):
         return self.lib.poismf_hip_session_nnz(self.h, int(which))
+
+    def add(self, coo):
+        """X += coo on the resident matrix, both orientations, merged on the device (include/poismf_hip.h section 2b).  coo: a SciPy
+        sparse matrix (or any object with row / col / data / shape) of the session's shape whose values are finite and > 0;
+        triplets repeated inside it are summed first, a cell the session already stores then gets one rounded addition, a new
+        cell is inserted at its place.  Returns the number of cells that were not stored before.  ValueError -- before anything
+        changes -- for a wrong shape, an index outside the matrix, a value that is not finite and positive, and for a session
+        that cannot be merged into: one that holds a shard, or whose host CSR / CSC had a row that was not strictly ascending."""
+        if hasattr(coo, "tocoo"):
+            coo = coo.tocoo()
+        if tuple(coo.shape) != (self.dimA, self.dimB):
+            raise ValueError(f"add: the update has shape {tuple(coo.shape)}, the session {(self.dimA, self.dimB)}")
+        row, col = _index_array(coo.row, "add: row indices"), _index_array(coo.col, "add: column indices")
+        val = np.ascontiguousarray(coo.data, dtype=np.float32 if self.use_float else np.float64)
+        if not (row.ndim == col.ndim == val.ndim == 1 and len(row) == len(col) == len(val)):
+            raise ValueError("add: row, col and data must be one-dimensional and of one length")
+        if len(val) == 0:
+            return 0
+        if int(row.max()) >= self.dimA or int(col.max()) >= self.dimB:
+            raise ValueError("add: a row / column index lies outside the matrix")
+        if not (np.isfinite(val).all() and (val > 0).all()):
+            raise ValueError("add: every value must be finite and > 0 (deletions and decrements are not supported)")
+        if len(val) >= 2 ** 32:
+            raise ValueError("add: at most 2^32 - 1 triplets per call")
+        fresh = C.c_size_t(0)
+        rc = self.lib.poismf_hip_session_add_coo(self.h, _ptr(row), _ptr(col), _ptr(val), len(val), C.byref(fresh))
+        if rc == 3:
+            raise ValueError("add: a row / column index lies outside the matrix")
+        if rc == 4:
+            raise ValueError("add: every value must be finite and > 0 (deletions and decrements are not supported)")
+        if rc == 5:
+            raise ValueError("add: this session cannot be merged into: it holds a shard of the matrix, or a row of its CSR / CSC "
+                             "is not strictly ascending (Session.from_coo sessions always qualify)")
+        if rc:
+            raise MemoryError("poismf_hip_session_add_coo failed (out of memory or a device error)")
+        return fresh.value
+
+    def matrix(self, which):
+        """(values, indices, indptr) of the resident CSR shard (which = 1) or CSC shard (which = 0), downloaded: the layout of the
+        csr / csc tuples Session() takes, indptr local to the shard.  The only way to see the CSR of a from_coo session."""
+        lo, hi = self.shardA if which else self.shardB
+        nnz = self.nnz(which)
+        val = np.empty(nnz, np.float32 if self.use_float else np.float64)
+        ind, ptr = np.empty(nnz, np.uint64), np.empty(hi - lo + 1, np.uint64)
+        if self.lib.poismf_hip_session_get_matrix(self.h, int(bool(which)), _ptr(ptr), _ptr(ind), _ptr(val)):
+            raise RuntimeError("poismf_hip_session_get_matrix failed")
+        return val, ind, ptr
+
+    def half_sweep_rows(self, which, rows, params, step_size, cnst_div, want_unchanged=False):
+        """half_sweep over the listed rows of half `which` only (0: rows of B, 1: rows of A; global row numbers, distinct, inside
+        the shard, any order): every listed row gets the bits a full half_sweep from the same factors would give it, every other
+        row of the moving factor keeps its own.  Returns the listed rows found unchanged (TNCG early stop, want_unchanged)."""
+        lo, hi = self.shardA if which else self.shardB
+        rows = np.asarray(rows)
+        if rows.ndim != 1:
+            raise ValueError("half_sweep_rows: rows must be one-dimensional")
+        if rows.size and not (np.issubdtype(rows.dtype, np.integer) and rows.dtype != np.bool_):
+            raise ValueError("half_sweep_rows: rows must be integers")
+        if rows.size and (int(rows.min()) < lo or int(rows.max()) >= hi):
+            raise ValueError(f"half_sweep_rows: a row lies outside the session's rows [{lo}, {hi})")
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if len(np.unique(rows)) != len(rows):
+            raise ValueError("half_sweep_rows: a row is listed twice")
+        if len(rows) == 0:
+            return 0
+        n = C.c_size_t(0)
+        rc = self.lib.poismf_hip_half_sweep_rows(self.h, int(bool(which)), _ptr(rows), len(rows), C.byref(params), step_size, cnst_div,
+                                                 C.byref(n) if want_unchanged else None)
+        if rc == 3:
+            raise ValueError("half_sweep_rows: rows must be distinct and inside the session's shard")
+        if rc:
+            raise RuntimeError("poismf_hip_half_sweep_rows failed")
+        return n.value
+
+    def update(self, coo, params, step_size):
+        """A returning user: add(coo), then half_sweep_rows(1, users) and half_sweep_rows(0, items) over the sorted distinct rows /
+        columns of coo, both with this step and cnst_div(params.l2_reg, step_size).  ONE LOCAL REFIT of the touched rows against
+        the current factors, not the reference's step schedule (no halving between the halves, no sweep over the other rows).
+        Returns (users, items)."""
+        if hasattr(coo, "tocoo"):
+            coo = coo.tocoo()
+        self.add(coo)
+        users, items = np.unique(np.asarray(coo.row)).astype(np.int64), np.unique(np.asarray(coo.col)).astype(np.int64)
+        step_size = self.real(step_size)
+        cnst_div = self.cnst_div(params.l2_reg, step_size)
+        self.half_sweep_rows(1, users, params, step_size, cnst_div)
+        self.half_sweep_rows(0, items, params, step_size, cnst_div)
+        return users, items
 
     def predict(self, ix_u, ix_i):
         """A[ix_u[i]] . B[ix_i[i]] from the resident factors (ref: src/pred.c:42-64)"""

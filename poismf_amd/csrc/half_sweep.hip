@@ -250,10 +250,9 @@ hipStream_t launch_stream(const PlannedLaunch& L, hipStream_t main, hipStream_t 
 
 // The half's prologue: column sums of the fixed factor (or the caller's k-vector), the padded gather copy, and the arguments every launch of
 // the half starts from.
-int half_prologue(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div, bool prologue, bool early_stop,
-                  const real_t* bsum_override, real_t neg_step_override, real_t neg_step2, HalfArgs<real_t>& a)
+int half_prologue(poismf_hip_session* s, int which, const Half& h, bool subset, const poismf_hip_params* p, real_t step_size, real_t cnst_div,
+                  bool prologue, bool early_stop, const real_t* bsum_override, real_t neg_step_override, real_t neg_step2, HalfArgs<real_t>& a)
 {
-    Half& h = s->half[which];
     real_t* M = which ? s->dA : s->dB;
     const real_t* F = which ? s->dB : s->dA;
     const size_t dimF = which ? s->dimB : s->dimA;
@@ -291,7 +290,9 @@ int half_prologue(poismf_hip_session* s, int which, const poismf_hip_params* p, 
         Mp = which ? s->dAp : s->dBp;
         if (prologue) {
             s->padded_fresh[which ? 0 : 1] = true;   // the copy of F was just re-derived (or was current)
-            s->padded_fresh[which ? 1 : 0] = h.row_begin == 0 && h.row_end == h.dimM;
+            // (a call over listed rows leaves the moving factor's copy as fresh as it was: its row kernels store every row they update to
+            // both copies and touch no other -- it can never MAKE the copy fresh)
+            if (!subset) s->padded_fresh[which ? 1 : 0] = h.row_begin == 0 && h.row_end == h.dimM;
         }
     }
 
@@ -531,13 +532,15 @@ int team_check(poismf_hip_session* s)
 // seg < 0: every segment of the shard, one pass after the other (plan_call); seg >= 0: that segment only -- segment 0 then also runs the
 // prologue (column sums, refresh of the padded gather copy, reset of the early-stop counter), and the counter is read by whichever call
 // passes n_unchanged (the last segment).  Either way a segment's launches are the same launches.
+// view != nullptr: a half that shares the session half's matrix arrays and has a permutation, descriptors and bins of its own over SOME of
+// its rows (poismf_hip_half_sweep_rows) -- everything below runs on it as it runs on the whole half.
 int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div,
                            size_t* n_unchanged, const real_t* bsum_override, real_t neg_step_override, real_t neg_step2,
-                           int seg)
+                           int seg, const Half* view)
 {
     HIP_TRY(hipSetDevice(s->device));
     which = which ? 1 : 0;
-    Half& h = s->half[which];
+    const Half& h = view != nullptr ? *view : s->half[which];
     if (seg >= (int)h.segs.size()) return 1;
     const bool early_stop = (p->method == POISMF_TNCG) && p->early_stop && (n_unchanged != nullptr || seg >= 0);
     const bool is_pg = p->method == POISMF_PG;
@@ -548,7 +551,8 @@ int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p
         const std::vector<PlannedLaunch>& launches = passes[i];
         const bool prologue = seg <= 0 && i == 0, last = i + 1 == passes.size();
         HalfArgs<real_t> base;
-        if (half_prologue(s, which, p, step_size, cnst_div, prologue, early_stop, bsum_override, neg_step_override, neg_step2, base)) return 1;
+        if (half_prologue(s, which, h, view != nullptr, p, step_size, cnst_div, prologue, early_stop, bsum_override, neg_step_override, neg_step2, base))
+            return 1;
         if (s->profiling && i == 0) {
             HIP_TRY(hipEventCreate(&rec.t0));
             HIP_TRY(hipEventCreate(&rec.t1));

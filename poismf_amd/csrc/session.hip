@@ -125,11 +125,20 @@ int finish_half_collect(Half& h, hipStream_t stream, HalfPending& pend)
     for (auto& sg : h.segs) sg.bins = bins_of(len.data(), sg.row_lo, sg.row_hi);
     return 0;
 }
-static int finish_half(Half& h, hipStream_t stream, int nseg = 1)
+int finish_half(Half& h, hipStream_t stream, int nseg)
 {
     HalfPending pend;
     if (finish_half_launch(h, stream, pend, nseg)) { pmf_free(pend.d_flag, stream); pmf_free(pend.d_len, stream); return 1; }
     return finish_half_collect(h, stream, pend);
+}
+
+// descriptors of the n rows d_perm names, in its order (a listed-rows half-sweep builds its own: session_update.hip)
+int row_desc_launch(const unsigned long long* d_indptr, const unsigned* d_perm, size_t n, RowDesc* d_desc, hipStream_t stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(row_desc_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, stream, d_indptr, d_perm, n, d_desc);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // Upload rows [r0, r1) of a host CSR (size_t indices) with shard-local pointers; the indices are narrowed to u32 on

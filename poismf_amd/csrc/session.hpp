@@ -90,6 +90,7 @@ struct poismf_hip_session {
     size_t topn_cap = 0;              // ... in bytes
     std::vector<unsigned long long> topn_indptr;   // exclude_seen: host copy of the CSR shard's row pointers (fetched by the first such call)
     int csr_rows_sorted = -1;         // exclude_seen: -1 not checked yet, 0 some resident CSR row is not strictly ascending, 1 all are
+    int csc_rows_sorted = -1;         // the same of the CSC shard's rows (session_update.hip merges into ascending rows only)
     // New rows against the resident B (fold_in.hip; include/poismf_hip.h section 1m).  The rows are the A half of a GUEST: a session of its
     // own rows, factor (dA, dAp), column-sum vector, queue heads, team words and `seen` bookkeeping, which BORROWS this session's dB, dBp, ld,
     // streams and events.  Kept here from the first such call to the session's end and refilled by every later one.
@@ -139,6 +140,8 @@ poismf_hip_session* session_alloc(int device, void* stream, size_t dimA, size_t 
 int build_half(Half& h, hipStream_t stream, const real_t* val, const sparse_ix* indptr, const sparse_ix* indices,
                size_t dimM, size_t dimF, size_t r0, size_t r1, int device = 0, HalfPending* pend = nullptr);
 int finish_half_collect(Half& h, hipStream_t stream, HalfPending& pend);
+int finish_half(Half& h, hipStream_t stream, int nseg = 1);
+int row_desc_launch(const unsigned long long* d_indptr, const unsigned* d_perm, size_t n, RowDesc* d_desc, hipStream_t stream);
 void free_half(Half& h, hipStream_t stream);
 
 // half_sweep.hip
@@ -146,7 +149,7 @@ int nc_for_k(size_t k);
 int team_check(poismf_hip_session* s);
 int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p, real_t step_size, real_t cnst_div,
                     size_t* n_unchanged, const real_t* bsum_override, real_t neg_step_override, real_t neg_step2 = (real_t)1,
-                    int seg = -1);
+                    int seg = -1, const Half* view = nullptr);
 
 // drivers.hip: the interrupt flag of the running call, and its device-visible twin (nullptr until a call has allocated it)
 bool interrupt_requested();
