@@ -98,7 +98,20 @@ POISMF_HIP_API int factors_multiple(
  * size_t).  There is no C function for this in the reference; the entry point takes what _process_data holds
  * (host triplets) and fills what run_poismf takes.  Output arrays are caller-allocated with capacity n
  * (values, indices) and dim + 1 (indptr); *nnz_out receives the number of distinct (i,j).  Requires n < 2^32.
- * Returns 0, or 1 when out of memory / no device.
+ *
+ * The summation rule.  The stored value of a cell is a function of that cell's own triplet values, in the order the
+ * caller gave them, and of nothing else: with the cell's triplets t1, t2, ... in input order it is
+ *     s = t1;  s = s + t2;  s = s + t3;  ...        every addition rounded in real_t
+ * (what SciPy's csr_sum_duplicates does on a row once its duplicates are adjacent; d triplets cost d - 1 dependent
+ * additions and |s - exact sum| <= (d - 1) u sum|t|, u = half an ulp of 1).  So the CSR and the CSC hold the same bits
+ * for a cell, a row shard holds the unsharded rows' bits, a cell's bits do not depend on the other triplets of the
+ * call or on their number, and repeated calls agree.  Every conversion in this library follows the rule: this entry
+ * point, poismf_hip_session_create_coo (shards included), eval_llk and the duplicates inside an update (section 2b).
+ * Where the values are small integers every order gives the same sum, and the results are SciPy's bit for bit; for
+ * other values SciPy's own order of equal columns is not defined (tocsr() sorts a row by column with an unstable sort).
+ *
+ * Returns 0; 1 when out of memory / no device; 3 when a row index is >= dimA or a column index >= dimB (a negative
+ * index of the R flavour included): checked before any device work, nothing is written.
  * ------------------------------------------------------------------------------------------- */
 POISMF_HIP_API int poismf_hip_coo_to_csr_csc(
     const sparse_ix *row, const sparse_ix *col, const real_t *val, size_t n, size_t dimA, size_t dimB,
@@ -128,7 +141,7 @@ POISMF_HIP_API int topN(
  * 1e. Poisson log-likelihood of fitted factors (the reference declares eval_llk, ref: src/poismf.h:258-269, and
  *     defines it nowhere -- SURVEY quirk Q12; this is the definition).
  *
- * For factors A [dimA x k], B [dimB x k] and cells (i, j, x) -- duplicate (i, j) summed first, as for a fit --
+ * For factors A [dimA x k], B [dimB x k] and cells (i, j, x) -- duplicate (i, j) summed first by the rule of section 1c, as for a fit --
  * with yhat_ij = sum_c A[i,c] B[j,c] (products and sums in double, in both precisions):
  *
  *     llk = sum_cells [ x log(yhat) - lgamma(x + 1) * full_llk ] - M
@@ -879,7 +892,7 @@ POISMF_HIP_API int poismf_hip_half_sweep_segment(poismf_hip_session *s, int whic
  *     on the device and the rows they touch are refit, without rebuilding the session.  No counterpart in the reference.
  *
  * poismf_hip_session_add_coo: X += D.  D is HOST COO of the session's shape with n < 2^32 triplets.  Duplicates inside D
- * are summed first (section 1c's conversion: the bits of tocsr()); a cell the session already stores then gets ONE rounded
+ * are summed first (section 1c's conversion and its summation rule); a cell the session already stores then gets ONE rounded
  * addition, a new cell is inserted at its place in the ascending row.  Both orientations are updated, so both halves of
  * the next sweep see the same matrix.  *n_new_cells (may be NULL) receives the number of cells that were not stored
  * before.  n == 0 is a no-op that returns 0.  No resident array comes to the host and nothing is sorted again: per

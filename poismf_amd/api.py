@@ -346,7 +346,8 @@ def _coo_arrays(coo, use_float):
 
 def coo_to_csr_csc(coo, use_float):
     """GPU replacement of harness.process_data (ref: poismf/__init__.py:404-414): SciPy COO -> (csr, csc) tuples of
-    (data real_t, indices size_t, indptr size_t) with duplicates summed and indices sorted."""
+    (data real_t, indices size_t, indptr size_t) with indices sorted and duplicates summed by the rule of section 1c of
+    include/poismf_hip.h (a cell's triplets added in input order).  ValueError for an index outside the matrix."""
     lib = load_library(use_float)
     dt = np.float32 if use_float else np.float64
     n = coo.nnz
@@ -357,8 +358,11 @@ def coo_to_csr_csc(coo, use_float):
     cv, ci, cp = np.empty(n, dt), np.empty(n, np.uint64), np.empty(dimA + 1, np.uint64)
     kv, ki, kp = np.empty(n, dt), np.empty(n, np.uint64), np.empty(dimB + 1, np.uint64)
     nnz = C.c_size_t(0)
-    if lib.poismf_hip_coo_to_csr_csc(_ptr(row), _ptr(col), _ptr(val), n, dimA, dimB, _ptr(cv), _ptr(ci), _ptr(cp), _ptr(kv),
-                                     _ptr(ki), _ptr(kp), C.byref(nnz)):
+    rc = lib.poismf_hip_coo_to_csr_csc(_ptr(row), _ptr(col), _ptr(val), n, dimA, dimB, _ptr(cv), _ptr(ci), _ptr(cp), _ptr(kv),
+                                       _ptr(ki), _ptr(kp), C.byref(nnz))
+    if rc == 3:
+        raise ValueError("a row / column index of the triplets lies outside the matrix")
+    if rc:
         raise MemoryError("Could not allocate enough memory.")
     m = nnz.value
     return (cv[:m].copy(), ci[:m].copy(), cp), (kv[:m].copy(), ki[:m].copy(), kp)
@@ -514,7 +518,7 @@ class PoisMF:
         self.is_fitted = False
 
     def fit(self, X):
-        # COO -> CSR + CSC on the device (bit-identical to the SciPy conversion of the reference's _process_data);
+        # COO -> CSR + CSC on the device (the reference's _process_data; SciPy's bits for integer counts, section 1c's sums otherwise);
         # the converted matrix stays in HBM and the alternation runs on it in place (run_poismf's loop, same return
         # codes and exceptions) -- nothing but the triplets goes up and nothing but the factors comes back
         import scipy.sparse as sp
@@ -1777,9 +1781,10 @@ class Session:
 
     @classmethod
     def from_coo(cls, coo, k, use_float, device=0, stream=None, shardA=None, shardB=None):
-        """Session whose CSR and CSC are built on the device from the triplets of a SciPy COO matrix (duplicates summed,
-        indices sorted: bit-identical to tocsr() / tocsc()); with shards, only the triplets of the shard's rows
-        (CSR) / columns (CSC) are kept."""
+        """Session whose CSR and CSC are built on the device from the triplets of a SciPy COO matrix (indices sorted, duplicates
+        summed: the sums of section 1c of include/poismf_hip.h -- a cell's triplets added in input order; SciPy's bits where the
+        values are integers); with shards, only the triplets of the shard's rows (CSR) / columns (CSC) are kept, and a kept cell
+        has the bits it has without shards."""
         if coo.nnz == 0:
             raise ValueError("'X' contains no non-zero entries.")
         return cls(None, None, coo.shape[0], coo.shape[1], k, use_float, device, stream, shardA, shardB,
@@ -1945,7 +1950,7 @@ class Session:
     def add(self, coo):
         """X += coo on the resident matrix, both orientations, merged on the device (include/poismf_hip.h section 2b).  coo: a SciPy
         sparse matrix (or any object with row / col / data / shape) of the session's shape whose values are finite and > 0;
-        triplets repeated inside it are summed first, a cell the session already stores then gets one rounded addition, a new
+        triplets repeated inside it are summed first (in input order, section 1c), a cell the session already stores then gets one rounded addition, a new
         cell is inserted at its place.  Returns the number of cells that were not stored before.  ValueError -- before anything
         changes -- for a wrong shape, an index outside the matrix, a value that is not finite and positive, and for a session
         that cannot be merged into: one that holds a shard, or whose host CSR / CSC had a row that was not strictly ascending."""

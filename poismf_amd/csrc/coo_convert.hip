@@ -5,14 +5,16 @@
 // entries and deliver sorted indices): at 1e8 triplets SciPy needs several seconds per orientation while
 // one GPU sweep takes 0.2 s.  Pure HBM-bound integer work: pack (major, minor) into a 64-bit key, LSD radix
 // sort the (key, value) pairs (rocPRIM's device radix sort -- a library primitive, used the way a library
-// GEMM would be), sum equal keys, split the keys again and binary-search the row pointers.
+// GEMM would be), add up each run of equal keys in the caller's order (one lane per run: the rule of include/poismf_hip.h
+// section 1c), split the keys again and binary-search the row pointers.
 //
 // Compiled into libpoismf_hip_{d,f}.so next to poismf_hip.hip; C-ABI in include/poismf_hip.h.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce_by_key.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
 #include <cstdio>
@@ -34,13 +36,32 @@ namespace {
         }                                                                                          \
     } while (0)
 
-// Triplets whose major index lies outside [m0, m1) get the all-ones key: they sort behind every real key, collapse
-// into one trailing entry in the reduction and are dropped there (row shards of the multi-GPU driver).
+// Triplets whose major index lies outside [m0, m1) get the all-ones key: they sort behind every real key, form
+// one trailing run and are dropped there (row shards of the multi-GPU driver).
 __global__ void pack_keys(const unsigned* major, const unsigned* minor, size_t n, unsigned m0, unsigned m1, unsigned long long* keys)
 {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const unsigned m = major[i];
         keys[i] = (m >= m0 && m < m1) ? (((unsigned long long)(m - m0) << 32) | (unsigned long long)minor[i]) : ~0ull;
+    }
+}
+// does a run of equal keys begin at position i of the sorted keys?
+struct RunHead {
+    const unsigned long long* keys;
+    __device__ bool operator()(unsigned i) const { return i == 0 || keys[i] != keys[i - 1]; }
+};
+// Run u of the sorted (key, value) pairs lies at [heads[u], heads[u + 1]) -- the last of the n_heads runs ends at n.  One lane per run, the
+// first n_runs of them: ukeys[u] = the run's key, out[u] = its values added up from the first on, one rounded addition each.
+__global__ __launch_bounds__(256) void sum_runs(const unsigned long long* keys, const real_t* vals, const unsigned* heads, size_t n_runs,
+                                                size_t n_heads, size_t n, unsigned long long* ukeys, real_t* out)
+{
+    for (size_t u = blockIdx.x * (size_t)blockDim.x + threadIdx.x; u < n_runs; u += (size_t)gridDim.x * blockDim.x) {
+        const size_t a = heads[u], b = u + 1 < n_heads ? (size_t)heads[u + 1] : n;
+        real_t s = vals[a];
+#pragma unroll 4
+        for (size_t j = a + 1; j < b; j++) s = s + vals[j];
+        ukeys[u] = keys[a];
+        out[u] = s;
     }
 }
 __global__ void row_len_kernel(const unsigned long long* indptr, size_t n, unsigned base, unsigned* len, unsigned* ids)
@@ -93,12 +114,14 @@ int poismf_hip_device_coo_to_cs(const unsigned* d_major, const unsigned* d_minor
     const size_t dim_major = major_end - major_begin;
     unsigned long long *keys_a = nullptr, *keys_b = nullptr;
     real_t* vals_b = nullptr;
+    unsigned* heads = nullptr;
     size_t* d_count = nullptr;
     void* tmp = nullptr;
     auto cleanup = [&]() {
         pmf_free(keys_a, stream);
         pmf_free(keys_b, stream);
         pmf_free(vals_b, stream);
+        pmf_free(heads, stream);
         pmf_free(d_count, stream);
         pmf_free(tmp, stream);
     };
@@ -119,19 +142,28 @@ int poismf_hip_device_coo_to_cs(const unsigned* d_major, const unsigned* d_minor
     TRY_OR_CLEAN(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_a, keys_b, d_val, vals_b, n, 0u, end_bit, stream));
     pmf_free(tmp, stream); tmp = nullptr;
 
-    // equal keys -> one entry holding the sum (keys_a is reused for the unique keys)
+    // equal keys -> one entry holding the sum (keys_a is reused for the unique keys).  The positions at which a run of equal keys
+    // begins are compacted (integer work: the same every time), then one lane per run adds the run up from its first triplet on:
+    // the stable sort kept a cell's triplets in the caller's order, so the sum is the one section 1c of the header defines, whatever
+    // else the call holds and wherever the run lies.  (A keyed floating-point reduction associates a run by where it falls against
+    // its thread and block boundaries -- DESIGN.md, "COO conversion".)
     size_t tmp2 = 0;
-    TRY_OR_CLEAN(rocprim::reduce_by_key(nullptr, tmp2, keys_b, vals_b, (unsigned int)n, keys_a, out_val, d_count,
-                                        rocprim::plus<real_t>(), rocprim::equal_to<unsigned long long>(), stream));
+    const rocprim::counting_iterator<unsigned> positions(0u);
+    TRY_OR_CLEAN(pmf_alloc(&heads, sizeof(unsigned) * n, stream));
+    TRY_OR_CLEAN(rocprim::select(nullptr, tmp2, positions, heads, d_count, n, RunHead{ keys_b }, stream));
     TRY_OR_CLEAN(pmf_alloc(&tmp, tmp2 ? tmp2 : 16, stream));
-    TRY_OR_CLEAN(rocprim::reduce_by_key(tmp, tmp2, keys_b, vals_b, (unsigned int)n, keys_a, out_val, d_count,
-                                        rocprim::plus<real_t>(), rocprim::equal_to<unsigned long long>(), stream));
-    size_t uniq = 0;
-    TRY_OR_CLEAN(pmf_download(&uniq, d_count, sizeof(size_t), stream));
-    if (uniq > 0) {   // the trailing entry of the dropped triplets, if any
+    TRY_OR_CLEAN(rocprim::select(tmp, tmp2, positions, heads, d_count, n, RunHead{ keys_b }, stream));
+    size_t n_heads = 0;
+    TRY_OR_CLEAN(pmf_download(&n_heads, d_count, sizeof(size_t), stream));
+    size_t uniq = n_heads;
+    if (uniq > 0) {   // the trailing run of the dropped triplets, if any: not summed (it can be most of the input), not counted
         unsigned long long last = 0;
-        TRY_OR_CLEAN(pmf_download(&last, keys_a + (uniq - 1), sizeof(last), stream));
+        TRY_OR_CLEAN(pmf_download(&last, keys_b + (n - 1), sizeof(last), stream));
         if (last == ~0ull) uniq--;
+    }
+    if (uniq > 0) {
+        const unsigned g1 = (unsigned)std::min<size_t>((uniq + 255) / 256, 256 * 8);
+        hipLaunchKernelGGL(sum_runs, dim3(g1), dim3(256), 0, stream, keys_b, vals_b, heads, uniq, n_heads, n, keys_a, out_val);
     }
     const unsigned g2 = (unsigned)std::min<size_t>((uniq + 255) / 256 + 1, 256 * 8);
     hipLaunchKernelGGL(split_keys, dim3(g2), dim3(256), 0, stream, keys_a, uniq, out_minor);
@@ -186,6 +218,10 @@ int poismf_hip_coo_to_csr_csc(const sparse_ix* row, const sparse_ix* col, const 
                               sparse_ix* csc_indices, sparse_ix* csc_indptr, size_t* nnz_out)
 {
     if (n == 0 || n > 0xffffffffull || dimA > 0x7fffffffull || dimB > 0x7fffffffull) return 1;
+    // (an index is narrowed to 32 bits below: one outside the matrix -- or a negative one read as size_t -- would land in another row,
+    // or leave a matrix whose tail no row pointer reaches: rc 3 before any device work, nothing written)
+    for (size_t i = 0; i < n; i++)
+        if ((size_t)row[i] >= dimA || (size_t)col[i] >= dimB) return 3;
     const int device = pmf_env_device();
     HIP_TRY(hipSetDevice(device));
     hipStream_t stream = nullptr;
