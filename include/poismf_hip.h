@@ -900,7 +900,7 @@ POISMF_HIP_API int poismf_hip_half_sweep_segment(poismf_hip_session *s, int whic
  * cells gives the new row pointers, one pass over the resident entries moves each to its new place (ranges between two
  * touched rows shift by a constant), and one lane per cell of D writes the new cell or adds to the moved entry.
  * Returns 0; 1 out of memory / no device; 3 an index lies outside the matrix; 4 a value is not finite or not > 0 (checked
- * on the host: deletions and decrements are out of scope); 5 the session is not eligible: either shard is not the whole
+ * on the host: deletions and decrements are section 2c's); 5 the session is not eligible: either shard is not the whole
  * matrix (or the session has no CSC), or some resident row of either orientation is not strictly ascending
  * (poismf_hip_session_create_coo sessions always qualify, a poismf_hip_session_create session built from unsorted host
  * arrays does not).  3, 4 and 5 are found before anything is written: the session is exactly as it was.
@@ -932,6 +932,52 @@ POISMF_HIP_API int poismf_hip_session_get_matrix(poismf_hip_session *s, int whic
                           sparse_ix *indptr, sparse_ix *indices, real_t *values);
 POISMF_HIP_API int poismf_hip_half_sweep_rows(poismf_hip_session *s, int which, const sparse_ix *rows, size_t n_rows,
                           const poismf_hip_params *p, real_t step_size, real_t cnst_div, size_t *n_unchanged);
+
+/* ---------------------------------------------------------------------------------------------
+ * 2c. Session updates: counts are taken back.  An order is cancelled, a like withdrawn, a user asks to be forgotten, an
+ *     item is delisted: counts leave the resident CSR and CSC on the device, without rebuilding the session.  The inverse
+ *     of section 2b; no counterpart in the reference.
+ *
+ * poismf_hip_session_sub_coo: X -= D.  D is HOST COO of the session's shape with n < 2^32 triplets.  Triplets repeated
+ * inside D are summed first (section 1c's conversion and its summation rule: in input order, so both orientations see the
+ * same bits); a cell the session stores then gets ONE rounded subtraction nv = x - d in the model's precision.  The cell
+ * is kept with value nv if and only if nv > 0; otherwise it is REMOVED: its entry leaves the row and the row gets shorter.
+ * No stored zero or negative value ever results.  val == NULL removes every listed stored cell outright, whatever it
+ * holds (a repeated triplet is then harmless).  A listed cell the session does not store is ABSENT: with strict != 0 any
+ * absent cell makes the call return 6 before anything is written, with strict == 0 absent cells are skipped and counted
+ * in *n_absent.  *n_removed receives the number of cells that left the matrix (either may be NULL).  Both orientations
+ * are updated and end with identical cell sets and identical value bits: "removed" is decided from the same x and d bits
+ * in both.  n == 0 returns 0 and launches nothing.
+ * Per orientation: one lane per cell of D finds its place in the resident row (2b's search) and decides gone = !(nv > 0);
+ * an exclusive scan of `gone` over D's cells gives the new row pointers; ONE pass over the resident entries moves each
+ * survivor left to its new place and drops the gone ones (ranges between two touched rows shift by a constant; inside
+ * a touched row an entry moves by the gone positions before it, a binary search); then one lane per surviving hit writes
+ * nv over the moved entry.  No resident array comes to the host and nothing is sorted again.
+ *
+ * poismf_hip_session_remove_rows: every stored cell of the listed rows of half `which` (1: users, rows of the CSR; 0: items)
+ * is removed -- from that orientation AND from the other one.  `rows` are global, distinct, inside the matrix, in any order.
+ * The cell list is built on the device from the resident rows themselves (the listed rows' ranges expanded into (major,
+ * minor) triplets; only their total count comes to the host) and goes through the core of sub_coo(val = NULL).  The rows
+ * stay in the matrix with length 0: the dimensions never change and the factor rows are untouched.  n_rows == 0 returns 0
+ * and launches nothing.  *n_removed (may be NULL) receives the number of cells removed.
+ *
+ * Returns 0; 1 out of memory / no device / n >= 2^32; 3 an index lies outside the matrix (remove_rows: or a row is listed
+ * twice); 4 val is given and some value is not finite or not > 0; 5 the session is not eligible (2b's rule: either shard
+ * is not the whole matrix, no CSC, or a resident row that is not strictly ascending); 6 strict was set and a cell is
+ * absent.  3, 4, 5 and 6 are found before anything is written: the session is exactly as it was.
+ * Memory and failure are 2b's: the CSR is done first, then the CSC; each orientation's new arrays are built beside the
+ * resident ones and swapped in when complete, so peak extra device memory is one half's arrays plus O(n + dim) scratch;
+ * a failure (rc 1) after the CSR has been swapped leaves the orientations in disagreement and the session only good for
+ * poismf_hip_session_destroy.
+ * Afterwards: poismf_hip_session_nnz is updated, each half is sorted and binned again with the segments it had, and
+ * exclude_seen of the batched calls, poismf_hip_session_llk, the new-rows calls and the half-sweeps no longer see the
+ * cells.  A matrix emptied to nnz == 0 is legal and a later poismf_hip_session_add_coo works on it.  The factors are
+ * untouched (refit the touched rows with poismf_hip_half_sweep_rows).
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_sub_coo(poismf_hip_session *s, const sparse_ix *row, const sparse_ix *col,
+                          const real_t *val, size_t n, int strict, size_t *n_removed, size_t *n_absent);
+POISMF_HIP_API int poismf_hip_session_remove_rows(poismf_hip_session *s, int which, const sparse_ix *rows, size_t n_rows,
+                          size_t *n_removed);
 
 /* run_poismf's outer loop (ref: src/poismf.c:506-608: B half, PG step halving, A half, TNCG early stop, SIGINT
  * handling and return codes 0 / 1 / 2 exactly as in section 1) on a session that already holds X and the starting

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_create_coo", "poismf_hip_session_stream", "poismf_hip_session_factors_dirty", "poismf_hip_session_run",
     "poismf_hip_session_set_segments", "poismf_hip_session_segment_rows", "poismf_hip_half_sweep_segment", "poismf_hip_session_plan",
     "poismf_hip_session_add_coo", "poismf_hip_session_get_matrix", "poismf_hip_half_sweep_rows",
+    "poismf_hip_session_sub_coo", "poismf_hip_session_remove_rows",
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
@@ -156,6 +157,10 @@ def load_library(use_float):
     lib.poismf_hip_half_sweep_segment.restype = i
     lib.poismf_hip_session_add_coo.argtypes = [vp, vp, vp, vp, sz, C.POINTER(sz)]
     lib.poismf_hip_session_add_coo.restype = i
+    lib.poismf_hip_session_sub_coo.argtypes = [vp, vp, vp, vp, sz, i, C.POINTER(sz), C.POINTER(sz)]
+    lib.poismf_hip_session_sub_coo.restype = i
+    lib.poismf_hip_session_remove_rows.argtypes = [vp, i, vp, sz, C.POINTER(sz)]
+    lib.poismf_hip_session_remove_rows.restype = i
     lib.poismf_hip_session_get_matrix.argtypes = [vp, i, vp, vp, vp]
     lib.poismf_hip_session_get_matrix.restype = i
     lib.poismf_hip_half_sweep_rows.argtypes = [vp, i, vp, sz, C.POINTER(lib.params_t), r, r, C.POINTER(sz)]
@@ -1967,7 +1972,7 @@ class Session:
         if int(row.max()) >= self.dimA or int(col.max()) >= self.dimB:
             raise ValueError("add: a row / column index lies outside the matrix")
         if not (np.isfinite(val).all() and (val > 0).all()):
-            raise ValueError("add: every value must be finite and > 0 (deletions and decrements are not supported)")
+            raise ValueError("add: every value must be finite and > 0 (counts are taken back with subtract / remove)")
         if len(val) >= 2 ** 32:
             raise ValueError("add: at most 2^32 - 1 triplets per call")
         fresh = C.c_size_t(0)
@@ -1975,13 +1980,94 @@ class Session:
         if rc == 3:
             raise ValueError("add: a row / column index lies outside the matrix")
         if rc == 4:
-            raise ValueError("add: every value must be finite and > 0 (deletions and decrements are not supported)")
+            raise ValueError("add: every value must be finite and > 0 (counts are taken back with subtract / remove)")
         if rc == 5:
             raise ValueError("add: this session cannot be merged into: it holds a shard of the matrix, or a row of its CSR / CSC "
                              "is not strictly ascending (Session.from_coo sessions always qualify)")
         if rc:
             raise MemoryError("poismf_hip_session_add_coo failed (out of memory or a device error)")
         return fresh.value
+
+    def _take_back(self, name, coo, values, missing):
+        """subtract's and remove's checks and call: (row, col[, val]) of coo against the session, then poismf_hip_session_sub_coo"""
+        if missing not in ("raise", "ignore"):
+            raise ValueError(f"{name}: missing must be 'raise' or 'ignore', not {missing!r}")
+        if hasattr(coo, "tocoo"):
+            coo = coo.tocoo()
+        if tuple(coo.shape) != (self.dimA, self.dimB):
+            raise ValueError(f"{name}: the update has shape {tuple(coo.shape)}, the session {(self.dimA, self.dimB)}")
+        row, col = _index_array(coo.row, f"{name}: row indices"), _index_array(coo.col, f"{name}: column indices")
+        val = np.ascontiguousarray(coo.data, dtype=np.float32 if self.use_float else np.float64) if values else None
+        if not (row.ndim == col.ndim == 1 and len(row) == len(col)) or (values and not (val.ndim == 1 and len(val) == len(row))):
+            raise ValueError(f"{name}: row, col{' and data' if values else ''} must be one-dimensional and of one length")
+        if len(row) == 0:
+            return 0
+        if int(row.max()) >= self.dimA or int(col.max()) >= self.dimB:
+            raise ValueError(f"{name}: a row / column index lies outside the matrix")
+        if values and not (np.isfinite(val).all() and (val > 0).all()):
+            raise ValueError(f"{name}: every value must be finite and > 0")
+        if len(row) >= 2 ** 32:
+            raise ValueError(f"{name}: at most 2^32 - 1 triplets per call")
+        removed, absent = C.c_size_t(0), C.c_size_t(0)
+        rc = self.lib.poismf_hip_session_sub_coo(self.h, _ptr(row), _ptr(col), _ptr(val) if values else None, len(row), int(missing == "raise"),
+                                                 C.byref(removed), C.byref(absent))
+        if rc == 3:
+            raise ValueError(f"{name}: a row / column index lies outside the matrix")
+        if rc == 4:
+            raise ValueError(f"{name}: every value must be finite and > 0")
+        if rc == 5:
+            raise ValueError(f"{name}: this session cannot be changed in place: it holds a shard of the matrix, or a row of its CSR / CSC "
+                             "is not strictly ascending (Session.from_coo sessions always qualify)")
+        if rc == 6:
+            raise ValueError(f"{name}: {absent.value} listed cell(s) are not stored in the session (missing='ignore' skips them); nothing was changed")
+        if rc:
+            raise MemoryError("poismf_hip_session_sub_coo failed (out of memory or a device error)")
+        return removed.value
+
+    def subtract(self, coo, missing="raise"):
+        """X -= coo on the resident matrix, both orientations, on the device (include/poismf_hip.h section 2c).  coo: a SciPy sparse matrix
+        (or any object with row / col / data / shape) of the session's shape whose values are finite and > 0; triplets repeated inside it are
+        summed first (in input order, section 1c), a stored cell then gets one rounded subtraction and stays if and only if the difference
+        is > 0: otherwise the cell leaves the matrix (no zero or negative value is ever stored).  A listed cell the session does not store
+        raises ValueError with missing="raise" -- before anything changes -- and is skipped with missing="ignore".  Returns the number of
+        cells removed.  ValueError, before anything changes, also for a wrong shape, an index outside the matrix, a value that is not finite
+        and positive, and a session that cannot be changed in place (add's rule).  The factors are untouched: see retract."""
+        return self._take_back("subtract", coo, True, missing)
+
+    def remove(self, cells, missing="ignore"):
+        """The listed cells leave the resident matrix, whatever they hold (section 2c).  cells: a sparse matrix or any object with row, col
+        and shape; its values are not read, a cell listed twice is removed once.  missing as in subtract.  Returns the number of cells removed."""
+        return self._take_back("remove", cells, False, missing)
+
+    def forget(self, which, rows):
+        """Every stored cell of the listed users (which = 1) or items (which = 0) leaves the resident matrix, in both orientations (section 2c):
+        the rows stay, with length 0, and so do their factor rows.  rows: global, distinct, inside the matrix, any order.  Returns the
+        number of cells removed."""
+        if which not in (0, 1):
+            raise ValueError(f"forget: which must be 0 (items) or 1 (users), not {which!r}")
+        dim = self.dimA if which else self.dimB
+        rows = np.asarray(rows)
+        if rows.ndim != 1:
+            raise ValueError("forget: rows must be one-dimensional")
+        if rows.size and not (np.issubdtype(rows.dtype, np.integer) and rows.dtype != np.bool_):
+            raise ValueError("forget: rows must be integers")
+        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= dim):
+            raise ValueError(f"forget: a row lies outside the matrix's rows [0, {dim})")
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if len(np.unique(rows)) != len(rows):
+            raise ValueError("forget: a row is listed twice")
+        if len(rows) == 0:
+            return 0
+        removed = C.c_size_t(0)
+        rc = self.lib.poismf_hip_session_remove_rows(self.h, int(which), _ptr(rows), len(rows), C.byref(removed))
+        if rc == 3:
+            raise ValueError("forget: rows must be distinct and inside the matrix")
+        if rc == 5:
+            raise ValueError("forget: this session cannot be changed in place: it holds a shard of the matrix, or a row of its CSR / CSC "
+                             "is not strictly ascending (Session.from_coo sessions always qualify)")
+        if rc:
+            raise MemoryError("poismf_hip_session_remove_rows failed (out of memory or a device error)")
+        return removed.value
 
     def matrix(self, which):
         """(values, indices, indptr) of the resident CSR shard (which = 1) or CSC shard (which = 0), downloaded: the layout of the
@@ -2028,6 +2114,24 @@ class Session:
         if hasattr(coo, "tocoo"):
             coo = coo.tocoo()
         self.add(coo)
+        users, items = np.unique(np.asarray(coo.row)).astype(np.int64), np.unique(np.asarray(coo.col)).astype(np.int64)
+        step_size = self.real(step_size)
+        cnst_div = self.cnst_div(params.l2_reg, step_size)
+        self.half_sweep_rows(1, users, params, step_size, cnst_div)
+        self.half_sweep_rows(0, items, params, step_size, cnst_div)
+        return users, items
+
+    def retract(self, coo, params, step_size, remove=False):
+        """Counts taken back from known users: subtract(coo) -- or remove(coo) with remove=True -- then half_sweep_rows(1, users) and
+        half_sweep_rows(0, items) over the sorted distinct rows / columns of coo, both with this step and cnst_div(params.l2_reg, step_size):
+        exactly update's refit.  ONE LOCAL REFIT of the touched rows against the current factors, not the reference's step schedule.
+        Returns (users, items)."""
+        if hasattr(coo, "tocoo"):
+            coo = coo.tocoo()
+        if remove:
+            self.remove(coo)
+        else:
+            self.subtract(coo)
         users, items = np.unique(np.asarray(coo.row)).astype(np.int64), np.unique(np.asarray(coo.col)).astype(np.int64)
         step_size = self.real(step_size)
         cnst_div = self.cnst_div(params.l2_reg, step_size)

@@ -10,59 +10,20 @@
 #include <numeric>
 #include <vector>
 
-#include "session.hpp"
-#include "cores.hpp"
-#include "tb_batch.hpp"
+#include "session_merge.hpp"
 
 namespace {
-
-typedef unsigned long long u64;
 
 // ---- the merge of one orientation -----------------------------------------------------------------------------------------------------
 // D arrives as a CS matrix of the half's shape (dptr [dimM + 1], dmin / dval [u], duplicates summed, rows ascending).  A cell e of D in row
 // r has lb[e], its lower bound among the resident row's indices, and is NEW unless the entry there is its own.  S is the exclusive scan of
 // "new" over D's cells, so S[dptr[r]] new cells precede row r: the new row pointers need no scan over the rows.
 
-// One lane per cell of D: its row (D's row pointers searched), the lower bound in the resident row, new or not.
-__global__ __launch_bounds__(256) void upd_locate_kernel(const u64* dptr, const unsigned* dmin, size_t u, size_t dimM, const u64* indptr,
-                                                         const unsigned* indices, unsigned* rowof, unsigned* lb, unsigned* isnew)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < u; e += (size_t)gridDim.x * blockDim.x) {
-        size_t lo = 0, hi = dimM;   // the last r with dptr[r] <= e (dptr[r + 1] > e: the row is not empty)
-        while (lo < hi) {
-            const size_t mid = lo + (hi - lo + 1) / 2;
-            if (dptr[mid] <= e) lo = mid; else hi = mid - 1;
-        }
-        const u64 p0 = indptr[lo], p1 = indptr[lo + 1];
-        const unsigned c = dmin[e];
-        u64 a = p0, b = p1;
-        while (a < b) {
-            const u64 mid = a + (b - a) / 2;
-            if (indices[mid] < c) a = mid + 1; else b = mid;
-        }
-        rowof[e] = (unsigned)lo;
-        lb[e] = (unsigned)(a - p0);
-        isnew[e] = (a < p1 && indices[a] == c) ? 0u : 1u;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) isnew[u] = 0u;   // (the scan runs over u + 1 values: S[u] is the number of new cells)
-}
-
 // The new cells' lower bounds side by side, in D's order (monotone within a row): what the scatter searches.
 __global__ __launch_bounds__(256) void upd_newlb_kernel(const unsigned* lb, const unsigned* isnew, const unsigned* S, size_t u, unsigned* newlb)
 {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < u; e += (size_t)gridDim.x * blockDim.x)
         if (isnew[e]) newlb[S[e]] = lb[e];
-}
-
-// Per touched row t (ascending): where its resident entries begin and end, and the new cells before it; Sx[nT] = all new cells.
-__global__ __launch_bounds__(256) void upd_touched_kernel(const unsigned* T, size_t nT, const u64* dptr, const unsigned* S, size_t u, const u64* indptr,
-                                                          u64* ta, u64* tb, unsigned* Sx)
-{
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t <= nT; t += (size_t)gridDim.x * blockDim.x) {
-        if (t == nT) { Sx[t] = S[u]; continue; }
-        const unsigned r = T[t];
-        ta[t] = indptr[r]; tb[t] = indptr[r + 1]; Sx[t] = S[dptr[r]];
-    }
 }
 
 __global__ __launch_bounds__(256) void upd_indptr_kernel(const u64* indptr, const u64* dptr, const unsigned* S, size_t dimM, u64* out)
@@ -76,8 +37,6 @@ __global__ __launch_bounds__(256) void upd_indptr_kernel(const u64* indptr, cons
 // by one constant.  An entry p outside every touched row moves by the new cells of the touched rows before it; entry j of touched row t
 // moves by Sx[t] + #{new cells of the row with lb <= j}, a search in the row's slice of newlb.  Loads of a thread's UPD_PER entries are
 // issued together, lanes on consecutive entries; nothing waits for another workgroup.
-constexpr int UPD_PER = 16;
-constexpr int UPD_CHUNK = 256 * UPD_PER;
 template <class T>
 __global__ __launch_bounds__(256) void upd_scatter_kernel(const unsigned* __restrict__ indices, const T* __restrict__ values, size_t nnz,
                                                           const u64* __restrict__ ta, const u64* __restrict__ tb, const unsigned* __restrict__ Sx,
@@ -149,25 +108,6 @@ __global__ __launch_bounds__(256) void upd_place_kernel(const u64* dptr, const u
     }
 }
 
-unsigned grid_for(size_t n, size_t cap = 4096) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, cap)); }
-
-// Everything one orientation's merge allocates; freed by the destructor whichever way the merge ends.
-struct MergeScratch {
-    hipStream_t stream;
-    u64 *dptr = nullptr, *ta = nullptr, *tb = nullptr, *new_indptr = nullptr;
-    unsigned *dmin = nullptr, *rowof = nullptr, *lb = nullptr, *isnew = nullptr, *S = nullptr, *newlb = nullptr, *T = nullptr, *Sx = nullptr;
-    unsigned* new_indices = nullptr;
-    real_t *dval = nullptr, *new_values = nullptr;
-    void* tmp = nullptr;
-    explicit MergeScratch(hipStream_t st) : stream(st) {}
-    ~MergeScratch()
-    {
-        for (void* p : { (void*)dptr, (void*)ta, (void*)tb, (void*)new_indptr, (void*)dmin, (void*)rowof, (void*)lb, (void*)isnew, (void*)S, (void*)newlb,
-                         (void*)T, (void*)Sx, (void*)new_indices, (void*)dval, (void*)new_values, tmp })
-            pmf_free(p, stream);
-    }
-};
-
 // D (n triplets on the device, major / minor as this half sees them; `touched`: its distinct major indices, ascending) merged into half h:
 // new arrays are built beside the resident ones and take their place only when everything has succeeded.  0 or 1; *n_new: cells not stored before.
 int merge_half(poismf_hip_session* s, Half& h, const unsigned* d_major, const unsigned* d_minor, const real_t* d_val, size_t n,
@@ -224,28 +164,6 @@ int merge_half(poismf_hip_session* s, Half& h, const unsigned* d_major, const un
     return 0;
 }
 
-// are the rows of half `which` strictly ascending (found out once, kept with the session)?  1 yes, 0 no, -1 device error
-int rows_ascending(poismf_hip_session* s, int which)
-{
-    const Half& h = s->half[which];
-    std::vector<u64> unused;
-    int* word = which ? &s->csr_rows_sorted : &s->csc_rows_sorted;
-    PmfTopnSeen seen = { h.d_indptr, h.d_indices, h.row_begin, h.row_end, &unused, word };
-    if (poismf_hip_topn_seen_sorted(seen, s->stream)) return -1;
-    return *word;
-}
-
-// the distinct values of ix (all below dim), ascending: marks over the dimension, no sort
-std::vector<unsigned> distinct_sorted(const sparse_ix* ix, size_t n, size_t dim)
-{
-    std::vector<unsigned char> mark(dim, 0);
-    for (size_t i = 0; i < n; i++) mark[(size_t)ix[i]] = 1;
-    std::vector<unsigned> v;
-    for (size_t r = 0; r < dim; r++)
-        if (mark[r]) v.push_back((unsigned)r);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void rows_len_kernel(const u64* indptr, const unsigned* rows, size_t n, unsigned* len)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -265,10 +183,7 @@ int poismf_hip_session_add_coo(poismf_hip_session* s, const sparse_ix* row, cons
         if ((long long)row[i] < 0 || (size_t)row[i] >= s->dimA || (long long)col[i] < 0 || (size_t)col[i] >= s->dimB) return 3;
     for (size_t i = 0; i < n; i++)
         if (!std::isfinite(val[i]) || !(val[i] > (real_t)0)) return 4;
-    for (int which = 0; which < 2; which++) {
-        const Half& h = s->half[which];
-        if (h.d_indptr == nullptr || h.row_begin != 0 || h.row_end != h.dimM || h.dimM != (which ? s->dimA : s->dimB)) return 5;
-    }
+    if (!whole_matrix_halves(s)) return 5;
     pmf_last_hip_error() = hipSuccess;
     HIP_TRY(hipSetDevice(s->device));
     for (int which = 0; which < 2; which++) {
