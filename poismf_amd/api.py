@@ -19,6 +19,13 @@ import numpy as np
 
 from . import build as _build
 from . import harness
+from . import serving
+# the serving calls' argument checks and helpers live in serving.py; every name stays reachable here
+from .serving import (_batch_rc, _csr_list, _diverse_outputs, _eval_lists_args, _eval_ranking_args, _include_of_rows, _include_rows,
+                      _index_array, _inv_norms, _list_eval_args, _list_eval_outputs, _list_eval_scratch, _list_rows, _new_rows_args,
+                      _new_stats, _opt_ptr, _outside_shard, _ptr, _rank_batch_args, _rank_include_list, _shared_table_args,
+                      _similar_args, _similar_scores, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
+                      _topn_include_args, _topn_outputs, _topn_quota_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
 
 _METHOD = {"tncg": 1, "cg": 2, "pg": 3}  # ref: src/poismf.h:225
 _LIBS = {}
@@ -296,10 +303,6 @@ def set_device_cache_mb(mb, use_float=None):
         return {k_: int(lib.poismf_hip_set_device_cache_mb(int(mb))) for k_, lib in list(_LIBS.items())}
     key = "r" if use_float == "r" else bool(use_float)
     return {key: int(load_library(key).poismf_hip_set_device_cache_mb(int(mb)))}
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _check_arrays(use_float, reals, idx):
@@ -600,462 +603,37 @@ def _transform(self, X):
 
 PoisMF.transform = _transform
 
-def _index_array(a, what):
-    """a 1-d index list as C-contiguous uint64; ValueError for a negative or non-integer entry"""
-    a = np.asarray(a)
-    if a.ndim != 1:
-        a = a.reshape(-1)
-    if a.size and a.dtype.kind not in "iu":
-        raise ValueError(f"{what} must be integers")
-    if a.size and a.dtype.kind == "i" and int(a.min()) < 0:
-        raise ValueError(f"{what}: negative index")
-    return np.ascontiguousarray(a, dtype=np.uint64)
+
+class _HostFactors:
+    """Host factors A [dimA x k], B [dimB x k] as the target of a serving call (serving.py): what a Session offers that path, with
+    the factors going up on every call.  They are brought to the model's real_t only once a call needs them."""
+
+    def __init__(self, A, B, dimA, dimB, k, use_float):
+        self.A, self.B, self.dimA, self.dimB, self.k, self.use_float = A, B, int(dimA), int(dimB), int(k), bool(use_float)
+
+    def _factors(self):
+        dt = np.float32 if self.use_float else np.float64
+        self.A, self.B = np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt)
+        return self.A, self.B
+
+    def item_norms(self):
+        """n2[j] = the fused chain of row j of B with itself, predict_multiple's bits (Session.item_norms on host factors)"""
+        B = self._factors()[1]
+        every = np.arange(self.dimB, dtype=np.uint64)
+        n2 = np.empty(self.dimB, B.dtype)
+        _predict_multiple(n2, B, B, every, every)
+        return n2
+
+    def _entry(self, name, exclude_seen):
+        A, B = self._factors()
+        return getattr(load_library(self.use_float), "poismf_hip_" + name), (_ptr(A), _ptr(B), self.k, self.dimA, self.dimB), ()
 
 
-def _csr_list(lst, m, dimB, what, row_max=None, dense_ok=False, keep_zeros=False):
-    """A per-user item list of the batched entry points -- a SciPy sparse matrix with one row per user (its stored columns,
-    duplicates merged; cells stored as zero dropped unless keep_zeros), with dense_ok anything scipy.sparse.csr_matrix() accepts,
-    or an (indptr, indices) pair -- checked as the library checks it: m rows, indices below dimB and strictly ascending within a
-    row.  Returns (indptr, indices) as uint64 arrays starting at 0."""
-    if isinstance(lst, (tuple, list)) and len(lst) == 2 and not hasattr(lst, "tocsr"):
-        indptr, indices = _index_array(lst[0], what + " indptr"), _index_array(lst[1], what + " indices")
-    else:
-        import scipy.sparse as sp
-        if not dense_ok and not sp.issparse(lst):
-            raise ValueError(f"{what} must be a SciPy sparse matrix or an (indptr, indices) pair")
-        csr = sp.csr_matrix(lst)
-        if csr.shape[0] != m:
-            raise ValueError(f"{what} has {csr.shape[0]} rows for {m} users")
-        if csr.shape[1] > dimB:
-            raise ValueError(f"{what} has more columns than there are items")
-        csr.sum_duplicates()
-        if not keep_zeros:
-            csr.eliminate_zeros()
-        csr.sort_indices()
-        indptr, indices = _index_array(csr.indptr, what + " indptr"), _index_array(csr.indices, what + " indices")
-    if len(indptr) != m + 1:
-        raise ValueError(f"{what} has {max(len(indptr) - 1, 0)} rows for {m} users")
-    if np.any(indptr[1:] < indptr[:-1]) or int(indptr[-1]) > len(indices):
-        raise ValueError(f"{what}: row pointers must not decrease and must stay inside the index list")
-    lo, hi = int(indptr[0]), int(indptr[-1])
-    seg = indices[lo:hi]
-    if len(seg) and int(seg.max()) >= dimB:
-        raise ValueError(f"an item index of {what} is out of range")
-    if len(seg) > 1:
-        bad = seg[1:] <= seg[:-1]
-        starts = indptr[1:-1].astype(np.int64) - lo - 1          # position (in bad) of each later row's first entry
-        starts = starts[(starts >= 0) & (starts < len(bad))]
-        bad[starts] = False
-        if np.any(bad):
-            raise ValueError(f"{what}: the item indices of a row must be strictly ascending")
-    if row_max is not None and m and int((indptr[1:] - indptr[:-1]).max()) > row_max:
-        raise ValueError(f"{what}: a row is longer than {row_max}")
-    return np.ascontiguousarray(indptr - indptr[0]), np.ascontiguousarray(seg)
-
-
-def _topn_batch_args(users, n, exclude, dimA, dimB):
-    """The argument checks of the batched top-N (include/poismf_hip.h section 1f) that need no device, as the library itself
-    makes them; returns (users, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if n > dimB:
-        raise ValueError("n is larger than the number of items")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if exclude is None:
-        return users, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    if m and int((indptr[1:] - indptr[:-1]).max()) > dimB - n:
-        raise ValueError("n is larger than the number of items a user has left after exclusion")
-    return users, indptr, indices
-
-
-def _new_rows_args(X_new, dimB, use_float):
-    """The rows of users the model has never seen, as the fold-in calls take them (include/poismf_hip.h section 1m), checked without
-    a device as the library itself checks them: a SciPy sparse matrix with one row per new user and the model's number of columns,
-    coerced as transform() coerces it (CSR, duplicates summed, indices sorted).  Returns (data real_t, indptr, indices) with uint64
-    index arrays."""
-    import scipy.sparse as sp
-    if not sp.issparse(X_new):
-        raise ValueError("the new rows must be a SciPy sparse matrix with one row per new user")
-    if X_new.shape[1] != dimB:
-        raise ValueError(f"the new rows have {X_new.shape[1]} columns, the model {dimB} items")
-    csr = sp.csr_matrix(X_new)
-    if len(csr.indptr) != csr.shape[0] + 1 or np.any(np.diff(csr.indptr) < 0) or int(csr.indptr[-1]) > len(csr.indices):
-        raise ValueError("the new rows: row pointers must not decrease and must stay inside the index list")
-    if len(csr.indices) and (int(csr.indices.min()) < 0 or int(csr.indices.max()) >= dimB):
-        raise ValueError("an item index of the new rows is out of range")
-    csr.sum_duplicates(); csr.sort_indices()
-    dt = np.float32 if use_float else np.float64
-    return (np.ascontiguousarray(csr.data, dtype=dt), np.ascontiguousarray(csr.indptr, dtype=np.uint64),
-            np.ascontiguousarray(csr.indices, dtype=np.uint64))
-
-
-def _new_stats(Bsum, Amean, k, use_float):
-    """Bsum (with l1 already added) and Amean of the fold-in calls as C-contiguous real_t k-vectors"""
-    dt = np.float32 if use_float else np.float64
-    Bsum, Amean = np.ascontiguousarray(Bsum, dtype=dt).reshape(-1), np.ascontiguousarray(Amean, dtype=dt).reshape(-1)
-    if len(Bsum) != k or len(Amean) != k:
-        raise ValueError(f"Bsum and Amean must have k = {k} entries")
-    return Bsum, Amean
-
-
-def _topn_deep_args(users, n, exclude, dimA, dimB):
-    """The argument checks of the deep batched top-N (include/poismf_hip.h section 1l) that need no device, as the library itself
-    makes them: n up to TOPN_DEEP_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).  Returns (users,
-    excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_DEEP_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the deep batched limit of {TOPN_DEEP_MAX_N_TOP}")
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if exclude is None:
-        return users, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, indptr, indices
-
-
-def _topn_quota_args(users, n, group_of, quota, exclude, dimA, dimB):
-    """The argument checks of the batched top-N with per-group quotas (include/poismf_hip.h section 1n) that need no device, as the
-    library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).
-    group_of: an integer array with one group id per item.  quota: one int for every group, or an array with one entry per group
-    (its length is then the number of groups and must cover every id).  Returns (users, group_of, quota, excl_indptr or None,
-    excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if dimB > TOPN_QUOTA_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the quota call's limit of {TOPN_QUOTA_MAX_ITEMS}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if group_of is None:
-        raise ValueError("group_of is required: one group id per item")
-    group_of = _index_array(group_of, "group_of")
-    if len(group_of) != dimB:
-        raise ValueError(f"group_of has {len(group_of)} entries for {dimB} items")
-    need = int(group_of.max()) + 1
-    if quota is None:
-        raise ValueError("quota is required: one int for every group, or one entry per group")
-    if np.ndim(quota) == 0:
-        if isinstance(quota, (bool, np.bool_)) or not isinstance(quota, (int, np.integer)):
-            raise ValueError("quota must be integers")
-        if int(quota) < 0:
-            raise ValueError("quota: negative entry")
-        quota = np.full(need, min(int(quota), 2**63), np.uint64)
-    else:
-        quota = _index_array(quota, "quota")
-        if len(quota) < need:
-            raise ValueError(f"quota has {len(quota)} entries, group_of names group {need - 1}")
-    if len(quota) > 2**31 - 1:
-        raise ValueError("there are more groups than the quota call supports (2^31 - 1)")
-    if exclude is None:
-        return users, group_of, quota, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, group_of, quota, indptr, indices
-
-
-def _topn_adjusted_args(users, n, adjust, exclude, dimA, dimB, dtype=np.float64):
-    """The argument checks of the batched top-N with per-(user, item) score factors (include/poismf_hip.h section 1r) that need no
-    device, as the library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are
-    padded).  adjust: None (no cell listed), a SciPy sparse matrix with one row per user of the batch whose stored values are the
-    factors -- stored zeros are KEPT: a factor of 0 is a factor -- or an (indptr, indices, factors) triple; a row's indices strictly
-    ascending (a sparse matrix is sorted first) and at most TOPN_ADJUSTED_MAX_ROW of them.  The factors are converted to `dtype`,
-    the model's real_t, and must be finite and non-negative AFTER that conversion (a double above float32's range is refused for a
-    float32 model).  Returns (users, adj_indptr, adj_indices, adj_factor, excl_indptr or None, excl_indices or None): uint64 arrays
-    and the factors in `dtype`."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if dimB > TOPN_ADJUSTED_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the adjusted call's limit of {TOPN_ADJUSTED_MAX_ITEMS}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if adjust is None:
-        pair, f = (np.zeros(m + 1, np.uint64), np.zeros(0, np.uint64)), np.zeros(0, dtype)
-    elif isinstance(adjust, (tuple, list)) and not hasattr(adjust, "tocsr"):
-        if len(adjust) != 3:
-            raise ValueError("adjust must be a SciPy sparse matrix or an (indptr, indices, factors) triple")
-        pair, f = (adjust[0], adjust[1]), np.asarray(adjust[2])
-    else:
-        import scipy.sparse as sp
-        if not sp.issparse(adjust):
-            raise ValueError("adjust must be a SciPy sparse matrix or an (indptr, indices, factors) triple")
-        csr = sp.csr_matrix(adjust)
-        if csr.shape[0] != m:
-            raise ValueError(f"adjust has {csr.shape[0]} rows for {m} users")
-        if csr.shape[1] > dimB:
-            raise ValueError("adjust has more columns than there are items")
-        if not csr.has_sorted_indices:
-            csr = csr.copy()
-            csr.sort_indices()          # (stored zeros stay; a cell stored twice fails the ascending check below)
-        pair, f = (csr.indptr, csr.indices), csr.data
-    if f.ndim != 1 or (f.size and f.dtype.kind not in "fiu"):
-        raise ValueError("adjust: the factors must be a 1-d array of real numbers")
-    a_indptr, a_indices = _csr_list(pair, m, dimB, "adjust", row_max=TOPN_ADJUSTED_MAX_ROW)   # (from 0; the factors follow below)
-    lo = int(np.asarray(pair[0]).reshape(-1)[0])
-    hi = lo + int(a_indptr[-1])
-    if len(f) < hi:
-        raise ValueError("adjust: there are fewer factors than item indices")
-    with np.errstate(over="ignore"):
-        f = np.ascontiguousarray(f[lo:hi], dtype=dtype)
-    if np.isnan(f).any():
-        raise ValueError("adjust: NaN factor")
-    if np.isinf(f).any():
-        raise ValueError("adjust: a factor is infinite in the model's precision")
-    if (f < 0).any():
-        raise ValueError("adjust: negative factor (a factor of 0 keeps a cell at score 0; exclude= bars one)")
-    if exclude is None:
-        return users, a_indptr, a_indices, f, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, a_indptr, a_indices, f, indptr, indices
-
-
-def _topn_weighted_args(users, n, item_weight, exclude, dimA, dimB, dtype=np.float64):
-    """The argument checks of the batched top-N with per-item score weights (include/poismf_hip.h section 1o) that need no device, as
-    the library itself makes them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded).
-    item_weight: a 1-d array with one weight per item, or one number for all; converted to `dtype`, the model's real_t, and finite
-    and non-negative AFTER that conversion (a double above float32's range is refused for a float32 model).  Returns (users,
-    item_weight, excl_indptr or None, excl_indices or None): uint64 arrays around the weights in `dtype`."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if dimB > TOPN_WEIGHTED_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the weighted call's limit of {TOPN_WEIGHTED_MAX_ITEMS}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if item_weight is None:
-        raise ValueError("item_weight is required: one weight per item, or one number for all")
-    w = np.asarray(item_weight)
-    if w.dtype.kind not in "fiu":
-        raise ValueError("item_weight must be real numbers")
-    if w.ndim == 0:
-        w = np.full(dimB, w)
-    elif w.ndim != 1:
-        raise ValueError("item_weight must be a 1-d array with one weight per item, or one number")
-    if len(w) != dimB:
-        raise ValueError(f"item_weight has {len(w)} entries for {dimB} items")
-    with np.errstate(over="ignore"):
-        w = np.ascontiguousarray(w, dtype=dtype)
-    if np.isnan(w).any():
-        raise ValueError("item_weight: NaN entry")
-    if np.isinf(w).any():
-        raise ValueError("item_weight: an entry is infinite in the model's precision")
-    if (w < 0).any():
-        raise ValueError("item_weight: negative entry (a weight of 0 keeps an item at score 0; exclude= bars one)")
-    if exclude is None:
-        return users, w, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, w, indptr, indices
-
-
-def _inv_norms(n2, dimB, dtype):
-    """similar_items: inv[j] = real_t(1) / sqrt(n2[j]) in real_t, 0 where n2[j] == 0; n2[j] is the fused chain of B[j] with itself"""
-    n2 = np.ascontiguousarray(n2, dtype=dtype).reshape(-1)
-    if len(n2) != dimB:
-        raise ValueError(f"item_norm has {len(n2)} entries for {dimB} items")
-    if not np.isfinite(n2).all() or (n2 < 0).any():
-        raise ValueError("item_norm must be finite and non-negative: the squared norms of the rows of B")
-    inv = np.zeros(dimB, dtype)
-    np.divide(dtype(1), np.sqrt(n2), out=inv, where=n2 != 0)
-    return inv
-
-
-def _topn_diverse_args(users, n, pool, lam, inv_norm, exclude, dimA, dimB, dtype=np.float64):
-    """The argument checks of the diversified batched top-N (include/poismf_hip.h section 1p) that need no device, as the library
-    itself makes them: n in 1 .. TOPN_BATCH_MAX_N_TOP, pool in n .. TOPN_DEEP_MAX_N_TOP (either may exceed what a user has left: short
-    rows are padded), lam in [0, 1], and inv_norm -- _inv_norms' array, one entry per item -- finite and non-negative in `dtype`, the
-    model's real_t.  Returns (users, inv_norm, excl_indptr or None, excl_indices or None): uint64 arrays around the norms in `dtype`."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n, pool = int(n), int(pool)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if pool < n:
-        raise ValueError(f"pool = {pool} is below n = {n}: the picks are made among the pool")
-    if pool > TOPN_DEEP_MAX_N_TOP:
-        raise ValueError(f"pool = {pool} is above the deep batched limit of {TOPN_DEEP_MAX_N_TOP}")
-    if isinstance(lam, (bool, np.bool_)) or not isinstance(lam, (int, float, np.integer, np.floating)):
-        raise ValueError("lam must be a real number in [0, 1]")
-    if not 0.0 <= float(lam) <= 1.0:   # (NaN fails both)
-        raise ValueError(f"lam = {lam} is outside [0, 1]")
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if dimB > TOPN_DIVERSE_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the diversified call's limit of {TOPN_DIVERSE_MAX_ITEMS}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if inv_norm is None:
-        raise ValueError("the items' inverse norms are required: one per item")
-    inv = np.asarray(inv_norm)
-    if inv.dtype.kind not in "fiu" or inv.ndim != 1:
-        raise ValueError("the items' inverse norms must be a 1-d array of real numbers")
-    if len(inv) != dimB:
-        raise ValueError(f"there are {len(inv)} inverse norms for {dimB} items")
-    with np.errstate(over="ignore"):
-        inv = np.ascontiguousarray(inv, dtype=dtype)
-    if np.isnan(inv).any():
-        raise ValueError("inverse norm: NaN entry")
-    if np.isinf(inv).any():
-        raise ValueError("inverse norm: an entry is infinite in the model's precision")
-    if (inv < 0).any():
-        raise ValueError("inverse norm: negative entry")
-    if exclude is None:
-        return users, inv, None, None
-    indptr, indices = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, inv, indptr, indices
-
-
-def _diverse_outputs(m, n, dt, output_score, output_value):
-    """the three output arrays of the diversified calls: items, relevances and values, the latter two empty unless asked for"""
-    return (np.empty((m, n), np.uint64), np.empty((m, n) if output_score else (0, n), dt), np.empty((m, n) if output_value else (0, n), dt))
-
-
-def _similar_args(items, n, exclude_self, dimB):
-    """similar_items: the query items as uint64 and the exclusion lists that leave each query itself out (or None); n, the items and
-    the number of items are checked here, before any norm is computed"""
-    items = _index_array(items, "items")
-    if int(n) <= 0:
-        raise ValueError("n must be positive")
-    if int(n) > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {int(n)} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if dimB > TOPN_WEIGHTED_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the weighted call's limit of {TOPN_WEIGHTED_MAX_ITEMS}")
-    if len(items) and int(items.max()) >= dimB:
-        raise ValueError("an item index is out of range")
-    if not exclude_self:
-        return items, None
-    return items, (np.arange(len(items) + 1, dtype=np.uint64), items.copy())
-
-
-def _similar_scores(sc, inv, items):
-    """similar_items: wscore * inv[query] in real_t, a second rounded multiplication; padded entries stay -inf"""
-    if sc.size:
-        q = inv[items.astype(np.int64)][:, None]
-        np.multiply(sc, q, out=sc, where=np.isfinite(sc))
-    return sc
-
-
-def _topn_include_args(users, n, include, exclude, dimA, dimB):
-    """The argument checks of the batched top-N over include lists (include/poismf_hip.h section 1h) that need no device, as the
-    library itself makes them: n may exceed what a user has left (short rows are padded).  Returns (users, incl_indptr,
-    incl_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    ip, ii = _csr_list(include, m, dimB, "include", TOPN_INCLUDE_MAX_ROW, keep_zeros=True)
-    if exclude is None:
-        return users, ip, ii, None, None
-    ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, ip, ii, ep, ei
-
-
-def _shared_table_args(include, include_of, m, dimB):
-    """A table of lists shared between users and every user's row of it (include/poismf_hip.h sections 1i and 1k), checked without a
-    device as the library itself checks them: `include` is the table (any number of rows G >= 1), include_of an integer array with
-    one entry per user, or one int for all.  Returns (list_indptr, list_indices, list_of) as uint64 arrays."""
-    if include is None:
-        raise ValueError("include_of needs include, the table of lists it refers to")
-    if isinstance(include, (tuple, list)) and len(include) == 2 and not hasattr(include, "tocsr"):
-        G = max(len(np.asarray(include[0]).reshape(-1)) - 1, 0)
-    elif hasattr(include, "shape") and len(include.shape) == 2:
-        G = int(include.shape[0])
-    else:
-        raise ValueError("include must be a SciPy sparse matrix or an (indptr, indices) pair")
-    if G < 1:
-        raise ValueError("include: the table of lists has no rows")
-    lp, li = _csr_list(include, G, dimB, "include", keep_zeros=True)
-    if len(li) > TOPN_SHARED_MAX_CELLS:
-        raise ValueError(f"include: the table of lists holds more than {TOPN_SHARED_MAX_CELLS} indices")
-    if isinstance(include_of, (bool, np.bool_)):
-        raise ValueError("include_of must be integers")
-    if isinstance(include_of, (int, np.integer)):
-        if include_of < 0:
-            raise ValueError("include_of: negative index")
-        lof = np.full(m, int(include_of), np.uint64)
-    else:
-        if np.ndim(include_of) != 1:
-            raise ValueError("include_of must be a 1-d array with one entry per user, or one int")
-        lof = _index_array(include_of, "include_of")
-    if len(lof) != m:
-        raise ValueError(f"include_of has {len(lof)} entries for {m} users")
-    if m and int(lof.max()) >= G:
-        raise ValueError(f"an entry of include_of is not a row of include ({G} lists)")
-    return lp, li, lof
-
-
-def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
-    """The argument checks of the batched top-N over lists shared between users (include/poismf_hip.h section 1i) that need no
-    device, as the library itself makes them: `include` is the table of lists (any number of rows G >= 1), include_of names every
-    user's row of it (an integer array with one entry per user, or one int for all).  Returns (users, list_indptr, list_indices,
-    list_of, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    n = int(n)
-    if n <= 0:
-        raise ValueError("n must be positive")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"n = {n} is above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    lp, li, lof = _shared_table_args(include, include_of, m, dimB)
-    if exclude is None:
-        return users, lp, li, lof, None, None
-    ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-    return users, lp, li, lof, ep, ei
-
-
-def _opt_ptr(a):
-    return _ptr(a) if a is not None and len(a) else None
-
-
-def _batch_rc(rc, what):
-    if rc == 2:
-        raise ValueError(f"invalid arguments for the batched {what} (an index out of range, an unsorted or overlong row, or too few items left)")
-    if rc:
-        raise MemoryError(f"batched {what} failed (no usable HIP device or out of memory)")
-
-
-def _outside_shard(users, shardA):
-    """exclude_seen of a session's batched calls: its CSR holds the rows shardA of A only"""
-    if len(users) and (int(users.min()) < shardA[0] or int(users.max()) >= shardA[1]):
-        raise ValueError("exclude_seen: a user lies outside this session's rows of A")
+def _host(self):
+    """a fitted model's factors as a serving target"""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    return _HostFactors(self.A, self.B, self.nusers, self.nitems, self.k, self.use_float)
 
 
 def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=None, include_of=None):
@@ -1071,37 +649,7 @@ def _topN_batch(self, users, n=10, exclude=None, output_score=False, include=Non
     user's row of it: an integer array with one entry per user, or one int for all (section 1i).  The answers are those of
     include= with every user's list written out, bit for bit; the table is read once, and users of one list share the rows of B
     they read.  Few lists for many users belong here, a list per user belongs in include= alone."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    if include_of is not None:
-        users, lp, li, lof, indptr, indices = _topn_shared_args(users, n, include, include_of, exclude, self.nusers, self.nitems)
-    elif include is not None:
-        users, ip, ii, indptr, indices = _topn_include_args(users, n, include, exclude, self.nusers, self.nitems)
-    else:
-        users, indptr, indices = _topn_batch_args(users, n, exclude, self.nusers, self.nitems)
-    dt = np.float32 if self.use_float else np.float64
-    m, n = len(users), int(n)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
-    if m == 0:
-        return ix, sc
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    lib = load_library(self.use_float)
-    if include_of is not None:
-        _batch_rc(lib.poismf_hip_topn_shared(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(lp), _opt_ptr(li),
-                                             len(lp) - 1, _ptr(lof), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                             _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
-    if include is not None:
-        _batch_rc(lib.poismf_hip_topn_include(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii),
-                                              _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                              _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
-    _batch_rc(lib.poismf_hip_topn_batch(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
-                                        _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-    return ix, sc
+    return serving.topn_batch(_host(self), users, n, False, exclude, output_score, include, include_of)
 
 
 PoisMF.topN_batch = _topN_batch
@@ -1113,22 +661,7 @@ def _topN_deep(self, users, n=1000, exclude=None, output_score=False):
     exclude as in topN_batch.  n may exceed what a user has left, or the number of items: the row is padded with TOPN_NONE and
     -inf.  Up to n = TOPN_BATCH_MAX_N_TOP the answers are topN_batch's bit for bit, which keeps its lists on chip and is the faster
     of the two there.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    users, indptr, indices = _topn_deep_args(users, n, exclude, self.nusers, self.nitems)
-    dt = np.float32 if self.use_float else np.float64
-    m, n = len(users), int(n)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
-    if m == 0:
-        return ix, sc
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    lib = load_library(self.use_float)
-    _batch_rc(lib.poismf_hip_topn_deep(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n,
-                                       _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                       _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-    return ix, sc
+    return serving.topn_deep(_host(self), users, n, False, exclude, output_score)
 
 
 PoisMF.topN_deep = _topN_deep
@@ -1141,39 +674,10 @@ def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_
     (include/poismf_hip.h section 1n).  group_of: one group id per item.  quota: one int for every group, or an array with one
     entry per group; 0 bars a group, n or more leaves it unconstrained.  A user for whom the quotas admit fewer than n items gets a
     row padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    users, group_of, quota, indptr, indices = _topn_quota_args(users, n, group_of, quota, exclude, self.nusers, self.nitems)
-    dt = np.float32 if self.use_float else np.float64
-    m, n = len(users), int(n)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
-    if m == 0:
-        return ix, sc
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    lib = load_library(self.use_float)
-    _batch_rc(lib.poismf_hip_topn_quota(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, _ptr(group_of), len(quota),
-                                        _ptr(quota), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-    return ix, sc
+    return serving.topn_quota(_host(self), users, n, group_of, quota, False, exclude, output_score)
 
 
 PoisMF.topN_quota = _topN_quota
-
-
-def _weighted_host_call(use_float, Q, B, k, users, n, w, indptr, indices, output_score):
-    """poismf_hip_topn_weighted on host arrays: the rows `users` of Q ranked against all of B"""
-    m = len(users)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), np.float32 if use_float else np.float64)
-    if m == 0:
-        return ix, sc
-    lib = load_library(use_float)
-    _batch_rc(lib.poismf_hip_topn_weighted(_ptr(Q), _ptr(B), k, Q.shape[0], B.shape[0], _ptr(users), m, n, _ptr(w),
-                                           _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                           _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-    return ix, sc
 
 
 def _topN_weighted(self, users, n=10, item_weight=None, exclude=None, output_score=False):
@@ -1184,13 +688,7 @@ def _topN_weighted(self, users, n=10, item_weight=None, exclude=None, output_sco
     of 0 does not bar an item -- it scores 0 and ties with its like by index; exclude= bars one.  The scores returned are the
     weighted ones: predict's, times the weight, rounded once.  n may exceed what a user has left: the row is padded with TOPN_NONE
     and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    dt = np.float32 if self.use_float else np.float64
-    users, w, indptr, indices = _topn_weighted_args(users, n, item_weight, exclude, self.nusers, self.nitems, dt)
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    return _weighted_host_call(self.use_float, A, B, self.k, users, int(n), w, indptr, indices, output_score)
+    return serving.topn_weighted(_host(self), users, n, item_weight, False, exclude, output_score)
 
 
 PoisMF.topN_weighted = _topN_weighted
@@ -1205,22 +703,7 @@ def _topN_adjusted(self, users, n=10, adjust=None, exclude=None, output_score=Fa
     predict's score times its factor, rounded once; every other cell predict's score.  A factor of 0 does not bar a cell -- it
     scores 0 and ties with its like by index; a cell both listed and excluded is excluded.  n may exceed what a user has left: the
     row is padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n], scores [m x n], empty unless output_score)."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    dt = np.float32 if self.use_float else np.float64
-    users, a_indptr, a_indices, f, indptr, indices = _topn_adjusted_args(users, n, adjust, exclude, self.nusers, self.nitems, dt)
-    m, n = len(users), int(n)
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
-    if m == 0:
-        return ix, sc
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    lib = load_library(self.use_float)
-    _batch_rc(lib.poismf_hip_topn_adjusted(_ptr(A), _ptr(B), self.k, A.shape[0], B.shape[0], _ptr(users), m, n, _ptr(a_indptr),
-                                           _opt_ptr(a_indices), _opt_ptr(f), _ptr(indptr) if indptr is not None else None,
-                                           _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-    return ix, sc
+    return serving.topn_adjusted(_host(self), users, n, adjust, False, exclude, output_score)
 
 
 PoisMF.topN_adjusted = _topN_adjusted
@@ -1237,17 +720,8 @@ def _similar_items(self, items, n=10, output_score=False, exclude_self=True, ite
     uint64 [m x n], similarities [m x n], empty unless output_score); a row is padded with TOPN_NONE and -inf past the last item."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
-    dt = np.float32 if self.use_float else np.float64
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    items, excl = _similar_args(items, n, exclude_self, self.nitems)
-    if item_norm is None:
-        every = np.arange(self.nitems, dtype=np.uint64)
-        item_norm = np.empty(self.nitems, dt)
-        _predict_multiple(item_norm, B, B, every, every)
-    inv = _inv_norms(item_norm, self.nitems, dt)
-    items, w, indptr, indices = _topn_weighted_args(items, n, inv, excl, self.nitems, self.nitems, dt)
-    ix, sc = _weighted_host_call(self.use_float, B, B, self.k, items, int(n), w, indptr, indices, output_score)
-    return ix, _similar_scores(sc, inv, items)
+    rows_of_B = _HostFactors(self.B, self.B, self.nitems, self.nitems, self.k, self.use_float)   # (the queries and the corpus)
+    return serving.similar_items(rows_of_B, items, n, output_score, exclude_self, item_norm)
 
 
 PoisMF.similar_items = _similar_items
@@ -1262,28 +736,7 @@ def _topN_diverse(self, users, n=10, pool=100, lam=0.7, exclude=None, output_sco
     beyond the pool.  item_norm= takes the squared norms precomputed (Session.item_norms()), as similar_items does.  A row the pool
     leaves short is padded with TOPN_NONE and -inf.  Returns (items uint64 [m x n] in pick order, their scores [m x n] -- predict's,
     empty unless output_score --, the value each was picked at [m x n], empty unless output_value)."""
-    if not self.is_fitted:
-        raise ValueError("Model has not been fitted.")
-    dt = np.float32 if self.use_float else np.float64
-    B = np.ascontiguousarray(self.B, dtype=dt)
-    # (everything else is judged before the norms are computed: zeros stand in for them)
-    inv = np.zeros(self.nitems, dt) if item_norm is None else _inv_norms(item_norm, self.nitems, dt)
-    users, inv, indptr, indices = _topn_diverse_args(users, n, pool, lam, inv, exclude, self.nusers, self.nitems, dt)
-    m, n = len(users), int(n)
-    ix, sc, val = _diverse_outputs(m, n, dt, output_score, output_value)
-    if m == 0:
-        return ix, sc, val
-    if item_norm is None:
-        every = np.arange(self.nitems, dtype=np.uint64)
-        item_norm = np.empty(self.nitems, dt)
-        _predict_multiple(item_norm, B, B, every, every)
-        inv = _inv_norms(item_norm, self.nitems, dt)
-    A = np.ascontiguousarray(self.A, dtype=dt)
-    lib = load_library(self.use_float)
-    _batch_rc(lib.poismf_hip_topn_diverse(_ptr(A), _ptr(B), self.k, self.nusers, self.nitems, _ptr(users), m, n, int(pool), float(lam),
-                                          _ptr(inv), _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                          _ptr(ix), _ptr(sc) if output_score else None, _ptr(val) if output_value else None), "top-N")
-    return ix, sc, val
+    return serving.topn_diverse(_host(self), users, n, pool, lam, False, exclude, output_score, output_value, item_norm)
 
 
 PoisMF.topN_diverse = _topN_diverse
@@ -1302,8 +755,7 @@ def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False)
     m, n = len(indptr) - 1, int(n)
     _, ep, ei = _topn_batch_args(np.arange(m, dtype=np.uint64), n, exclude, max(m, 1), self.nitems)
     dt = np.float32 if self.use_float else np.float64
-    ix = np.empty((m, n), np.uint64)
-    sc = np.empty((m, n) if output_score else (0, n), dt)
+    ix, sc = _topn_outputs(m, n, dt, output_score)
     if m == 0:
         return ix, sc
     B = np.ascontiguousarray(self.B, dtype=dt)
@@ -1311,36 +763,11 @@ def _topN_new(self, X, n=10, exclude=None, exclude_own=True, output_score=False)
     _batch_rc(load_library(self.use_float).poismf_hip_topn_new(
         _ptr(B), _ptr(Bsum), _ptr(Amean), _opt_ptr(data), _ptr(indptr), _opt_ptr(indices), self.k, self.nitems, m, self.l2_reg_,
         self.weight_mult, self.initial_step, int(self.niter_), int(self.maxupd_), _METHOD[self.method], bool(self.limit_step),
-        bool(self.reuse_prev), n, int(bool(exclude_own)), _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ix),
-        _ptr(sc) if output_score else None, None), "top-N of new rows")
+        bool(self.reuse_prev), n, int(bool(exclude_own)), _opt_ptr(ep), _opt_ptr(ei), _ptr(ix), _opt_ptr(sc), None), "top-N of new rows")
     return ix, sc
 
 
 PoisMF.topN_new = _topN_new
-
-
-def _rank_include_list(include, m, dimB):
-    """The include lists of the batched ranks (include/poismf_hip.h section 1j), checked as the library checks them: (incl_indptr,
-    incl_indices) as uint64 arrays"""
-    return _csr_list(include, m, dimB, "include", TOPN_INCLUDE_MAX_ROW, keep_zeros=True)
-
-
-def _rank_batch_args(users, test, exclude, dimA, dimB, k):
-    """The argument checks of the batched ranks (include/poismf_hip.h sections 1g and 1j) that need no device, as the library itself
-    makes them; returns (users, test_indptr, test_indices, excl_indptr or None, excl_indices or None) as uint64 arrays."""
-    users = _index_array(users, "users")
-    m = len(users)
-    if m and int(users.max()) >= dimA:
-        raise ValueError("a user index is out of range")
-    if not 1 <= int(k) <= 512:
-        raise ValueError("the number of factors is outside what the batched entry points support")
-    if test is None:
-        raise ValueError("the held-out list is missing")
-    tp, ti = _csr_list(test, m, dimB, "test", RANK_BATCH_MAX_ROW)
-    if exclude is None:
-        return users, tp, ti, None, None
-    ep, ei = _csr_list(exclude, m, dimB, "exclude", (RANK_BATCH_BUDGET_MB << 20) // 8)
-    return users, tp, ti, ep, ei
 
 
 def rank_batch(A, B, users, test, exclude=None, include=None, include_of=None, unite_test=False):
@@ -1359,108 +786,8 @@ def rank_batch(A, B, users, test, exclude=None, include=None, include_of=None, u
     A, B = np.asarray(A), np.asarray(B)
     if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
         raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
-    use_float = A.dtype == np.float32
-    users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, A.shape[0], B.shape[0], A.shape[1])
-    m = len(users)
-    if include_of is not None:
-        lp, li, lof = _shared_table_args(include, include_of, m, B.shape[0])
-    elif unite_test:
-        raise ValueError("unite_test needs include_of: a list per user has its held-out row united in by the caller")
-    elif include is not None:
-        ip, ii = _rank_include_list(include, m, B.shape[0])
-    ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
-    if m == 0:
-        return ranks, n_adm
-    A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
-    lib = load_library(use_float)
-    if include_of is not None:
-        _batch_rc(lib.poismf_hip_rank_shared(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
-                                             _ptr(lp), _opt_ptr(li), len(lp) - 1, _ptr(lof), int(bool(unite_test)),
-                                             _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
-        return ranks, n_adm
-    if include is not None:
-        _batch_rc(lib.poismf_hip_rank_include(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
-                                              _ptr(ip), _opt_ptr(ii), _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks),
-                                              _ptr(n_adm)), "ranks")
-        return ranks, n_adm
-    _batch_rc(lib.poismf_hip_rank_batch(_ptr(A), _ptr(B), A.shape[1], A.shape[0], B.shape[0], _ptr(users), m, _ptr(tp), _opt_ptr(ti),
-                                        _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
-    return ranks, n_adm
-
-
-def _eval_ranking_args(X_test, exclude, users, k, dimA, dimB):
-    """eval_ranking's inputs, given for the whole matrix, cut down to the batch: (users, the (indptr, indices) of their held-out rows,
-    their exclude rows or None, k)"""
-    import scipy.sparse as sp
-    k = int(k)
-    if k < 1:
-        raise ValueError("k must be at least 1")
-    if not sp.issparse(X_test):
-        raise ValueError("X_test must be a SciPy sparse matrix")
-    if X_test.shape != (dimA, dimB):
-        raise ValueError(f"X_test has shape {X_test.shape}, the model {(dimA, dimB)}")
-    csr = sp.csr_matrix(X_test)
-    csr.sum_duplicates()
-    csr.eliminate_zeros()
-    if users is None:
-        users = np.flatnonzero(np.diff(csr.indptr)).astype(np.uint64)
-    else:
-        users = _index_array(users, "users")
-        if len(users) and int(users.max()) >= dimA:
-            raise ValueError("a user index is out of range")
-    rows = users.astype(np.int64)
-    if exclude is not None and sp.issparse(exclude):
-        if exclude.shape != (dimA, dimB):
-            raise ValueError(f"exclude has shape {exclude.shape}, the model {(dimA, dimB)}")
-        exclude = sp.csr_matrix(exclude)[rows]
-    test = csr[rows]
-    test.sort_indices()
-    return users, (np.asarray(test.indptr, np.uint64), np.asarray(test.indices, np.uint64)), exclude, k
-
-
-def _include_rows(include, users, dimA, dimB):
-    """eval_ranking's include=, given either for the whole matrix (a sparse matrix of the model's shape, whose rows for `users` are
-    taken) or for the batch (an (indptr, indices) pair with one row per user): the batch's (indptr, indices), checked"""
-    import scipy.sparse as sp
-    if sp.issparse(include):
-        if include.shape != (dimA, dimB):
-            raise ValueError(f"include has shape {include.shape}, the model {(dimA, dimB)}")
-        include = sp.csr_matrix(include)[users.astype(np.int64)]
-    return _rank_include_list(include, len(users), dimB)
-
-
-def _include_of_rows(include_of, users, dimA):
-    """eval_ranking's include_of=, given for the whole model (one int, or an integer array with one entry per user of the model,
-    indexed by user id): what rank_batch takes -- the int itself, or the entries of `users`"""
-    if isinstance(include_of, (bool, np.bool_)):
-        raise ValueError("include_of must be integers")
-    if isinstance(include_of, (int, np.integer)):
-        return include_of
-    if np.ndim(include_of) != 1:
-        raise ValueError("include_of must be a 1-d array with one entry per user of the model, or one int")
-    lof = _index_array(include_of, "include_of")
-    if len(lof) != dimA:
-        raise ValueError(f"include_of has {len(lof)} entries, the model {dimA} users")
-    return lof[users.astype(np.int64)]
-
-
-def _unite_rows(a, b):
-    """Row by row, the union of two CSR-shaped lists with strictly ascending rows and the same number of rows: (indptr, indices) as
-    uint64 arrays, rows strictly ascending.  No device is involved."""
-    ap, ai = np.asarray(a[0], np.int64), np.asarray(a[1], np.int64)
-    bp, bi = np.asarray(b[0], np.int64), np.asarray(b[1], np.int64)
-    if len(ap) != len(bp):
-        raise ValueError("the two lists have different numbers of rows")
-    m = len(ap) - 1
-    ai, bi = ai[ap[0]:ap[-1]], bi[bp[0]:bp[-1]]
-    if len(ai) and int(ai.max()) >= 2 ** 32 or len(bi) and int(bi.max()) >= 2 ** 32:
-        raise ValueError("an item index is out of range")
-    rows = np.concatenate((np.repeat(np.arange(m, dtype=np.int64), np.diff(ap)), np.repeat(np.arange(m, dtype=np.int64), np.diff(bp))))
-    key = np.unique((rows << 32) | np.concatenate((ai, bi)))      # one sort: (row, item) ascending, repeats merged
-    rows, items = key >> 32, key & (2 ** 32 - 1)
-    indptr = np.zeros(m + 1, np.uint64)
-    indptr[1:] = np.cumsum(np.bincount(rows, minlength=m))
-    return indptr, np.ascontiguousarray(items, dtype=np.uint64)
+    target = _HostFactors(A, B, A.shape[0], B.shape[0], A.shape[1], A.dtype == np.float32)
+    return serving.rank_batch(target, users, test, False, exclude, include, include_of, unite_test)
 
 
 def _ranking_result(tp, ranks, n_adm, k, per_user):
@@ -1509,99 +836,6 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, 
 PoisMF.eval_ranking = _eval_ranking
 
 
-def _list_rows(items, dimB):
-    """The lists of the list-wise evaluation (include/poismf_hip.h section 1q), checked as the library checks them: a 2-d integer
-    array [m x n], 1 <= n <= TOPN_BATCH_MAX_N_TOP, whose rows hold distinct items below dimB followed only by TOPN_NONE -- what every
-    topN_* call returns.  Returns it as a C-contiguous uint64 array."""
-    a = np.asarray(items)
-    if a.ndim != 2:
-        raise ValueError("the lists must be a 2-d array with one row per user")
-    if a.dtype.kind not in "iu":
-        raise ValueError("the lists must hold integers")
-    m, n = a.shape
-    if n < 1:
-        raise ValueError("the lists have no column")
-    if n > TOPN_BATCH_MAX_N_TOP:
-        raise ValueError(f"lists of {n} items are above the batched limit of {TOPN_BATCH_MAX_N_TOP}")
-    if a.dtype.kind == "i" and a.size and int(a.min()) < 0:
-        raise ValueError("the lists: negative index (an empty entry is TOPN_NONE)")
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    real = a != TOPN_NONE
-    if np.any(real[:, 1:] & ~real[:, :-1]):
-        raise ValueError("the lists: an item follows an empty entry of its row")
-    if np.any(a[real] >= dimB):
-        raise ValueError("an item index of the lists is out of range")
-    if n > 1:
-        srt = np.sort(a, axis=1)
-        if np.any((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] != TOPN_NONE)):
-            raise ValueError("the lists: a row names an item twice")
-    return a
-
-
-def _list_eval_scratch(m, n, cells, dimB, budget_bytes, real_size):
-    """poismf_hip_list_eval_scratch_bytes, the same arithmetic on the host (include/poismf_hip.h section 1q): the one scratch
-    allocation of a call in bytes, 0 when budget_bytes is below what the norms, the counts, one user and its cells need.  Returns
-    (bytes, users per chunk, cells per chunk)."""
-    up = lambda v: (v + 31) // 32 * 32
-    m, n = max(int(m), 1), min(max(int(n), 1), TOPN_BATCH_MAX_N_TOP)
-    dimB = min(max(int(dimB), 1), LIST_EVAL_MAX_ITEMS)
-    full = LIST_EVAL_BUDGET_MB << 20
-    budget = full if budget_bytes == 0 or budget_bytes > full else int(budget_bytes)
-    fixed = up(dimB * real_size) + up(dimB * 4) + 256 + 4
-    per_user = 4 * n + 16
-    row_cells = min(int(cells), RANK_BATCH_MAX_ROW)
-    if budget < fixed + per_user + row_cells * 8:
-        return 0, 0, 0
-    room = budget - fixed
-    cell_cap = min(int(cells), max(row_cells, room // 2 // 8))
-    chunk = min(m, (room - cell_cap * 8) // per_user, 262144)
-    total = 0
-    for part in (dimB * real_size, dimB * 4, chunk * n * 4, (chunk + 1) * 4, cell_cap * 4, cell_cap * 4, chunk * 8, chunk * 4):
-        total = up(total + part)
-    return total, chunk, cell_cap
-
-
-def _list_eval_args(items, test, item_norm, budget_mb, dimB, k, dtype):
-    """The argument checks of the list-wise evaluation (section 1q) that need no device, as the library itself makes them.  Returns
-    (lists uint64 [m x n], test_indptr or None, test_indices or None, inverse norms in `dtype` or None, budget in bytes, 0 for the
-    default)."""
-    if dimB < 1:
-        raise ValueError("there are no items")
-    if dimB > LIST_EVAL_MAX_ITEMS:
-        raise ValueError(f"{dimB} items are above the list evaluation's limit of {LIST_EVAL_MAX_ITEMS}")
-    if not 1 <= int(k) <= (512 if dtype == np.float32 else 256):
-        raise ValueError("the number of factors is outside what the batched entry points support")
-    lists = _list_rows(items, dimB)
-    m, n = lists.shape
-    tp = ti = None
-    if test is not None:
-        tp, ti = _csr_list(test, m, dimB, "test", RANK_BATCH_MAX_ROW)
-    inv = None
-    if item_norm is not None:
-        if np.asarray(item_norm).dtype.kind not in "fiu":
-            raise ValueError("item_norm must be real numbers")
-        with np.errstate(over="ignore"):
-            inv = _inv_norms(item_norm, dimB, dtype)
-        if not np.isfinite(inv).all():
-            raise ValueError("item_norm: an inverse norm is infinite in the model's precision")
-    budget = 0
-    if budget_mb is not None:
-        if isinstance(budget_mb, (bool, np.bool_)) or not isinstance(budget_mb, (int, float, np.integer, np.floating)):
-            raise ValueError("budget_mb must be a positive number")
-        if not float(budget_mb) > 0 or not np.isfinite(float(budget_mb)):
-            raise ValueError("budget_mb must be a positive number")
-        budget = max(int(float(budget_mb) * 2**20), 1)
-    if _list_eval_scratch(m, n, len(ti) if ti is not None else 0, dimB, budget, np.dtype(dtype).itemsize)[0] == 0:
-        raise ValueError(f"budget_mb = {budget_mb} is below what the norms, the counts and one user need")
-    return lists, tp, ti, inv, budget
-
-
-def _list_eval_outputs(lists, ti, inv, dimB):
-    m = lists.shape[0]
-    return (np.empty(len(ti), np.uint32) if ti is not None else None, np.empty(m, np.int64) if inv is not None else None,
-            np.zeros(m, np.uint32), np.zeros(dimB, np.uint32))
-
-
 def list_eval(B, items, test=None, item_norm=None, budget_mb=None):
     """poismf_hip_list_eval on host factors B [dimB x k] (float32 or float64): list-wise evaluation of the lists `items` [m x n] --
     what any topN_* call returned, from any source (include/poismf_hip.h section 1q).  test: the held-out items, a SciPy sparse
@@ -1622,69 +856,10 @@ def list_eval(B, items, test=None, item_norm=None, budget_mb=None):
         return pos, cos, length, expo
     B = np.ascontiguousarray(B)
     lib = load_library(dt == np.float32)
-    _batch_rc(lib.poismf_hip_list_eval(_ptr(B), B.shape[1], B.shape[0], _ptr(lists), lists.shape[0], lists.shape[1],
-                                       _ptr(inv) if inv is not None else None, _ptr(tp) if tp is not None else None, _opt_ptr(ti), budget,
-                                       _opt_ptr(pos), _ptr(cos) if cos is not None else None, _ptr(length), _ptr(expo)), "list evaluation")
+    _batch_rc(lib.poismf_hip_list_eval(_ptr(B), B.shape[1], B.shape[0], _ptr(lists), lists.shape[0], lists.shape[1], _opt_ptr(inv),
+                                       _opt_ptr(tp), _opt_ptr(ti), budget, _opt_ptr(pos), _opt_ptr(cos), _ptr(length), _ptr(expo)),
+              "list evaluation")
     return pos, cos, length, expo
-
-
-def _eval_lists_args(items, users, X_test, k, exclude, item_pop, dimA, dimB):
-    """eval_lists' inputs cut down to the batch: (lists uint64 [m x k], the (indptr, indices) of the held-out rows with every
-    excluded cell removed, or None; item_pop as float64, or None)"""
-    import scipy.sparse as sp
-    lists = _list_rows(items, dimB)
-    m, width = lists.shape
-    if k is not None:
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
-            raise ValueError("k must be an integer")
-        if not 1 <= int(k) <= width:
-            raise ValueError(f"k = {k} is outside 1 .. {width}, the lists' width")
-        lists = np.ascontiguousarray(lists[:, :int(k)])
-    if users is None:
-        if (X_test is not None or exclude is not None) and m != dimA:
-            raise ValueError(f"without users= the lists must have one row per user of the model: {m} rows for {dimA} users")
-        users = np.arange(m, dtype=np.uint64)
-    else:
-        users = _index_array(users, "users")
-        if len(users) != m:
-            raise ValueError(f"there are {m} lists for {len(users)} users")
-        if m and int(users.max()) >= dimA:
-            raise ValueError("a user index is out of range")
-    rows = users.astype(np.int64)
-    if item_pop is not None:
-        item_pop = np.asarray(item_pop)
-        if item_pop.ndim != 1 or item_pop.dtype.kind not in "fiu" or len(item_pop) != dimB:
-            raise ValueError(f"item_pop must be a 1-d array of real numbers with one entry per item ({dimB})")
-        item_pop = item_pop.astype(np.float64)
-        if not np.isfinite(item_pop).all() or (item_pop < 0).any():
-            raise ValueError("item_pop must be finite and non-negative")
-    test = None
-    if X_test is not None:
-        if not sp.issparse(X_test):
-            raise ValueError("X_test must be a SciPy sparse matrix")
-        if X_test.shape != (dimA, dimB):
-            raise ValueError(f"X_test has shape {X_test.shape}, the model {(dimA, dimB)}")
-        csr = sp.csr_matrix(X_test)
-        csr.sum_duplicates()
-        csr.eliminate_zeros()
-        t = csr[rows]
-        t.sort_indices()
-        tp, ti = np.asarray(t.indptr, np.int64), np.asarray(t.indices, np.int64)
-        if exclude is not None:
-            if sp.issparse(exclude):
-                if exclude.shape != (dimA, dimB):
-                    raise ValueError(f"exclude has shape {exclude.shape}, the model {(dimA, dimB)}")
-                exclude = sp.csr_matrix(exclude)[rows]
-            ep, ei = _csr_list(exclude, m, dimB, "exclude", dense_ok=True, keep_zeros=True)
-            trow = np.repeat(np.arange(m, dtype=np.int64), np.diff(tp))
-            erow = np.repeat(np.arange(m, dtype=np.int64), np.diff(ep.astype(np.int64)))
-            keep = ~np.isin((trow << 32) | ti, (erow << 32) | ei.astype(np.int64))
-            tp = np.concatenate(([0], np.cumsum(np.bincount(trow[keep], minlength=m)))).astype(np.int64)
-            ti = ti[keep]
-        test = (tp.astype(np.uint64), ti.astype(np.uint64))
-    elif exclude is not None:
-        raise ValueError("exclude removes held-out cells: it needs X_test")
-    return lists, test, item_pop
 
 
 def _lists_result(lists, test, pos, cos, length, expo, item_pop, per_user):
@@ -2165,6 +1340,11 @@ class Session:
             raise MemoryError("poismf_hip_session_topn failed")
         return ix, sc
 
+    def _entry(self, name, exclude_seen):
+        """a serving call (serving.py) on this session: the library's function for `name`, its leading argument, and what stands in
+        front of the exclusion lists"""
+        return getattr(self.lib, "poismf_hip_session_" + name), (self.h,), (int(bool(exclude_seen)),)
+
     def topn_batch(self, users, top_n=10, exclude_seen=False, exclude=None, output_score=False, include=None, include_of=None):
         """The top_n best items of every user in `users` from the resident factors, in one fused pass (include/poismf_hip.h section
         1f): "score descending, item index ascending", scores bit for bit those of predict().  exclude_seen leaves out the items of
@@ -2176,33 +1356,7 @@ class Session:
         names each user's row of it -- an integer array with one entry per user, or one int for all (section 1i): the same answers
         bit for bit, the table read once and the rows of B shared by the users of a list.  Few lists for many users belong
         there, a list per user in include= alone."""
-        if include_of is not None:
-            users, lp, li, lof, indptr, indices = _topn_shared_args(users, top_n, include, include_of, exclude, self.dimA, self.dimB)
-        elif include is not None:
-            users, ip, ii, indptr, indices = _topn_include_args(users, top_n, include, exclude, self.dimA, self.dimB)
-        else:
-            users, indptr, indices = _topn_batch_args(users, top_n, exclude, self.dimA, self.dimB)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
-        if m == 0:
-            return ix, sc
-        if include_of is not None:
-            _batch_rc(self.lib.poismf_hip_session_topn_shared(self.h, _ptr(users), m, n, _ptr(lp), _opt_ptr(li), len(lp) - 1, _ptr(lof),
-                                                              int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
-                                                              _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-            return ix, sc
-        if include is not None:
-            _batch_rc(self.lib.poismf_hip_session_topn_include(self.h, _ptr(users), m, n, _ptr(ip), _opt_ptr(ii), int(bool(exclude_seen)),
-                                                               _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                                               _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-            return ix, sc
-        _batch_rc(self.lib.poismf_hip_session_topn_batch(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
-                                                         _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                                         _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
+        return serving.topn_batch(self, users, top_n, exclude_seen, exclude, output_score, include, include_of)
 
     def topn_deep(self, users, top_n=1000, exclude_seen=False, exclude=None, output_score=False):
         """topn_batch for deep lists: the top_n <= TOPN_DEEP_MAX_N_TOP best items of every user in `users` from the resident factors
@@ -2210,18 +1364,7 @@ class Session:
         exceed what a user has left, or the number of items: the row is padded with TOPN_NONE and -inf.  Up to
         TOPN_BATCH_MAX_N_TOP the answers are topn_batch's bit for bit.  Returns (items uint64 [m x top_n], scores [m x top_n], empty
         unless output_score)."""
-        users, indptr, indices = _topn_deep_args(users, top_n, exclude, self.dimA, self.dimB)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
-        if m == 0:
-            return ix, sc
-        _batch_rc(self.lib.poismf_hip_session_topn_deep(self.h, _ptr(users), m, n, int(bool(exclude_seen)),
-                                                        _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                                        _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
+        return serving.topn_deep(self, users, top_n, exclude_seen, exclude, output_score)
 
     def topn_quota(self, users, top_n=10, group_of=None, quota=1, exclude_seen=False, exclude=None, output_score=False):
         """topn_batch with "at most quota[g] items of group g on a page", from the resident factors in one fused pass
@@ -2230,18 +1373,7 @@ class Session:
         top_n <= TOPN_BATCH_MAX_N_TOP are taken.  group_of: one group id per item.  quota: one int for every group, or an array with
         one entry per group; 0 bars a group, top_n or more leaves it unconstrained.  A row the quotas leave short is padded with
         TOPN_NONE and -inf.  Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score)."""
-        users, group_of, quota, indptr, indices = _topn_quota_args(users, top_n, group_of, quota, exclude, self.dimA, self.dimB)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), np.float32 if self.use_float else np.float64)
-        if m == 0:
-            return ix, sc
-        _batch_rc(self.lib.poismf_hip_session_topn_quota(self.h, _ptr(users), m, n, _ptr(group_of), len(quota), _ptr(quota),
-                                                         int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
-                                                         _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
+        return serving.topn_quota(self, users, top_n, group_of, quota, exclude_seen, exclude, output_score)
 
     def topn_weighted(self, users, top_n=10, item_weight=None, exclude_seen=False, exclude=None, output_score=False, query_items=False):
         """topn_batch under score x item_weight[item], from the resident factors in one fused pass (include/poismf_hip.h section 1o):
@@ -2251,21 +1383,7 @@ class Session:
         weighted ones.  A short row is padded with TOPN_NONE and -inf.  query_items: `users` are rows of the resident B instead --
         the queries of an item-to-item call (similar_items); exclude_seen has no meaning then.  Returns (items uint64 [m x top_n],
         scores [m x top_n], empty unless output_score)."""
-        dt = np.float32 if self.use_float else np.float64
-        if query_items and exclude_seen:
-            raise ValueError("exclude_seen has no meaning with query_items: the session holds no seen rows for items")
-        users, w, indptr, indices = _topn_weighted_args(users, top_n, item_weight, exclude, self.dimB if query_items else self.dimA, self.dimB, dt)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), dt)
-        if m == 0:
-            return ix, sc
-        _batch_rc(self.lib.poismf_hip_session_topn_weighted(self.h, _ptr(users), m, n, _ptr(w), int(bool(query_items)), int(bool(exclude_seen)),
-                                                            _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                                            _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
+        return serving.topn_weighted(self, users, top_n, item_weight, exclude_seen, exclude, output_score, bool(query_items))
 
     def topn_adjusted(self, users, top_n=10, adjust=None, exclude_seen=False, exclude=None, output_score=False):
         """topn_batch where single cells of the score matrix carry a factor of their own, from the resident factors, exact and in
@@ -2275,19 +1393,7 @@ class Session:
         triple; None lists no cell.  A factor of 0 does not bar a cell -- it scores 0 and ties with its like by index; a cell both
         listed and excluded is excluded.  The scores returned are the adjusted ones.  A short row is padded with TOPN_NONE and -inf.
         Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score)."""
-        dt = np.float32 if self.use_float else np.float64
-        users, a_indptr, a_indices, f, indptr, indices = _topn_adjusted_args(users, top_n, adjust, exclude, self.dimA, self.dimB, dt)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), dt)
-        if m == 0:
-            return ix, sc
-        _batch_rc(self.lib.poismf_hip_session_topn_adjusted(self.h, _ptr(users), m, n, _ptr(a_indptr), _opt_ptr(a_indices), _opt_ptr(f),
-                                                            int(bool(exclude_seen)), _ptr(indptr) if indptr is not None else None,
-                                                            _opt_ptr(indices), _ptr(ix), _ptr(sc) if output_score else None), "top-N")
-        return ix, sc
+        return serving.topn_adjusted(self, users, top_n, adjust, exclude_seen, exclude, output_score)
 
     def item_norms(self):
         """n2[j] = the fused chain of row j of the resident B with itself, predict_multiple's bits: what similar_items takes as
@@ -2302,11 +1408,7 @@ class Session:
         """The top_n best items by cosine similarity of their rows of the resident B to each item of `items`: PoisMF.similar_items from
         the session, through topn_weighted(query_items=True).  item_norm: item_norms(), computed once per model; without it every
         call computes it again, which brings the factors to the host."""
-        dt = np.float32 if self.use_float else np.float64
-        items, excl = _similar_args(items, top_n, exclude_self, self.dimB)
-        inv = _inv_norms(self.item_norms() if item_norm is None else item_norm, self.dimB, dt)
-        ix, sc = self.topn_weighted(items, top_n, item_weight=inv, exclude=excl, output_score=output_score, query_items=True)
-        return ix, _similar_scores(sc, inv, items)
+        return serving.similar_items(self, items, top_n, output_score, exclude_self, item_norm, query_items=True)
 
     def topn_diverse(self, users, top_n=10, pool=100, lam=0.7, exclude_seen=False, exclude=None, output_score=False, output_value=False,
                      item_norm=None):
@@ -2316,23 +1418,7 @@ class Session:
         item_norms(), computed once per model; without it every call computes it again, which brings the factors to the host.
         Returns (items uint64 [m x top_n] in pick order, their scores, empty unless output_score, the values they were picked at,
         empty unless output_value); a short row is padded with TOPN_NONE and -inf."""
-        dt = np.float32 if self.use_float else np.float64
-        # (everything else is judged before the norms are computed: zeros stand in for them)
-        inv = np.zeros(self.dimB, dt) if item_norm is None else _inv_norms(item_norm, self.dimB, dt)
-        users, inv, indptr, indices = _topn_diverse_args(users, top_n, pool, lam, inv, exclude, self.dimA, self.dimB, dt)
-        m, n = len(users), int(top_n)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ix, sc, val = _diverse_outputs(m, n, dt, output_score, output_value)
-        if m == 0:
-            return ix, sc, val
-        if item_norm is None:
-            inv = _inv_norms(self.item_norms(), self.dimB, dt)
-        _batch_rc(self.lib.poismf_hip_session_topn_diverse(self.h, _ptr(users), m, n, int(pool), float(lam), _ptr(inv), int(bool(exclude_seen)),
-                                                           _ptr(indptr) if indptr is not None else None, _opt_ptr(indices),
-                                                           _ptr(ix), _ptr(sc) if output_score else None,
-                                                           _ptr(val) if output_value else None), "top-N")
-        return ix, sc, val
+        return serving.topn_diverse(self, users, top_n, pool, lam, exclude_seen, exclude, output_score, output_value, item_norm)
 
     def rank_batch(self, users, test, exclude_seen=False, exclude=None, include=None, include_of=None, unite_test=False):
         """For every cell of `test` (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair with
@@ -2345,33 +1431,7 @@ class Session:
         array with one entry per batch entry, or one int for all (section 1k): the same answers, the table read once and the rows
         of B shared by the users of a list.  unite_test (with include_of only) ranks every user among its list united with its own
         held-out row, which is what a shared pool of negatives needs."""
-        users, tp, ti, ep, ei = _rank_batch_args(users, test, exclude, self.dimA, self.dimB, self.k)
-        m = len(users)
-        if include_of is not None:
-            lp, li, lof = _shared_table_args(include, include_of, m, self.dimB)
-        elif unite_test:
-            raise ValueError("unite_test needs include_of: a list per user has its held-out row united in by the caller")
-        elif include is not None:
-            ip, ii = _rank_include_list(include, m, self.dimB)
-        if exclude_seen:
-            _outside_shard(users, self.shardA)
-        ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
-        if m == 0:
-            return ranks, n_adm
-        if include_of is not None:
-            _batch_rc(self.lib.poismf_hip_session_rank_shared(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), _ptr(lp), _opt_ptr(li),
-                                                              len(lp) - 1, _ptr(lof), int(bool(unite_test)), int(bool(exclude_seen)),
-                                                              _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)),
-                      "ranks")
-            return ranks, n_adm
-        if include is not None:
-            _batch_rc(self.lib.poismf_hip_session_rank_include(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), _ptr(ip), _opt_ptr(ii),
-                                                               int(bool(exclude_seen)), _ptr(ep) if ep is not None else None, _opt_ptr(ei),
-                                                               _ptr(ranks), _ptr(n_adm)), "ranks")
-            return ranks, n_adm
-        _batch_rc(self.lib.poismf_hip_session_rank_batch(self.h, _ptr(users), m, _ptr(tp), _opt_ptr(ti), int(bool(exclude_seen)),
-                                                         _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm)), "ranks")
-        return ranks, n_adm
+        return serving.rank_batch(self, users, test, exclude_seen, exclude, include, include_of, unite_test)
 
     def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None):
         """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
@@ -2395,10 +1455,9 @@ class Session:
         pos, cos, length, expo = _list_eval_outputs(lists, ti, inv, self.dimB)
         if lists.shape[0] == 0:
             return pos, cos, length, expo
-        _batch_rc(self.lib.poismf_hip_session_list_eval(self.h, _ptr(lists), lists.shape[0], lists.shape[1],
-                                                        _ptr(inv) if inv is not None else None, _ptr(tp) if tp is not None else None,
-                                                        _opt_ptr(ti), budget, _opt_ptr(pos), _ptr(cos) if cos is not None else None,
-                                                        _ptr(length), _ptr(expo)), "list evaluation")
+        _batch_rc(self.lib.poismf_hip_session_list_eval(self.h, _ptr(lists), lists.shape[0], lists.shape[1], _opt_ptr(inv), _opt_ptr(tp),
+                                                        _opt_ptr(ti), budget, _opt_ptr(pos), _opt_ptr(cos), _ptr(length), _ptr(expo)),
+                  "list evaluation")
         return pos, cos, length, expo
 
     def eval_lists(self, items, users=None, X_test=None, k=None, exclude=None, item_norm=None, item_pop=None, per_user=False):
@@ -2453,13 +1512,11 @@ class Session:
         n = int(top_n)
         _, ep, ei = _topn_batch_args(np.arange(m, dtype=np.uint64), n, exclude, max(m, 1), self.dimB)
         dt = np.float32 if self.use_float else np.float64
-        ix = np.empty((m, n), np.uint64)
-        sc = np.empty((m, n) if output_score else (0, n), dt)
+        ix, sc = _topn_outputs(m, n, dt, output_score)
         A_new = np.empty((m, self.k), dt) if return_factors else None
         if m:
-            _batch_rc(self.lib.poismf_hip_session_topn_new(*args, n, int(bool(exclude_own)), _ptr(ep) if ep is not None else None,
-                                                           _opt_ptr(ei), _ptr(ix), _ptr(sc) if output_score else None,
-                                                           _ptr(A_new) if return_factors else None), "top-N of new rows")
+            _batch_rc(self.lib.poismf_hip_session_topn_new(*args, n, int(bool(exclude_own)), _opt_ptr(ep), _opt_ptr(ei), _ptr(ix),
+                                                           _opt_ptr(sc), _opt_ptr(A_new)), "top-N of new rows")
         return (ix, sc, A_new) if return_factors else (ix, sc)
 
     def rank_new(self, X_new, test, params, niter, exclude_own=True, exclude=None, return_factors=False, Bsum=None, Amean=None):
@@ -2473,9 +1530,8 @@ class Session:
         ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(m, np.uint32)
         A_new = np.empty((m, self.k), np.float32 if self.use_float else np.float64) if return_factors else None
         if m:
-            _batch_rc(self.lib.poismf_hip_session_rank_new(*args, _ptr(tp), _opt_ptr(ti), int(bool(exclude_own)),
-                                                           _ptr(ep) if ep is not None else None, _opt_ptr(ei), _ptr(ranks), _ptr(n_adm),
-                                                           _ptr(A_new) if return_factors else None), "ranks of new rows")
+            _batch_rc(self.lib.poismf_hip_session_rank_new(*args, _ptr(tp), _opt_ptr(ti), int(bool(exclude_own)), _opt_ptr(ep),
+                                                           _opt_ptr(ei), _ptr(ranks), _ptr(n_adm), _opt_ptr(A_new)), "ranks of new rows")
         return (ranks, n_adm, A_new) if return_factors else (ranks, n_adm)
 
     def eval_ranking_new(self, X_observed, X_test, params, niter, k=10, per_user=False, exclude_own=True, exclude=None, Bsum=None,
