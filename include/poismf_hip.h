@@ -842,7 +842,9 @@ POISMF_HIP_API void *poismf_hip_session_stream(poismf_hip_session *s);
  * must be told about outside writes: call poismf_hip_session_factors_dirty(s, which) (which = 0: B was
  * written, 1: A) after every write through a pointer obtained earlier (calling the getter again or
  * set_factors has the same effect).  Sessions with partial shards re-derive the copy from the compact
- * factor before every half-sweep in any case. */
+ * factor before every half-sweep in any case.
+ * A pointer obtained here is DEAD after poismf_hip_session_append_rows / _adopt_new (section 2d) has grown that factor:
+ * the grown factor lives in a new allocation.  Call the getter again. */
 POISMF_HIP_API real_t *poismf_hip_session_A(poismf_hip_session *s);
 POISMF_HIP_API real_t *poismf_hip_session_B(poismf_hip_session *s);
 POISMF_HIP_API void poismf_hip_session_factors_dirty(poismf_hip_session *s, int which);
@@ -978,6 +980,55 @@ POISMF_HIP_API int poismf_hip_session_sub_coo(poismf_hip_session *s, const spars
                           const real_t *val, size_t n, int strict, size_t *n_removed, size_t *n_absent);
 POISMF_HIP_API int poismf_hip_session_remove_rows(poismf_hip_session *s, int which, const sparse_ix *rows, size_t n_rows,
                           size_t *n_removed);
+
+/* ---------------------------------------------------------------------------------------------
+ * 2d. Session updates: the matrix grows.  A user signs up, an item is listed: new rows join the resident CSR / CSC and
+ *     the resident factors on the device, without rebuilding the session.  No counterpart in the reference.
+ *
+ * poismf_hip_session_append_rows: which = 1 appends n_new users (rows of A and of the CSR; dimA becomes dimA + n_new),
+ * which = 0 appends n_new items (rows of B and of the CSC; dimB grows).  The new rows take the numbers old dim .. old dim
+ * + n_new - 1; *first_row (may be NULL) receives old dim.  F is HOST [n_new x k], the new rows of the grown factor, or NULL:
+ * zero rows.  The new rows' cells are HOST CS rows over the OTHER dimension: indptr [n_new + 1] (from any start, never
+ * decreasing), indices below the other dimension and strictly ascending within a row, values finite and > 0 -- neither
+ * is repaired; indptr == NULL: the rows are empty.  Both orientations receive the cells: the grown one as new rows at
+ * its end, the other one as entries at the end of each touched row (their index exceeds every stored one).  Afterwards
+ * the session is bit for bit the one poismf_hip_session_create_coo builds from the grown matrix at the grown dimensions
+ * followed by set_factors([old; F], other): both matrices, poismf_hip_session_nnz, "all values positive", the segments each
+ * half had, the plan and the results of every later half-sweep, likelihood, serving and new-rows call.  n_new == 0 returns 0
+ * and does nothing.
+ * The growth: ONE kernel builds the grown factor -- its compact copy and, where the session keeps one, its line-padded copy,
+ * pad columns, the all-zero row and the slack behind it included -- in one pass over the old compact factor; the grown
+ * orientation's row pointers are the old ones followed by nnz; its permutation and descriptors are sized anew; the per-row
+ * counters of a profiling session keep the old rows' values and are zero for the new rows.  The other orientation's
+ * arrays are untouched by the growth.  The cells then go through section 2b's merge as device triplets, the CSR first, and
+ * each half is sorted and binned again with the segments it had.  exclude_seen of the batched calls sees the new rows; column-sum
+ * partials of the grown factor (poismf_hip_session_partials_ready) are dropped; the guest of the new-rows calls (section
+ * 1m) follows a grown B and keeps its own rows and factors.  The scratch of the likelihood, of the batched calls and the
+ * team launches' row backup are sized by the call that uses them and need nothing.
+ * Returns 0; 1 out of memory, a device error, a grown dimension > 0x7fffffff or n >= 2^32 cells; 3 an index outside the
+ * other dimension, a row that is not strictly ascending, or decreasing pointers; 4 a value that is not finite or not > 0;
+ * 5 the session is not eligible (2b's rule).  3, 4 and 5 are found on the host before anything is written: the session is
+ * exactly as it was.
+ * Memory and failure: the growth allocates all its new arrays beside the old ones -- the grown factor (and its padded copy)
+ * and the grown half's row pointers, so peak extra device memory is one factor in both copies plus 8 (dim + 1) bytes -- and
+ * swaps them in only when all exist: a failure (rc 1) of the growth leaves the session as it was.  The cell merge behind it
+ * is 2b's, with 2b's bound (one half's arrays) and 2b's price: a failure while the CSR is merged leaves the grown session
+ * with its new rows empty, a failure while the CSC is merged leaves the orientations in disagreement and the session
+ * only good for poismf_hip_session_destroy.
+ * Pointers obtained earlier from poismf_hip_session_A (which = 1) / poismf_hip_session_B (which = 0) are DEAD after the call.
+ *
+ * poismf_hip_session_adopt_new: the rows the session's guest holds from the last section 1m call (factors_new, topn_new,
+ * rank_new) become resident users -- their CSR and their solved factors: append_rows(1, ...) with everything taken from
+ * the device.  The factor rows are read from the guest's factor, the cells are expanded from the guest's CSR into triplets;
+ * nothing crosses PCIe except the rows' counts.  *first_row / *n_rows (may be NULL) receive the first new user and how many
+ * there are.  Returns as append_rows, and 5 when there is no guest or a guest row is not strictly ascending, 4 when the
+ * guest's rows hold a value that is not > 0.  The guest is left as it was.  The result is bit for bit append_rows(1, the
+ * same rows, F = what poismf_hip_session_factors_new returned).
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_append_rows(poismf_hip_session *s, int which, size_t n_new,
+                          const real_t *F, const real_t *val, const sparse_ix *indptr, const sparse_ix *indices,
+                          size_t *first_row);
+POISMF_HIP_API int poismf_hip_session_adopt_new(poismf_hip_session *s, size_t *first_row, size_t *n_rows);
 
 /* run_poismf's outer loop (ref: src/poismf.c:506-608: B half, PG step halving, A half, TNCG early stop, SIGINT
  * handling and return codes 0 / 1 / 2 exactly as in section 1) on a session that already holds X and the starting

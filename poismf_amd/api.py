@@ -22,7 +22,7 @@ from . import harness
 from . import serving
 # the serving calls' argument checks and helpers live in serving.py; every name stays reachable here
 from .serving import (_batch_rc, _csr_list, _diverse_outputs, _eval_lists_args, _eval_ranking_args, _include_of_rows, _include_rows,
-                      _index_array, _inv_norms, _list_eval_args, _list_eval_outputs, _list_eval_scratch, _list_rows, _new_rows_args,
+                      _index_array, _inv_norms, _list_eval_args, _list_eval_outputs, _list_eval_scratch, _list_rows, _new_rows_args, _append_rows_args,
                       _new_stats, _opt_ptr, _outside_shard, _ptr, _rank_batch_args, _rank_include_list, _shared_table_args,
                       _similar_args, _similar_scores, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
                       _topn_include_args, _topn_outputs, _topn_quota_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_set_segments", "poismf_hip_session_segment_rows", "poismf_hip_half_sweep_segment", "poismf_hip_session_plan",
     "poismf_hip_session_add_coo", "poismf_hip_session_get_matrix", "poismf_hip_half_sweep_rows",
     "poismf_hip_session_sub_coo", "poismf_hip_session_remove_rows",
+    "poismf_hip_session_append_rows", "poismf_hip_session_adopt_new",
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
@@ -168,6 +169,10 @@ def load_library(use_float):
     lib.poismf_hip_session_sub_coo.restype = i
     lib.poismf_hip_session_remove_rows.argtypes = [vp, i, vp, sz, C.POINTER(sz)]
     lib.poismf_hip_session_remove_rows.restype = i
+    lib.poismf_hip_session_append_rows.argtypes = [vp, i, sz, vp, vp, vp, vp, C.POINTER(sz)]
+    lib.poismf_hip_session_append_rows.restype = i
+    lib.poismf_hip_session_adopt_new.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    lib.poismf_hip_session_adopt_new.restype = i
     lib.poismf_hip_session_get_matrix.argtypes = [vp, i, vp, vp, vp]
     lib.poismf_hip_session_get_matrix.restype = i
     lib.poismf_hip_half_sweep_rows.argtypes = [vp, i, vp, sz, C.POINTER(lib.params_t), r, r, C.POINTER(sz)]
@@ -1243,6 +1248,90 @@ class Session:
         if rc:
             raise MemoryError("poismf_hip_session_remove_rows failed (out of memory or a device error)")
         return removed.value
+
+    def _grown(self, which, n):
+        """the Python object follows a growth the library has made: the dimension and the shard every serving check reads"""
+        if which:
+            self.dimA += n
+            self.shardA = (0, self.dimA)
+        else:
+            self.dimB += n
+            self.shardB = (0, self.dimB)
+
+    def _append_rc(self, rc, name):
+        if rc == 3:
+            raise ValueError("append: an index of the new rows lies outside the other dimension, or a row is not strictly ascending")
+        if rc == 4:
+            raise ValueError("append: every value must be finite and > 0")
+        if rc == 5:
+            raise ValueError("append: this session cannot grow in place: it holds a shard of the matrix, a row of its CSR / CSC is not strictly "
+                             "ascending (Session.from_coo sessions always qualify), or there are no new rows to adopt")
+        if rc:
+            raise MemoryError(f"{name} failed (out of memory, a device error, or a dimension beyond 2^31 - 1)")
+
+    def append(self, which, X_new=None, factors=None, n_new=None):
+        """New users (which = 1) or new items (which = 0) join the resident model in place (include/poismf_hip.h section 2d): the matrix
+        gets n new rows (users) or columns (items) numbered from the old dimension on, the factor n new rows.  X_new: a SciPy sparse matrix
+        with one row per new row and the OTHER dimension's width (dimB columns for users, dimA for items), values finite and > 0; it is
+        converted to CSR with duplicates summed and indices sorted; None: the new rows are empty, and n_new says how many.  factors:
+        [n x k], the new rows of the factor; None: zeros.  Afterwards the session is bit for bit a fresh Session.from_coo on the grown
+        matrix with set_factors of the grown factors.  Returns the first new row number.  ValueError -- before anything changes -- for
+        a which other than 0 / 1, a wrong width, a wrong factor shape, factors that are not finite, values that are not finite and
+        positive, and a session that cannot grow in place (add's rule); MemoryError when the device runs out of memory."""
+        if which not in (0, 1) or isinstance(which, bool):
+            raise ValueError(f"append: which must be 0 (items) or 1 (users), not {which!r}")
+        other = self.dimB if which else self.dimA
+        n, data, indptr, indices, F = _append_rows_args(X_new, factors, n_new, other, self.k, self.use_float)
+        first = C.c_size_t(self.dimA if which else self.dimB)
+        if n == 0:
+            return first.value
+        rc = self.lib.poismf_hip_session_append_rows(self.h, int(which), n, _ptr(F) if F is not None else None, _opt_ptr(data),
+                                                     _ptr(indptr) if indptr is not None else None, _opt_ptr(indices), C.byref(first))
+        self._append_rc(rc, "poismf_hip_session_append_rows")
+        self._grown(which, n)
+        return first.value
+
+    def adopt_new(self):
+        """The rows of the last transform / topn_new / rank_new call become resident users, their solved factors their rows of A, without
+        leaving the device (section 2d).  Returns (first new user, number of new users).  ValueError when there is no such call to adopt,
+        when one of its rows was not strictly ascending or held a value that is not > 0, and for a session that cannot grow in place."""
+        first, n = C.c_size_t(self.dimA), C.c_size_t(0)
+        self._append_rc(self.lib.poismf_hip_session_adopt_new(self.h, C.byref(first), C.byref(n)), "poismf_hip_session_adopt_new")
+        self._grown(1, n.value)
+        return first.value, n.value
+
+    def append_users(self, X_new, params, niter, factors=None, Bsum=None, Amean=None):
+        """New users join the model.  factors=None: transform(X_new, params, niter, Bsum, Amean) folds them in against the resident B, then
+        adopt_new() makes them resident -- rows, cells and solved factors stay on the device (Bsum / Amean as in transform: serving
+        code passes them in).  Otherwise append(1, X_new, factors).  Returns the new users' numbers."""
+        if factors is not None:
+            first = self.append(1, X_new, factors)
+            return np.arange(first, self.dimA, dtype=np.int64)
+        _append_rows_args(X_new, None, None, self.dimB, self.k, self.use_float)   # (adopt_new refuses what append would: say so before the solve)
+        if X_new.shape[0] == 0:
+            return np.zeros(0, np.int64)
+        self.transform(X_new, params, niter, Bsum=Bsum, Amean=Amean)
+        first, n = self.adopt_new()
+        return np.arange(first, first + n, dtype=np.int64)
+
+    def append_items(self, X_new, params, step_size, start=None):
+        """New items join the model: append(0, X_new, factors = start in every row), then half_sweep_rows(0, the new items) with this step and
+        cnst_div(params.l2_reg, step_size).  ONE LOCAL REFIT of the new rows of B against the resident A, not the reference's step
+        schedule (as in update).  X_new: one row per new item, dimA columns.  start: a [k] vector, the point every new item starts from;
+        its default is the column means of the resident B, AT THE COST OF DOWNLOADING BOTH FACTORS: serving code computes it once and
+        passes it in.  Returns the new items' numbers."""
+        dt = np.float32 if self.use_float else np.float64
+        if start is None:
+            start = self.get_factors()[1].mean(axis=0)
+        start = np.ascontiguousarray(start, dtype=dt).reshape(-1)
+        if len(start) != self.k:
+            raise ValueError(f"append_items: start must have k = {self.k} entries")
+        n = X_new.shape[0] if hasattr(X_new, "shape") and len(X_new.shape) == 2 else 0
+        first = self.append(0, X_new, np.ascontiguousarray(np.broadcast_to(start, (n, self.k))))
+        items = np.arange(first, self.dimB, dtype=np.int64)
+        step_size = self.real(step_size)
+        self.half_sweep_rows(0, items, params, step_size, self.cnst_div(params.l2_reg, step_size))
+        return items
 
     def matrix(self, which):
         """(values, indices, indptr) of the resident CSR shard (which = 1) or CSC shard (which = 0), downloaded: the layout of the

@@ -127,12 +127,6 @@ __global__ __launch_bounds__(256) void rem_place_kernel(const u64* dptr, const T
     }
 }
 
-// does row r of D hold a cell?
-struct RowTouched {
-    const u64* dptr;
-    __device__ bool operator()(unsigned r) const { return dptr[r + 1] > dptr[r]; }
-};
-
 // D (n triplets on the device, major / minor as this half sees them; d_val == nullptr: the cells go outright; `touched`: D's distinct major
 // indices, ascending, or nullptr: found on the device from D's row pointers) taken out of half h: new arrays are built beside the resident
 // ones and take their place only when everything has succeeded.  0, 1, or 6: strict and a cell is absent (nothing written).

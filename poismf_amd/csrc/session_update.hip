@@ -2,7 +2,6 @@
 // on the device (locate, scan, scatter, place -- no resident array comes to the host and nothing is sorted again), the download of a half's
 // matrix, and a half-sweep over listed rows (a view of the half with a permutation, descriptors and bins of its own: half_sweep.hip runs it).
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -13,156 +12,6 @@
 #include "session_merge.hpp"
 
 namespace {
-
-// ---- the merge of one orientation -----------------------------------------------------------------------------------------------------
-// D arrives as a CS matrix of the half's shape (dptr [dimM + 1], dmin / dval [u], duplicates summed, rows ascending).  A cell e of D in row
-// r has lb[e], its lower bound among the resident row's indices, and is NEW unless the entry there is its own.  S is the exclusive scan of
-// "new" over D's cells, so S[dptr[r]] new cells precede row r: the new row pointers need no scan over the rows.
-
-// The new cells' lower bounds side by side, in D's order (monotone within a row): what the scatter searches.
-__global__ __launch_bounds__(256) void upd_newlb_kernel(const unsigned* lb, const unsigned* isnew, const unsigned* S, size_t u, unsigned* newlb)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < u; e += (size_t)gridDim.x * blockDim.x)
-        if (isnew[e]) newlb[S[e]] = lb[e];
-}
-
-__global__ __launch_bounds__(256) void upd_indptr_kernel(const u64* indptr, const u64* dptr, const unsigned* S, size_t dimM, u64* out)
-{
-    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r <= dimM; r += (size_t)gridDim.x * blockDim.x) out[r] = indptr[r] + S[dptr[r]];
-}
-
-// The bandwidth kernel: every resident entry moves to its new place.  The resident arrays are walked in chunks of UPD_CHUNK consecutive
-// entries, a workgroup per chunk in a grid-stride loop, so a row of millions of entries is cut over many workgroups like any other range.
-// Per chunk ONE search finds the touched rows [t_lo, t_hi) that overlap it -- none for most chunks of a small D: the chunk is then a shift
-// by one constant.  An entry p outside every touched row moves by the new cells of the touched rows before it; entry j of touched row t
-// moves by Sx[t] + #{new cells of the row with lb <= j}, a search in the row's slice of newlb.  Loads of a thread's UPD_PER entries are
-// issued together, lanes on consecutive entries; nothing waits for another workgroup.
-template <class T>
-__global__ __launch_bounds__(256) void upd_scatter_kernel(const unsigned* __restrict__ indices, const T* __restrict__ values, size_t nnz,
-                                                          const u64* __restrict__ ta, const u64* __restrict__ tb, const unsigned* __restrict__ Sx,
-                                                          size_t nT, const unsigned* __restrict__ newlb, unsigned* __restrict__ out_indices,
-                                                          T* __restrict__ out_values)
-{
-    const size_t nchunks = (nnz + UPD_CHUNK - 1) / UPD_CHUNK;
-    for (size_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
-        const size_t c0 = ch * (size_t)UPD_CHUNK, c1 = std::min(c0 + (size_t)UPD_CHUNK, nnz);
-        // (uniform over the workgroup) t_lo: the first touched row that ends behind c0; t_hi: the first that begins at or behind c1
-        size_t t_lo = 0, t_hi = nT;
-        {
-            size_t lo = 0, hi = nT;
-            while (lo < hi) { const size_t mid = lo + (hi - lo) / 2; if (tb[mid] <= c0) lo = mid + 1; else hi = mid; }
-            t_lo = lo;
-            hi = nT;
-            while (lo < hi) { const size_t mid = lo + (hi - lo) / 2; if (ta[mid] < c1) lo = mid + 1; else hi = mid; }
-            t_hi = lo;
-        }
-        unsigned ix[UPD_PER];
-        T v[UPD_PER];
-#pragma unroll
-        for (int q = 0; q < UPD_PER; q++) {
-            const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
-            if (p < c1) { ix[q] = indices[p]; v[q] = values[p]; }
-        }
-        if (t_lo == t_hi) {
-            const size_t shift = Sx[t_lo];
-#pragma unroll
-            for (int q = 0; q < UPD_PER; q++) {
-                const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
-                if (p < c1) { out_indices[p + shift] = ix[q]; out_values[p + shift] = v[q]; }
-            }
-            continue;
-        }
-#pragma unroll
-        for (int q = 0; q < UPD_PER; q++) {
-            const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
-            if (p >= c1) continue;
-            size_t lo = t_lo, hi = t_hi;   // the first touched row of the chunk's that begins behind p
-            while (lo < hi) { const size_t mid = lo + (hi - lo) / 2; if (ta[mid] <= p) lo = mid + 1; else hi = mid; }
-            size_t shift = Sx[lo];
-            if (lo > t_lo && p < tb[lo - 1]) {   // inside touched row lo - 1: its new cells at or before this entry come first
-                const size_t t = lo - 1;
-                const unsigned j = (unsigned)(p - ta[t]);
-                size_t a = Sx[t], b = Sx[t + 1];
-                while (a < b) { const size_t mid = a + (b - a) / 2; if (newlb[mid] <= j) a = mid + 1; else b = mid; }
-                shift = a;
-            }
-            out_indices[p + shift] = ix[q];
-            out_values[p + shift] = v[q];
-        }
-    }
-}
-
-// One lane per cell of D.  Resident entries before it in its row: lb; new cells before it in its row: S[e] - S[dptr[r]] -- and that holds
-// for a hit as well (the new cells with lb <= its entry's place are exactly those before it in D's row).  A new cell writes itself there,
-// a hit adds its value to the entry the scatter has moved there: one rounded addition, D holds no cell twice.
-template <class T>
-__global__ __launch_bounds__(256) void upd_place_kernel(const u64* dptr, const unsigned* dmin, const T* dval, size_t u, const unsigned* rowof,
-                                                        const unsigned* lb, const unsigned* isnew, const unsigned* S, const u64* new_indptr,
-                                                        unsigned* out_indices, T* out_values)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < u; e += (size_t)gridDim.x * blockDim.x) {
-        const unsigned r = rowof[e];
-        const u64 pos = new_indptr[r] + lb[e] + (S[e] - S[dptr[r]]);
-        if (isnew[e]) { out_indices[pos] = dmin[e]; out_values[pos] = dval[e]; }
-        else out_values[pos] += dval[e];
-    }
-}
-
-// D (n triplets on the device, major / minor as this half sees them; `touched`: its distinct major indices, ascending) merged into half h:
-// new arrays are built beside the resident ones and take their place only when everything has succeeded.  0 or 1; *n_new: cells not stored before.
-int merge_half(poismf_hip_session* s, Half& h, const unsigned* d_major, const unsigned* d_minor, const real_t* d_val, size_t n,
-               const std::vector<unsigned>& touched, size_t* n_new)
-{
-    const hipStream_t st = s->stream;
-    const size_t dimM = h.dimM, nT = touched.size();
-    MergeScratch m(st);
-    HIP_TRY(pmf_alloc(&m.dptr, sizeof(u64) * (dimM + 1), st));
-    HIP_TRY(pmf_alloc(&m.dmin, sizeof(unsigned) * n, st));
-    HIP_TRY(pmf_alloc(&m.dval, sizeof(real_t) * n, st));
-    size_t u = 0;
-    if (poismf_hip_device_coo_to_cs(d_major, d_minor, d_val, n, 0, dimM, m.dmin, m.dval, m.dptr, &u, st)) return 1;
-    HIP_TRY(pmf_alloc(&m.rowof, sizeof(unsigned) * u, st));
-    HIP_TRY(pmf_alloc(&m.lb, sizeof(unsigned) * u, st));
-    HIP_TRY(pmf_alloc(&m.isnew, sizeof(unsigned) * (u + 1), st));
-    HIP_TRY(pmf_alloc(&m.S, sizeof(unsigned) * (u + 1), st));
-    HIP_TRY(pmf_alloc(&m.T, sizeof(unsigned) * nT, st));
-    HIP_TRY(pmf_alloc(&m.ta, sizeof(u64) * nT, st));
-    HIP_TRY(pmf_alloc(&m.tb, sizeof(u64) * nT, st));
-    HIP_TRY(pmf_alloc(&m.Sx, sizeof(unsigned) * (nT + 1), st));
-    HIP_TRY(pmf_alloc(&m.new_indptr, sizeof(u64) * (dimM + 1), st));
-    HIP_TRY(pmf_upload(m.T, touched.data(), sizeof(unsigned) * nT, st));
-    hipLaunchKernelGGL(upd_locate_kernel, dim3(grid_for(u)), dim3(256), 0, st, m.dptr, m.dmin, u, dimM, h.d_indptr, h.d_indices, m.rowof, m.lb, m.isnew);
-    size_t tmp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, m.isnew, m.S, 0u, u + 1, rocprim::plus<unsigned>(), st));
-    HIP_TRY(pmf_alloc(&m.tmp, tmp_bytes ? tmp_bytes : 16, st));
-    HIP_TRY(rocprim::exclusive_scan(m.tmp, tmp_bytes, m.isnew, m.S, 0u, u + 1, rocprim::plus<unsigned>(), st));
-    unsigned fresh = 0;
-    HIP_TRY(pmf_download(&fresh, m.S + u, sizeof(unsigned), st));
-    const size_t nnz_new = h.nnz + fresh;
-    HIP_TRY(pmf_alloc(&m.newlb, sizeof(unsigned) * (fresh ? fresh : 1), st));
-    HIP_TRY(pmf_alloc(&m.new_indices, sizeof(unsigned) * (nnz_new ? nnz_new : 1), st));
-    HIP_TRY(pmf_alloc(&m.new_values, sizeof(real_t) * (nnz_new ? nnz_new : 1), st));
-    hipLaunchKernelGGL(upd_newlb_kernel, dim3(grid_for(u)), dim3(256), 0, st, m.lb, m.isnew, m.S, u, m.newlb);
-    hipLaunchKernelGGL(upd_touched_kernel, dim3(grid_for(nT + 1)), dim3(256), 0, st, m.T, nT, m.dptr, m.S, u, h.d_indptr, m.ta, m.tb, m.Sx);
-    hipLaunchKernelGGL(upd_indptr_kernel, dim3(grid_for(dimM + 1)), dim3(256), 0, st, h.d_indptr, m.dptr, m.S, dimM, m.new_indptr);
-    if (h.nnz > 0) {
-        const size_t nchunks = (h.nnz + UPD_CHUNK - 1) / UPD_CHUNK;
-        const unsigned grid = (unsigned)std::min<size_t>(nchunks, (size_t)s->num_cu * 8);
-        hipLaunchKernelGGL((upd_scatter_kernel<real_t>), dim3(grid), dim3(256), 0, st, h.d_indices, h.d_values, h.nnz, m.ta, m.tb, m.Sx, nT, m.newlb,
-                           m.new_indices, m.new_values);
-    }
-    hipLaunchKernelGGL((upd_place_kernel<real_t>), dim3(grid_for(u)), dim3(256), 0, st, m.dptr, m.dmin, m.dval, u, m.rowof, m.lb, m.isnew, m.S,
-                       m.new_indptr, m.new_indices, m.new_values);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    // the swap: from here on the half is the merged one
-    pmf_free(h.d_indptr, st); pmf_free(h.d_indices, st); pmf_free(h.d_values, st);
-    h.d_indptr = m.new_indptr; h.d_indices = m.new_indices; h.d_values = m.new_values;
-    m.new_indptr = nullptr; m.new_indices = nullptr; m.new_values = nullptr;
-    h.nnz = nnz_new;
-    *n_new = fresh;
-    return 0;
-}
 
 __global__ __launch_bounds__(256) void rows_len_kernel(const u64* indptr, const unsigned* rows, size_t n, unsigned* len)
 {
@@ -211,7 +60,7 @@ int poismf_hip_session_add_coo(poismf_hip_session* s, const sparse_ix* row, cons
         for (int which = 1; which >= 0 && ok; which--) {
             Half& h = s->half[which];
             const int nseg = (int)std::max<size_t>(h.segs.size(), 1);
-            ok = merge_half(s, h, which ? d_row : d_col, which ? d_col : d_row, d_val, n, which ? rows : cols, &fresh[which]) == 0 &&
+            ok = merge_half(s, h, which ? d_row : d_col, which ? d_col : d_row, d_val, n, which ? &rows : &cols, &fresh[which]) == 0 &&
                  finish_half(h, s->stream, nseg) == 0;
         }
         if (!ok) break;

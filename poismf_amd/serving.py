@@ -189,6 +189,45 @@ def _new_rows_args(X_new, dimB, use_float):
             np.ascontiguousarray(csr.indices, dtype=np.uint64))
 
 
+def _append_rows_args(X_new, factors, n_new, other, k, use_float):
+    """The new rows of Session.append (include/poismf_hip.h section 2d), checked without a device as the library itself checks them:
+    X_new a SciPy sparse matrix with one row per new row and `other` columns (or None: n_new empty rows), coerced to CSR with
+    duplicates summed and indices sorted, every value finite and > 0; factors [n x k] and finite, or None.  Returns (n, data real_t,
+    indptr, indices, factors real_t) with uint64 index arrays; the three matrix entries are None without X_new."""
+    import scipy.sparse as sp
+    dt = _real_t(use_float)
+    data = indptr = indices = None
+    if X_new is not None:
+        if not sp.issparse(X_new):
+            raise ValueError("append: the new rows must be a SciPy sparse matrix with one row per new row")
+        if X_new.shape[1] != other:
+            raise ValueError(f"append: the new rows have {X_new.shape[1]} columns, the other dimension is {other}")
+        csr = sp.csr_matrix(X_new)
+        csr.sum_duplicates(); csr.sort_indices()
+        n = csr.shape[0]
+        if n_new is not None and int(n_new) != n:
+            raise ValueError(f"append: n_new = {n_new} but the new rows are {n}")
+        data = np.ascontiguousarray(csr.data, dtype=dt)
+        if not (np.isfinite(data).all() and (data > 0).all()):
+            raise ValueError("append: every value must be finite and > 0")
+        indptr, indices = np.ascontiguousarray(csr.indptr, dtype=np.uint64), np.ascontiguousarray(csr.indices, dtype=np.uint64)
+    elif n_new is not None:
+        if isinstance(n_new, bool) or not isinstance(n_new, (int, np.integer)) or n_new < 0:
+            raise ValueError(f"append: n_new must be a non-negative integer, not {n_new!r}")
+        n = int(n_new)
+    elif factors is not None:
+        n = np.shape(factors)[0] if np.ndim(factors) == 2 else -1
+    else:
+        raise ValueError("append: give the new rows, or n_new empty rows")
+    if factors is not None:
+        if np.ndim(factors) != 2 or np.shape(factors) != (n, k):
+            raise ValueError(f"append: factors must have shape ({max(n, 0)}, {k}), not {np.shape(factors)}")
+        factors = np.ascontiguousarray(factors, dtype=dt)
+        if not np.isfinite(factors).all():
+            raise ValueError("append: factors must be finite")
+    return n, data, indptr, indices, factors
+
+
 def _new_stats(Bsum, Amean, k, use_float):
     """Bsum (with l1 already added) and Amean of the fold-in calls as C-contiguous real_t k-vectors"""
     dt = _real_t(use_float)
