@@ -1030,6 +1030,50 @@ POISMF_HIP_API int poismf_hip_session_append_rows(poismf_hip_session *s, int whi
                           size_t *first_row);
 POISMF_HIP_API int poismf_hip_session_adopt_new(poismf_hip_session *s, size_t *first_row, size_t *n_rows);
 
+/* ---------------------------------------------------------------------------------------------
+ * 2e. Session updates: counts fade.  Time decay makes last month's plays count for less than last week's: every stored
+ *     count is scaled on the device, in both orientations, and what fades below a floor leaves the matrix, without
+ *     rebuilding the session.  Unlike 2b-2d it is not driven by a cell list: it touches every entry.  No counterpart in
+ *     the reference.
+ *
+ * poismf_hip_session_scale: for every stored cell (u, i) with value x, nv = ((x * gamma) * row_scale[u]) * col_scale[i]:
+ * three multiplications in the model's precision, in this order, each rounded once.  row_scale is HOST [dimA], col_scale
+ * HOST [dimB]; either may be NULL: all ones (multiplying a finite value by 1 is exact, so an absent operand may be skipped:
+ * the bits are those of the formula).  Both orientations compute the same nv bits from the same operands.  The cell stays
+ * with value nv if and only if nv > floor; otherwise it is REMOVED: its entry leaves the row and the row gets shorter
+ * (section 2c's rule is the case floor == 0).  No zero, negative or non-finite value is ever stored; a subnormal nv is a
+ * value like any other and is not flushed.  *n_removed (may be NULL) receives the number of cells that left.  Rows stay,
+ * possibly with length 0: the dimensions never change and the factors are untouched (every row has changed: refit with
+ * poismf_hip_half_sweep).  A scale of 0 on a row or column is poismf_hip_session_remove_rows on it.  A matrix emptied to
+ * nnz == 0 is legal and a later poismf_hip_session_add_coo works on it.  nnz == 0 returns 0 and launches nothing; so does
+ * gamma == 1 with both vectors NULL and floor == 0.
+ * Per orientation, over chunks of consecutive resident entries, a workgroup per chunk, so that a row of millions of entries
+ * is cut over many workgroups like any other range: a DECIDE pass reads the values (the indices only when the vector over
+ * them is given; the row of an entry, when the vector over the rows is given, is found from the chunk's slice of the row
+ * pointers: one search per chunk, none over the whole dimension per entry) and writes a keep bit per entry, a kept count
+ * per chunk and the number of results that are not finite; an exclusive scan over the chunk counts and one lane per row
+ * (the chunk's base plus the keep bits of the chunk before the row's first entry) give the new row pointers; a COMPACT pass
+ * computes every survivor's nv again from the same operands and stores it with its index at its new place, survivors in
+ * their order, so rows stay strictly ascending.  When NO cell leaves -- the common case, floor == 0 and scales in (0, 1] --
+ * an IN-PLACE pass rewrites the values only: row pointers, indices, the sort permutation, the bins, the segments and the
+ * row pointers exclude_seen keeps are untouched.  No resident array comes to the host; only the two vectors go up and only
+ * counts come down.
+ * Returns 0; 1 out of memory / a device error; 4 gamma, floor or an entry of a vector is not finite or is < 0 (checked on
+ * the host); 5 the session is not eligible (2b's rule: either shard is not the whole matrix, no CSC, or a resident row
+ * that is not strictly ascending); 7 some nv is not finite (a scale above 1 overflowed): found by the CSR's decide pass
+ * before anything resident is written.  After 4, 5 and 7 the session is exactly as it was.
+ * Memory and failure are 2b's and 2c's: the CSR is done first, then the CSC; when cells leave, each orientation's new
+ * arrays are built beside the resident ones and swapped in when complete, so peak extra device memory is one half's
+ * arrays plus O(nnz / 8 + dim) bytes of scratch; a failure (rc 1) after the CSR has been written leaves the orientations in
+ * disagreement and the session only good for poismf_hip_session_destroy.  The count of leaving cells and of non-finite
+ * results is the CSR's; a CSC pass that finds another returns 1.
+ * Afterwards, when cells left: poismf_hip_session_nnz is updated, each half is sorted and binned again with the segments
+ * it had, and exclude_seen of the batched calls, poismf_hip_session_llk, the new-rows calls and the half-sweeps no longer
+ * see the cells.  Either way "all values positive" holds.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_scale(poismf_hip_session *s, real_t gamma,
+                          const real_t *row_scale, const real_t *col_scale, real_t floor, size_t *n_removed);
+
 /* run_poismf's outer loop (ref: src/poismf.c:506-608: B half, PG step halving, A half, TNCG early stop, SIGINT
  * handling and return codes 0 / 1 / 2 exactly as in section 1) on a session that already holds X and the starting
  * factors; `p->step_size` is the initial step.  PoisMF.fit uses it with poismf_hip_session_create_coo so that the

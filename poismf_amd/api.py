@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_add_coo", "poismf_hip_session_get_matrix", "poismf_hip_half_sweep_rows",
     "poismf_hip_session_sub_coo", "poismf_hip_session_remove_rows",
     "poismf_hip_session_append_rows", "poismf_hip_session_adopt_new",
+    "poismf_hip_session_scale",
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
@@ -173,6 +174,8 @@ def load_library(use_float):
     lib.poismf_hip_session_append_rows.restype = i
     lib.poismf_hip_session_adopt_new.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
     lib.poismf_hip_session_adopt_new.restype = i
+    lib.poismf_hip_session_scale.argtypes = [vp, r, vp, vp, r, C.POINTER(sz)]
+    lib.poismf_hip_session_scale.restype = i
     lib.poismf_hip_session_get_matrix.argtypes = [vp, i, vp, vp, vp]
     lib.poismf_hip_session_get_matrix.restype = i
     lib.poismf_hip_half_sweep_rows.argtypes = [vp, i, vp, sz, C.POINTER(lib.params_t), r, r, C.POINTER(sz)]
@@ -1247,6 +1250,53 @@ class Session:
                              "is not strictly ascending (Session.from_coo sessions always qualify)")
         if rc:
             raise MemoryError("poismf_hip_session_remove_rows failed (out of memory or a device error)")
+        return removed.value
+
+    def decay(self, gamma=1.0, floor=0.0, users=None, items=None):
+        """Every stored count is scaled on the device, in both orientations, and what fades leaves (include/poismf_hip.h section 2e): cell
+        (u, i) holding x becomes ((x * gamma) * users[u]) * items[i] -- three multiplications in the session's precision, in this order,
+        each rounded once -- and stays if and only if that is > floor; otherwise the cell leaves the matrix (no zero or negative value is
+        ever stored; a subnormal result stays).  gamma, floor: finite and >= 0, rounded to the session's precision.  users / items: an
+        array-like of one factor per user (length dimA) / per item (length dimB), finite and >= 0, or None: all ones; a 0 forgets the row.
+        Time decay is decay(0.9) once per period.  Returns the number of cells removed; when it is 0 only the values were rewritten, in
+        place.  ValueError -- before anything changes -- for a gamma, floor or factor that is negative, NaN or infinite, a vector that is
+        not one-dimensional, of the wrong length or boolean, a scaled value that is not finite (a factor above 1 overflowed), and a session
+        that cannot be changed in place (add's rule).  The factors are untouched, and every row has changed: refit with sweep or half_sweep."""
+        dt = np.float32 if self.use_float else np.float64
+        scalars = {}
+        for name, v in (("gamma", gamma), ("floor", floor)):
+            v = self.real(v)
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"decay: {name} must be finite and >= 0, not {v!r}")
+            scalars[name] = v
+        vectors = {}
+        for name, v, dim in (("users", users, self.dimA), ("items", items, self.dimB)):
+            if v is None:
+                vectors[name] = None
+                continue
+            v = np.asarray(v)
+            if v.ndim != 1:
+                raise ValueError(f"decay: {name} must be one-dimensional")
+            if v.dtype == np.bool_:
+                raise ValueError(f"decay: {name} must be numbers, not booleans")
+            if len(v) != dim:
+                raise ValueError(f"decay: {name} has {len(v)} entries, the session {dim}")
+            v = np.ascontiguousarray(v, dtype=dt)
+            if not (np.isfinite(v).all() and (v >= 0).all()):
+                raise ValueError(f"decay: every entry of {name} must be finite and >= 0")
+            vectors[name] = v
+        removed = C.c_size_t(0)
+        su, si = (None if v is None else _ptr(v) for v in (vectors["users"], vectors["items"]))
+        rc = self.lib.poismf_hip_session_scale(self.h, scalars["gamma"], su, si, scalars["floor"], C.byref(removed))
+        if rc == 4:
+            raise ValueError("decay: gamma, floor and every entry of users / items must be finite and >= 0")
+        if rc == 5:
+            raise ValueError("decay: this session cannot be changed in place: it holds a shard of the matrix, or a row of its CSR / CSC "
+                             "is not strictly ascending (Session.from_coo sessions always qualify)")
+        if rc == 7:
+            raise ValueError("decay: a scaled value is not finite; nothing was changed")
+        if rc:
+            raise MemoryError("poismf_hip_session_scale failed (out of memory or a device error)")
         return removed.value
 
     def _grown(self, which, n):

@@ -2,9 +2,9 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Twenty-eight translation units per precision -- the host side in eight (session.hip the session object, planner.hip the planner,
+Twenty-nine translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
-session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session -- the three on session_merge.hpp; they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
+session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
 the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip), the
 batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip) and the batched ranks among
@@ -39,6 +39,7 @@ UNITS = {
     "session_update": ("session_update.hip", []),
     "session_remove": ("session_remove.hip", []),
     "session_grow": ("session_grow.hip", []),
+    "session_scale": ("session_scale.hip", []),
     "poismf_hip_tncg": ("poismf_hip.hip", ["-DPMF_TU=1"]),
     "poismf_hip_cg": ("poismf_hip.hip", ["-DPMF_TU=2"]),
     "poismf_hip_pg": ("poismf_hip.hip", ["-DPMF_TU=3"]),
