@@ -73,29 +73,11 @@ __global__ __launch_bounds__(256) void grow_indptr_kernel(const u64* indptr, siz
 __global__ __launch_bounds__(256) void grow_major_kernel(const u64* indptr, size_t n, size_t total, unsigned first, unsigned* major)
 {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        size_t lo = 0, hi = n - 1;
-        while (lo < hi) {
-            const size_t mid = lo + (hi - lo + 1) / 2;
-            if (indptr[mid] <= e) lo = mid; else hi = mid - 1;
-        }
-        major[e] = first + (unsigned)lo;
+        major[e] = first + (unsigned)upd_row_of(indptr, 0, n - 1, e);
     }
 }
 
 // ---- the growth step ----------------------------------------------------------------------------------------------------------------------
-
-// everything the growth allocates; what has not been handed to the session is freed by the destructor
-struct Grown {
-    hipStream_t stream;
-    real_t *M = nullptr, *Mp = nullptr;
-    u64* indptr = nullptr;
-    unsigned *eval_rows = nullptr, *dec_rows = nullptr;
-    explicit Grown(hipStream_t st) : stream(st) {}
-    ~Grown()
-    {
-        for (void* p : { (void*)M, (void*)Mp, (void*)indptr, (void*)eval_rows, (void*)dec_rows }) pmf_free(p, stream);
-    }
-};
 
 // n_new empty rows behind half `which` (1: users, 0: items), their factor rows from d_F (device [n_new x k], or nullptr: zeros).  All new
 // arrays are built beside the old ones and take their place only when all exist: a failure (1) leaves the session as it was.  Afterwards
@@ -105,31 +87,34 @@ int grow(poismf_hip_session* s, int which, size_t n_new, const real_t* d_F)
     const hipStream_t st = s->stream;
     Half& h = s->half[which];
     const size_t k = s->k, old_dim = h.dimM, new_dim = old_dim + n_new;
-    const size_t rowb = k * sizeof(real_t), padb = s->ld * sizeof(real_t);
+    const size_t slack = 16 / sizeof(real_t);   // (the 16 bytes session_alloc promises behind a factor)
     real_t*& M = which ? s->dA : s->dB;
     real_t*& Mp = which ? s->dAp : s->dBp;
-    Grown g(st);
-    HIP_TRY(pmf_alloc(&g.M, new_dim * rowb + rowb + 16, st));
-    if (s->ld != 0) HIP_TRY(pmf_alloc(&g.Mp, new_dim * padb + padb + 16, st));
-    HIP_TRY(pmf_alloc(&g.indptr, sizeof(u64) * (new_dim + 1), st));
-    if (h.d_eval_rows != nullptr) HIP_TRY(pmf_alloc(&g.eval_rows, sizeof(unsigned) * new_dim, st));
-    if (h.d_dec_rows != nullptr) HIP_TRY(pmf_alloc(&g.dec_rows, 2 * sizeof(unsigned) * new_dim, st));
+    Scratch sc(st);   // (what has not been handed to the session goes with it)
+    real_t *new_M = nullptr, *new_Mp = nullptr;
+    u64* new_indptr = nullptr;
+    unsigned *eval_rows = nullptr, *dec_rows = nullptr;
+    HIP_TRY(sc.get(&new_M, (new_dim + 1) * k + slack));
+    if (s->ld != 0) HIP_TRY(sc.get(&new_Mp, (new_dim + 1) * s->ld + slack));
+    HIP_TRY(sc.get(&new_indptr, new_dim + 1));
+    if (h.d_eval_rows != nullptr) HIP_TRY(sc.get(&eval_rows, new_dim));
+    if (h.d_dec_rows != nullptr) HIP_TRY(sc.get(&dec_rows, 2 * new_dim));
     {
         const size_t ld = s->ld != 0 ? s->ld : k;
         const size_t pieces = (new_dim + 1) * (ld * sizeof(real_t) / 16) + 1;
         const unsigned blocks = (unsigned)std::min<size_t>((pieces + 255) / 256, (size_t)s->num_cu * 16);
-        hipLaunchKernelGGL((grow_factor_kernel<real_t>), dim3(blocks), dim3(256), 0, st, M, d_F, old_dim, new_dim, (int)k, (int)ld, g.M, g.Mp);
+        hipLaunchKernelGGL((grow_factor_kernel<real_t>), dim3(blocks), dim3(256), 0, st, M, d_F, old_dim, new_dim, (int)k, (int)ld, new_M, new_Mp);
     }
-    hipLaunchKernelGGL(grow_indptr_kernel, dim3(grid_for(new_dim + 1)), dim3(256), 0, st, h.d_indptr, old_dim, (u64)h.nnz, new_dim, g.indptr);
+    hipLaunchKernelGGL(grow_indptr_kernel, dim3(grid_for(new_dim + 1)), dim3(256), 0, st, h.d_indptr, old_dim, (u64)h.nnz, new_dim, new_indptr);
     HIP_TRY(hipGetLastError());
     // a profiling session's per-row counters: the old rows keep theirs, the new rows start at zero
-    if (g.eval_rows != nullptr) {
-        HIP_TRY(hipMemcpyAsync(g.eval_rows, h.d_eval_rows, sizeof(unsigned) * old_dim, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemsetAsync(g.eval_rows + old_dim, 0, sizeof(unsigned) * n_new, st));
+    if (eval_rows != nullptr) {
+        HIP_TRY(hipMemcpyAsync(eval_rows, h.d_eval_rows, sizeof(unsigned) * old_dim, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(eval_rows + old_dim, 0, sizeof(unsigned) * n_new, st));
     }
-    if (g.dec_rows != nullptr) {
-        HIP_TRY(hipMemcpyAsync(g.dec_rows, h.d_dec_rows, 2 * sizeof(unsigned) * old_dim, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemsetAsync(g.dec_rows + 2 * old_dim, 0, 2 * sizeof(unsigned) * n_new, st));
+    if (dec_rows != nullptr) {
+        HIP_TRY(hipMemcpyAsync(dec_rows, h.d_dec_rows, 2 * sizeof(unsigned) * old_dim, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(dec_rows + 2 * old_dim, 0, 2 * sizeof(unsigned) * n_new, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     // the swap: from here on the session has the grown dimension
@@ -137,8 +122,8 @@ int grow(poismf_hip_session* s, int which, size_t n_new, const real_t* d_F)
     pmf_free(M, st); pmf_free(Mp, st); pmf_free(h.d_indptr, st);
     pmf_free(h.d_perm, st); pmf_free(h.d_desc, st);   // (finish_half sizes them anew)
     pmf_free(h.d_eval_rows, st); pmf_free(h.d_dec_rows, st);
-    M = g.M; Mp = g.Mp; h.d_indptr = g.indptr; h.d_eval_rows = g.eval_rows; h.d_dec_rows = g.dec_rows;
-    g.M = g.Mp = nullptr; g.indptr = nullptr; g.eval_rows = g.dec_rows = nullptr;
+    M = sc.release(new_M); Mp = sc.release(new_Mp); h.d_indptr = sc.release(new_indptr);
+    h.d_eval_rows = sc.release(eval_rows); h.d_dec_rows = sc.release(dec_rows);
     h.d_perm = nullptr; h.d_desc = nullptr;
     // (the padded copy was built from the compact rows: it is as fresh as it was -- padded_fresh[which] stays)
     (which ? s->dimA : s->dimB) = new_dim;
@@ -159,34 +144,19 @@ int grow(poismf_hip_session* s, int which, size_t n_new, const real_t* d_F)
 int grow_and_merge(poismf_hip_session* s, int which, size_t n_new, const real_t* d_F, const unsigned* d_new, const unsigned* d_other,
                    const real_t* d_val, size_t n, const std::vector<unsigned>& touched_new, const std::vector<unsigned>* touched_other)
 {
-    int nseg[2];
-    for (int w = 0; w < 2; w++) nseg[w] = (int)std::max<size_t>(s->half[w].segs.size(), 1);
+    Half& g = s->half[which];
+    const int nseg = (int)std::max<size_t>(g.segs.size(), 1);
     if (grow(s, which, n_new, d_F)) return 1;
-    if (n == 0) return finish_half(s->half[which], s->stream, nseg[which]);
-    // one orientation after the other, the CSR first (2b's order)
-    for (int w = 1; w >= 0; w--) {
-        Half& h = s->half[w];
+    if (n == 0) return finish_half(g, s->stream, nseg);
+    const int rc = both_halves(s, [&](int w, Half& h, bool* swapped) {
         const bool grown = w == which;
         size_t fresh = 0;
-        if (merge_half(s, h, grown ? d_new : d_other, grown ? d_other : d_new, d_val, n, grown ? &touched_new : touched_other, &fresh) ||
-            finish_half(h, s->stream, nseg[w])) {
-            if (s->half[which].d_perm == nullptr) (void)finish_half(s->half[which], s->stream, nseg[which]);   // the grown half, rows empty
-            return 1;
-        }
-    }
-    return 0;
-}
-
-// 2b's eligibility rule, in full: 0, 5 or 1 (device error)
-int eligible(poismf_hip_session* s)
-{
-    if (!whole_matrix_halves(s)) return 5;
-    for (int which = 0; which < 2; which++) {
-        const int asc = rows_ascending(s, which);
-        if (asc < 0) return 1;
-        if (asc == 0) return 5;
-    }
-    return 0;
+        const int r = merge_half(s, h, grown ? d_new : d_other, grown ? d_other : d_new, d_val, n, grown ? &touched_new : touched_other, &fresh);
+        *swapped = r == 0;
+        return r;
+    });
+    if (rc && g.d_perm == nullptr) (void)finish_half(g, s->stream, nseg);   // the grown half is owed one even when a merge fails: its rows stay empty
+    return rc ? 1 : 0;
 }
 
 }  // namespace
@@ -222,38 +192,27 @@ int poismf_hip_session_append_rows(poismf_hip_session* s, int which, size_t n_ne
     HIP_TRY(hipSetDevice(s->device));
     if (const int e = eligible(s)) return e;
     const hipStream_t st = s->stream;
-    std::vector<unsigned> touched_new, touched_other, h32;
+    std::vector<unsigned> touched_new, touched_other, major, h32;
     try {
         if (n > 0) {
             touched_other = distinct_sorted(indices + base, n, other);
-            for (size_t i = 0; i < n_new; i++)
+            major.resize(n);   // the cells' new-row index, from the row pointers
+            for (size_t i = 0; i < n_new; i++) {
                 if (indptr[i + 1] > indptr[i]) touched_new.push_back((unsigned)(dim + i));
+                for (size_t p = (size_t)indptr[i]; p < (size_t)indptr[i + 1]; p++) major[p - base] = (unsigned)(dim + i);
+            }
             h32.resize(n);
         }
     } catch (const std::bad_alloc&) { return 1; }
+    Scratch sc(st);
     real_t *d_F = nullptr, *d_val = nullptr;
     unsigned *d_new = nullptr, *d_other = nullptr;
-    int rc = 1;
-    do {
-        if (F != nullptr) {
-            if (pmf_alloc(&d_F, n_new * s->k * sizeof(real_t), st) != hipSuccess) break;
-            if (pmf_upload_big(d_F, F, n_new * s->k * sizeof(real_t), s->device, st) != hipSuccess) break;
-        }
-        if (n > 0) {
-            if (pmf_alloc(&d_new, sizeof(unsigned) * n, st) != hipSuccess || pmf_alloc(&d_other, sizeof(unsigned) * n, st) != hipSuccess ||
-                pmf_alloc(&d_val, sizeof(real_t) * n, st) != hipSuccess)
-                break;
-            for (size_t i = 0; i < n_new; i++)
-                for (size_t p = (size_t)indptr[i]; p < (size_t)indptr[i + 1]; p++) h32[p - base] = (unsigned)(dim + i);
-            if (pmf_upload(d_new, h32.data(), sizeof(unsigned) * n, st) != hipSuccess) break;
-            for (size_t p = 0; p < n; p++) h32[p] = (unsigned)indices[base + p];
-            if (pmf_upload(d_other, h32.data(), sizeof(unsigned) * n, st) != hipSuccess) break;
-            if (pmf_upload(d_val, val + base, sizeof(real_t) * n, st) != hipSuccess) break;
-        }
-        rc = grow_and_merge(s, which, n_new, d_F, d_new, d_other, d_val, n, touched_new, &touched_other);
-    } while (0);
-    for (void* p : { (void*)d_F, (void*)d_val, (void*)d_new, (void*)d_other }) pmf_free(p, st);
-    return rc;
+    if (F != nullptr) {
+        HIP_TRY(sc.get(&d_F, n_new * s->k));
+        HIP_TRY(pmf_upload_big(d_F, F, n_new * s->k * sizeof(real_t), s->device, st));
+    }
+    if (n > 0 && upload_cells(sc, major.data(), indices + base, val + base, n, h32, &d_new, &d_other, &d_val)) return 1;
+    return grow_and_merge(s, which, n_new, d_F, d_new, d_other, d_val, n, touched_new, &touched_other);
 }
 
 int poismf_hip_session_adopt_new(poismf_hip_session* s, size_t* first_row, size_t* n_rows)
@@ -278,26 +237,23 @@ int poismf_hip_session_adopt_new(poismf_hip_session* s, size_t* first_row, size_
     if (const int e = eligible(s)) return e;
     const hipStream_t st = s->stream;
     std::vector<unsigned> touched_new;
+    Scratch sc(st);
     unsigned* d_new = nullptr;
-    int rc = 1;
-    do {
-        if (n > 0) {
-            // the counts: the guest's row pointers say which new rows hold a cell; the cells themselves stay on the device
-            std::vector<u64> ip;
-            try {
-                ip.resize(n_new + 1);
-                if (pmf_download(ip.data(), gh.d_indptr, sizeof(u64) * (n_new + 1), st) != hipSuccess) break;
-                for (size_t i = 0; i < n_new; i++)
-                    if (ip[i + 1] > ip[i]) touched_new.push_back((unsigned)(dim + i));
-            } catch (const std::bad_alloc&) { break; }
-            if (pmf_alloc(&d_new, sizeof(unsigned) * n, st) != hipSuccess) break;
-            hipLaunchKernelGGL(grow_major_kernel, dim3(grid_for(n)), dim3(256), 0, st, gh.d_indptr, n_new, n, (unsigned)dim, d_new);
-            if (hipGetLastError() != hipSuccess) break;
-        }
-        // the guest's factor rows, column indices and values are read where they are
-        rc = grow_and_merge(s, 1, n_new, g->dA, d_new, gh.d_indices, gh.d_values, n, touched_new, nullptr);
-    } while (0);
-    pmf_free(d_new, st);
+    if (n > 0) {
+        // the counts: the guest's row pointers say which new rows hold a cell; the cells themselves stay on the device
+        std::vector<u64> ip;
+        try {
+            ip.resize(n_new + 1);
+            HIP_TRY(pmf_download(ip.data(), gh.d_indptr, sizeof(u64) * (n_new + 1), st));
+            for (size_t i = 0; i < n_new; i++)
+                if (ip[i + 1] > ip[i]) touched_new.push_back((unsigned)(dim + i));
+        } catch (const std::bad_alloc&) { return 1; }
+        HIP_TRY(sc.get(&d_new, n));
+        hipLaunchKernelGGL(grow_major_kernel, dim3(grid_for(n)), dim3(256), 0, st, gh.d_indptr, n_new, n, (unsigned)dim, d_new);
+        HIP_TRY(hipGetLastError());
+    }
+    // the guest's factor rows, column indices and values are read where they are
+    const int rc = grow_and_merge(s, 1, n_new, g->dA, d_new, gh.d_indices, gh.d_values, n, touched_new, nullptr);
     if (rc == 0 && n_rows != nullptr) *n_rows = n_new;
     return rc;
 }

@@ -5,7 +5,6 @@
 // survivors -- or, when no cell leaves, one pass rewrites the values in place and nothing else of the half is touched.  The chunking
 // and the host-side eligibility helpers are session_merge.hpp's.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -31,21 +30,12 @@ struct ChunkRows {
 // relative to c0 (0 for the row that began before the chunk) when they fit; the caller puts a barrier behind it.
 __device__ __forceinline__ ChunkRows scl_chunk_rows(const u64* __restrict__ indptr, size_t dimM, size_t c0, size_t c1, unsigned* s_off)
 {
-    size_t lo = 0, hi = dimM - 1;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (indptr[mid] <= c0) lo = mid; else hi = mid - 1;
-    }
-    const size_t r_lo = lo;
-    hi = dimM - 1;
-    while (lo < hi) {
-        const size_t mid = lo + (hi - lo + 1) / 2;
-        if (indptr[mid] <= c1 - 1) lo = mid; else hi = mid - 1;
-    }
+    const size_t r_lo = upd_row_of(indptr, 0, dimM - 1, c0);
+    const size_t r_hi = upd_row_of(indptr, r_lo, dimM - 1, c1 - 1);
     ChunkRows c;
     c.r_lo = r_lo;
-    c.nrows = (unsigned)std::min<size_t>(lo - r_lo + 1, 0xffffffffu);
-    c.staged = lo - r_lo + 1 <= SCL_STAGE;
+    c.nrows = (unsigned)std::min<size_t>(r_hi - r_lo + 1, 0xffffffffu);
+    c.staged = r_hi - r_lo + 1 <= SCL_STAGE;
     if (c.staged)
         for (unsigned j = threadIdx.x; j < c.nrows; j += 256) {
             const u64 p = indptr[r_lo + j];
@@ -66,7 +56,7 @@ __device__ __forceinline__ size_t scl_row_of(const ChunkRows& c, const unsigned*
         }
         return c.r_lo + lo;
     }
-    size_t lo = c.r_lo, hi = c.r_lo + c.nrows - 1;
+    size_t lo = c.r_lo, hi = c.r_lo + c.nrows - 1;   // (upd_row_of's search written out: through the helper scl_inplace_kernel grows)
     const u64 p = c0 + e;
     while (lo < hi) {
         const size_t mid = lo + (hi - lo + 1) / 2;
@@ -83,6 +73,32 @@ template <class T> __device__ __forceinline__ T scl_value(T x, T gamma, T major,
     a = a * (user_major ? major : minor);
     a = a * (user_major ? minor : major);
     return a;
+}
+
+// The new value of entry c0 + e of the chunk (value x, index ix): its operands are fetched here -- the major scale through the entry's
+// row, the minor one through its index -- for the decide and the in-place pass; the compact pass carries the same three lines itself.
+template <class T>
+__device__ __forceinline__ T scl_entry(T x, unsigned ix, unsigned e, size_t c0, const ChunkRows& rows, const unsigned* s_off,
+                                       const u64* __restrict__ indptr, T gamma, const T* __restrict__ major, const T* __restrict__ minor,
+                                       int user_major)
+{
+    const T M = major != nullptr ? major[scl_row_of(rows, s_off, indptr, c0, e)] : (T)1;
+    const T m = minor != nullptr ? minor[ix] : (T)1;
+    return scl_value(x, gamma, M, m, user_major != 0);
+}
+
+// a thread's UPD_PER entries of the chunk [c0, c1) for the passes that write no index: the values, and the indices only when the
+// minor vector is given; 0 behind c1
+template <class T>
+__device__ __forceinline__ void scl_chunk_load(const unsigned* __restrict__ indices, const T* values, bool with_indices, size_t c0, size_t c1,
+                                               unsigned (&ix)[UPD_PER], T (&v)[UPD_PER])
+{
+#pragma unroll
+    for (int q = 0; q < UPD_PER; q++) {
+        const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
+        ix[q] = 0; v[q] = (T)0;
+        if (p < c1) { v[q] = values[p]; if (with_indices) ix[q] = indices[p]; }
+    }
 }
 
 // The decide pass: reads the values (and the indices when the minor vector is given; looks rows up when the major one is), writes a keep
@@ -108,12 +124,7 @@ __global__ __launch_bounds__(256) void scl_decide_kernel(const u64* __restrict__
         }
         unsigned ix[UPD_PER];
         T v[UPD_PER];
-#pragma unroll
-        for (int q = 0; q < UPD_PER; q++) {
-            const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
-            ix[q] = 0; v[q] = (T)0;
-            if (p < c1) { v[q] = values[p]; if (minor != nullptr) ix[q] = indices[p]; }
-        }
+        scl_chunk_load(indices, values, minor != nullptr, c0, c1, ix, v);
         unsigned wcnt = 0;
 #pragma unroll
         for (int q = 0; q < UPD_PER; q++) {
@@ -121,9 +132,7 @@ __global__ __launch_bounds__(256) void scl_decide_kernel(const u64* __restrict__
             const bool in = c0 + e < c1;
             bool stays = false;
             if (in) {
-                const T M = major != nullptr ? major[scl_row_of(rows, s_off, indptr, c0, e)] : (T)1;
-                const T m = minor != nullptr ? minor[ix[q]] : (T)1;
-                const T nv = scl_value(v[q], gamma, M, m, user_major != 0);
+                const T nv = scl_entry(v[q], ix[q], e, c0, rows, s_off, indptr, gamma, major, minor, user_major);
                 if (!isfinite(nv)) bad++;
                 stays = nv > floor;
             }
@@ -205,6 +214,7 @@ __global__ __launch_bounds__(256) void scl_compact_kernel(const u64* __restrict_
             const unsigned e = (unsigned)q * 256 + threadIdx.x;
             const u64 word = s_word[q * 4 + wave];
             if (c0 + e >= c1 || !((word >> lane) & 1ull)) continue;
+            // (scl_entry's text written out: through the helper this kernel's instruction count moves)
             const T M = major != nullptr ? major[scl_row_of(rows, s_off, indptr, c0, e)] : (T)1;
             const T m = minor != nullptr ? minor[ix[q]] : (T)1;
             const u64 pos = cbase + s_pre[q * 4 + wave] + (u64)__popcll(word & ((1ull << lane) - 1));
@@ -232,38 +242,16 @@ __global__ __launch_bounds__(256) void scl_inplace_kernel(const u64* __restrict_
         }
         unsigned ix[UPD_PER];
         T v[UPD_PER];
-#pragma unroll
-        for (int q = 0; q < UPD_PER; q++) {
-            const size_t p = c0 + (size_t)q * 256 + threadIdx.x;
-            ix[q] = 0; v[q] = (T)0;
-            if (p < c1) { v[q] = values[p]; if (minor != nullptr) ix[q] = indices[p]; }
-        }
+        scl_chunk_load(indices, values, minor != nullptr, c0, c1, ix, v);
 #pragma unroll
         for (int q = 0; q < UPD_PER; q++) {
             const unsigned e = (unsigned)q * 256 + threadIdx.x;
             if (c0 + e >= c1) continue;
-            const T M = major != nullptr ? major[scl_row_of(rows, s_off, indptr, c0, e)] : (T)1;
-            const T m = minor != nullptr ? minor[ix[q]] : (T)1;
-            values[c0 + e] = scl_value(v[q], gamma, M, m, user_major != 0);
+            values[c0 + e] = scl_entry(v[q], ix[q], e, c0, rows, s_off, indptr, gamma, major, minor, user_major);
         }
         if (major != nullptr) __syncthreads();   // (s_off is the next chunk's from here on)
     }
 }
-
-// Everything one orientation's pass allocates; freed by the destructor whichever way the pass ends.
-struct ScaleScratch {
-    hipStream_t stream;
-    u64 *keep = nullptr, *kept = nullptr, *base = nullptr, *nonfinite = nullptr, *new_indptr = nullptr;
-    unsigned* new_indices = nullptr;
-    real_t* new_values = nullptr;
-    void* tmp = nullptr;
-    explicit ScaleScratch(hipStream_t st) : stream(st) {}
-    ~ScaleScratch()
-    {
-        for (void* p : { (void*)keep, (void*)kept, (void*)base, (void*)nonfinite, (void*)new_indptr, (void*)new_indices, (void*)new_values, tmp })
-            pmf_free(p, stream);
-    }
-};
 
 // Half h (nnz > 0) scaled: d_major / d_minor are the scale vectors of its rows / of its indices on the device (nullptr: ones).
 // `expect` (the CSC's pass): the count of leaving cells the CSR found; a different one is an error.  0, 1, or 7: some result is not
@@ -275,22 +263,21 @@ int scale_half(poismf_hip_session* s, Half& h, int which, real_t gamma, const re
     const size_t dimM = h.dimM, nnz = h.nnz;
     const size_t nchunks = (nnz + UPD_CHUNK - 1) / UPD_CHUNK;
     const unsigned grid = (unsigned)std::min<size_t>(nchunks, (size_t)s->num_cu * 8);
-    ScaleScratch m(st);
+    Scratch sc(st);
+    u64 *keep = nullptr, *kept = nullptr, *base = nullptr, *nonfinite = nullptr, *new_indptr = nullptr;
+    unsigned* new_indices = nullptr;
+    real_t* new_values = nullptr;
     *swapped = false;
-    HIP_TRY(pmf_alloc(&m.keep, sizeof(u64) * nchunks * SCL_WORDS, st));
-    HIP_TRY(pmf_alloc(&m.kept, sizeof(u64) * (nchunks + 1), st));
-    HIP_TRY(pmf_alloc(&m.base, sizeof(u64) * (nchunks + 1), st));
-    HIP_TRY(pmf_alloc(&m.nonfinite, sizeof(u64), st));
-    HIP_TRY(hipMemsetAsync(m.nonfinite, 0, sizeof(u64), st));
+    HIP_TRY(sc.get(&keep, nchunks * SCL_WORDS));
+    HIP_TRY(sc.get(&kept, nchunks + 1));
+    HIP_TRY(sc.get(&base, nchunks + 1));
+    HIP_TRY(sc.get(&nonfinite, 1));
+    HIP_TRY(hipMemsetAsync(nonfinite, 0, sizeof(u64), st));
     hipLaunchKernelGGL((scl_decide_kernel<real_t>), dim3(grid), dim3(256), 0, st, h.d_indptr, h.d_indices, h.d_values, nnz, dimM, gamma, d_major,
-                       d_minor, which, floor, m.keep, m.kept, m.nonfinite);
-    size_t tmp_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, m.kept, m.base, (u64)0, nchunks + 1, rocprim::plus<u64>(), st));
-    HIP_TRY(pmf_alloc(&m.tmp, tmp_bytes ? tmp_bytes : 16, st));
-    HIP_TRY(rocprim::exclusive_scan(m.tmp, tmp_bytes, m.kept, m.base, (u64)0, nchunks + 1, rocprim::plus<u64>(), st));
+                       d_minor, which, floor, keep, kept, nonfinite);
     u64 stay = 0, bad = 0;
-    HIP_TRY(pmf_download(&stay, m.base + nchunks, sizeof(u64), st));
-    HIP_TRY(pmf_download(&bad, m.nonfinite, sizeof(u64), st));
+    if (scan_exclusive(sc, kept, base, nchunks + 1, &stay)) return 1;
+    HIP_TRY(pmf_download(&bad, nonfinite, sizeof(u64), st));
     if (stay > nnz) return 1;
     *n_gone = nnz - (size_t)stay;
     if (expect != nullptr) {
@@ -305,19 +292,15 @@ int scale_half(poismf_hip_session* s, Half& h, int which, real_t gamma, const re
         return 0;
     }
     const size_t nnz_new = (size_t)stay;
-    HIP_TRY(pmf_alloc(&m.new_indptr, sizeof(u64) * (dimM + 1), st));
-    HIP_TRY(pmf_alloc(&m.new_indices, sizeof(unsigned) * (nnz_new ? nnz_new : 1), st));
-    HIP_TRY(pmf_alloc(&m.new_values, sizeof(real_t) * (nnz_new ? nnz_new : 1), st));
-    hipLaunchKernelGGL(scl_indptr_kernel, dim3(grid_for(dimM + 1)), dim3(256), 0, st, h.d_indptr, dimM, nnz, m.keep, m.base, m.new_indptr);
+    HIP_TRY(sc.get(&new_indptr, dimM + 1));
+    HIP_TRY(sc.get(&new_indices, nnz_new ? nnz_new : 1));
+    HIP_TRY(sc.get(&new_values, nnz_new ? nnz_new : 1));
+    hipLaunchKernelGGL(scl_indptr_kernel, dim3(grid_for(dimM + 1)), dim3(256), 0, st, h.d_indptr, dimM, nnz, keep, base, new_indptr);
     hipLaunchKernelGGL((scl_compact_kernel<real_t>), dim3(grid), dim3(256), 0, st, h.d_indptr, h.d_indices, h.d_values, nnz, dimM, gamma, d_major,
-                       d_minor, which, m.keep, m.base, m.new_indices, m.new_values);
+                       d_minor, which, keep, base, new_indices, new_values);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    // the swap: from here on the half is the scaled one
-    pmf_free(h.d_indptr, st); pmf_free(h.d_indices, st); pmf_free(h.d_values, st);
-    h.d_indptr = m.new_indptr; h.d_indices = m.new_indices; h.d_values = m.new_values;
-    m.new_indptr = nullptr; m.new_indices = nullptr; m.new_values = nullptr;
-    h.nnz = nnz_new;
+    swap_in(h, sc, new_indptr, new_indices, new_values, nnz_new);   // from here on the half is the scaled one
     *swapped = true;
     return 0;
 }
@@ -344,40 +327,26 @@ int poismf_hip_session_scale(poismf_hip_session* s, real_t gamma, const real_t* 
     if (gamma == (real_t)1 && row_scale == nullptr && col_scale == nullptr && floor == (real_t)0) return 0;
     pmf_last_hip_error() = hipSuccess;
     HIP_TRY(hipSetDevice(s->device));
-    if (!whole_matrix_halves(s)) return 5;
-    for (int which = 0; which < 2; which++) {
-        const int asc = rows_ascending(s, which);
-        if (asc < 0) return 1;
-        if (asc == 0) return 5;
-    }
+    if (const int e = eligible(s)) return e;
     const hipStream_t st = s->stream;
+    Scratch sc(st);
     real_t *d_row = nullptr, *d_col = nullptr;
-    int rc = 1;
+    if (row_scale != nullptr) {
+        HIP_TRY(sc.get(&d_row, s->dimA));
+        HIP_TRY(pmf_upload(d_row, row_scale, sizeof(real_t) * s->dimA, st));
+    }
+    if (col_scale != nullptr) {
+        HIP_TRY(sc.get(&d_col, s->dimB));
+        HIP_TRY(pmf_upload(d_col, col_scale, sizeof(real_t) * s->dimB, st));
+    }
     size_t gone = 0;
-    bool written = false;
-    do {
-        if (row_scale != nullptr) {
-            if (pmf_alloc(&d_row, sizeof(real_t) * s->dimA, st) != hipSuccess) break;
-            if (pmf_upload(d_row, row_scale, sizeof(real_t) * s->dimA, st) != hipSuccess) break;
-        }
-        if (col_scale != nullptr) {
-            if (pmf_alloc(&d_col, sizeof(real_t) * s->dimB, st) != hipSuccess) break;
-            if (pmf_upload(d_col, col_scale, sizeof(real_t) * s->dimB, st) != hipSuccess) break;
-        }
-        rc = 0;
-        for (int which = 1; which >= 0 && rc == 0; which--) {   // the CSR first: it decides what leaves and whether every result is finite
-            Half& h = s->half[which];
-            const int nseg = (int)std::max<size_t>(h.segs.size(), 1);
-            size_t left = 0;
-            bool swapped = false;
-            rc = scale_half(s, h, which, gamma, which ? d_row : d_col, which ? d_col : d_row, floor, which ? nullptr : &gone, &left, &swapped);
-            if (which) gone = left;
-            if (rc == 0 && swapped) { written = true; rc = finish_half(h, st, nseg); }   // (sorted and binned again)
-        }
-    } while (0);
-    if (written) s->topn_indptr.clear();   // exclude_seen reads the shortened rows' pointers
-    pmf_free(d_row, st);
-    pmf_free(d_col, st);
+    // (the CSR comes first: it decides what leaves and whether every result is finite)
+    const int rc = both_halves(s, [&](int which, Half& h, bool* swapped) {
+        size_t left = 0;
+        const int r = scale_half(s, h, which, gamma, which ? d_row : d_col, which ? d_col : d_row, floor, which ? nullptr : &gone, &left, swapped);
+        if (which) gone = left;
+        return r;
+    });
     if (rc == 0 && n_removed != nullptr) *n_removed = gone;
     return rc;
 }

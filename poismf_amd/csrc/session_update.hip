@@ -11,16 +11,6 @@
 
 #include "session_merge.hpp"
 
-namespace {
-
-__global__ __launch_bounds__(256) void rows_len_kernel(const u64* indptr, const unsigned* rows, size_t n, unsigned* len)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        len[i] = (unsigned)(indptr[rows[i] + 1] - indptr[rows[i]]);
-}
-
-}  // namespace
-
 extern "C" {
 
 int poismf_hip_session_add_coo(poismf_hip_session* s, const sparse_ix* row, const sparse_ix* col, const real_t* val, size_t n, size_t* n_new_cells)
@@ -32,44 +22,21 @@ int poismf_hip_session_add_coo(poismf_hip_session* s, const sparse_ix* row, cons
         if ((long long)row[i] < 0 || (size_t)row[i] >= s->dimA || (long long)col[i] < 0 || (size_t)col[i] >= s->dimB) return 3;
     for (size_t i = 0; i < n; i++)
         if (!std::isfinite(val[i]) || !(val[i] > (real_t)0)) return 4;
-    if (!whole_matrix_halves(s)) return 5;
     pmf_last_hip_error() = hipSuccess;
     HIP_TRY(hipSetDevice(s->device));
-    for (int which = 0; which < 2; which++) {
-        const int asc = rows_ascending(s, which);
-        if (asc < 0) return 1;
-        if (asc == 0) return 5;
-    }
+    if (const int e = eligible(s)) return e;
     std::vector<unsigned> rows, cols, h32;
     try { rows = distinct_sorted(row, n, s->dimA); cols = distinct_sorted(col, n, s->dimB); h32.resize(n); } catch (const std::bad_alloc&) { return 1; }
+    Scratch sc(s->stream);
     unsigned *d_row = nullptr, *d_col = nullptr;
     real_t* d_val = nullptr;
-    int rc = 1;
+    if (upload_cells(sc, row, col, val, n, h32, &d_row, &d_col, &d_val)) return 1;
     size_t fresh[2] = { 0, 0 };
-    do {
-        if (pmf_alloc(&d_row, sizeof(unsigned) * n, s->stream) != hipSuccess || pmf_alloc(&d_col, sizeof(unsigned) * n, s->stream) != hipSuccess ||
-            pmf_alloc(&d_val, sizeof(real_t) * n, s->stream) != hipSuccess)
-            break;
-        for (size_t i = 0; i < n; i++) h32[i] = (unsigned)row[i];
-        if (pmf_upload(d_row, h32.data(), sizeof(unsigned) * n, s->stream) != hipSuccess) break;
-        for (size_t i = 0; i < n; i++) h32[i] = (unsigned)col[i];
-        if (pmf_upload(d_col, h32.data(), sizeof(unsigned) * n, s->stream) != hipSuccess) break;
-        if (pmf_upload(d_val, val, sizeof(real_t) * n, s->stream) != hipSuccess) break;
-        // one orientation after the other: the CSR (major = row), then the CSC (major = column); each is finished with the segments it had
-        bool ok = true;
-        for (int which = 1; which >= 0 && ok; which--) {
-            Half& h = s->half[which];
-            const int nseg = (int)std::max<size_t>(h.segs.size(), 1);
-            ok = merge_half(s, h, which ? d_row : d_col, which ? d_col : d_row, d_val, n, which ? &rows : &cols, &fresh[which]) == 0 &&
-                 finish_half(h, s->stream, nseg) == 0;
-        }
-        if (!ok) break;
-        rc = 0;
-    } while (0);
-    pmf_free(d_row, s->stream);
-    pmf_free(d_col, s->stream);
-    pmf_free(d_val, s->stream);
-    s->topn_indptr.clear();   // exclude_seen reads the merged rows' pointers
+    const int rc = both_halves(s, [&](int which, Half& h, bool* swapped) {
+        const int r = merge_half(s, h, which ? d_row : d_col, which ? d_col : d_row, d_val, n, which ? &rows : &cols, &fresh[which]);
+        *swapped = r == 0;   // (a merge that succeeds has swapped)
+        return r;
+    });
     if (rc == 0 && n_new_cells != nullptr) *n_new_cells = fresh[1];
     return rc;
 }
@@ -124,31 +91,25 @@ int poismf_hip_half_sweep_rows(poismf_hip_session* s, int which, const sparse_ix
     Half v;   // the view: the half's matrix and counters, a permutation, descriptors and one segment of its own
     v.dimM = h.dimM; v.dimF = h.dimF; v.row_begin = h.row_begin; v.row_end = h.row_end; v.nnz = h.nnz; v.x_positive = h.x_positive;
     v.d_indptr = h.d_indptr; v.d_indices = h.d_indices; v.d_values = h.d_values; v.d_eval_rows = h.d_eval_rows; v.d_dec_rows = h.d_dec_rows;
+    Scratch sc(s->stream);   // (owns the view's permutation and descriptors: they go when this call returns)
     unsigned* d_len = nullptr;
-    int rc = 1;
-    do {
-        if (pmf_alloc(&v.d_perm, sizeof(unsigned) * n_rows, s->stream) != hipSuccess || pmf_alloc(&v.d_desc, sizeof(RowDesc) * n_rows, s->stream) != hipSuccess ||
-            pmf_alloc(&d_len, sizeof(unsigned) * n_rows, s->stream) != hipSuccess)
-            break;
-        if (pmf_upload(v.d_perm, local.data(), sizeof(unsigned) * n_rows, s->stream) != hipSuccess) break;
-        hipLaunchKernelGGL(rows_len_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s->stream, h.d_indptr, v.d_perm, n_rows, d_len);
-        if (pmf_download(len.data(), d_len, sizeof(unsigned) * n_rows, s->stream) != hipSuccess) break;
-        // longest first, equal lengths by row number: the order finish_half gives a whole half
-        std::iota(order.begin(), order.end(), 0u);
-        std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return len[a] != len[b] ? len[a] > len[b] : local[a] < local[b]; });
-        std::vector<unsigned> perm(n_rows), slen(n_rows);
-        for (size_t i = 0; i < n_rows; i++) { perm[i] = local[order[i]]; slen[i] = len[order[i]]; }
-        if (pmf_upload(v.d_perm, perm.data(), sizeof(unsigned) * n_rows, s->stream) != hipSuccess) break;
-        if (row_desc_launch(h.d_indptr, v.d_perm, n_rows, v.d_desc, s->stream)) break;
-        v.segs.push_back({ 0u, (unsigned)n_rows, bins_of(slen.data(), 0, n_rows) });
-        if (half_sweep_impl(s, which, p, step_size, cnst_div, n_unchanged, nullptr, (real_t)0, (real_t)1, -1, &v)) break;
-        if (hipStreamSynchronize(s->stream) != hipSuccess) break;   // (the launches read the view's arrays, which go now)
-        rc = 0;
-    } while (0);
-    pmf_free(d_len, s->stream);
-    pmf_free(v.d_perm, s->stream);
-    pmf_free(v.d_desc, s->stream);
-    return rc;
+    HIP_TRY(sc.get(&v.d_perm, n_rows));
+    HIP_TRY(sc.get(&v.d_desc, n_rows));
+    HIP_TRY(sc.get(&d_len, n_rows));
+    HIP_TRY(pmf_upload(v.d_perm, local.data(), sizeof(unsigned) * n_rows, s->stream));
+    hipLaunchKernelGGL(rows_len_kernel, dim3(grid_for(n_rows)), dim3(256), 0, s->stream, h.d_indptr, v.d_perm, n_rows, false, d_len);
+    HIP_TRY(pmf_download(len.data(), d_len, sizeof(unsigned) * n_rows, s->stream));
+    // longest first, equal lengths by row number: the order finish_half gives a whole half
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return len[a] != len[b] ? len[a] > len[b] : local[a] < local[b]; });
+    std::vector<unsigned> perm(n_rows), slen(n_rows);
+    for (size_t i = 0; i < n_rows; i++) { perm[i] = local[order[i]]; slen[i] = len[order[i]]; }
+    HIP_TRY(pmf_upload(v.d_perm, perm.data(), sizeof(unsigned) * n_rows, s->stream));
+    if (row_desc_launch(h.d_indptr, v.d_perm, n_rows, v.d_desc, s->stream)) return 1;
+    v.segs.push_back({ 0u, (unsigned)n_rows, bins_of(slen.data(), 0, n_rows) });
+    if (half_sweep_impl(s, which, p, step_size, cnst_div, n_unchanged, nullptr, (real_t)0, (real_t)1, -1, &v)) return 1;
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the launches read the view's arrays, which go now)
+    return 0;
 }
 
 }  // extern "C"

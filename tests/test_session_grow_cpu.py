@@ -11,7 +11,7 @@ import pytest
 import scipy.sparse as sp
 
 from poismf_amd import api, build
-from tests.test_session_update_cpu import DIMA, DIMB, ROOT, stub_session
+from tests.test_session_update_cpu import DIMA, DIMB, ROOT, assert_the_unit_uses_the_shared_pieces, stub_session
 
 NAMES = ("poismf_hip_session_append_rows", "poismf_hip_session_adopt_new")
 K = 4   # stub_session's
@@ -53,6 +53,10 @@ def test_the_three_units_share_the_merge_through_the_header():
         assert not set(shared) & set(kernels(unit)), unit
         assert "int merge_half(" not in read(unit)
     assert set(kernels("session_grow.hip")) == {"grow_factor_kernel", "grow_indptr_kernel", "grow_major_kernel"}
+
+
+def test_the_unit_uses_the_shared_pieces():
+    assert_the_unit_uses_the_shared_pieces("session_grow.hip")
 
 
 def rows_of(n, width, cells=((0, 0, 1.0),), dtype=np.float64):

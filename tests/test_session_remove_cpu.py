@@ -11,7 +11,7 @@ import pytest
 import scipy.sparse as sp
 
 from poismf_amd import api, build
-from tests.test_session_update_cpu import DIMA, DIMB, ROOT, stub_session, triplets
+from tests.test_session_update_cpu import DIMA, DIMB, ROOT, assert_the_unit_uses_the_shared_pieces, stub_session, triplets
 
 NAMES = ("poismf_hip_session_sub_coo", "poismf_hip_session_remove_rows")
 
@@ -49,6 +49,10 @@ def test_the_two_units_share_their_kernels_through_the_header():
         defined = re.findall(r"__global__[^\n]*?void\s+(\w+)\s*\(", read(unit))
         assert not set(shared) & set(defined), unit
     assert "rem_compact_kernel" in re.findall(r"__global__[^\n]*?void\s+(\w+)\s*\(", read("session_remove.hip"))
+
+
+def test_the_unit_uses_the_shared_pieces():
+    assert_the_unit_uses_the_shared_pieces("session_remove.hip")
 
 
 BAD_CELLS = {

@@ -11,7 +11,7 @@ import scipy.sparse as sp
 
 from poismf_amd import api, build
 from tests.session_scale_values import expected
-from tests.test_session_update_cpu import DIMA, DIMB, stub_session
+from tests.test_session_update_cpu import DIMA, DIMB, assert_the_unit_uses_the_shared_pieces, stub_session
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "poismf_hip_session_scale"
@@ -41,6 +41,10 @@ def test_the_unit_is_registered_and_brings_kernels_of_its_own():
     shared, own = kernels("session_merge.hpp"), kernels("session_scale.hip")
     assert "upd_scatter_kernel" in shared and not set(shared) & set(own)
     assert set(own) == {"scl_decide_kernel", "scl_indptr_kernel", "scl_compact_kernel", "scl_inplace_kernel"}
+
+
+def test_the_unit_uses_the_shared_pieces():
+    assert_the_unit_uses_the_shared_pieces("session_scale.hip")
 
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------------

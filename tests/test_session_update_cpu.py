@@ -63,6 +63,24 @@ def test_the_unit_is_registered():
     assert build.UNITS["session_update"] == ("session_update.hip", [])
 
 
+def assert_the_unit_uses_the_shared_pieces(unit):
+    """what the four units that change a resident matrix share has one home, session_merge.hpp: the eligibility rule, the two rocPRIM calls
+    (scan_exclusive, touched_rows_on_device) and the owner of device scratch -- `unit` brings no second copy of any of them"""
+    read = lambda name: open(os.path.join(build.CSRC, name)).read()
+    shared, text = read("session_merge.hpp"), read(unit)
+    assert re.search(r"^int eligible\(", shared, re.M) and "class Scratch" in shared
+    assert "rocprim::exclusive_scan(" in shared and "rocprim::select(" in shared
+    assert not re.search(r"^\s*(int|bool)\s+eligible\(", text, re.M), unit
+    assert "eligible(s)" in text, unit   # ... and asks it
+    assert "rocprim::exclusive_scan(" not in text and "rocprim::select(" not in text, unit
+    assert not re.search(r"^\s*(?:virtual\s+)?~\w+\s*\(\s*\)", text, re.M), unit   # no struct with a destructor (that frees through pmf_free) of its own
+    assert "whole_matrix_halves(" not in text and "while (0)" not in text, unit   # no inline copy of the rule, no do / while (0) ladder
+
+
+def test_the_unit_uses_the_shared_pieces():
+    assert_the_unit_uses_the_shared_pieces("session_update.hip")
+
+
 BAD_UPDATES = {
     "wrong shape": triplets([0], [0], [1.0], shape=(DIMA, DIMB + 1)),
     "row == dimA": triplets([DIMA], [0], [1.0]),
