@@ -792,6 +792,55 @@ POISMF_HIP_API size_t poismf_hip_topn_adjusted_scratch_bytes(size_t n_users, siz
 POISMF_HIP_API size_t poismf_hip_topn_adjusted_slices(size_t len, size_t n_top, int bound);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1s. Batched re-rank: whole per-user candidate lists put in the model's order, with scores, in one call (no counterpart in the
+ *     reference).  Section 1l retrieves up to 1024 items out of the whole catalogue and section 1h the best n_top <= 128 of a list;
+ *     this is the stage between them: the lists another system produced (a retrieval stage, a search result, a store's stock),
+ *     hundreds to thousands of items per user, come back complete and ordered -- for business rules, blending with another ranker,
+ *     pagination past the first page.  Only the listed rows of B are read; nothing is thrown away, so the scores are sorted, not
+ *     selected.
+ *
+ * For a batch of users u_0 .. u_{m-1} (any order, repeats allowed) and per user
+ *
+ *   I(u), E(u), score(u, j)   exactly those of section 1h: the include list incl_indptr [m + 1] / incl_indices (rows strictly
+ *                ascending, indices < dimB, rows may be empty), exclude_seen on a session and / or the exclusion list excl_indptr /
+ *                excl_indices (excl_indptr = NULL: no list), and the fused chain  s = +0; s = fma(A[u,c], B[j,c], s)  in real_t, bit
+ *                for bit what predict_multiple / poismf_hip_session_predict return.
+ *   answer(u)    ALL of I(u) \ E(u) under section 1f's total order: score descending, then item index ascending.  It is a function
+ *                of (A[u], B, I(u), E(u)) alone: not of the other users, the batch order, how rows are binned by their length, how a
+ *                long row is cut into runs or how the batch is cut into chunks.  Its first min(|answer|, n) entries, n <= 128, are
+ *                poismf_hip_topn_include's row for the same lists, bit for bit.
+ *   output       shaped like the input: row i of out_ix (and, unless NULL, of out_score) occupies entries
+ *                incl_indptr[i] - incl_indptr[0] .. incl_indptr[i + 1] - incl_indptr[0]; its first out_count[i] entries are the
+ *                answer, the rest POISMF_HIP_TOPN_NONE / -inf.  out_count [m] may be NULL (the count is then the number of entries
+ *                of the row that are not POISMF_HIP_TOPN_NONE).  Host arrays.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for everything that is 2 in
+ * section 1h apart from its n_top clause, and for an include row longer than POISMF_HIP_ORDER_MAX_ROW (section 1g's held-out row
+ * limit; a longer list belongs on the dense path).  n_users == 0 returns 0.  Factors are assumed finite.
+ *
+ * Three kernels by row length.  Rows of at most poismf_hip_order_include_wave_row() candidates: one wave
+ * per row, keys in registers, a bitonic network on lane exchanges alone.  Rows of at most poismf_hip_order_include_run() (a power
+ * of two): one workgroup per row, whose network goes through LDS only where its distance leaves the wave.  Longer rows: sorted runs
+ * of that length, then pairwise merge passes (merge path under the total order) between two areas of the scratch.  Both aids are
+ * testing aids and make no HIP call.  No float atomics; no result depends on the order in which anything arrives.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1r share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB
+ * for any number of users and cells: the batch is cut into chunks of consecutive users whose lists, keys and results fit.
+ * poismf_hip_order_include_scratch_bytes (testing aid, no HIP call; n_cells is incl_indptr[n_users] - incl_indptr[0]) is the size
+ * both entry points allocate; it does not depend on k.  poismf_hip_order_include's own copies of B and of A (all of A, or only the
+ * batch's rows) come on top.  The session flavour, poismf_hip_session_order_include, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_ORDER_MAX_ROW 65536                /* longest include row of the re-rank */
+POISMF_HIP_API int poismf_hip_order_include(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, sparse_ix *out_count);
+POISMF_HIP_API size_t poismf_hip_order_include_scratch_bytes(size_t n_users, size_t n_cells, size_t dimB, size_t k);
+POISMF_HIP_API size_t poismf_hip_order_include_run(void);
+POISMF_HIP_API size_t poismf_hip_order_include_wave_row(void);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -1155,6 +1204,12 @@ POISMF_HIP_API int poismf_hip_session_topn_include(poismf_hip_session *s, const 
         const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
         int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score);
+
+/* Section 1s from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_order_include(poismf_hip_session *s, const sparse_ix *users, size_t n_users, int exclude_seen,
+        const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, sparse_ix *out_count);
 
 /* Section 1i from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_diverse", "poismf_hip_session_topn_diverse", "poismf_hip_topn_diverse_scratch_bytes",
     "poismf_hip_list_eval", "poismf_hip_session_list_eval", "poismf_hip_list_eval_scratch_bytes",
     "poismf_hip_topn_adjusted", "poismf_hip_session_topn_adjusted", "poismf_hip_topn_adjusted_scratch_bytes", "poismf_hip_topn_adjusted_slices",
+    "poismf_hip_order_include", "poismf_hip_session_order_include", "poismf_hip_order_include_scratch_bytes", "poismf_hip_order_include_run",
+    "poismf_hip_order_include_wave_row",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -96,6 +98,7 @@ LIST_EVAL_BUDGET_MB = 256           # the header)
 LIST_EVAL_MAX_ITEMS = 2**24
 TOPN_ADJUSTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_ADJUSTED_MAX_ITEMS and POISMF_HIP_TOPN_ADJUSTED_MAX_ROW of section 1r
 TOPN_ADJUSTED_MAX_ROW = 2**22       # (tests/test_topn_adjusted_cpu.py compares them with the header)
+ORDER_MAX_ROW = 65536               # POISMF_HIP_ORDER_MAX_ROW of section 1s (tests/test_order_include_cpu.py compares the two)
 
 
 def load_library(use_float):
@@ -250,6 +253,16 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_include.restype = i
     lib.poismf_hip_topn_include_scratch_bytes.argtypes = [sz, sz, sz, sz, sz]
     lib.poismf_hip_topn_include_scratch_bytes.restype = sz
+    lib.poismf_hip_order_include.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_order_include.restype = i
+    lib.poismf_hip_session_order_include.argtypes = [vp, vp, sz, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_order_include.restype = i
+    lib.poismf_hip_order_include_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_order_include_scratch_bytes.restype = sz
+    lib.poismf_hip_order_include_run.argtypes = []
+    lib.poismf_hip_order_include_run.restype = sz
+    lib.poismf_hip_order_include_wave_row.argtypes = []
+    lib.poismf_hip_order_include_wave_row.restype = sz
     lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
     lib.poismf_hip_topn_include_slice.restype = sz
     lib.poismf_hip_topn_shared.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
@@ -673,6 +686,18 @@ def _topN_deep(self, users, n=1000, exclude=None, output_score=False):
 
 
 PoisMF.topN_deep = _topN_deep
+
+
+def _order_candidates(self, users, include, exclude=None, output_score=False):
+    """Every user's WHOLE candidate list in the model's order ("score descending, item index ascending"), sorted on the GPU in one
+    call (include/poismf_hip.h section 1s): the re-rank stage between topN_deep and a page.  include: a list per user in the forms
+    of topN_batch(include=), rows of at most ORDER_MAX_ROW items; exclude as in topN_batch: an excluded candidate is dropped.  Returns
+    the compacted CSR (indptr int64 [m + 1], items uint64) and, with output_score, the scores behind it: row i is
+    items[indptr[i]:indptr[i + 1]], best first; its first n <= TOPN_BATCH_MAX_N_TOP entries are topN_batch(include=)'s row."""
+    return serving.order_candidates(_host(self), users, include, False, exclude, output_score)
+
+
+PoisMF.order_candidates = _order_candidates
 
 
 def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_score=False):
@@ -1504,6 +1529,14 @@ class Session:
         TOPN_BATCH_MAX_N_TOP the answers are topn_batch's bit for bit.  Returns (items uint64 [m x top_n], scores [m x top_n], empty
         unless output_score)."""
         return serving.topn_deep(self, users, top_n, exclude_seen, exclude, output_score)
+
+    def order_candidates(self, users, include, exclude_seen=False, exclude=None, output_score=False):
+        """Every user's WHOLE candidate list in the model's order, sorted on the device from the resident factors in one call
+        (include/poismf_hip.h section 1s): order, scores, exclude_seen and exclude as in topn_batch, include as in
+        topn_batch(include=) with rows of at most ORDER_MAX_ROW items.  An excluded candidate is dropped.  Returns the compacted CSR
+        (indptr int64 [m + 1], items uint64) and, with output_score, the scores behind it: row i is items[indptr[i]:indptr[i + 1]],
+        best first; its first top_n <= TOPN_BATCH_MAX_N_TOP entries are topn_batch(include=)'s row."""
+        return serving.order_candidates(self, users, include, exclude_seen, exclude, output_score)
 
     def topn_quota(self, users, top_n=10, group_of=None, quota=1, exclude_seen=False, exclude=None, output_score=False):
         """topn_batch with "at most quota[g] items of group g on a page", from the resident factors in one fused pass

@@ -2,12 +2,12 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Twenty-nine translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
+Thirty translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
 session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
 the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip), the
-batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip) and the batched ranks among
+batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip), the re-rank of whole include lists (order_include.hip, with order_sort.hpp, on tb_gather.hpp) and the batched ranks among
 include lists (rank_include.hip) and among lists shared between users (rank_shared.hip), the deep batched top-N (topn_deep.hip, with
 tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and with per-(user, item) score factors (topn_adjust.hip: a dense pass on tb_select.hpp, a sparse one on tb_gather.hpp and a merge) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the eleven share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted / topn_adjust the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units, topn_diverse and topn_adjust tb_gather.hpp) and the
 new rows against a resident B (fold_in.hip: the guest of a session, on session.hpp and tb_batch.hpp) and the list-wise evaluation
@@ -51,6 +51,8 @@ UNITS = {
     "rank_batch": ("rank_batch.hip", []),
     "topn_include": ("topn_include.hip", []),
     "topn_shared": ("topn_shared.hip", []),
+    # the re-rank's score is a sequential fma chain: nothing in it is to be paired into packed fp32 instructions
+    "order_include": ("order_include.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     "rank_include": ("rank_include.hip", []),
     "rank_shared": ("rank_shared.hip", []),
     "topn_deep": ("topn_deep.hip", []),

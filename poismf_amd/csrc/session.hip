@@ -718,6 +718,24 @@ int poismf_hip_session_topn_include(poismf_hip_session* s, const sparse_ix* user
                                        exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Whole per-user include lists in the model's order from the resident (compact) factors (order_include.hip; include/poismf_hip.h
+// section 1s), ordered as the calls above and in the same scratch.
+int poismf_hip_session_order_include(poismf_hip_session* s, const sparse_ix* users, size_t n_users, int exclude_seen, const sparse_ix* incl_indptr,
+                                     const sparse_ix* incl_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, sparse_ix* out_ix,
+                                     real_t* out_score, sparse_ix* out_count)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_order_include_check(users, n_users, s->dimA, s->dimB, s->k, incl_indptr, incl_indices, excl_indptr, excl_indices))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_order_include_core(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, incl_indptr, incl_indices,
+                                         exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score,
+                                         out_count);
+}
+
 // Batched top-N over candidate lists shared between users from the resident (compact) factors (topn_shared.hip; include/poismf_hip.h
 // section 1i), ordered as the calls above and in the same scratch.
 int poismf_hip_session_topn_shared(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* list_indptr,

@@ -53,6 +53,15 @@ int poismf_hip_topn_include_run(hipStream_t stream, const real_t* dA, const real
                                 const sparse_ix* incl_indices, PmfTopnSeen* seen, const sparse_ix* excl_indptr,
                                 const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score);
 
+// (order_include.hip; section 1s) the same pair for the re-rank of whole include lists: the check makes no device call, the core returns
+// 0 or 1; out_ix / out_score are shaped like the lists, out_score and out_count may be NULL
+int poismf_hip_order_include_check(const sparse_ix* users, size_t n_users, size_t dimA, size_t dimB, size_t k, const sparse_ix* incl_indptr,
+                                   const sparse_ix* incl_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_order_include_core(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                  const sparse_ix* users, size_t n_users, const sparse_ix* incl_indptr, const sparse_ix* incl_indices,
+                                  PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
+                                  size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score, sparse_ix* out_count);
+
 // (topn_shared.hip; section 1i) the same pair for the top-N over lists shared between users: list_of[i] names user i's row of the table
 int poismf_hip_topn_shared_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,
                                  const sparse_ix* list_indptr, const sparse_ix* list_indices, size_t n_lists, const sparse_ix* list_of,

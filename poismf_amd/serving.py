@@ -1,5 +1,5 @@
 """The serving calls' host side: the argument checks that need no device, each rule written once, and the one path every batched
-top-N and rank call takes to the library (include/poismf_hip.h sections 1f-1r).
+top-N, re-rank and rank call takes to the library (include/poismf_hip.h sections 1f-1s).
 
 A call is made against a *target*: a ``Session`` (resident factors) or ``api._HostFactors`` (host factors that go up with the call).
 Both offer ``dimA``, ``dimB``, ``k``, ``use_float``, ``item_norms()`` and ``_entry(name, exclude_seen)``, which gives the library's
@@ -741,6 +741,28 @@ def topn_batch(target, users, n, exclude_seen, exclude, output_score, include, i
         users, *excl = _topn_batch_args(users, n, exclude, target.dimA, target.dimB)
         name, middle = "topn_batch", tuple
     return _topn_call(target, name, users, int(n), middle, exclude_seen, excl, output_score)
+
+
+def order_candidates(target, users, include, exclude_seen, exclude, output_score):
+    """section 1s: whole include lists in the model's order.  The library's output is shaped like the lists (a row's answer, then
+    TOPN_NONE / -inf); what is returned is that with the padding taken out: (indptr, items[, scores])."""
+    users = _index_array(users, "users")
+    m, dt = len(users), _real_t(target.use_float)
+    _users_in_range(users, target.dimA)
+    if include is None:
+        raise ValueError("include is required: a candidate list per user")
+    ip, ii = _csr_list(include, m, target.dimB, "include", api.ORDER_MAX_ROW, keep_zeros=True)
+    ep, ei = _exclude_list(exclude, m, target.dimB)
+    if exclude_seen:
+        _outside_shard(users, target.shardA)
+    ix, sc, cnt = np.empty(len(ii), np.uint64), np.empty(len(ii) if output_score else 0, dt), np.zeros(m, np.uint64)
+    if m:
+        fn, lead, flag = target._entry("order_include", exclude_seen)
+        _batch_rc(fn(*lead, _ptr(users), m, *flag, _ptr(ip), _opt_ptr(ii), _opt_ptr(ep), _opt_ptr(ei), _ptr(ix), _opt_ptr(sc), _ptr(cnt)),
+                  "re-rank")
+    indptr = np.concatenate(([0], np.cumsum(cnt, dtype=np.int64)))
+    keep = ix != api.TOPN_NONE
+    return (indptr, ix[keep], sc[keep]) if output_score else (indptr, ix[keep])
 
 
 def topn_deep(target, users, n, exclude_seen, exclude, output_score):
