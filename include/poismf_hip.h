@@ -49,7 +49,37 @@ extern "C" {
 #endif
 
 /* ref: src/poismf.h:225  typedef enum Method {tncg = 1, cg = 2, pg = 3} Method; */
-typedef enum poismf_hip_method { POISMF_TNCG = 1, POISMF_CG = 2, POISMF_PG = 3 } poismf_hip_method;
+typedef enum poismf_hip_method { POISMF_TNCG = 1, POISMF_CG = 2, POISMF_PG = 3, POISMF_MM = 4 } poismf_hip_method;
+
+/* ---------------------------------------------------------------------------------------------
+ * 0. Method 4, "mm": step-free multiplicative row updates (not in the reference).
+ *
+ * The majorise-minimise (EM) update of KL-NMF with the l2 term in closed form.  Per row, with s the row's constant
+ * k-vector exactly as CG gets it (the column sums of the fixed factor + l1, or for w_mult != 1 the Bsum_w row of
+ * adjustment_Bsum, ref: src/poismf.c:85-123 -- never scaled by a step), w = w_mult, l = l2_reg, b_j / x_j the
+ * fixed factor's rows and the counts of the row's nonzeros, the row objective is fun_single's
+ *     f(a) = s.a + l a.a - w sum_j x_j log(a.b_j)
+ * and one update is, for every c < k,
+ *     r_c  = sum_j (x_j / (a.b_j)) b_jc
+ *     m_c  = w a_c r_c
+ *     a_c' = m_c == 0 ? 0 : 2 m_c / (s_c + sqrt(s_c^2 + 8 l m_c))
+ * the positive root of 2 l a^2 + s_c a - m_c = 0 (l = 0 needs no branch, nothing cancels).  sqrt and the division
+ * are IEEE-rounded; every operation is rounded once in real_t.  `maxupd` updates are made per row and half-sweep.  There is
+ * no step size, the iterates stay non-negative without a projection, and f never rises.
+ * Three rules make it total:
+ *   floor       zero is absorbing under the update and rows without data are zeroed every half, so before a row's first
+ *               update every element of its starting point is raised to POISMF_HIP_MM_FLOOR (a NaN element becomes the floor);
+ *   non-finite  an update that would produce an element that is not finite (some a.b_j is 0 or underflows) is not made:
+ *               the row keeps the point it had and makes no further update in this half-sweep (the session's decisions
+ *               report the updates actually made);
+ *   empty rows  are zero, as for every method.
+ * step_size, limit_step and cnst_div are ignored, as are early_stop and reuse_prev.  The outer alternation is CG's: B before
+ * A, no step schedule.  factors_multiple makes niter * maxupd updates in one half-sweep, as for CG.  The rows run on the
+ * engines PG's rows run on, planned exactly as PG's are.
+ * ------------------------------------------------------------------------------------------- */
+/* Nobody has measured a best value for the floor: 1e-10 is a proposal, small against any fitted factor and far above the
+ * smallest normal float, so that the first predictions a.b_j stay normal for factors of ordinary size. */
+#define POISMF_HIP_MM_FLOOR 1e-10
 
 /* ---------------------------------------------------------------------------------------------
  * 1. Drop-in entry point.
@@ -58,7 +88,7 @@ typedef enum poismf_hip_method { POISMF_TNCG = 1, POISMF_CG = 2, POISMF_PG = 3 }
  * Same name, same argument order (NOTE indptr before indices), same in-place A/B semantics, same
  * return codes: 0 ok, 1 out of memory (host or device; also printed to stderr as the reference
  * does, ref: src/poismf.c:501), 2 interrupted by SIGINT (ref: src/poismf.c:618-630).
- * `method` is the reference's enum passed as int (1 tncg, 2 cg, 3 pg).
+ * `method` is the reference's enum passed as int (1 tncg, 2 cg, 3 pg), or 4: "mm" (section 0).
  * `nthreads` is accepted and ignored (the row loop runs on the GPU).
  * A, B, X* are HOST pointers owned by the caller; A and B are overwritten with the result.
  * The device used is HIP device $POISMF_HIP_DEVICE (default 0).

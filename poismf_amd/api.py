@@ -27,7 +27,14 @@ from .serving import (_batch_rc, _csr_list, _diverse_outputs, _eval_lists_args, 
                       _similar_args, _similar_scores, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
                       _topn_include_args, _topn_outputs, _topn_quota_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
 
-_METHOD = {"tncg": 1, "cg": 2, "pg": 3}  # ref: src/poismf.h:225
+_METHOD = {"tncg": 1, "cg": 2, "pg": 3, "mm": 4}  # ref: src/poismf.h:225; "mm": include/poismf_hip.h section 0 (not in the reference)
+
+
+def _method_code(method):
+    """the C enum of a method name; an unknown name is a ValueError"""
+    if method not in _METHOD:
+        raise ValueError(f"method must be one of {sorted(_METHOD)}, not {method!r}")
+    return _METHOD[method]
 _LIBS = {}
 
 
@@ -490,7 +497,7 @@ def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_
     widths: poismf_hip_debug_plan_widths -- a lane instance specialised on the used width of its factor rows is marked "[KU=<width>]";
     engines: poismf_hip_debug_plan_engines -- that, and a one-wave register launch on the quad engine is marked "[quad]";
     missing: poismf_hip_debug_plan_missing -- of that listing, only the launches the dispatcher has no kernel instance for (none, normally).
-    method: "pg", "cg", "tncg", or "eval" (the evaluation-only kernels of debug_row_eval, planned like CG)."""
+    method: "pg", "cg", "tncg", "mm" (planned as "pg" is), or "eval" (the evaluation-only kernels of debug_row_eval, planned like CG)."""
     lib = load_library(use_float)
     row_nnz = np.ascontiguousarray(row_nnz, dtype=np.uint32)
     real = C.c_float if use_float else C.c_double
@@ -498,7 +505,7 @@ def debug_plan(row_nnz, k, dimF, method, use_float, nseg=1, seg=-1, maxupd=1, w_
           lib.poismf_hip_debug_plan_widths if widths else lib.poismf_hip_debug_plan)
     fn.restype = C.c_size_t
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, real, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-    args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), 4 if method == "eval" else _METHOD[method], int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
+    args = (_ptr(row_nnz), len(row_nnz), int(nseg), int(seg), int(k), int(dimF), 5 if method == "eval" else _method_code(method), int(maxupd), w_mult, int(bool(limit_step)), int(num_cu))
     buf = C.create_string_buffer(int(fn(*args, None, 0)) + 1)
     fn(*args, buf, len(buf))
     return [(name.strip(), int(rows)) for name, rows in (item.rsplit(" rows=", 1) for item in buf.value.decode().split(";") if item.strip())]
@@ -528,7 +535,7 @@ class PoisMF:
     def __init__(self, k=50, method="tncg", l2_reg="auto", l1_reg=0.0, niter="auto", maxupd="auto",
                  limit_step=True, initial_step=1e-7, early_stop=True, reuse_prev=False, weight_mult=1.0,
                  random_state=1, use_float=True, handle_interrupt=True, nthreads=-1):
-        assert method in ("tncg", "cg", "pg")
+        _method_code(method)
         self.k = int(k)
         self.method = method
         self.l2_reg_, self.maxupd_, self.niter_ = harness.auto_defaults(method, self.k, l2_reg, maxupd, niter)
@@ -1039,7 +1046,7 @@ class Session:
 
     def make_params(self, method, l2_reg, l1_reg=0.0, w_mult=1.0, step_size=1e-7, limit_step=True, maxupd=1,
                     early_stop=False, reuse_prev=False):
-        return self.lib.params_t(l2_reg, l1_reg, w_mult, step_size, _METHOD[method], int(limit_step), int(maxupd),
+        return self.lib.params_t(l2_reg, l1_reg, w_mult, step_size, _method_code(method), int(limit_step), int(maxupd),
                                  int(early_stop), int(reuse_prev))
 
     def half_sweep(self, which, params, step_size, cnst_div, want_unchanged=False, seg=None):

@@ -2,9 +2,9 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Thirty translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
+Thirty-one translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
-session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
+session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver, one for the multiplicative update "mm" and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
 the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip), the
 batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip), the re-rank of whole include lists (order_include.hip, with order_sort.hpp, on tb_gather.hpp) and the batched ranks among
@@ -43,7 +43,10 @@ UNITS = {
     "poismf_hip_tncg": ("poismf_hip.hip", ["-DPMF_TU=1"]),
     "poismf_hip_cg": ("poismf_hip.hip", ["-DPMF_TU=2"]),
     "poismf_hip_pg": ("poismf_hip.hip", ["-DPMF_TU=3"]),
-    "poismf_hip_eval": ("poismf_hip.hip", ["-DPMF_TU=4"]),   # evaluation-only kernels behind poismf_hip_debug_row_eval (testing aid)
+    "poismf_hip_eval": ("poismf_hip.hip", ["-DPMF_TU=5"]),   # evaluation-only kernels behind poismf_hip_debug_row_eval (testing aid)
+    # the multiplicative update's row kernels (method "mm"): the same file once more, under a flag of its own -- the -DPMF_TIMING build, which swaps
+    # the -DPMF_TU= units for one, keeps this unit as it is
+    "poismf_hip_mm": ("poismf_hip.hip", ["-DPMF_MM_UNIT"]),
     "coo_convert": ("coo_convert.hip", []),
     "serve": ("serve.hip", []),
     "llk": ("llk.hip", []),
@@ -79,7 +82,7 @@ def _deps(source):
 # flavour -> flags: the reference builds its core twice for Python (ref: setup.py:225-243) and once for R with int indices
 # (ref: src/poismf.h:75-89); the R flavour differs on the host side only and links the double flavour's row kernels
 FLAVOURS = {"d": [], "f": ["-DUSE_FLOAT"], "r": ["-D_FOR_R"]}
-_KERNEL_UNITS = ("poismf_hip_tncg", "poismf_hip_cg", "poismf_hip_pg", "poismf_hip_all")
+_KERNEL_UNITS = ("poismf_hip_tncg", "poismf_hip_cg", "poismf_hip_pg", "poismf_hip_mm", "poismf_hip_all")
 
 
 def _flavour(use_float):

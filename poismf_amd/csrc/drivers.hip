@@ -207,7 +207,7 @@ int fold_in_solve(poismf_hip_session* s, const real_t* Bsum, real_t l2_reg, real
         }
     } else {
         for (size_t c = 0; c < ks; c++) bs[c] = Bsum[c];
-        if (method == POISMF_CG) p.maxupd = maxupd * niter;      // ref: :175-178
+        if (method == POISMF_CG || method == POISMF_MM) p.maxupd = maxupd * niter;      // ref: :175-178 ("mm": as CG, all updates in one half-sweep)
         rc = half_sweep_impl(s, 1, &p, step_size, (real_t)1, nullptr, bs.data(), -step_size);
     }
     return rc;

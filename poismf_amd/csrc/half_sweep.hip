@@ -316,7 +316,7 @@ int half_prologue(poismf_hip_session* s, int which, const Half& h, bool subset, 
     a.reuse_prev = p->reuse_prev;
     a.early_stop = early_stop;
     a.n_unchanged = s->d_counter;
-    a.stop = is_pg ? nullptr : device_stop_word();   // (pinned host memory, portable: the same address on every device)
+    a.stop = pg_like(p->method) ? nullptr : device_stop_word();   // (pinned host memory, portable: the same address on every device)
     a.eval_rows = s->profiling ? h.d_eval_rows : nullptr;
     a.dec_rows = s->profiling ? h.d_dec_rows : nullptr;
     a.team_err = s->d_team_err + 2;
@@ -420,7 +420,7 @@ int issue_half(poismf_hip_session* s, int which, int method, const std::vector<P
         // neither the cross-row pipeline nor start delays account for it; the workgroup-wide ticket's two barriers per row remain).
         // (Not for CG / TNCG, whose rows differ in cost and want the longest-first queue: CG fp32 B half 11.25 -> 13.17 ms; not for the
         // eight-wave register kernel, one workgroup per CU: 1.83 -> 1.90.)
-        if (method == POISMF_PG && L.engine == Engine::Lane && L.nw > 1) grid_mult = 1u << 20;
+        if (pg_like(method) && L.engine == Engine::Lane && L.nw > 1) grid_mult = 1u << 20;
         const size_t lds = lds_bytes_per_block(a.geom, sizeof(real_t), L.nw);
         const unsigned waves_per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(16, LDS_PER_CU / lds));
         unsigned grid = (unsigned)std::min<size_t>(L.count, (size_t)s->num_cu * waves_per_cu * grid_mult);
@@ -543,7 +543,7 @@ int half_sweep_impl(poismf_hip_session* s, int which, const poismf_hip_params* p
     const Half& h = view != nullptr ? *view : s->half[which];
     if (seg >= (int)h.segs.size()) return 1;
     const bool early_stop = (p->method == POISMF_TNCG) && p->early_stop && (n_unchanged != nullptr || seg >= 0);
-    const bool is_pg = p->method == POISMF_PG;
+    const bool is_pg = pg_like(p->method);   // (PG and the multiplicative update: equal work per nonzero, rows dealt out statically)
     const PlanCtx c = plan_ctx(s->k, which ? s->dimB : s->dimA, p->method, p->maxupd, p->w_mult, p->limit_step != 0, s->teams_off, s->num_cu);
     const std::vector<std::vector<PlannedLaunch>> passes = plan_call(h.segs, seg, c);
     ProfRec rec{};

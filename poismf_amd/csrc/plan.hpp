@@ -70,12 +70,14 @@ template <class T> struct HalfArgs {
                                       // starts -- the main stream holds the other bins' kernels back until the long rows are on the chip
 };
 
-enum { K_PG = 3, K_CG = 2, K_TNCG = 1, K_EVAL = 4 };
+enum { K_PG = 3, K_CG = 2, K_TNCG = 1, K_MM = 4, K_EVAL = 5 };
+// K_MM / POISMF_MM: the step-free multiplicative update (solvers.hpp, mm_row; include/poismf_hip.h section 0).  Per nonzero and pass it does PG's
+// work, so it is planned as PG is -- the same bins, engines and instances -- and its kernels live in a translation unit of their own.
 // K_EVAL / POISMF_EVAL: not a solver -- the row kernels evaluate the device's own fun_single + grad_single (RowParams::maxupd == 0) or
 // fun_and_grad (maxupd == 1) at each row's starting point and hand the gradient back in place of the updated row, the function
 // value through the decisions words (testing aid: poismf_hip_debug_row_eval, include/poismf_hip.h).  Planned like CG, so every
-// engine CG would pick for a row length is reachable; its kernels live in a translation unit of their own (PMF_TU=4).
-constexpr int POISMF_EVAL = 4;
+// engine CG would pick for a row length is reachable; its kernels live in a translation unit of their own (PMF_TU=5).
+constexpr int POISMF_EVAL = 5;
 
 // One row of the sorted order: where its nonzeros start in the shard's CSR arrays, how many, and which row it is.
 struct RowDesc { unsigned p0_lo, p0_hi, nnz, lrow; };
@@ -138,7 +140,10 @@ constexpr int REG_NNZ_MAX_CG = PMF_REG_MAX_CG, REG_NNZ_MAX_TNCG = PMF_REG_MAX_TN
 // ... and from a tile of two slots per lane (kernel-resource-usage: CG with 40 steps of two slots spills 360 bytes per lane even at one wave per
 // SIMD, 36 steps 60; TNC's ~21 k-vectors leave room for 112 nonzeros of tile)
 constexpr int REG2_NNZ_MAX_CG = 144, REG2_NNZ_MAX_TNCG = 112;
-constexpr int plan_method(int method) { return method == POISMF_EVAL ? POISMF_CG : method; }   // the evaluation-only kernels are planned like CG
+// the evaluation-only kernels are planned like CG, the multiplicative update like PG
+constexpr int plan_method(int method) { return method == POISMF_EVAL ? POISMF_CG : method == POISMF_MM ? POISMF_PG : method; }
+// ... and whatever is planned like PG is handed out like PG: equal work per nonzero, rows dealt statically, no stop word read per row
+constexpr bool pg_like(int method) { return plan_method(method) == POISMF_PG; }
 constexpr unsigned reg_nnz_max(int method, int ns = 1)
 {
     const int m = plan_method(method);
@@ -288,7 +293,7 @@ inline int lane_used_width(size_t k, int s_load, int method, const LaneShape& ls
 // and finds a planned shape in it with LaneShape::operator==; lane_shape_for and lane_used_width above name rows of it and nothing else, and every
 // row is named by some plan (tests/test_plan_instances.py).  A new instance is a row here and the branch of lane_shape_for that picks it.
 // (the rows with a used width are built only where PMF_LANE_KU50 is on)
-constexpr unsigned LANE_PG = 1u << K_PG, LANE_CG = 1u << K_CG | 1u << K_EVAL, LANE_CG_TNCG = LANE_CG | 1u << K_TNCG;   // (EVAL keeps the set CG has)
+constexpr unsigned LANE_PG = 1u << K_PG | 1u << K_MM, LANE_CG = 1u << K_CG | 1u << K_EVAL, LANE_CG_TNCG = LANE_CG | 1u << K_TNCG;   // (EVAL keeps the set CG has)
 #define PMF_LANE_INSTANCES_F64(X)                   \
     X(LANE_CG_TNCG, 25, 1, 0, 0, 1, 1,  0,  0,  0) \
     X(LANE_CG,      25, 1, 0, 0, 1, 1, 32,  0,  0) \
@@ -379,15 +384,16 @@ struct OneLaunch {
 };
 
 
-// One function per row-kernel translation unit (PMF_TU = 1 tncg, 2 cg, 3 pg): launches the instance the plan names.
+// One function per row-kernel translation unit (PMF_TU = 1 tncg, 2 cg, 3 pg, 4 mm, 5 eval): launches the instance the plan names.
 int pmf_launch_one_tu1(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu2(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu3(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 int pmf_launch_one_tu4(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
+int pmf_launch_one_tu5(int method, const OneLaunch& o, const HalfArgs<real_t>& a);
 inline int pmf_launch_one(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
 {
     return method == POISMF_PG ? pmf_launch_one_tu3(method, o, a) : method == POISMF_CG ? pmf_launch_one_tu2(method, o, a) :
-           method == POISMF_EVAL ? pmf_launch_one_tu4(method, o, a) : pmf_launch_one_tu1(method, o, a);
+           method == POISMF_MM ? pmf_launch_one_tu4(method, o, a) : method == POISMF_EVAL ? pmf_launch_one_tu5(method, o, a) : pmf_launch_one_tu1(method, o, a);
 }
 // -DPMF_TIMING development builds: read and reset the phase timers (they live in the row-kernel translation unit)
 int pmf_read_timing(unsigned long long* out);

@@ -143,7 +143,7 @@ size_t padded_row_bytes(size_t k)
 PlanCtx plan_ctx(size_t k, size_t dimF, int method, size_t maxupd, real_t w_mult, bool limit_step, bool teams_off, int num_cu)
 {
     const int pm = plan_method(method);   // the evaluation-only kernels (plan.hpp, K_EVAL) are planned like CG
-    const bool single_pass = method == POISMF_PG && maxupd <= 1 && w_mult == (real_t)1.;
+    const bool single_pass = pm == POISMF_PG && maxupd <= 1 && w_mult == (real_t)1.;   // (one update of "mm" is one pass too)
     return { k, dimF, padded_row_bytes(k) / sizeof(real_t), pm, single_pass, limit_step, teams_off, num_cu };
 }
 
@@ -279,7 +279,7 @@ std::vector<PlannedLaunch> plan_half(const std::vector<Bin>& bins, const PlanCtx
 // The kernel instance a launch runs, as plan() and the launch profile name it.
 std::string launch_name(int method, const PlannedLaunch& L)
 {
-    const char* m = method == POISMF_PG ? "pg" : method == POISMF_EVAL ? "eval" : method == POISMF_CG ? "cg" : "tncg";
+    const char* m = method == POISMF_PG ? "pg" : method == POISMF_MM ? "mm" : method == POISMF_EVAL ? "eval" : method == POISMF_CG ? "cg" : "tncg";
     const char* t = sizeof(real_t) == 4 ? "float" : "double";
     const LaneShape& l = L.lane;
     char txt[160] = "", lp[16] = "";

@@ -1,5 +1,5 @@
 // poismf_hip.hip -- the row kernels of the MI355X implementation of poismf's alternating factor-update path and their
-// launchers.  Compiled once per inner solver and precision (-DPMF_TU=1 tncg / 2 cg / 3 pg / 4 the evaluation-only kernels of poismf_hip_debug_row_eval; without it all three, the
+// launchers.  Compiled once per inner solver and precision (-DPMF_TU=1 tncg / 2 cg / 3 pg / 5 the evaluation-only kernels of poismf_hip_debug_row_eval, -DPMF_MM_UNIT the multiplicative update; without either the first four, the
 // -DPMF_TIMING development build) into libpoismf_hip_d.so / libpoismf_hip_f.so (-DUSE_FLOAT); the host side
 // (sessions, planning, issuing a half-sweep, run_poismf) is session.hip, planner.hip, half_sweep.hip, drivers.hip and multi_device.hip; the C-ABI is declared in include/poismf_hip.h.
 //
@@ -13,6 +13,13 @@
 #include <cstdlib>
 #include <type_traits>
 
+// The unit of the multiplicative update (-DPMF_MM_UNIT, poismf_amd/build.py) is part of the default build and of the -DPMF_TIMING development
+// build alike: it is this file with PMF_TU = K_MM, and it keeps no phase timers.
+#ifdef PMF_MM_UNIT
+#undef PMF_TIMING
+#define PMF_TU 4
+#endif
+
 #include "plan.hpp"
 #include "reg_eval.hpp"
 #include "quad_eval.hpp"
@@ -21,11 +28,12 @@
 
 // Translation units.  The row kernels of the three solvers are the bulk of the compile time, so the build compiles this
 // file once per solver (poismf_amd/build.py): PMF_TU = K_TNCG / K_CG / K_PG instantiates the row kernels of one solver and
-// exports one function, pmf_launch_one_tu<N>.  Without PMF_TU all three land in one translation unit.
+// exports one function, pmf_launch_one_tu<N>.  Without PMF_TU all three (and the evaluation-only kernels) land in one translation unit; the
+// multiplicative update's (K_MM) are in their own unit in every build.
 #ifndef PMF_TU
 #define PMF_TU -1
 #endif
-constexpr bool tu_has(int kmethod) { return PMF_TU == -1 || PMF_TU == kmethod; }
+constexpr bool tu_has(int kmethod) { return PMF_TU == kmethod || (PMF_TU == -1 && kmethod != K_MM); }
 
 // An engine with `static constexpr bool COLD_CONSTANTS = true` has no register to spare for constants that are used once per row: solve_row
 // builds those where they are used (lane_eval.hpp: the instances with a used width).
@@ -99,6 +107,8 @@ __device__ __forceinline__ void solve_row(const HalfArgs<T>& a, EV& ev, const T 
         return;
     } else if constexpr (METHOD == K_PG) {
         pg_row(ev, a.P, x, shift);
+    } else if constexpr (METHOD == K_MM) {
+        mm_row(ev, a.P, x, shift, st);                                  // (shift: the constant term as CG gets it -- no step has touched it)
     } else if constexpr (METHOD == K_CG) {
         // cached line search: streamed rows of the LDS engine (plan_geom decides), fp64 single-wave rows of the register engine
         if constexpr (EV::MAY_CACHE) {
@@ -140,7 +150,7 @@ __device__ __forceinline__ void solve_row(const HalfArgs<T>& a, EV& ev, const T 
 template <int METHOD, class T> __device__ __forceinline__ unsigned take_ticket(const HalfArgs<T>& a)
 {
     unsigned st = 0u;
-    if constexpr (METHOD != K_PG) {
+    if constexpr (!pg_like(METHOD)) {
         if (a.stop != nullptr) st = __hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     const unsigned t = atomicAdd(a.queue, 1u);
@@ -163,7 +173,7 @@ __device__ __forceinline__ void sweep_rows(const HalfArgs<T>& a, EV& ev, unsigne
     T bs[NC];
     ev.load_vec(a.bsum, bs);
     const RowDesc* desc = a.desc + a.perm_begin;
-    if constexpr (EV::PIPELINED && (EV::PIPE_MW == 1 || (EV::PIPE_MW == 2 && METHOD == K_PG))) {
+    if constexpr (EV::PIPELINED && (EV::PIPE_MW == 1 || (EV::PIPE_MW == 2 && pg_like(METHOD)))) {
         // Software pipeline over the rows of this wave.  A row costs three dependent round trips to memory -- its
         // descriptor, its indices, the factor rows those name -- and the solver in between leaves the memory pipe idle.
         // Tickets (and descriptors) are fetched two rows ahead and the indices one row ahead, so that a row's gather
@@ -185,7 +195,7 @@ __device__ __forceinline__ void sweep_rows(const HalfArgs<T>& a, EV& ev, unsigne
             }
             unsigned t = r;
             r += gridDim.x;
-            if constexpr (METHOD != K_PG) {
+            if constexpr (!pg_like(METHOD)) {
                 // (statically dealt rows: the stop word alone, one read of pinned host memory per row that nothing waits for until the ticket
                 // is used, two rows later)
                 if (a.stop != nullptr && __hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) t = 0xffffffffu;
@@ -235,7 +245,7 @@ __device__ __forceinline__ void sweep_rows(const HalfArgs<T>& a, EV& ev, unsigne
                 }
             }
             if (r >= a.nrows) break;
-            if constexpr (METHOD != K_PG) {
+            if constexpr (!pg_like(METHOD)) {
                 if (a.queue == nullptr && a.stop != nullptr && uniform(__hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) != 0u) break;
             }
             const RowDesc d = desc[r];
@@ -407,18 +417,23 @@ __global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(1, 1))
 #ifndef PMF_TNC_EXTRA
 #define PMF_TNC_EXTRA 100
 #endif
-constexpr int reg_waves(int tile_regs, int method)
+// ("mm" on doubles: PG's passes, but the IEEE division and square root of its epilogue expand into some twenty registers of temporaries that PG
+// does not have -- at PG's allowance every instance PG fills to within that of its budget would spill)
+#ifndef PMF_MM64_EXTRA
+#define PMF_MM64_EXTRA 112
+#endif
+constexpr int reg_waves(int tile_regs, int method, int real_bytes = 4)
 {
-    const int need = tile_regs + (method == K_PG ? PMF_PG_EXTRA : method == K_CG ? PMF_CG_EXTRA : PMF_TNC_EXTRA);
+    const int need = tile_regs + (method == K_MM && real_bytes == 8 ? PMF_MM64_EXTRA : pg_like(method) ? PMF_PG_EXTRA : method == K_CG ? PMF_CG_EXTRA : PMF_TNC_EXTRA);
     for (int w : { 8, 6, 5, 4, 3, 2 })
         if ((512 / w) / 8 * 8 >= need) return w;
     return 1;
 }
 // Register-tile engine (reg_eval.hpp) for rows of at most (64 / G) S nonzeros: no LDS at all, waves per CU set by VGPRs.
 // PG on floats keeps the tile step-interleaved (reg_eval.hpp, PAIR_); CG and TNCG keep the slot layout.
-template <class T, int METHOD, int G, int NS> constexpr bool reg_pairs() { return METHOD == K_PG && sizeof(T) == 4 && G == 16 && NS == 1; }
+template <class T, int METHOD, int G, int NS> constexpr bool reg_pairs() { return pg_like(METHOD) && sizeof(T) == 4 && G == 16 && NS == 1; }
 template <class T, int METHOD, int S, int G, int NS>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(4 * S * NS, METHOD)))) void half_sweep_reg_kernel(const HalfArgs<T> a)
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(4 * S * NS, METHOD, sizeof(T))))) void half_sweep_reg_kernel(const HalfArgs<T> a)
 {
     using EV = RegEval<T, S, G, NS, 1, 1, reg_pairs<T, METHOD, G, NS>()>;
     EV ev;
@@ -442,20 +457,28 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(
     EV ev;
     sweep_rows<EV, float, EV::NC, K_PG, 1>(a, ev, nullptr);
 }
+// ... and for the multiplicative update (a kernel of its own name: the PG kernel's is what the tools and tests that read the library know)
+template <int Q>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(reg_waves(QuadEval<Q>::TILE_REGS, K_MM)))) void half_sweep_quad_mm_kernel(const HalfArgs<float> a)
+{
+    using EV = QuadEval<Q>;
+    EV ev;
+    sweep_rows<EV, float, EV::NC, K_MM, 1>(a, ev, nullptr);
+}
 
 // The same engine with NW = 2, 4 or 8 wavefronts per row (reg_eval.hpp, NW_ > 1): rows of up to NW (64 / G) S nonzeros.
 // The fewest waves whose shares fit their registers are used: every evaluation ends in a barrier and a round trip
 // through LDS, which costs more the more waves take part (C2-shaped PG(10), ns per nonzero and half: 100-nonzero rows on
 // one wave 0.06; 200-nonzero rows 0.137 on eight waves).
-constexpr int regw_waves(int tile_regs, int method, int nw)
+constexpr int regw_waves(int tile_regs, int method, int nw, int real_bytes = 4)
 {
     // (PG: the cross-wave scratch pointers and wave index are 8 more registers than the one-wave kernel keeps; without the
     // allowance the S = 28 instances sat at 3 waves per SIMD with 20-28 bytes of scratch)
-    const int w = reg_waves(tile_regs + (method == K_PG ? 8 : 0), method);
+    const int w = reg_waves(tile_regs + (pg_like(method) ? 8 : 0), method, real_bytes);
     return nw >= 16 && w < 4 ? 4 : (nw >= 8 && w < 2 ? 2 : w);   // eight waves are two per SIMD, sixteen four
 }
 template <class T, int METHOD, int S, int G, int NS, int NW>
-__global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(regw_waves(4 * S * NS, METHOD, NW)))) void half_sweep_regw_kernel(const HalfArgs<T> a)
+__global__ __launch_bounds__(WAVE* NW) __attribute__((amdgpu_waves_per_eu(regw_waves(4 * S * NS, METHOD, NW, sizeof(T))))) void half_sweep_regw_kernel(const HalfArgs<T> a)
 {
     using EV = RegEval<T, S, G, NS, NW>;
     __shared__ __attribute__((aligned(16))) unsigned char smem[EV::SMEM_BYTES];
@@ -690,6 +713,9 @@ template <class F> int with_method(int method, F f)
         case POISMF_CG:
             if constexpr (tu_has(K_CG)) return f(integral_constant<int, K_CG>{});
             else return 1;
+        case POISMF_MM:
+            if constexpr (tu_has(K_MM)) return f(integral_constant<int, K_MM>{});
+            else return 1;
         case POISMF_EVAL:
             if constexpr (tu_has(K_EVAL)) return f(integral_constant<int, K_EVAL>{});
             else return 1;
@@ -764,11 +790,15 @@ int launch_reg(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
 // build without it
 int launch_quad(int method, const OneLaunch& o, const HalfArgs<real_t>& a)
 {
-    if (method != POISMF_PG || a.geom.k != QUAD_K || a.geom.ldF != QUAD_LD) return 1;
+    if (!pg_like(method) || a.geom.k != QUAD_K || a.geom.ldF != QUAD_LD) return 1;
     return with_steps(o.reg_S, [&](auto s) {
-        if constexpr (tu_has(K_PG) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16)
-            return launch_occ<half_sweep_quad_kernel<decltype(s)::value * REG_JG / 16>, WAVE>(o, a);
-        else return 1;
+        if constexpr (tu_has(K_PG) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16) {
+            if (method == POISMF_PG) return launch_occ<half_sweep_quad_kernel<decltype(s)::value * REG_JG / 16>, WAVE>(o, a);
+        }
+        if constexpr (tu_has(K_MM) && sizeof(real_t) == 4 && PMF_REG_QUAD != 0 && REG_G == 16) {
+            if (method == POISMF_MM) return launch_occ<half_sweep_quad_mm_kernel<decltype(s)::value * REG_JG / 16>, WAVE>(o, a);
+        }
+        return 1;
     });
 }
 // ... 2, 4 or 8 waves per row
@@ -872,8 +902,11 @@ int pmf_launch_one_tu2(int method, const OneLaunch& o, const HalfArgs<real_t>& a
 #if PMF_TU == 3 || PMF_TU == -1
 int pmf_launch_one_tu3(int method, const OneLaunch& o, const HalfArgs<real_t>& a) { return launch_one_here(method, o, a); }
 #endif
-#if PMF_TU == 4 || PMF_TU == -1
+#if PMF_TU == 4
 int pmf_launch_one_tu4(int method, const OneLaunch& o, const HalfArgs<real_t>& a) { return launch_one_here(method, o, a); }
+#endif
+#if PMF_TU == 5 || PMF_TU == -1
+int pmf_launch_one_tu5(int method, const OneLaunch& o, const HalfArgs<real_t>& a) { return launch_one_here(method, o, a); }
 #endif
 
 #ifdef PMF_TIMING

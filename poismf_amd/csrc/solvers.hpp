@@ -61,6 +61,75 @@ __device__ __forceinline__ void pg_row(EV& ev, const RowParams<T>& P, T (&x)[NC]
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multiplicative (majorise-minimise) update -- not in the reference; include/poismf_hip.h section 0, DESIGN.md 4.30
+// ------------------------------------------------------------------------------------------------
+// One pass over the tile per update, the pass PG makes (r = sum_j (x_j / (a.b_j)) b_j, on the lean path where the engine has one); then, per element
+// and in the engine's own layout (the epilogue is elementwise, so a lane's copy of an element computes its original's bits),
+//     m = w a r,    a' = m == 0 ? 0 : 2 m / (s + sqrt(s s + 8 l2 m))
+// with s the row's constant term as CG gets it.  IEEE square root and division, no contraction: every operation is rounded once in T.
+// An engine without `act` (quad_eval.hpp) carries a factor dimension in every lane; the others keep zeros outside the row's k elements.
+template <class EV, class = void> struct has_act : std::false_type {};
+template <class EV> struct has_act<EV, std::void_t<decltype(std::declval<const EV&>().act[0])>> : std::true_type {};
+
+// (the register engine's multi-wave kernels: RegEval and QuadEval are the engines with PG_LEAN and a member NW)
+template <class EV, class = void> struct mm_interleaved : std::false_type {};
+template <class EV> struct mm_interleaved<EV, std::void_t<decltype(EV::PG_LEAN)>> : std::integral_constant<bool, (EV::NW > 1)> {};
+
+__device__ __forceinline__ float mm_sqrt(float v) { return __builtin_sqrtf(v); }
+__device__ __forceinline__ double mm_sqrt(double v) { return __builtin_sqrt(v); }
+
+template <class EV, class T, int NC>
+__device__ __forceinline__ void mm_row(EV& ev, const RowParams<T>& P, T (&x)[NC], const T (&s)[NC], SolveStats& st)
+{
+    auto on = [&](int i) -> bool {
+        if constexpr (has_act<EV>::value) return ev.act[i];
+        else return true;
+    };
+    // the floor: zero is absorbing under the update (and what a row without data was set to in the half before); a NaN compares false and takes the floor too
+    const T lo = (T)POISMF_HIP_MM_FLOOR;
+    PMF_EW x[i] = on(i) ? (x[i] > lo ? x[i] : lo) : (T)0;
+    const T l8 = (T)8 * P.l2;
+    int u = 0;
+    for (; u < P.maxupd; u++) {
+        T g[NC];
+        PMF_EW g[i] = (T)0;
+        if constexpr (pg_lean<EV>::value) {
+            ev.set_point_as_is(x);
+            ev.template eval<false, true, false, true>((T)1, g);
+        } else {
+            ev.set_point(x);
+            ev.template eval<false, true>((T)1, g);
+        }
+        T xn[NC];
+        bool bad = false;
+        {
+#pragma clang fp contract(off)
+            PMF_EW {
+                const T m = (P.w * x[i]) * g[i];
+                const T d = s[i] + mm_sqrt(s[i] * s[i] + l8 * m);
+                T v = (m + m) / d;
+                v = m == (T)0 ? (T)0 : v;
+                xn[i] = on(i) ? v : (T)0;
+                bad |= not_finite(xn[i]);
+                // one element after the other: the division's and the square root's expansions take a handful of registers each, and interleaved
+                // for all NC elements they cost the S = 28 one-wave register instance its third wave (60 bytes of scratch at PG's budget) and the
+                // generic two-slot LDS instance its second (264 registers).  Not in the multi-wave register kernels on floats: there the order costs
+                // the eight-wave S = 8 / 16 / 24 instances 12 .. 28 bytes of scratch that the interleaved epilogue does not need.
+                if constexpr (!(mm_interleaved<EV>::value && sizeof(T) == 4)) {
+                    if (i + 1 < NC) asm volatile("" : "+v"(xn[i]), "+v"(g[i + 1]));
+                }
+            }
+        }
+        // not finite (some a.b_j was 0, or underflowed): the row keeps the point it had and stops.  Wave-uniform -- and the same in every wave of a
+        // row, whose combine leaves every wave with the same bits -- so the passes' barriers stay matched.
+        if (__builtin_amdgcn_ballot_w64(bad) != 0ull) break;
+        PMF_EW x[i] = xn[i];
+        PMF_STAMP(ev, 9);
+    }
+    st.niter = u;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Objective / gradient wrappers on top of RowEval
 // ------------------------------------------------------------------------------------------------
 // f = bsum.a + l2 (a.a) - w sum x log(a.F_j)                     ref: src/poismf.c:194-208

@@ -11,14 +11,15 @@ import scipy.sparse as sp
 
 
 def auto_defaults(method, k, l2_reg="auto", maxupd="auto", niter="auto"):
-    """ref: poismf/__init__.py:250-255.  (R differs: pg maxupd auto = 1, ref: R/poismf.R:241.)"""
-    assert method in ("tncg", "cg", "pg")
+    """ref: poismf/__init__.py:250-255.  (R differs: pg maxupd auto = 1, ref: R/poismf.R:241.)
+    "mm" (not in the reference) takes CG's l2_reg and niter, and ten updates per row and half-sweep."""
+    assert method in ("tncg", "cg", "pg", "mm")
     if l2_reg == "auto":
-        l2_reg = {"tncg": 1e3, "cg": 1e4, "pg": 1e9}[method]
+        l2_reg = {"tncg": 1e3, "cg": 1e4, "pg": 1e9, "mm": 1e4}[method]
     if maxupd == "auto":
-        maxupd = {"tncg": 15 * k, "cg": 5, "pg": 10}[method]
+        maxupd = {"tncg": 15 * k, "cg": 5, "pg": 10, "mm": 10}[method]
     if niter == "auto":
-        niter = {"tncg": 10, "cg": 30, "pg": 10}[method]
+        niter = {"tncg": 10, "cg": 30, "pg": 10, "mm": 30}[method]
     return float(l2_reg), int(maxupd), int(niter)
 
 
