@@ -19,6 +19,7 @@
 
 #include <stdbool.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -871,6 +872,57 @@ POISMF_HIP_API size_t poismf_hip_order_include_run(void);
 POISMF_HIP_API size_t poismf_hip_order_include_wave_row(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1t. Sampled negatives: for many users at once, m distinct items per user that are not in the user's exclusion set, drawn on the
+ *     device from a seeded stream per user (no counterpart in the reference).  This is the input of the sampled evaluation: what
+ *     sections 1h, 1j, 1k and 1s take as include lists.  No factor is read, so the host flavour needs no model.  A sample is a
+ *     function of its inputs alone, defined with integers only:
+ *
+ *   stream       a user's id is its stream's id.  Draw d = 0, 1, 2, ... of user u is the Philox4x32-10 block (Salmon et al., SC'11)
+ *                with key (seed & 0xffffffff, seed >> 32) and counter (d, 0, u & 0xffffffff, u >> 32).  Of its four output words
+ *                w0 .. w3, r = (w1 << 32) | w0; w2 and w3 are unused.  poismf_hip_philox4x32(counter[4], key[2], out[4]) is that
+ *                block function on the host (no HIP call): the kernel calls the same code.
+ *   candidate    item_weight == NULL (uniform): j_d = (r * dimB) >> 64, the high half of the 128-bit product.  Otherwise
+ *                t = (r * W) >> 64 and j_d = the first item with C_j > t, where C is the inclusive prefix sum of item_weight [dimB]
+ *                (uint32_t each) in uint64_t, exact, and W = C_{dimB-1}.  An item of weight 0 is never drawn.
+ *   E(u)         the batch's exclusion list excl_indptr [n_users + 1] / excl_indices (rows strictly ascending, indices < dimB;
+ *                excl_indptr = NULL: no list), on a session united with the user's resident CSR row when exclude_seen.
+ *   the rule     walk d upward; candidate j_d is ACCEPTED iff it is not in E(u) and was not accepted at an earlier draw.  Stop at m
+ *                accepted, or at d = POISMF_HIP_NEG_DRAWS(m) = 16 m + 256.
+ *   output       items [n_users x m]: row i holds the accepted set ascending -- ready to be passed as an include row -- then
+ *                POISMF_HIP_TOPN_NONE; count [n_users] its size; draws [n_users] (may be NULL) the number of draws the row
+ *                consumed: the m-th accept's d + 1, or the cap.  Host arrays.
+ *
+ * The cap is a condition, not a tuning: while at least half of the draw mass is admissible and not yet picked, a draw is accepted
+ * with probability >= 1/2, and fewer than m accepts in 16 m + 256 draws then have probability below exp(-50) (Chernoff).  A row comes
+ * back short (count < m, no error) only when m approaches the admissible mass, and there short is the right answer.
+ *
+ * Consequences: a row depends on (seed, u, m, dimB, E(u), item_weight) and on nothing else -- not the batch, its chunks, or the
+ * position in `users`; a user listed twice gets the same row twice; while the cap does not bite, the row for m' < m is a subset of
+ * the row for m; one pool of negatives shared by everybody (section 1k's include_of) is this call with one stream id and no
+ * exclusions.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for m < 1 or
+ * m > POISMF_HIP_NEG_MAX_M, dimB < 1 or dimB > 2^24, users / items / count == NULL, a negative user (int indices), on a session a
+ * user >= dimA or, with exclude_seen, outside the session's rows of A, an exclusion list that section 1f refuses, and W = 0.
+ * n_users == 0 returns 0.  On the host flavour any id is valid, ids of 2^32 and more included.
+ *
+ * One wave per user, 64 draws a round; the accepted set is an open-addressing table in LDS in which the lowest draw of equal
+ * candidates wins, the row is sorted in LDS.  No floating point anywhere.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1s share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB
+ * for any number of users: the prefix sums, and chunks of consecutive users with their exclusion lists and rows.
+ * poismf_hip_sample_negatives_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate.  The device is that
+ * of POISMF_HIP_DEVICE.  The session flavour, poismf_hip_session_sample_negatives, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_NEG_MAX_M 4096                     /* most items per user */
+#define POISMF_HIP_NEG_DRAWS(m) (16 * (m) + 256)      /* the cap on a row's draws */
+POISMF_HIP_API int poismf_hip_sample_negatives(size_t dimB, const sparse_ix *users, size_t n_users, size_t m, uint64_t seed,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices, const uint32_t *item_weight,
+        sparse_ix *items, sparse_ix *count, sparse_ix *draws);
+POISMF_HIP_API size_t poismf_hip_sample_negatives_scratch_bytes(size_t n_users, size_t m, size_t dimB, int weighted);
+POISMF_HIP_API void poismf_hip_philox4x32(const uint32_t *counter, const uint32_t *key, uint32_t *out);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -1240,6 +1292,11 @@ POISMF_HIP_API int poismf_hip_session_order_include(poismf_hip_session *s, const
         const sparse_ix *incl_indptr, const sparse_ix *incl_indices,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         sparse_ix *out_ix, real_t *out_score, sparse_ix *out_count);
+
+/* Section 1t for users of the session (with exclude_seen, the session's own CSR rows join E(u)), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_sample_negatives(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t m,
+        uint64_t seed, int exclude_seen, const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        const uint32_t *item_weight, sparse_ix *items, sparse_ix *count, sparse_ix *draws);
 
 /* Section 1i from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_topn_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,

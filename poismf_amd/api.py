@@ -82,6 +82,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_topn_adjusted", "poismf_hip_session_topn_adjusted", "poismf_hip_topn_adjusted_scratch_bytes", "poismf_hip_topn_adjusted_slices",
     "poismf_hip_order_include", "poismf_hip_session_order_include", "poismf_hip_order_include_scratch_bytes", "poismf_hip_order_include_run",
     "poismf_hip_order_include_wave_row",
+    "poismf_hip_sample_negatives", "poismf_hip_session_sample_negatives", "poismf_hip_sample_negatives_scratch_bytes", "poismf_hip_philox4x32",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -106,6 +107,8 @@ LIST_EVAL_MAX_ITEMS = 2**24
 TOPN_ADJUSTED_MAX_ITEMS = 2**24     # POISMF_HIP_TOPN_ADJUSTED_MAX_ITEMS and POISMF_HIP_TOPN_ADJUSTED_MAX_ROW of section 1r
 TOPN_ADJUSTED_MAX_ROW = 2**22       # (tests/test_topn_adjusted_cpu.py compares them with the header)
 ORDER_MAX_ROW = 65536               # POISMF_HIP_ORDER_MAX_ROW of section 1s (tests/test_order_include_cpu.py compares the two)
+NEG_MAX_M = 4096                    # POISMF_HIP_NEG_MAX_M of section 1t and its limit on the number of items
+NEG_MAX_ITEMS = 2**24               # (tests/test_sample_negatives_cpu.py compares the first with the header)
 
 
 def load_library(use_float):
@@ -270,6 +273,14 @@ def load_library(use_float):
     lib.poismf_hip_order_include_run.restype = sz
     lib.poismf_hip_order_include_wave_row.argtypes = []
     lib.poismf_hip_order_include_wave_row.restype = sz
+    lib.poismf_hip_sample_negatives.argtypes = [sz, vp, sz, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_sample_negatives.restype = i
+    lib.poismf_hip_session_sample_negatives.argtypes = [vp, vp, sz, sz, C.c_uint64, i, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_sample_negatives.restype = i
+    lib.poismf_hip_sample_negatives_scratch_bytes.argtypes = [sz, sz, sz, i]
+    lib.poismf_hip_sample_negatives_scratch_bytes.restype = sz
+    lib.poismf_hip_philox4x32.argtypes = [vp, vp, vp]
+    lib.poismf_hip_philox4x32.restype = None
     lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
     lib.poismf_hip_topn_include_slice.restype = sz
     lib.poismf_hip_topn_shared.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
@@ -707,6 +718,51 @@ def _order_candidates(self, users, include, exclude=None, output_score=False):
 PoisMF.order_candidates = _order_candidates
 
 
+class _NoFactors:
+    """The target of a serving call that reads no factors (serving.py): the negative sampler on host arrays.  dimA None: any id
+    names a stream."""
+
+    def __init__(self, dimB, dimA=None):
+        self.dimA, self.dimB, self.use_float = dimA, int(dimB), False
+
+    def _entry(self, name, exclude_seen):
+        return getattr(load_library(self.use_float), "poismf_hip_" + name), (self.dimB,), ()
+
+
+def sample_negatives(dimB, users, m, exclude=None, item_weight=None, seed=0, return_draws=False):
+    """Sampled negatives on the GPU (include/poismf_hip.h section 1t): for every entry of `users`, up to m distinct items below dimB
+    that are not in the user's `exclude` row (a SciPy sparse matrix with one row per entry of `users`, or an (indptr, indices) pair
+    with strictly ascending rows), drawn from the Philox4x32-10 stream that `seed` and the user's id name.  A row depends on (seed,
+    user id, m, dimB, its exclude row, item_weight) alone: the same call anywhere gives the same sample, and a user listed twice the
+    same row twice.  item_weight: None (uniform) or one weight per item.  An integer array is taken as it is, 0 .. 2^32 - 1 each; a
+    float array must be finite and non-negative and is scaled as rint(w / max(w) * 2^31) -- a weight below max(w) / 2^32 becomes 0
+    and the item is never drawn.  Returns (indptr int64 [len(users) + 1], indices uint64), every row ascending: the form include=
+    takes; with return_draws also the number of draws each row consumed.  A row is shorter than m only when m approaches the number of
+    admissible items (section 1t's cap of 16 m + 256 draws)."""
+    return serving.sample_negatives(_NoFactors(dimB), users, m, False, exclude, item_weight, seed, return_draws)
+
+
+def _sample_negatives(self, users, m, exclude=None, item_weight=None, seed=0, return_draws=False):
+    """api.sample_negatives for users and items of the fitted model: users are checked against its rows.  The model does not keep
+    X: pass the training matrix's rows as `exclude` to leave out what a user has seen."""
+    if not self.is_fitted:
+        raise ValueError("Model has not been fitted.")
+    return serving.sample_negatives(_NoFactors(self.nitems, self.nusers), users, m, False, exclude, item_weight, seed, return_draws)
+
+
+PoisMF.sample_negatives = _sample_negatives
+
+
+def _sampled_include(sample, users, test, exclude, include, negatives, negatives_weight, seed, dimB):
+    """eval_ranking's negatives=: the include lists are `negatives` sampled items per user that avoid its exclusions and its own
+    held-out row (sample(users, m, exclude, item_weight, seed) makes the call)"""
+    if negatives is None:
+        return include
+    m = serving._negatives_m(negatives)
+    avoid = test if exclude is None else serving._unite_rows(serving._exclude_list(exclude, len(users), dimB), test)
+    return sample(users, m, avoid, negatives_weight, seed)
+
+
 def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_score=False):
     """topN_batch with "at most quota[g] items of group g on a page": the user's complete ranked list ("score descending, item index
     ascending", minus `exclude` as in topN_batch) is walked and an item is taken iff fewer than quota[g] items of its group
@@ -840,7 +896,8 @@ def _ranking_result(tp, ranks, n_adm, k, per_user):
     return out
 
 
-def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, include=None, include_of=None):
+def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, include=None, include_of=None, negatives=None,
+                  negatives_weight=None, seed=0):
     """Held-out ranking metrics of the fitted model, from exact ranks computed in one fused pass on the GPU (include/poismf_hip.h
     section 1g; the definitions are those of poismf_amd/metrics.py).  X_test: a SciPy sparse matrix with the model's shape whose
     stored cells are the held-out positives (values play no part; explicit zeros dropped, duplicates merged).  users: the rows to
@@ -857,11 +914,17 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, 
     pair with any number of rows and at most the model's number of columns -- and include_of names each user's row of it: one int
     for all, or an integer array with one entry per user of the model (indexed by user id; the entries of `users` are taken here).
     The held-out rows are united in on the device, so a pool of negatives sampled once for everybody is passed as it is and no
-    per-user list is built."""
+    per-user list is built.
+    negatives: an int m -- sampled evaluation with the lists drawn here (section 1t): every evaluated user gets m sampled negatives
+    that avoid its `exclude` row and its own held-out row, as sample_negatives(users, m, exclude=<both>, item_weight=negatives_weight,
+    seed=seed) returns them, and they are passed as include=.  Not together with include=."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
+    if negatives is not None and (include is not None or include_of is not None):
+        raise ValueError("negatives= samples the candidate lists: it cannot be combined with include=")
     users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.nusers, self.nitems)
     dt = np.float32 if self.use_float else np.float64
+    include = _sampled_include(self.sample_negatives, users, test, exclude, include, negatives, negatives_weight, seed, self.nitems)
     if include_of is not None:
         ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude,
                                   include=include, include_of=_include_of_rows(include_of, users, self.nusers), unite_test=True)
@@ -1612,11 +1675,23 @@ class Session:
         held-out row, which is what a shared pool of negatives needs."""
         return serving.rank_batch(self, users, test, exclude_seen, exclude, include, include_of, unite_test)
 
-    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None):
+    def sample_negatives(self, users, m, exclude_seen=True, exclude=None, item_weight=None, seed=0, return_draws=False):
+        """api.sample_negatives for users of the session (include/poismf_hip.h section 1t): with exclude_seen the items of the user's
+        row of the session's own CSR are left out (nothing is uploaded), exclude leaves out more.  Returns (indptr, indices), rows
+        ascending -- what include= takes -- and with return_draws the draws each row consumed."""
+        return serving.sample_negatives(self, users, m, exclude_seen, exclude, item_weight, seed, return_draws)
+
+    def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None,
+                     negatives=None, negatives_weight=None, seed=0):
         """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
         CSR (nothing is uploaded), exclude leaves out more; include as there (sampled evaluation, section 1j), include with
-        include_of as there too (pools shared between users, section 1k)."""
+        include_of as there too (pools shared between users, section 1k); negatives, negatives_weight and seed as there too: the
+        sample is Session.sample_negatives' with the same exclude_seen."""
+        if negatives is not None and (include is not None or include_of is not None):
+            raise ValueError("negatives= samples the candidate lists: it cannot be combined with include=")
         users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.dimA, self.dimB)
+        include = _sampled_include(lambda *a: self.sample_negatives(a[0], a[1], exclude_seen, *a[2:]), users, test, exclude, include, negatives,
+                                   negatives_weight, seed, self.dimB)
         if include_of is not None:
             ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include,
                                            include_of=_include_of_rows(include_of, users, self.dimA), unite_test=True)

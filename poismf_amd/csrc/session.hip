@@ -736,6 +736,22 @@ int poismf_hip_session_order_include(poismf_hip_session* s, const sparse_ix* use
                                          out_count);
 }
 
+// Sampled negatives for users of the session (sample_negatives.hip; include/poismf_hip.h section 1t), ordered as the calls above and in
+// the same scratch: no factor is read; with exclude_seen the resident CSR shard's rows join the exclusion lists.
+int poismf_hip_session_sample_negatives(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t m, uint64_t seed, int exclude_seen,
+                                        const sparse_ix* excl_indptr, const sparse_ix* excl_indices, const uint32_t* item_weight, sparse_ix* items,
+                                        sparse_ix* count, sparse_ix* draws)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || items == nullptr || count == nullptr) return 2;
+    if (const int rc = poismf_hip_sample_negatives_check(users, n_users, m, s->dimA, s->dimB, excl_indptr, excl_indices, item_weight)) return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_sample_negatives_core(s->stream, s->dimB, users, n_users, m, seed, exclude_seen ? &seen : nullptr, excl_indptr, excl_indices,
+                                            item_weight, &s->d_topn, &s->topn_cap, items, count, draws);
+}
+
 // Batched top-N over candidate lists shared between users from the resident (compact) factors (topn_shared.hip; include/poismf_hip.h
 // section 1i), ordered as the calls above and in the same scratch.
 int poismf_hip_session_topn_shared(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* list_indptr,

@@ -4,6 +4,7 @@
 // tb_stage_chunk and closes with tb_fetch_results -- and what the session (session.hip) hands to their cores
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
 #include <algorithm>
 #include <new>
@@ -131,6 +132,14 @@ int poismf_hip_topn_diverse_run(hipStream_t stream, const real_t* dA, const real
                                 const sparse_ix* users, size_t n_users, size_t n_top, size_t pool, double lambda, const real_t* item_inv_norm,
                                 PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch,
                                 size_t* scratch_cap, sparse_ix* out_ix, real_t* out_score, real_t* out_value);
+
+// (sample_negatives.hip; section 1t) the same pair for the negative sampler, which reads no factors: users below n_ids (0: any id names
+// a stream), item_weight [dimB] a host array or NULL; the check makes no device call, the core returns 0 or 1.  draws may be NULL
+int poismf_hip_sample_negatives_check(const sparse_ix* users, size_t n_users, size_t m, size_t n_ids, size_t dimB, const sparse_ix* excl_indptr,
+                                      const sparse_ix* excl_indices, const uint32_t* item_weight);
+int poismf_hip_sample_negatives_core(hipStream_t stream, size_t dimB, const sparse_ix* users, size_t n_users, size_t m, uint64_t seed,
+                                     PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices, const uint32_t* item_weight,
+                                     void** d_scratch, size_t* scratch_cap, sparse_ix* items, sparse_ix* count, sparse_ix* draws);
 
 #define TB_TRY(expr) do { if ((expr) != hipSuccess) return 1; } while (0)
 

@@ -1,5 +1,5 @@
 """The serving calls' host side: the argument checks that need no device, each rule written once, and the one path every batched
-top-N, re-rank and rank call takes to the library (include/poismf_hip.h sections 1f-1s).
+top-N, re-rank, rank and sampling call takes to the library (include/poismf_hip.h sections 1f-1t).
 
 A call is made against a *target*: a ``Session`` (resident factors) or ``api._HostFactors`` (host factors that go up with the call).
 Both offer ``dimA``, ``dimB``, ``k``, ``use_float``, ``item_norms()`` and ``_entry(name, exclude_seen)``, which gives the library's
@@ -465,6 +465,47 @@ def _topn_shared_args(users, n, include, include_of, exclude, dimA, dimB):
     return (users,) + _shared_table_args(include, include_of, m, dimB) + _exclude_list(exclude, m, dimB)
 
 
+def _negatives_m(m):
+    """the number of sampled items per user (include/poismf_hip.h section 1t) as an int within 1 .. NEG_MAX_M"""
+    m = int(m)
+    if not 1 <= m <= api.NEG_MAX_M:
+        raise ValueError(f"the number of sampled items per user must lie in 1 .. {api.NEG_MAX_M}")
+    return m
+
+
+def _negatives_weight(item_weight, dimB):
+    """The item weights of the negative sampler as the library takes them: None, or uint32 [dimB] with a positive sum.  An integer
+    array is taken as it is (0 .. 2^32 - 1); a float array, finite and non-negative, is scaled as rint(w / max(w) * 2^31)."""
+    if item_weight is None:
+        return None
+    w = np.asarray(item_weight)
+    if w.shape != (dimB,):
+        raise ValueError("item_weight must hold one weight per item")
+    if w.dtype.kind in "iub":
+        if w.size and (int(w.min()) < 0 or int(w.max()) >= 2 ** 32):
+            raise ValueError("an integer item_weight must lie in 0 .. 2^32 - 1")
+    else:
+        w = _finite_nonneg(w, np.float64, "item_weight holds a NaN", "an item_weight is", "item_weight holds a negative weight")
+        if w.max() > 0:
+            w = np.rint(w / w.max() * 2.0 ** 31)
+    if not w.any():
+        raise ValueError("every item_weight is 0: there is nothing to draw")
+    return np.ascontiguousarray(w, dtype=np.uint32)
+
+
+def _sample_negatives_args(users, m, exclude, item_weight, seed, dimA, dimB):
+    """The argument checks of the negative sampler (include/poismf_hip.h section 1t) that need no device, as the library itself makes
+    them; dimA None: any id is a stream's.  Returns (users, m, excl_indptr or None, excl_indices or None, weights or None, seed)."""
+    users, m = _index_array(users, "users"), _negatives_m(m)
+    if dimA is not None:
+        _users_in_range(users, dimA)
+    _item_count(dimB, api.NEG_MAX_ITEMS, "negative sampler")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must lie in 0 .. 2^64 - 1")
+    return (users, m) + _exclude_list(exclude, len(users), dimB) + (_negatives_weight(item_weight, dimB), seed)
+
+
 def _rank_include_list(include, m, dimB):
     """The include lists of the batched ranks (include/poismf_hip.h section 1j), checked as the library checks them: (incl_indptr,
     incl_indices) as uint64 arrays"""
@@ -763,6 +804,23 @@ def order_candidates(target, users, include, exclude_seen, exclude, output_score
     indptr = np.concatenate(([0], np.cumsum(cnt, dtype=np.int64)))
     keep = ix != api.TOPN_NONE
     return (indptr, ix[keep], sc[keep]) if output_score else (indptr, ix[keep])
+
+
+def sample_negatives(target, users, m, exclude_seen, exclude, item_weight, seed, return_draws):
+    """section 1t: sampled negatives.  The library's rows are m wide and padded with TOPN_NONE; what is returned is that with the
+    padding taken out: (indptr, items[, draws])."""
+    users, m, ep, ei, w, seed = _sample_negatives_args(users, m, exclude, item_weight, seed, target.dimA, target.dimB)
+    n = len(users)
+    if exclude_seen:
+        _outside_shard(users, target.shardA)
+    ix, cnt, draws = np.empty((n, m), np.uint64), np.zeros(n, np.uint64), np.zeros(n if return_draws else 0, np.uint64)
+    if n:
+        fn, lead, flag = target._entry("sample_negatives", exclude_seen)
+        _batch_rc(fn(*lead, _ptr(users), n, m, seed, *flag, _opt_ptr(ep), _opt_ptr(ei), _opt_ptr(w), _ptr(ix), _ptr(cnt), _opt_ptr(draws)),
+                  "negative sampling")
+    indptr = np.concatenate(([0], np.cumsum(cnt, dtype=np.int64)))
+    items = ix[ix != api.TOPN_NONE]
+    return (indptr, items, draws.astype(np.int64)) if return_draws else (indptr, items)
 
 
 def topn_deep(target, users, n, exclude_seen, exclude, output_score):
