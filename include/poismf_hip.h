@@ -923,6 +923,59 @@ POISMF_HIP_API size_t poismf_hip_sample_negatives_scratch_bytes(size_t n_users, 
 POISMF_HIP_API void poismf_hip_philox4x32(const uint32_t *counter, const uint32_t *key, uint32_t *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1u. Sampled ranks in one pass: section 1t's negatives drawn, scored and ranked against on the device, without the sample ever
+ *     being written out (no counterpart in the reference).  It is what a sampled evaluation needs -- one integer per held-out cell
+ *     and one per user -- where section 1t followed by section 1j moves every sampled index down to the host and up again.
+ *
+ * For a batch of users u_0 .. u_{n-1} (any order, repeats allowed), per user
+ *
+ *   T(u)         a held-out list exactly as in section 1g: test_indptr [n + 1], test_indices, strictly ascending rows.
+ *   E(u)         an exclusion set exactly as in section 1f: exclude_seen on a session and / or the CSR-shaped host list
+ *                excl_indptr / excl_indices (excl_indptr = NULL: no list).
+ *   S(u)         the row section 1t defines for (seed, u, m, dimB, E(u) united with T(u), item_weight): the same streams -- the
+ *                user's id is its stream's id --, the same 128-bit mapping, the same acceptance rule and the same cap
+ *                POISMF_HIP_NEG_DRAWS(m).  The sample avoids every held-out item of the user, excluded or not.
+ *   C(u), N(u)   C(u) = S(u) united with (T(u) \ E(u)), N(u) = |C(u)|.
+ *   rank(u, t)   for t in T(u) \ E(u): the number of j in C(u) that come before t under section 1f's total order ("score
+ *                descending, item index ascending") with section 1f's score bits.  A held-out cell whose item is in E(u) gets
+ *                POISMF_HIP_RANK_EXCLUDED; it is not an error.
+ *
+ * By definition this is section 1j's answer, out_rank and out_n_adm alike, for the include list I(u) = S(u) united with T(u) and
+ * the same E(u): what poismf_hip_sample_negatives with exclusion rows E(u) united with T(u), a row-wise union with T(u) on the host
+ * and poismf_hip_rank_include return in two calls.  A row of the output depends on (A[u], B, seed, u, m, dimB, T(u), E(u),
+ * item_weight) and on nothing else: not the batch, its chunks, or the user's position in `users`.  All counting is in integers;
+ * there are no float atomics.
+ *
+ *   output       out_rank: one unsigned int per entry of test_indices, in the caller's order; out_n_adm [n]: N(u); out_count [n]
+ *                (may be NULL): |S(u)|, below m only when section 1t's cap bites; out_draws [n] (may be NULL): section 1t's
+ *                `draws`.  Host arrays.  The sampled items themselves are not returned: section 1t returns them.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, in the cases of sections 1j
+ * and 1t together: m < 1 or m > POISMF_HIP_NEG_MAX_M; dimB < 1 or dimB > 2^24; a user index >= dimA; an item index >= dimB; a
+ * held-out or exclusion row not strictly ascending, or row pointers that decrease; users or test_indptr == NULL; k outside 1..512
+ * float / 1..256 double; exclude_seen for a user outside the session's rows of A; an exclusion list that section 1f refuses; a
+ * held-out row longer than POISMF_HIP_RANK_BATCH_MAX_ROW; W = 0.  n_users == 0 returns 0.  Factors are assumed finite.
+ *
+ * One work item per user: one wave draws into a list in LDS, which then feeds section 1j's gather and
+ * counting; m <= 256 takes one wave per user, a longer row a workgroup of three waves that share the scoring.  No kernel of this
+ * call stores a sampled row to device memory.  A user with more than POISMF_HIP_RANK_INCLUDE_GROUP valid held-out items has them
+ * searched in device memory, as in section 1j.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1t share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB
+ * for any number of users and held-out cells: the prefix sums, and chunks of consecutive users with their held-out rows and
+ * exclusion lists.  poismf_hip_rank_sampled_scratch_bytes (testing aid, no HIP call) is the size both entry points allocate; it
+ * does not depend on m or k.  poismf_hip_rank_sampled's own copies of B and of A (all of A, or only the batch's rows when
+ * n_users < dimA) come on top.  The session flavour, poismf_hip_session_rank_sampled, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_rank_sampled(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, size_t m, uint64_t seed,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices, const uint32_t *item_weight,
+        unsigned int *out_rank, unsigned int *out_n_adm, unsigned int *out_count, unsigned int *out_draws);
+POISMF_HIP_API size_t poismf_hip_rank_sampled_scratch_bytes(size_t n_users, size_t n_test_cells, size_t m, size_t dimB, size_t k,
+        int weighted);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -1316,6 +1369,12 @@ POISMF_HIP_API int poismf_hip_session_rank_include(poismf_hip_session *s, const 
         const sparse_ix *incl_indptr, const sparse_ix *incl_indices, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
         unsigned int *out_rank, unsigned int *out_n_adm);
+
+/* Section 1u from the session-resident factors (with exclude_seen, the session's own CSR rows join E(u)), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_rank_sampled(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
+        const sparse_ix *test_indptr, const sparse_ix *test_indices, size_t m, uint64_t seed, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices, const uint32_t *item_weight,
+        unsigned int *out_rank, unsigned int *out_n_adm, unsigned int *out_count, unsigned int *out_draws);
 
 /* Section 1k from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_rank_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users,

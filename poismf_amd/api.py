@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_order_include", "poismf_hip_session_order_include", "poismf_hip_order_include_scratch_bytes", "poismf_hip_order_include_run",
     "poismf_hip_order_include_wave_row",
     "poismf_hip_sample_negatives", "poismf_hip_session_sample_negatives", "poismf_hip_sample_negatives_scratch_bytes", "poismf_hip_philox4x32",
+    "poismf_hip_rank_sampled", "poismf_hip_session_rank_sampled", "poismf_hip_rank_sampled_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -279,6 +280,12 @@ def load_library(use_float):
     lib.poismf_hip_session_sample_negatives.restype = i
     lib.poismf_hip_sample_negatives_scratch_bytes.argtypes = [sz, sz, sz, i]
     lib.poismf_hip_sample_negatives_scratch_bytes.restype = sz
+    lib.poismf_hip_rank_sampled.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_rank_sampled.restype = i
+    lib.poismf_hip_session_rank_sampled.argtypes = [vp, vp, sz, vp, vp, sz, C.c_uint64, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_rank_sampled.restype = i
+    lib.poismf_hip_rank_sampled_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, i]
+    lib.poismf_hip_rank_sampled_scratch_bytes.restype = sz
     lib.poismf_hip_philox4x32.argtypes = [vp, vp, vp]
     lib.poismf_hip_philox4x32.restype = None
     lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
@@ -753,14 +760,19 @@ def _sample_negatives(self, users, m, exclude=None, item_weight=None, seed=0, re
 PoisMF.sample_negatives = _sample_negatives
 
 
-def _sampled_include(sample, users, test, exclude, include, negatives, negatives_weight, seed, dimB):
-    """eval_ranking's negatives=: the include lists are `negatives` sampled items per user that avoid its exclusions and its own
-    held-out row (sample(users, m, exclude, item_weight, seed) makes the call)"""
-    if negatives is None:
-        return include
-    m = serving._negatives_m(negatives)
-    avoid = test if exclude is None else serving._unite_rows(serving._exclude_list(exclude, len(users), dimB), test)
-    return sample(users, m, avoid, negatives_weight, seed)
+def rank_sampled(A, B, users, test, m, exclude=None, item_weight=None, seed=0, return_counts=False):
+    """Sampled ranks in one pass on the GPU (include/poismf_hip.h section 1u) on host factors A [dimA x k], B [dimB x k] (float32 or
+    float64, both alike): every user of `users` gets m sampled negatives as sample_negatives draws them for the exclusion rows
+    `exclude` united with its own held-out row of `test` (both in rank_batch's forms), and every cell of `test` is ranked among the
+    user's negatives and its other held-out items -- rank_batch(include=<the sample united with test>)'s answer, without the sample
+    leaving the device.  item_weight and seed as in sample_negatives.  Returns (ranks uint32, one per cell in row order,
+    RANK_EXCLUDED where the item is in the user's `exclude` row; n_adm uint32 [len(users)]: the sampled items plus the ranked
+    cells); with return_counts also (count, draws) int64 [len(users)]: the sample's size and the draws it consumed."""
+    A, B = np.asarray(A), np.asarray(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
+        raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
+    target = _HostFactors(A, B, A.shape[0], B.shape[0], A.shape[1], A.dtype == np.float32)
+    return serving.rank_sampled(target, users, test, m, False, exclude, item_weight, seed, return_counts)
 
 
 def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_score=False):
@@ -917,14 +929,19 @@ def _eval_ranking(self, X_test, k=10, exclude=None, users=None, per_user=False, 
     per-user list is built.
     negatives: an int m -- sampled evaluation with the lists drawn here (section 1t): every evaluated user gets m sampled negatives
     that avoid its `exclude` row and its own held-out row, as sample_negatives(users, m, exclude=<both>, item_weight=negatives_weight,
-    seed=seed) returns them, and they are passed as include=.  Not together with include=."""
+    seed=seed) returns them, and the cells are ranked among them and the user's other held-out items in the same pass on the device
+    (rank_sampled, section 1u): the answer of passing that sample as include=, without the sample coming down.  Not together with
+    include=."""
     if not self.is_fitted:
         raise ValueError("Model has not been fitted.")
     if negatives is not None and (include is not None or include_of is not None):
         raise ValueError("negatives= samples the candidate lists: it cannot be combined with include=")
     users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.nusers, self.nitems)
     dt = np.float32 if self.use_float else np.float64
-    include = _sampled_include(self.sample_negatives, users, test, exclude, include, negatives, negatives_weight, seed, self.nitems)
+    if negatives is not None:
+        ranks, n_adm = rank_sampled(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, negatives,
+                                    exclude, negatives_weight, seed)
+        return _ranking_result(test[0], ranks, n_adm, k, per_user)
     if include_of is not None:
         ranks, n_adm = rank_batch(np.ascontiguousarray(self.A, dtype=dt), np.ascontiguousarray(self.B, dtype=dt), users, test, exclude,
                                   include=include, include_of=_include_of_rows(include_of, users, self.nusers), unite_test=True)
@@ -1681,17 +1698,25 @@ class Session:
         ascending -- what include= takes -- and with return_draws the draws each row consumed."""
         return serving.sample_negatives(self, users, m, exclude_seen, exclude, item_weight, seed, return_draws)
 
+    def rank_sampled(self, users, test, m, exclude_seen=True, exclude=None, item_weight=None, seed=0, return_counts=False):
+        """api.rank_sampled from the resident factors (include/poismf_hip.h section 1u): every user's m negatives are drawn as
+        sample_negatives(users, m, exclude_seen, <exclude united with test>, item_weight, seed) draws them and every cell of `test` is
+        ranked among them and the user's other held-out items, in one pass; the sample stays on the device.  Returns (ranks, n_adm)
+        as rank_batch(include=<that sample united with test>) does, and with return_counts also (count, draws)."""
+        return serving.rank_sampled(self, users, test, m, exclude_seen, exclude, item_weight, seed, return_counts)
+
     def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None,
                      negatives=None, negatives_weight=None, seed=0):
         """PoisMF.eval_ranking from the resident factors; exclude_seen leaves out the items of the user's row of the session's own
         CSR (nothing is uploaded), exclude leaves out more; include as there (sampled evaluation, section 1j), include with
         include_of as there too (pools shared between users, section 1k); negatives, negatives_weight and seed as there too: the
-        sample is Session.sample_negatives' with the same exclude_seen."""
+        sample is Session.sample_negatives' with the same exclude_seen, drawn and ranked against by Session.rank_sampled."""
         if negatives is not None and (include is not None or include_of is not None):
             raise ValueError("negatives= samples the candidate lists: it cannot be combined with include=")
         users, test, exclude, k = _eval_ranking_args(X_test, exclude, users, k, self.dimA, self.dimB)
-        include = _sampled_include(lambda *a: self.sample_negatives(a[0], a[1], exclude_seen, *a[2:]), users, test, exclude, include, negatives,
-                                   negatives_weight, seed, self.dimB)
+        if negatives is not None:
+            ranks, n_adm = self.rank_sampled(users, test, negatives, exclude_seen, exclude, negatives_weight, seed)
+            return _ranking_result(test[0], ranks, n_adm, k, per_user)
         if include_of is not None:
             ranks, n_adm = self.rank_batch(users, test, exclude_seen=exclude_seen, exclude=exclude, include=include,
                                            include_of=_include_of_rows(include_of, users, self.dimA), unite_test=True)

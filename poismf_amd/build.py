@@ -2,7 +2,7 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Thirty-two translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
+Thirty-three translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
 session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver, one for the multiplicative update "mm" and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
@@ -11,7 +11,7 @@ batched top-N over include lists (topn_include.hip) and over lists shared betwee
 include lists (rank_include.hip) and among lists shared between users (rank_shared.hip), the deep batched top-N (topn_deep.hip, with
 tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and with per-(user, item) score factors (topn_adjust.hip: a dense pass on tb_select.hpp, a sparse one on tb_gather.hpp and a merge) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the eleven share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted / topn_adjust the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units, topn_diverse and topn_adjust tb_gather.hpp) and the
 new rows against a resident B (fold_in.hip: the guest of a session, on session.hpp and tb_batch.hpp) and the list-wise evaluation
-(list_eval.hip, on tb_gather.hpp and tb_batch.hpp) and the negative sampler (sample_negatives.hip, with philox.hpp, on tb_batch.hpp) -- are compiled to object files
+(list_eval.hip, on tb_gather.hpp and tb_batch.hpp) and the negative sampler (sample_negatives.hip, with philox.hpp, on tb_batch.hpp) and the fused sampled ranks (rank_sampled.hip, which shares the sampler's draw, sn_draw.hpp, and the include ranks' tb_gather.hpp and tb_rank.hpp) -- are compiled to object files
 side by side and linked.  What an object depends on is derived from its file's #include "..." lines (_deps), never listed by hand.
 Every object and library carries a `.stamp` with the digest of its command line and sources: an object is rebuilt exactly when that
 digest changes (a different POISMF_HIP_EXTRA_FLAGS rebuilds everything it reaches; file times play no part).  A full build takes ~11.5 minutes on 8 cores
@@ -67,6 +67,8 @@ UNITS = {
     "list_eval": ("list_eval.hip", []),
     # the negative sampler is integer code throughout: nothing in it is to be paired into packed fp32 instructions either
     "sample_negatives": ("sample_negatives.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
+    # the fused sampled ranks: the sampler's draw (sn_draw.hpp), then the include ranks' gather and counting on the list in LDS
+    "rank_sampled": ("rank_sampled.hip", []),
 }
 _INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"/]+)"', re.M)   # (the includes inside csrc/ are flat quoted names)
 

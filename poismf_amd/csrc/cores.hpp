@@ -2,6 +2,7 @@
 // each function and by every caller.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,18 @@ int poismf_hip_list_eval_run(hipStream_t stream, const real_t* dB, size_t dimB, 
                              const real_t* item_inv_norm, const sparse_ix* test_indptr, const sparse_ix* test_indices, size_t budget_bytes,
                              void** d_scratch, size_t* scratch_cap, unsigned int* out_pos, long long* out_cos, unsigned int* out_len,
                              unsigned int* exposure);
+// rank_sampled.hip (section 1u): the argument checks of both entry points (0, or 2; no device call) and the core on device-resident
+// factors, with tb_batch.hpp's conventions: dA rows are addressed by users[i], or by i itself when compact_A; `seen` is the session's
+// resident CSR shard (exclude_seen) or NULL; out_count and out_draws may be NULL; 0 or 1
+struct PmfTopnSeen;
+int poismf_hip_rank_sampled_check(const sparse_ix* users, size_t n_users, size_t m, size_t dimA, size_t dimB, size_t k, const sparse_ix* test_indptr,
+                                  const sparse_ix* test_indices, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                  const uint32_t* item_weight);
+int poismf_hip_rank_sampled_core(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                 const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr, const sparse_ix* test_indices, size_t m,
+                                 uint64_t seed, PmfTopnSeen* seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                 const uint32_t* item_weight, void** d_scratch, size_t* scratch_cap, unsigned int* out_rank,
+                                 unsigned int* out_n_adm, unsigned int* out_count, unsigned int* out_draws);
 // coo_convert.hip (rocPRIM-based helpers)
 int poismf_hip_device_sort_rows(const unsigned long long* d_indptr, size_t nloc, unsigned base, unsigned* d_perm, unsigned* d_len_sorted,
                                 hipStream_t stream);

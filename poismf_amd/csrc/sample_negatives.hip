@@ -4,22 +4,11 @@
 // among.  A row is a function of (seed, u, m, dimB, E(u), weights): the header's sequential rule "walk the draws upward, accept what
 // is admissible and not accepted before, stop at m accepts or at the cap" is carried out 64 draws at a time.
 //
-// One wave per user; lane l of a round takes draw d0 + l:
-//   draw      the ten Philox rounds, r = (w1 << 32) | w0, then j = (r dimB) >> 64, or t = (r W) >> 64 and the first item whose
-//             inclusive prefix sum C_j exceeds t: a search in the coarse index (every stride-th entry of C, staged in LDS once per
-//             workgroup), then at most ceil(log2(stride)) steps in C itself, which stays in L2.
-//   E(u)      tb_excluded: the chunk's staged list and the resident row.
-//   accepted  an open-addressing table in LDS, one word per slot: (item << 8) | tag, items being below 2^24.  Tag 0 marks an item
-//             accepted in an earlier round, tag l + 1 one claimed in this round by lane l.  A lane walks from its item's hash: an empty
-//             slot is taken by atomicCAS; a slot that holds its item takes an atomicMin of the lane's word, which, the items being
-//             equal, leaves the LOWEST lane -- the earliest draw -- in the slot.  A lane that reads its own word back is the item's
-//             first occurrence; an earlier round's word (tag 0) is below every lane's and stays.  The winners then clear their tags.
-//             The tag in the key's word takes the place of a companion owner word per slot and halves the table.
-//   the cut   __ballot of the winners, a prefix popcount for each one's place, and the lanes with count + place < m append to the
-//             row's list in LDS; the lane of the m-th accept writes `draws`.  Lanes at or past the cap never draw.
+// One wave per user.  The draw itself -- the Philox block, the candidate, the open-addressing table in LDS in which the earliest draw of
+// equal items wins, the ballot cut -- is sn_draw_row (sn_draw.hpp), which the fused sampled ranks (rank_sampled.hip) call too; the
+// admissibility test here is tb_excluded: the chunk's staged list and the resident row.  What this kernel adds is
 //   the row   a u32 bitonic network over the list in LDS (padded with TB_NONE to a power of two, which is also the row's padding).
-// Between rounds the table holds the accepted items only, fewer than m in at least 2 m slots; inside the last round it may hold up to
-// 63 items that the cut then leaves out.  No float anywhere.
+// No float anywhere.
 //
 // Two instances by LDS: m <= SN_SMALL_M four waves per workgroup, one user each, 3 KB per wave; above, one wave per workgroup with
 // the table sized to m -- 48 KB at m = 4096, 56 KB with the coarse index, two workgroups per CU and more for a smaller m.
@@ -36,52 +25,23 @@
 #include "devmem.hpp"
 #include "tb_tile.hpp"
 #include "tb_batch.hpp"
-#include "philox.hpp"
+#include "sn_draw.hpp"
 
 namespace {
 
-constexpr size_t SN_MAX_M = POISMF_HIP_NEG_MAX_M;
-constexpr size_t SN_MAX_ITEMS = (size_t)1 << 24;          // an item and a tag share a word
-constexpr size_t SN_SMALL_M = 256;                        // longest row of the four-wave instance
-constexpr unsigned SN_SMALL_SLOTS = 512;
-constexpr unsigned SN_COARSE = 1024;                      // entries of the coarse index of C
-constexpr unsigned SN_EMPTY = 0xffffffffu;                // (no word (item << 8) | tag: tags end at 64)
-static_assert(SN_SMALL_SLOTS >= 2 * SN_SMALL_M && SN_SMALL_M + 63 < SN_SMALL_SLOTS, "the table never fills");
 static_assert(SN_MAX_M * 4 + 2 * SN_MAX_M * 4 + SN_COARSE * 8 <= 80 * 1024, "two workgroups of the largest row per CU");
 
 struct SnArgs {
     const unsigned* users;                // the chunk's rows of A (exclude_seen)
     const unsigned long long* streams;    // the chunk's stream ids
-    unsigned n_users, m, cap, dimB;
-    unsigned log_slots, list_cap;         // table slots (a power of two) and list entries (a power of two >= m) per wave
-    unsigned key0, key1;
+    unsigned n_users;
+    unsigned list_cap;                    // list entries (a power of two >= m) per wave
+    SnDraw d;                             // m, the cap, the key, the table's size, the weights' prefix sums
     TbExcl excl;                          // E(u) of the chunk's users
-    const unsigned long long* C;          // [dimB] inclusive prefix sums of the weights
-    const unsigned long long* coarse;     // [n_coarse] C at the last item of every block of `stride` items
-    unsigned n_coarse, stride;
-    unsigned long long W;                 // C[dimB - 1]
     unsigned* items;                      // [chunk users x m]
     unsigned* cnt;                        // [chunk users]
     unsigned* draws;                      // [chunk users]
 };
-
-// the first item whose prefix sum exceeds t < W
-__device__ __forceinline__ unsigned sn_weighted_item(const SnArgs& a, const unsigned long long* coarse, unsigned long long t)
-{
-    unsigned lo = 0, hi = a.n_coarse - 1;   // (coarse[n_coarse - 1] = W > t)
-    while (lo < hi) {
-        const unsigned mid = (lo + hi) / 2;
-        if (coarse[mid] > t) hi = mid;
-        else lo = mid + 1;
-    }
-    unsigned jl = lo * a.stride, jh = min(jl + a.stride, a.dimB) - 1;   // (C[jh] is coarse[lo] > t, and everything before jl is <= t)
-    while (jl < jh) {
-        const unsigned mid = (jl + jh) / 2;
-        if (a.C[mid] > t) jh = mid;
-        else jl = mid + 1;
-    }
-    return jl;
-}
 
 // ascending bitonic network of one wave over lst[0 .. p), p a power of two
 __device__ __forceinline__ void sn_wave_sort(unsigned* lst, unsigned p, unsigned lane)
@@ -104,58 +64,22 @@ template <int WAVES, bool WEIGHTED> __global__ __launch_bounds__(64 * WAVES) voi
     const unsigned long long* coarse = (const unsigned long long*)sn_smem;
     if (WEIGHTED) {
         unsigned long long* cs = (unsigned long long*)sn_smem;
-        for (unsigned t = threadIdx.x; t < a.n_coarse; t += 64 * WAVES) cs[t] = a.coarse[t];
+        for (unsigned t = threadIdx.x; t < a.d.n_coarse; t += 64 * WAVES) cs[t] = a.d.coarse[t];
         __syncthreads();   // (the only workgroup barrier: from here on the waves share nothing else)
     }
     const unsigned ui = blockIdx.x * WAVES + wave;
     if (ui >= a.n_users) return;
-    const unsigned slots = 1u << a.log_slots;
+    const unsigned slots = 1u << a.d.log_slots;
     unsigned* tab = (unsigned*)(sn_smem + (WEIGHTED ? SN_COARSE * sizeof(unsigned long long) : 0)) + (size_t)wave * (slots + a.list_cap);
     unsigned* lst = tab + slots;
-    for (unsigned s = lane; s < slots; s += 64) tab[s] = SN_EMPTY;
     for (unsigned e = lane; e < a.list_cap; e += 64) lst[e] = TB_NONE;
-    tb_wave_sync();
 
-    const unsigned long long stream = a.streams[ui];
     const unsigned arow = a.users[ui];
-    const uint32_t key[2] = { a.key0, a.key1 };
-    const unsigned m = a.m;
-    unsigned count = 0;
-    for (unsigned d0 = 0; d0 < a.cap && count < m; d0 += 64) {
-        const unsigned d = d0 + lane;
-        unsigned j = 0;
-        bool cand = false;
-        if (d < a.cap) {
-            const uint32_t ctr[4] = { d, 0u, (uint32_t)stream, (uint32_t)(stream >> 32) };
-            uint32_t w[4];
-            pmf_philox4x32_10(ctr, key, w);
-            const unsigned long long r = ((unsigned long long)w[1] << 32) | w[0];
-            j = WEIGHTED ? sn_weighted_item(a, coarse, __umul64hi(r, a.W)) : (unsigned)__umul64hi(r, (unsigned long long)a.dimB);
-            cand = !tb_excluded(a.excl, ui, arow, j);
-        }
-        const unsigned mine = (j << 8) | (lane + 1);
-        unsigned slot = (j * 0x9E3779B1u) >> (32 - a.log_slots);
-        if (cand) {
-            for (;;) {
-                const unsigned prev = atomicCAS(&tab[slot], SN_EMPTY, mine);
-                if (prev == SN_EMPTY) break;
-                if ((prev >> 8) == j) { atomicMin(&tab[slot], mine); break; }
-                slot = (slot + 1) & (slots - 1);
-            }
-        }
-        tb_wave_sync();
-        const bool win = cand && tab[slot] == mine;   // (a later lane with the same item, or an item of an earlier round, reads another word)
-        const unsigned long long won = __ballot(win);
-        const unsigned place = count + (unsigned)__popcll(won & (((unsigned long long)1 << lane) - 1));
-        if (win) {
-            tab[slot] = j << 8;
-            if (place < m) lst[place] = j;
-            if (place == m - 1) a.draws[ui] = d + 1;
-        }
-        count = min(m, count + (unsigned)__popcll(won));
-        tb_wave_sync();
-    }
-    if (count < m && lane == 0) a.draws[ui] = a.cap;
+    const unsigned m = a.d.m;
+    unsigned draws;
+    const unsigned count = sn_draw_row<WEIGHTED>(a.d, coarse, tab, lst, a.streams[ui], lane,
+                                                 [&](unsigned j) { return !tb_excluded(a.excl, ui, arow, j); }, draws);
+    if (lane == 0) a.draws[ui] = draws;
 
     unsigned p = 1;
     while (p < count) p <<= 1;   // (p <= list_cap; the entries from count on are TB_NONE)
@@ -163,13 +87,6 @@ template <int WAVES, bool WEIGHTED> __global__ __launch_bounds__(64 * WAVES) voi
     unsigned* row = a.items + (size_t)ui * m;
     for (unsigned e = lane; e < m; e += 64) row[e] = lst[e];
     if (lane == 0) a.cnt[ui] = count;
-}
-
-inline unsigned sn_pow2_at_least(size_t n)
-{
-    unsigned l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
 }
 
 // The one scratch allocation of a call: what a chunk of users needs, in bytes from the start.
@@ -208,7 +125,7 @@ static_assert(SN_MAX_ITEMS <= TB_BUDGET / 4 / sizeof(unsigned), "the longest exc
 
 template <int WAVES, bool WEIGHTED> hipError_t sn_launch(const SnArgs& a, hipStream_t stream)
 {
-    const size_t lds = (WEIGHTED ? SN_COARSE * sizeof(unsigned long long) : 0) + (size_t)WAVES * (((size_t)1 << a.log_slots) + a.list_cap) * sizeof(unsigned);
+    const size_t lds = (WEIGHTED ? SN_COARSE * sizeof(unsigned long long) : 0) + (size_t)WAVES * (((size_t)1 << a.d.log_slots) + a.list_cap) * sizeof(unsigned);
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_negatives_kernel<WAVES, WEIGHTED>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -257,31 +174,12 @@ int poismf_hip_sample_negatives_core(hipStream_t stream, size_t dimB, const spar
     SnArgs a = {};
     a.users = (const unsigned*)(base + L.users);
     a.streams = (const unsigned long long*)(base + L.streams);
-    a.m = (unsigned)m;
-    a.cap = (unsigned)POISMF_HIP_NEG_DRAWS(m);
-    a.dimB = (unsigned)dimB;
-    a.log_slots = m <= SN_SMALL_M ? sn_pow2_at_least(SN_SMALL_SLOTS) : sn_pow2_at_least(2 * m);
+    a.d = sn_draw_of(m, dimB, seed);
     a.list_cap = m <= SN_SMALL_M ? (unsigned)SN_SMALL_M : 1u << sn_pow2_at_least(m);
-    a.key0 = (unsigned)(seed & 0xffffffffu);
-    a.key1 = (unsigned)(seed >> 32);
     a.items = (unsigned*)(base + L.items);
     a.cnt = (unsigned*)(base + L.cnt);
     a.draws = (unsigned*)(base + L.draws);
-    if (weighted) {
-        // the prefix sums by sequential integer additions, and every stride-th of them: uploaded once per call
-        std::vector<unsigned long long> hC, hcoarse;
-        try { hC.resize(dimB); } catch (const std::bad_alloc&) { return 1; }
-        unsigned long long acc = 0;
-        for (size_t j = 0; j < dimB; j++) hC[j] = acc += item_weight[j];
-        a.W = acc;
-        a.stride = (unsigned)pmf_ceil_div(dimB, SN_COARSE);
-        a.n_coarse = (unsigned)pmf_ceil_div(dimB, a.stride);
-        for (size_t b = 0; b < a.n_coarse; b++) hcoarse.push_back(hC[std::min(dimB, (b + 1) * a.stride) - 1]);
-        TB_TRY(pmf_upload(base + L.C, hC.data(), dimB * sizeof(unsigned long long), stream));
-        TB_TRY(pmf_upload(base + L.coarse, hcoarse.data(), hcoarse.size() * sizeof(unsigned long long), stream));
-        a.C = (const unsigned long long*)(base + L.C);
-        a.coarse = (const unsigned long long*)(base + L.coarse);
-    }
+    if (weighted) TB_TRY(sn_stage_weights(a.d, item_weight, dimB, base + L.C, base + L.coarse, stream));
 
     std::vector<unsigned> hu, hp, hx, hix, hc;
     std::vector<unsigned long long> hs;

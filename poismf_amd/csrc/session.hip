@@ -807,6 +807,26 @@ int poismf_hip_session_rank_include(poismf_hip_session* s, const sparse_ix* user
                                        out_n_adm);
 }
 
+// Sampled ranks in one pass from the resident (compact) factors (rank_sampled.hip; include/poismf_hip.h section 1u), ordered as the
+// calls above and in the same scratch: section 1t's draw and section 1j's ranks without the sample leaving the device.
+int poismf_hip_session_rank_sampled(poismf_hip_session* s, const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr,
+                                    const sparse_ix* test_indices, size_t m, uint64_t seed, int exclude_seen, const sparse_ix* excl_indptr,
+                                    const sparse_ix* excl_indices, const uint32_t* item_weight, unsigned int* out_rank, unsigned int* out_n_adm,
+                                    unsigned int* out_count, unsigned int* out_draws)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_rank == nullptr || out_n_adm == nullptr) return 2;
+    if (const int rc = poismf_hip_rank_sampled_check(users, n_users, m, s->dimA, s->dimB, s->k, test_indptr, test_indices, excl_indptr, excl_indices,
+                                                     item_weight))
+        return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_rank_sampled_core(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, test_indptr, test_indices, m, seed,
+                                        exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, item_weight, &s->d_topn, &s->topn_cap, out_rank,
+                                        out_n_adm, out_count, out_draws);
+}
+
 // Batched exact ranks among candidate lists shared between users from the resident (compact) factors (rank_shared.hip;
 // include/poismf_hip.h section 1k), ordered as the calls above and in the same scratch.
 int poismf_hip_session_rank_shared(poismf_hip_session* s, const sparse_ix* users, size_t n_users, const sparse_ix* test_indptr,

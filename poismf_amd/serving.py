@@ -823,6 +823,22 @@ def sample_negatives(target, users, m, exclude_seen, exclude, item_weight, seed,
     return (indptr, items, draws.astype(np.int64)) if return_draws else (indptr, items)
 
 
+def rank_sampled(target, users, test, m, exclude_seen, exclude, item_weight, seed, return_counts):
+    """section 1u: section 1t's sample drawn, scored and ranked against in one call; (ranks, n_adm[, count, draws])"""
+    users, tp, ti, _, _ = _rank_batch_args(users, test, None, target.dimA, target.dimB, target.k)
+    users, m, ep, ei, w, seed = _sample_negatives_args(users, m, exclude, item_weight, seed, target.dimA, target.dimB)
+    n = len(users)
+    if exclude_seen:
+        _outside_shard(users, target.shardA)
+    ranks, n_adm = np.empty(len(ti), np.uint32), np.empty(n, np.uint32)
+    cnt, draws = (np.zeros(n if return_counts else 0, np.uint32) for _ in range(2))
+    if n:
+        fn, lead, flag = target._entry("rank_sampled", exclude_seen)
+        _batch_rc(fn(*lead, _ptr(users), n, _ptr(tp), _opt_ptr(ti), m, seed, *flag, _opt_ptr(ep), _opt_ptr(ei), _opt_ptr(w), _ptr(ranks),
+                     _ptr(n_adm), _opt_ptr(cnt), _opt_ptr(draws)), "sampled ranks")
+    return (ranks, n_adm, cnt.astype(np.int64), draws.astype(np.int64)) if return_counts else (ranks, n_adm)
+
+
 def topn_deep(target, users, n, exclude_seen, exclude, output_score):
     """section 1l"""
     users, *excl = _topn_deep_args(users, n, exclude, target.dimA, target.dimB)
