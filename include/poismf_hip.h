@@ -976,6 +976,70 @@ POISMF_HIP_API size_t poismf_hip_rank_sampled_scratch_bytes(size_t n_users, size
         int weighted);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1v. Explain: the seen items behind each recommendation -- "because you bought X" -- for many (user, item) cells in one pass (no
+ *     counterpart in the reference; `implicit` computes its explain for ALS on the host, one user at a time).
+ *
+ * For Poisson factorisation the answer falls out of the model.  The EM view that method "mm" (section 0) uses allocates each count
+ * x_ui over the components with responsibilities phi_uic = a_uc b_ic / (a_u . b_i), and at a fixed point of "mm" the user's row is a
+ * sum of these allocations:  a_uc (s_c + 2 l2 a_uc) = sum_i x_ui phi_uic.  A score therefore splits additively over the seen items.
+ *
+ * Inputs per cell: a user u with factor row a; its seen row X(u), items i strictly ascending with counts x_i > 0; a query item j; a
+ * component scale g, k values finite and >= 0 (comp_scale == NULL: all ones).  Every operation is rounded once in real_t:
+ *
+ *   q_c     = (a_c * g_c) * b_jc                                        c < k
+ *   d_i     = 0; for c in 0..k-1: d_i    = fma(a_c, b_ic, d_i)          predict_multiple's score of (u, i), bit for bit
+ *   num_ij  = 0; for c in 0..k-1: num_ij = fma(b_ic, q_c, num_ij)
+ *   contrib(i -> j | u) = (x_i * num_ij) / d_i                          IEEE division
+ *
+ * and a contribution counts as +0 when d_i is 0 or the quotient is not finite: the call is total.
+ *
+ *   the identity With s the row's constant vector of section 0 (the column sums of B + l1) and g_c = 1 / s_c, a fixed point of "mm" has
+ *                  sum_{i in X(u)} contrib(i -> j | u) = sum_c a_uc (1 + 2 l2 a_uc / s_c) b_jc,
+ *                with l2 = 0 the score of (u, j) itself: the contributions are then shares of the score.  The default g = 1 gives an
+ *                unnormalised ranking of the same items' evidence.  (In exact arithmetic; nothing here depends on it.)
+ *   answer       for every cell (user i of the batch, column t of its query row) the m seen items with the largest contribution,
+ *                under "contribution descending, then item index ascending".  Items that contribute 0 are listed like any other.  A
+ *                seen row with fewer than m items is padded with POISMF_HIP_TOPN_NONE / -inf, as section 1h pads.  A query entry
+ *                that is POISMF_HIP_TOPN_NONE -- a padded top-N row handed straight in -- gives an all-padding cell.  A cell is a
+ *                function of (A[u], B[j], the rows of B of X(u), X(u), g, m) alone: not of the batch, how the queries are grouped,
+ *                how a long seen row is cut into slices or how the users are cut into chunks.
+ *   arguments    items [n_users x n_q] dense, row i the queries of user i; seen_indptr [n_users + 1] / seen_indices / seen_values a
+ *                host CSR with one row per user of the batch (row pointers from any non-negative start), the values real_t and
+ *                assumed finite; out_ix / out_contrib [n_users x n_q x m].  Host arrays.
+ *   range        m is 1 .. POISMF_HIP_EXPLAIN_MAX_M; n_q is 1 .. POISMF_HIP_EXPLAIN_MAX_QUERIES (a page of section 1f); k as in
+ *                section 1f; a seen row of the host entry holds at most POISMF_HIP_EXPLAIN_MAX_ROW items, the session's resident rows
+ *                are taken at any length.
+ *
+ * Returns 0; 1 on a device error / out of memory; 3, with nothing written and before any device work, for: m or n_q out of range; k
+ * outside 1..512 float / 1..256 double; a NULL among users, items, seen_indptr or the outputs; a user index >= dimA (session: outside
+ * its rows of A); a query that is neither below dimB nor POISMF_HIP_TOPN_NONE; row pointers that decrease or start below 0; a seen index
+ * >= dimB; a seen row that is not strictly ascending or is too long; a comp_scale entry that is NaN, infinite or negative.
+ * n_users == 0 returns 0.  Factors are assumed finite.
+ *
+ * One wave per (user, group of up to 15 queries, slice of the seen row): the 16 columns [a | q] are built
+ * once in LDS, the seen rows of B come 64 at a time through section 1h's ragged gather, in float four v_mfma_f32_16x16x4_f32
+ * row-blocks give the 64 denominators and 64 x 15 numerators of a pass (in double a VALU chain of the same layout), and every column
+ * keeps its best m in LDS, merged with each pass's 64 by the wave's bitonic network.  A seen row longer than
+ * poismf_hip_explain_slice(len, m) items (testing aid, no HIP call) is cut into slices of that many, whose sorted partial rows a
+ * second kernel merges per cell.  No float atomics; no result depends on the order in which anything arrives.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1u share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB for
+ * any number of users and seen items: chunks of consecutive users with their queries, work items, partial rows and results, and on
+ * the host entry their seen rows.  poismf_hip_explain_scratch_bytes (testing aid, no HIP call; n_cells: the seen items of the batch's
+ * users, resident: 1 for the session flavour) is the size an entry point allocates.  poismf_hip_explain's own copies of B and of A (all
+ * of A, or only the batch's rows) come on top.  The session flavour, poismf_hip_session_explain, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_EXPLAIN_MAX_M 64                   /* most seen items per cell */
+#define POISMF_HIP_EXPLAIN_MAX_QUERIES 128            /* most query items per user: POISMF_HIP_TOPN_BATCH_MAX_N_TOP */
+#define POISMF_HIP_EXPLAIN_MAX_ROW 4194304            /* longest seen row of the host entry: 2^22 items */
+POISMF_HIP_API int poismf_hip_explain(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, const sparse_ix *items, size_t n_q,
+        const sparse_ix *seen_indptr, const sparse_ix *seen_indices, const real_t *seen_values,
+        const real_t *comp_scale, size_t m, sparse_ix *out_ix, real_t *out_contrib);
+POISMF_HIP_API size_t poismf_hip_explain_scratch_bytes(size_t n_users, size_t n_q, size_t m, size_t n_cells, size_t k, int resident);
+POISMF_HIP_API size_t poismf_hip_explain_slice(size_t len, size_t m);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -1375,6 +1439,11 @@ POISMF_HIP_API int poismf_hip_session_rank_sampled(poismf_hip_session *s, const 
         const sparse_ix *test_indptr, const sparse_ix *test_indices, size_t m, uint64_t seed, int exclude_seen,
         const sparse_ix *excl_indptr, const sparse_ix *excl_indices, const uint32_t *item_weight,
         unsigned int *out_rank, unsigned int *out_n_adm, unsigned int *out_count, unsigned int *out_draws);
+
+/* Section 1v from the session-resident factors: the seen rows are the users' rows of the session's own CSR, so neither a factor nor
+ * a seen row is uploaded.  Ordered as the call above and in the same scratch. */
+POISMF_HIP_API int poismf_hip_session_explain(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
+        const sparse_ix *items, size_t n_q, const real_t *comp_scale, size_t m, sparse_ix *out_ix, real_t *out_contrib);
 
 /* Section 1k from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_rank_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users,

@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_order_include_wave_row",
     "poismf_hip_sample_negatives", "poismf_hip_session_sample_negatives", "poismf_hip_sample_negatives_scratch_bytes", "poismf_hip_philox4x32",
     "poismf_hip_rank_sampled", "poismf_hip_session_rank_sampled", "poismf_hip_rank_sampled_scratch_bytes",
+    "poismf_hip_explain", "poismf_hip_session_explain", "poismf_hip_explain_scratch_bytes", "poismf_hip_explain_slice",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -110,6 +111,9 @@ TOPN_ADJUSTED_MAX_ROW = 2**22       # (tests/test_topn_adjusted_cpu.py compares 
 ORDER_MAX_ROW = 65536               # POISMF_HIP_ORDER_MAX_ROW of section 1s (tests/test_order_include_cpu.py compares the two)
 NEG_MAX_M = 4096                    # POISMF_HIP_NEG_MAX_M of section 1t and its limit on the number of items
 NEG_MAX_ITEMS = 2**24               # (tests/test_sample_negatives_cpu.py compares the first with the header)
+EXPLAIN_MAX_M = 64                  # POISMF_HIP_EXPLAIN_MAX_M, POISMF_HIP_EXPLAIN_MAX_QUERIES and POISMF_HIP_EXPLAIN_MAX_ROW of section 1v
+EXPLAIN_MAX_QUERIES = 128           # (tests/test_explain_cpu.py compares them with the header)
+EXPLAIN_MAX_ROW = 2**22
 
 
 def load_library(use_float):
@@ -286,6 +290,14 @@ def load_library(use_float):
     lib.poismf_hip_session_rank_sampled.restype = i
     lib.poismf_hip_rank_sampled_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, i]
     lib.poismf_hip_rank_sampled_scratch_bytes.restype = sz
+    lib.poismf_hip_explain.argtypes = [vp, vp, i, sz, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    lib.poismf_hip_explain.restype = i
+    lib.poismf_hip_session_explain.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp]
+    lib.poismf_hip_session_explain.restype = i
+    lib.poismf_hip_explain_scratch_bytes.argtypes = [sz, sz, sz, sz, sz, i]
+    lib.poismf_hip_explain_scratch_bytes.restype = sz
+    lib.poismf_hip_explain_slice.argtypes = [sz, sz]
+    lib.poismf_hip_explain_slice.restype = sz
     lib.poismf_hip_philox4x32.argtypes = [vp, vp, vp]
     lib.poismf_hip_philox4x32.restype = None
     lib.poismf_hip_topn_include_slice.argtypes = [sz, sz]
@@ -773,6 +785,35 @@ def rank_sampled(A, B, users, test, m, exclude=None, item_weight=None, seed=0, r
         raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
     target = _HostFactors(A, B, A.shape[0], B.shape[0], A.shape[1], A.dtype == np.float32)
     return serving.rank_sampled(target, users, test, m, False, exclude, item_weight, seed, return_counts)
+
+
+def explain(A, B, users, items, seen, m=5, comp_scale=None):
+    """"Because you bought X", on the GPU (include/poismf_hip.h section 1v) on host factors A [dimA x k], B [dimB x k] (float32 or
+    float64, both alike): for every user of `users` and every query item of its row of `items` -- the (n_users, n) array a topN_* call
+    returned, TOPN_NONE entries included -- the m items of the user's seen row that contribute most to the query's score, under
+    "contribution descending, item index ascending".  seen: a SciPy sparse matrix with one row per user of the batch (the training
+    matrix's rows: the model does not keep X) or an (indptr, indices, values) triple with strictly ascending rows.
+    contrib(i -> j | u) = x_ui * sum_c b_ic (a_uc g_c) b_jc / (a_u . b_i); comp_scale is g, k values >= 0: None ranks unnormalised,
+    1 / (colsum(B) + l1) gives shares that sum to the score at a fixed point of method "mm" with l2 = 0.  Returns (ix uint64,
+    contrib) of shape (n_users, n, m); a seen row shorter than m, or a TOPN_NONE query, is padded with TOPN_NONE and -inf."""
+    A, B = np.asarray(A), np.asarray(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1] or A.dtype != B.dtype or A.dtype not in (np.float32, np.float64):
+        raise ValueError("A and B must be float32 or float64 matrices with the same number of columns")
+    if seen is None:
+        raise ValueError("seen is required: the users' rows of the training matrix")
+    target = _HostFactors(A, B, A.shape[0], B.shape[0], A.shape[1], A.dtype == np.float32)
+    return serving.explain(target, users, items, seen, m, comp_scale)
+
+
+def _explain(self, users, items, seen, m=5, comp_scale=None):
+    """api.explain on the fitted model's factors: the m seen items behind every entry of `items`, the page topN_batch returned for
+    `users`.  seen: the users' rows of the training matrix (the model does not keep X)."""
+    if seen is None:
+        raise ValueError("seen is required: the users' rows of the training matrix")
+    return serving.explain(_host(self), users, items, seen, m, comp_scale)
+
+
+PoisMF.explain = _explain
 
 
 def _topN_quota(self, users, n=10, group_of=None, quota=1, exclude=None, output_score=False):
@@ -1704,6 +1745,13 @@ class Session:
         ranked among them and the user's other held-out items, in one pass; the sample stays on the device.  Returns (ranks, n_adm)
         as rank_batch(include=<that sample united with test>) does, and with return_counts also (count, draws)."""
         return serving.rank_sampled(self, users, test, m, exclude_seen, exclude, item_weight, seed, return_counts)
+
+    def explain(self, users, items, m=5, comp_scale=None):
+        """api.explain from the resident factors (include/poismf_hip.h section 1v): the m seen items behind every entry of `items`,
+        the page topn_batch returned for `users`.  The seen rows are the users' rows of the session's own CSR: neither a factor nor
+        a row is uploaded.  Returns (ix uint64, contrib) of shape (n_users, n, m), bit for bit api.explain's for the same factors
+        and seen=matrix(1)'s rows."""
+        return serving.explain(self, users, items, None, m, comp_scale)
 
     def eval_ranking(self, X_test, k=10, exclude_seen=True, exclude=None, users=None, per_user=False, include=None, include_of=None,
                      negatives=None, negatives_weight=None, seed=0):

@@ -69,6 +69,8 @@ UNITS = {
     "sample_negatives": ("sample_negatives.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     # the fused sampled ranks: the sampler's draw (sn_draw.hpp), then the include ranks' gather and counting on the list in LDS
     "rank_sampled": ("rank_sampled.hip", []),
+    # the seen items behind a recommendation: the include lists' gather (tb_gather.hpp) under an MFMA tile, the re-rank's wave network (order_sort.hpp)
+    "explain": ("explain.hip", []),
 }
 _INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"/]+)"', re.M)   # (the includes inside csrc/ are flat quoted names)
 

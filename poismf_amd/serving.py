@@ -839,6 +839,86 @@ def rank_sampled(target, users, test, m, exclude_seen, exclude, item_weight, see
     return (ranks, n_adm, cnt.astype(np.int64), draws.astype(np.int64)) if return_counts else (ranks, n_adm)
 
 
+def _explain_args(users, items, m, comp_scale, dimA, dimB, k, dtype):
+    """The argument checks of explain (include/poismf_hip.h section 1v) that need no device, as the library itself makes them: m in
+    1 .. EXPLAIN_MAX_M; items a 2-d integer array with one row per user and 1 .. EXPLAIN_MAX_QUERIES columns, every entry below dimB
+    or TOPN_NONE -- what a topN_* call returned; comp_scale None or k values, finite and non-negative in `dtype`, the model's
+    real_t.  Returns (users, items as uint64, m, comp_scale or None)."""
+    users, m = _index_array(users, "users"), int(m)
+    if not 1 <= m <= api.EXPLAIN_MAX_M:
+        raise ValueError(f"m = {m} is outside 1 .. {api.EXPLAIN_MAX_M}")
+    _users_in_range(users, dimA)
+    q = np.asarray(items)
+    if q.ndim != 2 or q.shape[0] != len(users):
+        raise ValueError(f"items must be a 2-d array with one row per user: shape {q.shape} for {len(users)} users")
+    if not 1 <= q.shape[1] <= api.EXPLAIN_MAX_QUERIES:
+        raise ValueError(f"{q.shape[1]} query items per user are outside 1 .. {api.EXPLAIN_MAX_QUERIES}")
+    if q.dtype.kind not in "iu":
+        raise ValueError("items must hold integers")
+    if q.dtype.kind == "i" and q.size and int(q.min()) < 0:
+        raise ValueError("items: negative index (an empty entry is TOPN_NONE)")
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    if np.any((q >= dimB) & (q != api.TOPN_NONE)):
+        raise ValueError("a query item is out of range")
+    if comp_scale is not None:
+        g = np.asarray(comp_scale)
+        if g.shape != (k,) or g.dtype.kind not in "fiu":
+            raise ValueError(f"comp_scale must hold k = {k} real numbers")
+        comp_scale = _finite_nonneg(g, dtype, "comp_scale: NaN entry", "comp_scale: an entry is", "comp_scale: negative entry")
+    return users, q, m, comp_scale
+
+
+def _seen_rows(seen, n_users, dimB, dtype):
+    """explain's seen rows on host factors: a SciPy sparse matrix with one row per user of the batch (duplicates summed, stored zeros
+    dropped) or an (indptr, indices, values) triple with strictly ascending rows.  Returns (indptr, indices, values): uint64 arrays
+    from 0 and the counts in `dtype`."""
+    if isinstance(seen, (tuple, list)) and not hasattr(seen, "tocsr"):
+        if len(seen) != 3:
+            raise ValueError("seen must be a SciPy sparse matrix or an (indptr, indices, values) triple")
+        pair, x = (seen[0], seen[1]), np.asarray(seen[2])
+    else:
+        import scipy.sparse as sp
+        if not sp.issparse(seen):
+            raise ValueError("seen must be a SciPy sparse matrix or an (indptr, indices, values) triple")
+        csr = sp.csr_matrix(seen)
+        if csr.shape[0] != n_users:
+            raise ValueError(f"seen has {csr.shape[0]} rows for {n_users} users")
+        if csr.shape[1] > dimB:
+            raise ValueError("seen has more columns than there are items")
+        csr.sum_duplicates(); csr.eliminate_zeros(); csr.sort_indices()
+        pair, x = (csr.indptr, csr.indices), csr.data
+    if x.ndim != 1 or (x.size and x.dtype.kind not in "fiu"):
+        raise ValueError("seen: the counts must be a 1-d array of real numbers")
+    indptr, indices = _csr_list(pair, n_users, dimB, "seen", row_max=api.EXPLAIN_MAX_ROW)
+    lo = int(np.asarray(pair[0]).reshape(-1)[0])
+    if len(x) < lo + len(indices):
+        raise ValueError("seen: there are fewer counts than item indices")
+    return indptr, indices, np.ascontiguousarray(x[lo:lo + len(indices)], dtype=dtype)
+
+
+def explain(target, users, items, seen, m, comp_scale):
+    """section 1v: the m seen items behind every (user, query item) cell; `seen` is None on a session, whose rows are resident.
+    Returns (ix uint64, contrib) of shape (n_users, n, m)."""
+    dt = _real_t(target.use_float)
+    users, q, m, g = _explain_args(users, items, m, comp_scale, target.dimA, target.dimB, target.k, dt)
+    resident = seen is None
+    if resident:
+        _outside_shard(users, target.shardA)
+    else:
+        sp_, si, sx = _seen_rows(seen, len(users), target.dimB, dt)
+    out = np.empty(q.shape + (m,), np.uint64), np.empty(q.shape + (m,), dt)
+    if len(users) == 0:
+        return out
+    fn, lead, _ = target._entry("explain", False)
+    middle = () if resident else (_ptr(sp_), _opt_ptr(si), _opt_ptr(sx))
+    rc = fn(*lead, _ptr(users), len(users), _ptr(q), q.shape[1], *middle, _opt_ptr(g), m, _ptr(out[0]), _ptr(out[1]))
+    if rc == 3:
+        raise ValueError("invalid arguments for explain (an index out of range, an unsorted or overlong seen row, or a bad comp_scale)")
+    if rc:
+        raise MemoryError("explain failed (no usable HIP device or out of memory)")
+    return out
+
+
 def topn_deep(target, users, n, exclude_seen, exclude, output_score):
     """section 1l"""
     users, *excl = _topn_deep_args(users, n, exclude, target.dimA, target.dimB)
