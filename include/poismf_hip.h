@@ -1040,6 +1040,65 @@ POISMF_HIP_API size_t poismf_hip_explain_scratch_bytes(size_t n_users, size_t n_
 POISMF_HIP_API size_t poismf_hip_explain_slice(size_t len, size_t m);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1w. Sampled top-N: a seeded Plackett-Luce page -- n_top distinct items drawn without replacement with probability proportional to
+ *     score^(1/T) -- made in the same fused pass as section 1f's list, over ALL items (no counterpart in the reference).  Exploration,
+ *     spread of exposure, and model-weighted hard negatives, which section 1t (uniform or popularity-weighted) cannot give.  A deep
+ *     list (section 1l) plus noise on the host is not this: an item beyond the list's end can never be drawn.
+ *
+ * Inputs are section 1f's -- users u_0 .. u_{m-1} (any order, repeats allowed), n_top, E(u), score(u, j) -- a 64-bit seed and a
+ * temperature T in [0, POISMF_HIP_TOPN_SAMPLED_MAX_T].  For user u (the ROW OF A, not the position in the batch) and item j:
+ *
+ *   word(u, j)   word j & 3 of the Philox4x32-10 block (section 1t's block function) with key (seed & 0xffffffff, seed >> 32) and
+ *                counter (j >> 2, 1, u & 0xffffffff, u >> 32).  The 1 keeps these streams apart from section 1t's, whose counters
+ *                carry 0 there.  A row of A is below 2^31 in every entry point, so the last counter word is 0.
+ *   V            (word + 0.5) / 2^32, in (0, 1).
+ *   E            -log1p(-V): a standard exponential variate.  A small word gives a small E, and the small E are the cells that win.
+ *   r(u, j)      E^(-T), in real_t.  T <= 3 keeps it finite in float: E >= 2^-33, so r <= 2^99.
+ *   key(u, j)    score(u, j) * r(u, j): ONE multiplication rounded to real_t, made after the k-ordered fused chain and never
+ *                contracted into it (section 1o's rule).
+ *   answer(u)    the first n_top of {0..dimB-1} \ E(u) under "key descending, then item index ascending".  This is the exponential
+ *                race: the n_top largest score^(1/T) / E are a Plackett-Luce draw without replacement.
+ *
+ * r is a function of (seed, u, j, T) alone and the mathematical definition above is what the entry points approximate: the device
+ * evaluates the logarithm and the power with a relative error of the key of a few ulp of real_t (measured: DESIGN.md section 4.34), so
+ * two keys closer than that may come out in either order, on this device always the same one.  Consequences:
+ *   - a row depends on (seed, u, T, A[u], B, E(u)) and on nothing else: not the batch, the user's position in it, how the items are
+ *     cut into slices or the users into chunks.  A user listed twice gets the same row twice; another seed gives another page.
+ *   - T = 0 means r = 1 exactly: no Philox block is evaluated and the rows are section 1f's, bit for bit, for any seed.
+ *   - a score of 0 gives key 0 and ties with its like by index, as a weight of 0 does in section 1o.
+ *   - negative scores (signed factors) give a well-defined order that is NOT a sampling distribution: the largest E wins among them.
+ *   - keys that overflow to +inf (a score above 2^29 at T = 3 in float) tie by index.  Where a key is denormal or NaN the result is
+ *     unspecified, as in section 1o.
+ *
+ *   output       out_ix [n_users x n_top] the items in key order; out_score (may be NULL) their scores -- predict_multiple's bits, NOT
+ *                the keys; out_key (may be NULL) the keys.  Host arrays.
+ *   short rows   follow section 1h's rule: if fewer than n_top items are admissible, the rest of the row is POISMF_HIP_TOPN_NONE in
+ *                out_ix and -inf in out_score and out_key.
+ *   range        n_top is 1 .. POISMF_HIP_TOPN_BATCH_MAX_N_TOP; dimB at most POISMF_HIP_TOPN_SAMPLED_MAX_ITEMS.
+ *
+ * Returns 0; 1 on a device error / out of memory; 2, with nothing written and before any device work, for: everything that is 2 in
+ * section 1f except "too few items left"; a temperature that is NaN, negative or above POISMF_HIP_TOPN_SAMPLED_MAX_T;
+ * dimB > POISMF_HIP_TOPN_SAMPLED_MAX_ITEMS.  n_users == 0 returns 0.
+ *
+ * One tile kernel: section 1f's walk and selection, with an epilogue in which a lane computes four Philox
+ * blocks per tile step, not sixteen -- the four items of a block sit in four neighbouring lanes, which exchange the words by DPP --
+ * and turns each word into its factor on the hardware's log2 / exp2.  The selection sees finished keys only, so pruning and slicing
+ * stay exact; the winners' scores are made afterwards, n_top chains per user.  No float atomics.
+ *
+ * Memory: ONE scratch allocation per call (session: the one sections 1f - 1v share) of at most POISMF_HIP_TOPN_BATCH_BUDGET_MB MiB for
+ * any n_users, laid out as section 1o's without the weights.  poismf_hip_topn_sampled_scratch_bytes (testing aid, no HIP call) is the
+ * size both entry points allocate; it does not depend on k.  poismf_hip_topn_sampled's own copies of B and of A (all of A, or only
+ * the batch's rows) come on top.  The session flavour, poismf_hip_session_topn_sampled, is declared in section 2.
+ * ------------------------------------------------------------------------------------------- */
+#define POISMF_HIP_TOPN_SAMPLED_MAX_ITEMS 16777216    /* largest dimB of the sampled entry points (2^24) */
+#define POISMF_HIP_TOPN_SAMPLED_MAX_T 3.0             /* largest temperature */
+POISMF_HIP_API int poismf_hip_topn_sampled(const real_t *A, const real_t *B, int k, size_t dimA, size_t dimB,
+        const sparse_ix *users, size_t n_users, size_t n_top, double temperature, uint64_t seed,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_key);
+POISMF_HIP_API size_t poismf_hip_topn_sampled_scratch_bytes(size_t n_users, size_t n_top, size_t dimB, size_t k);
+
+/* ---------------------------------------------------------------------------------------------
  * 2. Device-resident session: the same path with X, A and B kept in HBM between calls, one
  *    half-sweep per call.  This is what bench.py times (inputs already resident) and what the
  *    one-process-per-GPU driver uses: each rank owns a contiguous range of A rows and of B rows,
@@ -1444,6 +1503,12 @@ POISMF_HIP_API int poismf_hip_session_rank_sampled(poismf_hip_session *s, const 
  * a seen row is uploaded.  Ordered as the call above and in the same scratch. */
 POISMF_HIP_API int poismf_hip_session_explain(poismf_hip_session *s, const sparse_ix *users, size_t n_users,
         const sparse_ix *items, size_t n_q, const real_t *comp_scale, size_t m, sparse_ix *out_ix, real_t *out_contrib);
+
+/* Section 1w from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
+POISMF_HIP_API int poismf_hip_session_topn_sampled(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_top,
+        double temperature, uint64_t seed, int exclude_seen,
+        const sparse_ix *excl_indptr, const sparse_ix *excl_indices,
+        sparse_ix *out_ix, real_t *out_score, real_t *out_key);
 
 /* Section 1k from the session-resident factors (and, with exclude_seen, the session's own CSR rows), ordered as the call above. */
 POISMF_HIP_API int poismf_hip_session_rank_shared(poismf_hip_session *s, const sparse_ix *users, size_t n_users,

@@ -25,7 +25,7 @@ from .serving import (_batch_rc, _csr_list, _diverse_outputs, _eval_lists_args, 
                       _index_array, _inv_norms, _list_eval_args, _list_eval_outputs, _list_eval_scratch, _list_rows, _new_rows_args, _append_rows_args,
                       _new_stats, _opt_ptr, _outside_shard, _ptr, _rank_batch_args, _rank_include_list, _shared_table_args,
                       _similar_args, _similar_scores, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
-                      _topn_include_args, _topn_outputs, _topn_quota_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
+                      _topn_include_args, _topn_outputs, _topn_quota_args, _topn_sampled_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
 
 _METHOD = {"tncg": 1, "cg": 2, "pg": 3, "mm": 4}  # ref: src/poismf.h:225; "mm": include/poismf_hip.h section 0 (not in the reference)
 
@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_sample_negatives", "poismf_hip_session_sample_negatives", "poismf_hip_sample_negatives_scratch_bytes", "poismf_hip_philox4x32",
     "poismf_hip_rank_sampled", "poismf_hip_session_rank_sampled", "poismf_hip_rank_sampled_scratch_bytes",
     "poismf_hip_explain", "poismf_hip_session_explain", "poismf_hip_explain_scratch_bytes", "poismf_hip_explain_slice",
+    "poismf_hip_topn_sampled", "poismf_hip_session_topn_sampled", "poismf_hip_topn_sampled_scratch_bytes",
 )
 TOPN_BATCH_MAX_N_TOP = 128   # POISMF_HIP_TOPN_BATCH_MAX_N_TOP of include/poismf_hip.h (tests/test_topn_batch_cpu.py compares the two)
 RANK_EXCLUDED = 0xFFFFFFFF   # the rank-excluded mark, RANK_BATCH_MAX_ROW the longest held-out row and RANK_BATCH_BUDGET_MB the scratch bound
@@ -114,6 +115,8 @@ NEG_MAX_ITEMS = 2**24               # (tests/test_sample_negatives_cpu.py compar
 EXPLAIN_MAX_M = 64                  # POISMF_HIP_EXPLAIN_MAX_M, POISMF_HIP_EXPLAIN_MAX_QUERIES and POISMF_HIP_EXPLAIN_MAX_ROW of section 1v
 EXPLAIN_MAX_QUERIES = 128           # (tests/test_explain_cpu.py compares them with the header)
 EXPLAIN_MAX_ROW = 2**22
+TOPN_SAMPLED_MAX_ITEMS = 2**24      # POISMF_HIP_TOPN_SAMPLED_MAX_ITEMS and POISMF_HIP_TOPN_SAMPLED_MAX_T of section 1w
+TOPN_SAMPLED_MAX_T = 3.0            # (tests/test_topn_sampled_cpu.py compares them with the header)
 
 
 def load_library(use_float):
@@ -230,6 +233,12 @@ def load_library(use_float):
     lib.poismf_hip_session_topn_weighted.restype = i
     lib.poismf_hip_topn_weighted_scratch_bytes.argtypes = [sz, sz, sz, sz]
     lib.poismf_hip_topn_weighted_scratch_bytes.restype = sz
+    lib.poismf_hip_topn_sampled.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, C.c_double, C.c_uint64, vp, vp, vp, vp, vp]
+    lib.poismf_hip_topn_sampled.restype = i
+    lib.poismf_hip_session_topn_sampled.argtypes = [vp, vp, sz, sz, C.c_double, C.c_uint64, i, vp, vp, vp, vp, vp]
+    lib.poismf_hip_session_topn_sampled.restype = i
+    lib.poismf_hip_topn_sampled_scratch_bytes.argtypes = [sz, sz, sz, sz]
+    lib.poismf_hip_topn_sampled_scratch_bytes.restype = sz
     lib.poismf_hip_topn_adjusted.argtypes = [vp, vp, i, sz, sz, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.poismf_hip_topn_adjusted.restype = i
     lib.poismf_hip_session_topn_adjusted.argtypes = [vp, vp, sz, sz, vp, vp, vp, i, vp, vp, vp, vp]
@@ -856,6 +865,22 @@ def _topN_adjusted(self, users, n=10, adjust=None, exclude=None, output_score=Fa
 
 
 PoisMF.topN_adjusted = _topN_adjusted
+
+
+def _topN_sampled(self, users, n=10, temperature=1.0, seed=0, exclude=None, output_score=False, output_key=False):
+    """A seeded stochastic page per user: n <= TOPN_BATCH_MAX_N_TOP distinct items drawn without replacement with probability
+    proportional to score^(1/temperature) (Plackett-Luce), over ALL items and in the same fused pass on the GPU as topN_batch
+    (include/poismf_hip.h section 1w) -- exploration, spread of exposure, model-weighted hard negatives.  Every (user, item) cell gets
+    key = score x E^(-temperature), E a standard exponential variate made from (seed, the user's row of A, the item) by Philox, and the
+    page is the first n under "key descending, item index ascending", minus `exclude` as in topN_batch.  A row depends on the seed, the
+    user and the model alone, not on the batch.  temperature in [0, TOPN_SAMPLED_MAX_T]: 0 gives topN_batch's rows bit for bit, 1 draws
+    proportional to the expected count.  n may exceed what a user has left: the row is padded with TOPN_NONE and -inf.  Returns
+    (items uint64 [m x n], scores [m x n] -- predict's, not the keys; empty unless output_score --, keys [m x n], empty unless
+    output_key)."""
+    return serving.topn_sampled(_host(self), users, n, temperature, seed, False, exclude, output_score, output_key)
+
+
+PoisMF.topN_sampled = _topN_sampled
 
 
 def _similar_items(self, items, n=10, output_score=False, exclude_self=True, item_norm=None):
@@ -1694,6 +1719,16 @@ class Session:
         listed and excluded is excluded.  The scores returned are the adjusted ones.  A short row is padded with TOPN_NONE and -inf.
         Returns (items uint64 [m x top_n], scores [m x top_n], empty unless output_score)."""
         return serving.topn_adjusted(self, users, top_n, adjust, exclude_seen, exclude, output_score)
+
+    def topn_sampled(self, users, top_n=10, temperature=1.0, seed=0, exclude_seen=False, exclude=None, output_score=False, output_key=False):
+        """A seeded stochastic page per user from the resident factors, in one fused pass (include/poismf_hip.h section 1w): top_n <=
+        TOPN_BATCH_MAX_N_TOP distinct items drawn without replacement with probability proportional to score^(1/temperature), as the
+        first top_n under "key descending, item index ascending" with key = score x E^(-temperature), E a standard exponential variate
+        made from (seed, the user's row of A, the item); exclude_seen and exclude as in topn_batch.  temperature in [0,
+        TOPN_SAMPLED_MAX_T]: 0 gives topn_batch's rows bit for bit.  A row depends on the seed, the user and the model alone.  A short
+        row is padded with TOPN_NONE and -inf.  Returns (items uint64 [m x top_n], scores [m x top_n] -- predict's, not the keys; empty
+        unless output_score --, keys [m x top_n], empty unless output_key)."""
+        return serving.topn_sampled(self, users, top_n, temperature, seed, exclude_seen, exclude, output_score, output_key)
 
     def item_norms(self):
         """n2[j] = the fused chain of row j of the resident B with itself, predict_multiple's bits: what similar_items takes as

@@ -2,14 +2,14 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Thirty-three translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
+Thirty-four translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
 session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver, one for the multiplicative update "mm" and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
 the serving kernels (serve.hip), the likelihood (llk.hip), the batched top-N (topn_batch.hip), the batched ranks (rank_batch.hip), the
 batched top-N over include lists (topn_include.hip) and over lists shared between users (topn_shared.hip), the re-rank of whole include lists (order_include.hip, with order_sort.hpp, on tb_gather.hpp) and the batched ranks among
 include lists (rank_include.hip) and among lists shared between users (rank_shared.hip), the deep batched top-N (topn_deep.hip, with
-tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and with per-(user, item) score factors (topn_adjust.hip: a dense pass on tb_select.hpp, a sparse one on tb_gather.hpp and a merge) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the eleven share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted / topn_adjust the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units, topn_diverse and topn_adjust tb_gather.hpp) and the
+tb_deep.hpp) and the batched top-N with per-group quotas (topn_quota.hip, with tb_quota.hpp) and with per-item score weights (topn_weighted.hip) and with per-(user, item) score factors (topn_adjust.hip: a dense pass on tb_select.hpp, a sparse one on tb_gather.hpp and a merge) and the sampled top-N (topn_sampled.hip: topn_weighted's walk and selection with a Philox epilogue, philox.hpp) and the diversified top-N (topn_diverse.hip: the deep core's chunk loop and an MMR kernel behind it; the eleven share tb_tile.hpp and tb_batch.hpp, topn_batch / topn_shared / topn_quota / topn_weighted / topn_adjust the selection of tb_select.hpp, the three rank units tb_rank.hpp, the two include units, topn_diverse and topn_adjust tb_gather.hpp) and the
 new rows against a resident B (fold_in.hip: the guest of a session, on session.hpp and tb_batch.hpp) and the list-wise evaluation
 (list_eval.hip, on tb_gather.hpp and tb_batch.hpp) and the negative sampler (sample_negatives.hip, with philox.hpp, on tb_batch.hpp) and the fused sampled ranks (rank_sampled.hip, which shares the sampler's draw, sn_draw.hpp, and the include ranks' tb_gather.hpp and tb_rank.hpp) -- are compiled to object files
 side by side and linked.  What an object depends on is derived from its file's #include "..." lines (_deps), never listed by hand.
@@ -63,6 +63,8 @@ UNITS = {
     "topn_weighted": ("topn_weighted.hip", []),
     "topn_diverse": ("topn_diverse.hip", []),
     "topn_adjust": ("topn_adjust.hip", []),
+    # the sampled top-N: topn_weighted's walk and selection under an epilogue that draws every cell's factor (philox.hpp, DPP, log2 / exp2)
+    "topn_sampled": ("topn_sampled.hip", []),
     "fold_in": ("fold_in.hip", []),
     "list_eval": ("list_eval.hip", []),
     # the negative sampler is integer code throughout: nothing in it is to be paired into packed fp32 instructions either

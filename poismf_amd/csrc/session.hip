@@ -648,6 +648,22 @@ int poismf_hip_session_topn_weighted(poismf_hip_session* s, const sparse_ix* use
                                         exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score);
 }
 
+// Sampled top-N from the resident (compact) factors (topn_sampled.hip; include/poismf_hip.h section 1w), ordered as the calls above and
+// in the same scratch.  The streams are named by the rows of A, which are the caller's rows here.
+int poismf_hip_session_topn_sampled(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, double temperature,
+                                    uint64_t seed, int exclude_seen, const sparse_ix* excl_indptr, const sparse_ix* excl_indices,
+                                    sparse_ix* out_ix, real_t* out_score, real_t* out_key)
+{
+    if (n_users == 0) return 0;
+    if (s == nullptr || out_ix == nullptr) return 2;
+    if (const int rc = poismf_hip_topn_sampled_check(users, n_users, n_top, s->dimA, s->dimB, s->k, temperature, excl_indptr, excl_indices)) return rc;
+    PmfTopnSeen seen;
+    if (exclude_seen && !session_seen(s, users, n_users, seen)) return 2;
+    HIP_TRY(hipSetDevice(s->device));
+    return poismf_hip_topn_sampled_run(s->stream, s->dA, s->dB, s->dimB, s->k, false, users, n_users, n_top, temperature, seed,
+                                       exclude_seen ? &seen : nullptr, excl_indptr, excl_indices, &s->d_topn, &s->topn_cap, out_ix, out_score, out_key);
+}
+
 // Batched top-N with per-(user, item) score factors from the resident (compact) factors (topn_adjust.hip; include/poismf_hip.h section
 // 1r), ordered as the calls above and in the same scratch.
 int poismf_hip_session_topn_adjusted(poismf_hip_session* s, const sparse_ix* users, size_t n_users, size_t n_top, const sparse_ix* adj_indptr,

@@ -114,6 +114,15 @@ int poismf_hip_topn_weighted_run(hipStream_t stream, const real_t* dA, const rea
                                  const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
                                  sparse_ix* out_ix, real_t* out_score);
 
+// (topn_sampled.hip; section 1w) the same pair for the sampled top-N: the check makes no device call, the core returns 0 or 1.
+// out_score and out_key may be NULL
+int poismf_hip_topn_sampled_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k, double temperature,
+                                  const sparse_ix* excl_indptr, const sparse_ix* excl_indices);
+int poismf_hip_topn_sampled_run(hipStream_t stream, const real_t* dA, const real_t* dB, size_t dimB, size_t k, bool compact_A,
+                                const sparse_ix* users, size_t n_users, size_t n_top, double temperature, uint64_t seed, PmfTopnSeen* seen,
+                                const sparse_ix* excl_indptr, const sparse_ix* excl_indices, void** d_scratch, size_t* scratch_cap,
+                                sparse_ix* out_ix, real_t* out_score, real_t* out_key);
+
 // (topn_adjust.hip; section 1r) the same pair for the top-N with per-(user, item) score factors: the adjust list is a host CSR with
 // one row per user of the batch and real_t factors; the check makes no device call, the core returns 0 or 1
 int poismf_hip_topn_adjusted_check(const sparse_ix* users, size_t n_users, size_t n_top, size_t dimA, size_t dimB, size_t k,

@@ -348,6 +348,23 @@ def _topn_weighted_args(users, n, item_weight, exclude, dimA, dimB, dtype=np.flo
     return (users, w) + _exclude_list(exclude, len(users), dimB)
 
 
+def _topn_sampled_args(users, n, temperature, seed, exclude, dimA, dimB):
+    """The argument checks of the sampled top-N (include/poismf_hip.h section 1w) that need no device, as the library itself makes
+    them: n up to TOPN_BATCH_MAX_N_TOP, and it may exceed what a user has left (short rows are padded); temperature a real number in
+    [0, TOPN_SAMPLED_MAX_T]; seed an integer in 0 .. 2^64 - 1.  Returns (users, temperature, seed, excl_indptr or None, excl_indices or
+    None): uint64 arrays around a float and an int."""
+    users, n = _users_and_n(users, n, api.TOPN_BATCH_MAX_N_TOP, "batched")
+    if isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating)):
+        raise ValueError(f"temperature must be a real number in [0, {api.TOPN_SAMPLED_MAX_T}]")
+    if not 0.0 <= float(temperature) <= api.TOPN_SAMPLED_MAX_T:   # (NaN fails both)
+        raise ValueError(f"temperature = {temperature} is outside [0, {api.TOPN_SAMPLED_MAX_T}]")
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2**64:
+        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    _item_count(dimB, api.TOPN_SAMPLED_MAX_ITEMS, "sampled call")
+    _users_in_range(users, dimA)
+    return (users, float(temperature), int(seed)) + _exclude_list(exclude, len(users), dimB)
+
+
 def _inv_norms(n2, dimB, dtype):
     """similar_items: inv[j] = real_t(1) / sqrt(n2[j]) in real_t, 0 where n2[j] == 0; n2[j] is the fused chain of B[j] with itself"""
     n2 = np.ascontiguousarray(n2, dtype=dtype).reshape(-1)
@@ -958,6 +975,12 @@ def topn_adjusted(target, users, n, adjust, exclude_seen, exclude, output_score)
                                                                _real_t(target.use_float))
     return _topn_call(target, "topn_adjusted", users, int(n), lambda: (_ptr(a_indptr), _opt_ptr(a_indices), _opt_ptr(f)), exclude_seen,
                       excl, output_score)
+
+
+def topn_sampled(target, users, n, temperature, seed, exclude_seen, exclude, output_score, output_key):
+    """section 1w: (items, scores, keys)"""
+    users, temperature, seed, *excl = _topn_sampled_args(users, n, temperature, seed, exclude, target.dimA, target.dimB)
+    return _topn_call(target, "topn_sampled", users, int(n), lambda: (temperature, seed), exclude_seen, excl, output_score, bool(output_key))
 
 
 def topn_diverse(target, users, n, pool, lam, exclude_seen, exclude, output_score, output_value, item_norm):
