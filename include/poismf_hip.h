@@ -1381,6 +1381,52 @@ POISMF_HIP_API int poismf_hip_session_adopt_new(poismf_hip_session *s, size_t *f
 POISMF_HIP_API int poismf_hip_session_scale(poismf_hip_session *s, real_t gamma,
                           const real_t *row_scale, const real_t *col_scale, real_t floor, size_t *n_removed);
 
+/* ---------------------------------------------------------------------------------------------
+ * 2f. The seeded leave-out split: which cells of a matrix are HELD OUT for evaluation, decided on the device from integers
+ *     alone, so that anybody holds out the same cells.  The held-out cells of a resident session come back as a CSR and
+ *     leave the resident CSR and CSC as section 2c takes cells out, without the matrix coming to the host.  No counterpart
+ *     in the reference.
+ *
+ * The rule.  For a stored cell (u, j): w = Philox4x32-10(counter = (j, 1, u & 0xffffffff, u >> 32), key = (seed &
+ * 0xffffffff, seed >> 32)) -- poismf_hip_philox4x32 of section 1t; counter word 1 is 1 where the sampler's streams have 0,
+ * so the two never share a block -- and key(u, j) = (w[0] << 32) | w[1].  The cells of a row are ordered by (key, item
+ * index), ascending.  With n_out, thresh in 0 .. 2^32 and min_keep,
+ *     h(u) = min(n_out, #{j in row u : w[0] < thresh}, max(len(u) - min_keep, 0)),
+ * and the held-out cells of u are the first h(u) of its row in that order.  thresh = 2^32 is leave-n_out-out; n_out =
+ * SIZE_MAX holds out every cell with probability thresh / 2^32; min_keep keeps every user trainable.  A row's answer
+ * depends on (seed, u, the row's item indices, n_out, thresh, min_keep) only: not on the values, the other listed users,
+ * the launch geometry or the machine.  No floating-point operation takes part.
+ *
+ * poismf_hip_session_holdout: `users` are distinct rows of the session's A in any order, or NULL: all rows, in order
+ * (n_users is then ignored); m is their number.  out_indptr [m + 1] is always written.  With out_indices == NULL the call
+ * only COUNTS: nothing changes and the caller sizes its buffers from out_indptr[m] (also *n_held, may be NULL).  Otherwise
+ * the held-out cells come back as a CSR over the listed users in their listed order: row i is user users[i], its cells in
+ * the resident row's order (item indices ascending), out_values the resident bits; out_cap is the room of out_indices /
+ * out_values, and a total above it returns 2 with nothing changed.  With remove != 0 the cells then leave the resident CSR
+ * and CSC exactly as poismf_hip_session_sub_coo(val = NULL) takes cells out, with its memory and failure rules and its
+ * "afterwards"; the triplets go there while they are still on the device.  m == 0 returns 0.
+ * Returns 0; 1 out of memory / a device error / 2^32 or more held-out cells; 2 out_cap is too small; 3 a user lies outside
+ * the matrix or is listed twice; 4 thresh > 2^32; 5 the session's CSR shard is not the whole matrix, or remove != 0 and the
+ * session is not eligible (2b's rule).  2 - 5 leave the session exactly as it was.
+ * Per call: a SELECT pass finds every listed row's h and its cut, the h-th smallest (key, item) pair, tiered by row length --
+ * up to 256 cells one wave holds the row in registers and descends the pair's 96 bits with ballots; up to 4096 cells a
+ * workgroup computes the keys once into LDS and descends eight bits at a time over an LDS histogram; longer rows compute
+ * the keys again per level until the bin that holds the cut fits LDS -- an exclusive scan of h places the rows, and an EMIT
+ * pass walks each row in its stored order, computes the keys again and writes the cells at or below the cut.  No key is
+ * stored in device memory and nothing is sorted.
+ *
+ * poismf_hip_holdout_mark: the same decision for a HOST CSR that has no session (indptr [dimA + 1] from any start, indices
+ * below dimB; the values play no part): the row pointers and indices go up, out_flag [nnz] comes down with 1 for a held-out
+ * cell and 0 for every other one, cells of unlisted users included.  users / n_users / *n_held as above.  Device:
+ * POISMF_HIP_DEVICE.  Returns 0, 1, 3 (also: decreasing row pointers, an index outside dimB) or 4.
+ * ------------------------------------------------------------------------------------------- */
+POISMF_HIP_API int poismf_hip_session_holdout(poismf_hip_session *s, const sparse_ix *users, size_t n_users, size_t n_out,
+                          uint64_t thresh, size_t min_keep, uint64_t seed, int remove, sparse_ix *out_indptr,
+                          sparse_ix *out_indices, real_t *out_values, size_t out_cap, size_t *n_held);
+POISMF_HIP_API int poismf_hip_holdout_mark(const sparse_ix *indptr, const sparse_ix *indices, size_t dimA, size_t dimB,
+                          const sparse_ix *users, size_t n_users, size_t n_out, uint64_t thresh, size_t min_keep,
+                          uint64_t seed, unsigned char *out_flag, size_t *n_held);
+
 /* run_poismf's outer loop (ref: src/poismf.c:506-608: B half, PG step halving, A half, TNCG early stop, SIGINT
  * handling and return codes 0 / 1 / 2 exactly as in section 1) on a session that already holds X and the starting
  * factors; `p->step_size` is the initial step.  PoisMF.fit uses it with poismf_hip_session_create_coo so that the

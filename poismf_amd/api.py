@@ -24,7 +24,7 @@ from . import serving
 from .serving import (_batch_rc, _csr_list, _diverse_outputs, _eval_lists_args, _eval_ranking_args, _include_of_rows, _include_rows,
                       _index_array, _inv_norms, _list_eval_args, _list_eval_outputs, _list_eval_scratch, _list_rows, _new_rows_args, _append_rows_args,
                       _new_stats, _opt_ptr, _outside_shard, _ptr, _rank_batch_args, _rank_include_list, _shared_table_args,
-                      _similar_args, _similar_scores, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
+                      _similar_args, _similar_scores, _holdout_args, _topn_adjusted_args, _topn_batch_args, _topn_deep_args, _topn_diverse_args,
                       _topn_include_args, _topn_outputs, _topn_quota_args, _topn_sampled_args, _topn_shared_args, _topn_weighted_args, _unite_rows)
 
 _METHOD = {"tncg": 1, "cg": 2, "pg": 3, "mm": 4}  # ref: src/poismf.h:225; "mm": include/poismf_hip.h section 0 (not in the reference)
@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "poismf_hip_session_sub_coo", "poismf_hip_session_remove_rows",
     "poismf_hip_session_append_rows", "poismf_hip_session_adopt_new",
     "poismf_hip_session_scale",
+    "poismf_hip_session_holdout", "poismf_hip_holdout_mark",
     "poismf_hip_session_launch_profile", "poismf_hip_session_decisions", "poismf_hip_session_decision_stats", "poismf_hip_factors_multiple_decisions",
     "poismf_hip_session_predict", "poismf_hip_session_topn", "poismf_hip_debug_row_eval", "poismf_hip_release_cache",
     "poismf_hip_set_device_cache_mb", "poismf_hip_session_colsum_blocks", "poismf_hip_session_colsum_partial", "poismf_hip_session_partials",
@@ -197,6 +198,10 @@ def load_library(use_float):
     lib.poismf_hip_session_adopt_new.restype = i
     lib.poismf_hip_session_scale.argtypes = [vp, r, vp, vp, r, C.POINTER(sz)]
     lib.poismf_hip_session_scale.restype = i
+    lib.poismf_hip_session_holdout.argtypes = [vp, vp, sz, sz, C.c_uint64, sz, C.c_uint64, i, vp, vp, vp, sz, C.POINTER(sz)]
+    lib.poismf_hip_session_holdout.restype = i
+    lib.poismf_hip_holdout_mark.argtypes = [vp, vp, sz, sz, vp, sz, sz, C.c_uint64, sz, C.c_uint64, vp, C.POINTER(sz)]
+    lib.poismf_hip_holdout_mark.restype = i
     lib.poismf_hip_session_get_matrix.argtypes = [vp, i, vp, vp, vp]
     lib.poismf_hip_session_get_matrix.restype = i
     lib.poismf_hip_half_sweep_rows.argtypes = [vp, i, vp, sz, C.POINTER(lib.params_t), r, r, C.POINTER(sz)]
@@ -779,6 +784,33 @@ def _sample_negatives(self, users, m, exclude=None, item_weight=None, seed=0, re
 
 
 PoisMF.sample_negatives = _sample_negatives
+
+
+def holdout_split(X, n_out=None, frac=None, min_keep=1, seed=0, users=None, use_float=False):
+    """Session.holdout's split for a host matrix that has no session (include/poismf_hip.h section 2f, poismf_hip_holdout_mark): the row
+    pointers and indices of X (a SciPy sparse matrix; converted to CSR with duplicates summed and indices sorted) go to the device, one
+    flag per stored cell comes back, and X is cut with it on the host.  Returns (X_train, X_test), both of X's shape and of the
+    precision use_float names: X_test holds the held-out cells of the listed users (None: all), X_train everything else.  The same cells
+    as Session.holdout on a session built from X with the same arguments."""
+    import scipy.sparse as sp
+    if not sp.issparse(X):
+        raise ValueError("holdout_split: X must be a SciPy sparse matrix")
+    X = sp.csr_matrix(X, dtype=np.float32 if use_float else np.float64)
+    X.sum_duplicates()
+    X.sort_indices()
+    n_out, thresh, min_keep, seed, users = _holdout_args(n_out, frac, min_keep, seed, users, X.shape[0])
+    indptr, indices = np.ascontiguousarray(X.indptr, dtype=np.uint64), np.ascontiguousarray(X.indices, dtype=np.uint64)
+    flag = np.zeros(X.nnz, np.uint8)
+    rc = load_library(use_float).poismf_hip_holdout_mark(_ptr(indptr), _ptr(indices), X.shape[0], X.shape[1], None if users is None else _ptr(users),
+                                                         0 if users is None else len(users), n_out, thresh, min_keep, seed, _ptr(flag), None)
+    if rc in (3, 4):
+        raise ValueError("holdout_split: users must be distinct and inside the matrix")
+    if rc:
+        raise MemoryError("poismf_hip_holdout_mark failed (no usable HIP device or out of memory)")
+    out = flag.astype(bool)
+    rows = np.repeat(np.arange(X.shape[0]), np.diff(X.indptr))
+    cut = [sp.csr_matrix((X.data[keep], (rows[keep], X.indices[keep])), shape=X.shape) for keep in (~out, out)]
+    return cut[0], cut[1]
 
 
 def rank_sampled(A, B, users, test, m, exclude=None, item_weight=None, seed=0, return_counts=False):
@@ -1476,6 +1508,36 @@ class Session:
         if rc:
             raise MemoryError("poismf_hip_session_scale failed (out of memory or a device error)")
         return removed.value
+
+    def holdout(self, n_out=None, frac=None, min_keep=1, seed=0, users=None, remove=True):
+        """The seeded leave-out split of the resident matrix, on the device (include/poismf_hip.h section 2f): every listed user (None: all)
+        gives up the first h of its cells under the order (Philox key of (seed, user, item), item), h = min(n_out, the cells a draw of
+        probability frac admits, len - min_keep).  n_out alone is leave-n_out-out, frac alone holds out each cell with probability frac,
+        min_keep cells always stay.  A user's held-out cells depend on (seed, user, its items, n_out, frac, min_keep) only: the same call
+        anywhere holds out the same cells, whatever the other users, and api.holdout_split marks the same ones on a host matrix.  Returns
+        them as a SciPy CSR of shape (len(users) or dimA, dimB), row i the cells of users[i], values the resident bits: the X_test of
+        eval_ranking and the other evaluation calls.  With remove (the default) the cells then leave the resident CSR and CSC as
+        remove() takes cells out, and the session is the training matrix's; refit with run or sweep.  ValueError -- before anything
+        changes -- when neither n_out nor frac is given, frac lies outside [0, 1], a user is out of range or listed twice, and for a
+        session that cannot be changed in place (add's rule)."""
+        import scipy.sparse as sp
+        n_out, thresh, min_keep, seed, users = _holdout_args(n_out, frac, min_keep, seed, users, self.dimA)
+        m = self.dimA if users is None else len(users)
+        indptr = np.zeros(m + 1, np.uint64)
+        held = C.c_size_t(0)
+        up, call = (None if users is None else _ptr(users)), self.lib.poismf_hip_session_holdout
+        rc = call(self.h, up, m, n_out, thresh, min_keep, seed, 0, _ptr(indptr), None, None, 0, C.byref(held)) if m else 0
+        indices, values = np.empty(held.value, np.uint64), np.empty(held.value, np.float32 if self.use_float else np.float64)
+        if rc == 0 and held.value:
+            rc = call(self.h, up, m, n_out, thresh, min_keep, seed, int(bool(remove)), _ptr(indptr), _ptr(indices), _ptr(values), held.value, None)
+        if rc == 3:
+            raise ValueError("holdout: users must be distinct and inside the matrix")
+        if rc == 5:
+            raise ValueError("holdout: this session cannot be changed in place: it holds a shard of the matrix, or a row of its CSR / CSC "
+                             "is not strictly ascending (Session.from_coo sessions always qualify)")
+        if rc:
+            raise MemoryError("poismf_hip_session_holdout failed (out of memory or a device error)")
+        return sp.csr_matrix((values, indices.astype(np.int64), indptr.astype(np.int64)), shape=(m, self.dimB))
 
     def _grown(self, which, n):
         """the Python object follows a growth the library has made: the dimension and the shard every serving check reads"""

@@ -2,7 +2,7 @@
 
     python -m poismf_amd.build [--force] [-v]
 
-Thirty-four translation units per precision -- the host side in nine (session.hip the session object, planner.hip the planner,
+Thirty-five translation units per precision -- the host side in ten (session_holdout.hip the seeded leave-out split of a resident matrix, with philox.hpp, the fifth on session_merge.hpp;session.hip the session object, planner.hip the planner,
 half_sweep.hip issuing a half-sweep, drivers.hip run_poismf / factors_multiple, multi_device.hip the in-process multi-device driver,
 session_update.hip the merge of new counts into a resident session and the half-sweep over listed rows, session_remove.hip the removal of counts, cells and whole rows from a resident session, session_grow.hip new rows joining a resident session, session_scale.hip the scaling of every resident count and the removal of what fades -- the four on session_merge.hpp; they share session.hpp), one per inner solver, one for the multiplicative update "mm" and one for the evaluation-only kernels (the row kernels of PG, CG and TNCG are the bulk
 of the compile time; poismf_hip.hip is compiled once for each with -DPMF_TU=...), the rocPRIM-based COO conversion (coo_convert.hip),
@@ -40,6 +40,8 @@ UNITS = {
     "session_remove": ("session_remove.hip", []),
     "session_grow": ("session_grow.hip", []),
     "session_scale": ("session_scale.hip", []),
+    # the seeded leave-out split: integer code throughout (philox.hpp), on session_merge.hpp; the removal behind it is session_remove's
+    "session_holdout": ("session_holdout.hip", []),
     "poismf_hip_tncg": ("poismf_hip.hip", ["-DPMF_TU=1"]),
     "poismf_hip_cg": ("poismf_hip.hip", ["-DPMF_TU=2"]),
     "poismf_hip_pg": ("poismf_hip.hip", ["-DPMF_TU=3"]),

@@ -158,6 +158,11 @@ const unsigned* device_stop_word();
 int fold_in_solve(poismf_hip_session* s, const real_t* Bsum, real_t l2_reg, real_t w_mult, real_t step_size, size_t niter, size_t maxupd,
                   int method, bool limit_step, bool reuse_mean);
 
+// session_remove.hip: n device triplets (d_val == nullptr: the cells go outright) leave the resident CSR and CSC; rows / cols: their distinct
+// rows / columns, ascending, or nullptr: found on the device
+int remove_both(poismf_hip_session* s, const unsigned* d_row, const unsigned* d_col, const real_t* d_val, size_t n, const std::vector<unsigned>* rows,
+                const std::vector<unsigned>* cols, int strict, size_t* n_removed, size_t* n_absent);
+
 // multi_device.hip
 int run_poismf_multi(const std::vector<int>& devices, real_t* A, real_t* Xr, sparse_ix* Xr_indptr, sparse_ix* Xr_indices, real_t* B, real_t* Xc,
                      sparse_ix* Xc_indptr, sparse_ix* Xc_indices, size_t dimA, size_t dimB, size_t k, const poismf_hip_params& p, size_t numiter);

@@ -167,7 +167,10 @@ int remove_half(poismf_hip_session* s, Half& h, const unsigned* d_major, const u
     return 0;
 }
 
+}  // namespace
+
 // Both orientations: d_row / d_col / d_val are n triplets on the device; rows / cols as remove_half's `touched`.  The counts are the CSR's.
+// (Declared in session.hpp: session_holdout.hip feeds it the cells it has chosen.)
 int remove_both(poismf_hip_session* s, const unsigned* d_row, const unsigned* d_col, const real_t* d_val, size_t n, const std::vector<unsigned>* rows,
                 const std::vector<unsigned>* cols, int strict, size_t* n_removed, size_t* n_absent)
 {
@@ -178,6 +181,8 @@ int remove_both(poismf_hip_session* s, const unsigned* d_row, const unsigned* d_
         return rc;
     });
 }
+
+namespace {
 
 // ---- whole rows: their cells as triplets -----------------------------------------------------------------------------------------------
 

@@ -523,6 +523,35 @@ def _sample_negatives_args(users, m, exclude, item_weight, seed, dimA, dimB):
     return (users, m) + _exclude_list(exclude, len(users), dimB) + (_negatives_weight(item_weight, dimB), seed)
 
 
+def _holdout_args(n_out, frac, min_keep, seed, users, dimA):
+    """The argument checks of the leave-out split (include/poismf_hip.h section 2f) that need no device.  Returns (n_out, thresh,
+    min_keep, seed, users or None): n_out None becomes SIZE_MAX, frac None becomes thresh = 2^32, otherwise thresh = min(int(frac *
+    2^32), 2^32); users None means every row."""
+    if n_out is None and frac is None:
+        raise ValueError("holdout: give n_out (cells per user), frac (share of the cells), or both")
+    if n_out is None:
+        n_out = 2 ** 64 - 1
+    elif isinstance(n_out, bool) or int(n_out) != n_out or not 0 <= int(n_out) < 2 ** 64:
+        raise ValueError("holdout: n_out must be a non-negative integer")
+    thresh = 2 ** 32
+    if frac is not None:
+        frac = float(frac)
+        if not 0.0 <= frac <= 1.0:   # (a NaN fails both comparisons)
+            raise ValueError("holdout: frac must lie in [0, 1]")
+        thresh = min(int(frac * 2 ** 32), 2 ** 32)
+    if isinstance(min_keep, bool) or int(min_keep) != min_keep or not 0 <= int(min_keep) < 2 ** 64:
+        raise ValueError("holdout: min_keep must be a non-negative integer")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must lie in 0 .. 2^64 - 1")
+    if users is not None:
+        users = _index_array(users, "users")
+        _users_in_range(users, dimA)
+        if len(np.unique(users)) != len(users):
+            raise ValueError("holdout: a user is listed twice")
+    return int(n_out), thresh, int(min_keep), seed, users
+
+
 def _rank_include_list(include, m, dimB):
     """The include lists of the batched ranks (include/poismf_hip.h section 1j), checked as the library checks them: (incl_indptr,
     incl_indices) as uint64 arrays"""
